@@ -6,7 +6,9 @@ A "step" = one FlowNetC deploy forward over one batch of 8 synthetic 448x320 ima
 `--mode train` times fwd + bwd + RCCL gradient all-reduce + Adam instead (configs[3]).
 
 Contract (driver): python bench.py --gpus N --steps K --warmup W ; for N > 1 it is launched through
-torch.distributed.run with one rank per GPU.  Rank 0 prints ONE JSON line.
+torch.distributed.run with one rank per GPU.  Rank 0 prints ONE JSON line.  Such a plain run measures the headline figure alone;
+`--full` adds the cold-clock figure, the correlation roofline, the CPU-oracle legs and the other configurations under `extra`.
+`--dump-outputs DIR` writes what the last timed step computed (DIR/<name>.npy) for output-for-output comparisons between builds.
 """
 from __future__ import annotations
 
@@ -56,8 +58,13 @@ def parse():
     ap.add_argument("--width", type=int, default=448)
     ap.add_argument("--mode", choices=["fwd", "train"], default="fwd")
     ap.add_argument("--net", choices=["C", "2"], default="C", help="C = FlowNetC (headline, configs[1]); 2 = full FlowNet2 stack (configs[2]: use --batch 4 --height 384 --width 768)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip the FlowNet2 768x384 / 1024x448 and train-step legs reported under `extra`")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the cold-clock figure, the correlation roofline, "
+                    "the CPU-oracle baseline and EPE, the committed-profile figures and (headline configuration) the legs under `extra`; "
+                    "without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the FlowNet2 768x384 / 1024x448 and train-step legs reported under `extra`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float32 / float64): fwd = the flow, train = the loss and a fixed sample of the updated weights")
     ap.add_argument("--graph", action="store_true", help="capture a forward step into a hipGraph and replay it (measured: no gain, the step is not launch-bound)")
     ap.add_argument("--corr-iters", type=int, default=200)
     ap.add_argument("--bucket-mb", type=int, default=48, help="gradient all-reduce bucket size (train mode)")
@@ -275,10 +282,12 @@ WGRAD_SIDE_PIXELS = [36000]       # --wgrad-side-pixels: GradientExchange's seco
 
 
 def run_workload(net, mode, B, H, W, steps, warmup, device, world, rank, bucket_mb=48, graph=False, settle_s=1.0, rt=None, local_grads=False,
-                 force_collective=False):
+                 force_collective=False, cold=True, settle_steps_fixed=None):
     """W untimed warm-up steps (+ untimed settling steps until `settle_s` seconds of back-to-back stepping have passed: the chip
     needs ~25 ms of load to come back to its steady clocks, and a short run otherwise sits inside that ramp), then EXACTLY `steps`
-    timed steps between barrier + synchronize on both sides.  Returns the measurements and what the caller needs for the oracle leg."""
+    timed steps between barrier + synchronize on both sides.  cold=False skips the cold figure (elapsed_cold is then None);
+    settle_steps_fixed settles for that many steps instead of by the clock (a training step's outputs depend on how many came before).
+    Returns the measurements and what the caller needs for the oracle leg."""
     rt = rt or CudaRuntime()
     be = rt.backend
     P_cpu = nets.init_params("C", seed=0) if net == "C" else nets.init_params_flownet2(seed=0)   # same weights on every rank
@@ -355,16 +364,19 @@ def run_workload(net, mode, B, H, W, steps, warmup, device, world, rank, bucket_
         gc.disable()
     # cold figure: the same K steps timed straight after the W warm-up steps, with NO settling steps in between (the clock ramp of the
     # first ~25 ms of load is inside it) -- reported as value_cold next to the steady-clock headline; rank-local, no barrier
-    rt.synchronize()
-    t_c = time.perf_counter()
-    for _ in range(steps):
-        step_fn()
-    rt.synchronize()
-    elapsed_cold = time.perf_counter() - t_c
+    elapsed_cold = None
+    if cold:
+        rt.synchronize()
+        t_c = time.perf_counter()
+        for _ in range(steps):
+            step_fn()
+        rt.synchronize()
+        elapsed_cold = time.perf_counter() - t_c
     # settling: untimed steps, back to back, until the chip has been under this load for settle_s seconds
     rt.synchronize()
     settle_steps, t_s = 0, time.perf_counter()
-    while warmup > 0 and time.perf_counter() - t_s < settle_s and settle_steps < 2000:
+    while warmup > 0 and (settle_steps < settle_steps_fixed if settle_steps_fixed is not None else
+                          time.perf_counter() - t_s < settle_s and settle_steps < 2000):
         for _ in range(16):
             step_fn()
         settle_steps += 16
@@ -387,7 +399,8 @@ def run_workload(net, mode, B, H, W, steps, warmup, device, world, rank, bucket_
     if gc_was_on:
         gc.enable()
     elapsed = parallel.max_over_ranks(elapsed, device)
-    elapsed_cold = parallel.max_over_ranks(elapsed_cold, device)
+    if cold:
+        elapsed_cold = parallel.max_over_ranks(elapsed_cold, device)
     res = {"elapsed": elapsed, "params": P, "marks": marks, "out": out, "P_cpu": P_cpu, "img0": img0, "img1": img1, "use_graph": use_graph,
            "gc_paused": gc_was_on, "settle_steps": settle_steps, "settling_s": settling_s, "elapsed_cold": elapsed_cold}
     if mode == "train":
@@ -591,6 +604,35 @@ def train_parity(device, B=8, H=320, W=448):
                    "for the library's fp32 kernels (library_fp32_...: the same torch graph in float32) as for ours (%.1f s)" % (time.time() - t0)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _dump_sample(t, n_max, seed):
+    """A flattened tensor as float32, or a fixed, seeded sample of n_max of its elements when it is larger (same indices every run)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n_max:
+        return flat.float().cpu().numpy()
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (n_max,), generator=g).sort().values.to(flat.device)
+    return flat[idx].float().cpu().numpy()
+
+
+def dump_outputs(path, mode, out, P):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy.  fwd: the flow [N,2,H,W] (float32; a seeded sample
+    when it exceeds the budget).  train: the loss (float64) and a seeded sample of the weights after the last Adam update, concatenated
+    in parameter order (39 M floats do not fit the budget)."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    if mode == "train":
+        np.save(os.path.join(path, "loss.npy"), np.asarray(float(out.detach()), dtype=np.float64))
+        flat = torch.cat([p.detach().reshape(-1) for p in P.values()])
+        np.save(os.path.join(path, "weights_sample.npy"), _dump_sample(flat, 1 << 20, seed=0))
+    else:
+        flow = out.detach()
+        arr = flow.float().cpu().numpy() if flow.numel() * 4 <= DUMP_BUDGET_BYTES else _dump_sample(flow, DUMP_BUDGET_BYTES // 4, seed=0)
+        np.save(os.path.join(path, "flow.npy"), arr)
+
+
 def _claim_stdout():
     """The driver reads ONE JSON line from stdout.  Native libraries print there too (RCCL's version banner goes to the C stdout at
     communicator init and is flushed at exit, BEHIND the line): file descriptor 1 is pointed at stderr for the life of the process and the
@@ -622,12 +664,15 @@ def main():
     _nets.set_sd_side_stream(args.sd_stream)
     WGRAD_SIDE_PIXELS[0] = args.wgrad_side_pixels
     B, H, W = args.batch, args.height, args.width
-    m = run_workload(args.net, args.mode, B, H, W, args.steps, args.warmup, device, world, rank, args.bucket_mb, args.graph)
+    m = run_workload(args.net, args.mode, B, H, W, args.steps, args.warmup, device, world, rank, args.bucket_mb, args.graph, cold=args.full,
+                     settle_steps_fixed=128 if (args.dump_outputs and args.mode == "train") else None)
     elapsed, marks, out, P_cpu, img0, img1 = m["elapsed"], m["marks"], m["out"], m["P_cpu"], m["img0"], m["img1"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, args.mode, out, m["params"])
 
     headline = args.mode == "fwd" and args.net == "C" and (B, H, W) == (8, 320, 448)
     multi_rank_train = None
-    if world > 1 and headline and not args.no_extras:
+    if world > 1 and headline and args.full and not args.no_extras:
         # The multi-rank line carries the leg that runs the path's one collective: BASELINE config 4 on all ranks, after the headline's
         # timed region (every rank calls it: barriers and all-reduces inside).  The forward headline above stays embarrassingly parallel.
         keep = {k: m[k] for k in ("settle_steps", "settling_s", "elapsed_cold", "use_graph", "gc_paused")}
@@ -641,9 +686,8 @@ def main():
             "metric": "image-pairs/sec " + ("FlowNetC " if args.net == "C" else "FlowNet2 (CSS+SD+fusion) ") + ("forward" if args.mode == "fwd" else ("fwd+bwd+allreduce+Adam" if world > 1 else "fwd+bwd+Adam")) + " at %dx%d" % (W, H),
             "value": round(pairs / elapsed, 2), "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            # the same K steps timed straight after the W warm-up steps (no settling steps: clock ramp included), and what came between
-            "value_cold": round(pairs / m["elapsed_cold"], 2), "ms_per_step_cold": round(m["elapsed_cold"] / args.steps * 1e3, 4),
-            "settling_s": round(m["settling_s"], 3), "untimed_steps_before_timed_region": args.warmup + args.steps + m["settle_steps"],
+            "settling_s": round(m["settling_s"], 3),
+            "untimed_steps_before_timed_region": args.warmup + (args.steps if m["elapsed_cold"] is not None else 0) + m["settle_steps"],
             "ms_per_step_p10_p50_p90": step_percentiles(marks), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": ("FlowNetC" if args.net == "C" else "FlowNet2") + " %s (correlation max_disp=20 stride_2=2), batch %d/GPU @%dx%d, synthetic uint8-valued "
@@ -656,9 +700,13 @@ def main():
                        "ranks_seen_by_rccl": ranks_seen if world > 1 else "no process group (world 1)"},
             "conv_tflops": round(conv_gf * (3 if args.mode == "train" else 1) * args.steps / elapsed / 1e3, 2),
         }
-        if args.mode == "fwd" and args.net == "C" and (B, H, W) == (8, 320, 448):
+        if m["elapsed_cold"] is not None:
+            # the same K steps timed straight after the W warm-up steps (no settling steps: clock ramp included)
+            res["value_cold"] = round(pairs / m["elapsed_cold"], 2)
+            res["ms_per_step_cold"] = round(m["elapsed_cold"] / args.steps * 1e3, 4)
+        if args.full and headline:
             res.update(step_mfma_busy())
-        if world == 1:
+        if world == 1 and args.full:
             res["roofline"] = corr_roofline(device, B, H, W, args.corr_iters)
             if args.mode == "fwd" and args.net == "C" and not args.no_cpu_baseline:
                 cb, epe = cpu_baseline(P_cpu, img0, img1, out)

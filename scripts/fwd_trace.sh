@@ -5,8 +5,8 @@ TAG=$1; shift
 R=gpurun_out/$TAG
 mkdir -p $R
 export FN2_AUTOTUNE_CACHE=$PWD/$R/autotune.txt
-python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-extras "$@" > /dev/null 2>&1
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/fwd -o f -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --corr-iters 4 "$@" > $R/fwd_profiled.json 2>/dev/null
+python bench.py --steps 3 --warmup 2 --full --no-cpu-baseline --no-extras "$@" > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/fwd -o f -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras --corr-iters 4 "$@" > $R/fwd_profiled.json 2>/dev/null
 python - <<PY
 import csv
 rows = list(csv.DictReader(open("$R/fwd/f_kernel_stats.csv")))

@@ -1,6 +1,6 @@
 import sys, os
 sys.path.insert(0, os.getcwd())
-sys.argv = ["bench.py", "--mode", "train", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-extras"]
+sys.argv = ["bench.py", "--mode", "train", "--steps", "30", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras"]
 import flownet2_amd.functional as Fn
 orig = Fn._cached
 def fake(cache, key, w, make):

@@ -1,7 +1,7 @@
 import sys, os
 sys.path.insert(0, os.getcwd())
 prio = int(sys.argv[1])
-sys.argv = ["bench.py", "--mode", "train", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-extras"]
+sys.argv = ["bench.py", "--mode", "train", "--steps", "30", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras"]
 import torch
 import flownet2_amd.functional as Fn
 try:

@@ -7,7 +7,10 @@ GPU box -- which has no /root/reference -- can run config 1 (one FlyingChairs pa
 Writes: flo_fixtures.json  (per *-gt.flo: sha256, size, magic, width, height, first/last (u,v), mean |flow|, and a
                             checksum of checksums),
         0000000-img0.png / -img1.png  (the first pair, PPM -> PNG, lossless),
-        0000000-gt.npz                (its ground-truth flow, float32 [384,512,2], deflate-compressed)."""
+        0000000-gt.npz                (its ground-truth flow, float32 [384,512,2], deflate-compressed),
+        all-gt.npz                    (the ground-truth flow of every pair, keyed by pair number, deflate-compressed: with the header
+                                       it reproduces each *-gt.flo byte for byte),
+        ppm_fixtures.json             (per image of the first pair: the PPM header, pixel shape, sha256 of the pixels and of the file)."""
 import glob
 import hashlib
 import json
@@ -41,6 +44,21 @@ def main():
         Image.open(os.path.join(SRC, "0000000-%s.ppm" % k)).save(os.path.join(DST, "0000000-%s.png" % k), optimize=True)
     raw = open(os.path.join(SRC, "0000000-gt.flo"), "rb").read()
     np.savez_compressed(os.path.join(DST, "0000000-gt.npz"), flow=np.frombuffer(raw, "<f4", offset=12).reshape(384, 512, 2))
+    flows = {}
+    for p in sorted(glob.glob(os.path.join(SRC, "*-gt.flo"))):
+        raw = open(p, "rb").read()
+        w, h = struct.unpack("<ii", raw[4:12])
+        flows[os.path.basename(p)[:-len("-gt.flo")]] = np.frombuffer(raw, "<f4", offset=12).reshape(h, w, 2)
+    np.savez_compressed(os.path.join(DST, "all-gt.npz"), **flows)
+    ppm = {}
+    for k in ("img0", "img1"):
+        name = "0000000-%s.ppm" % k
+        raw = open(os.path.join(SRC, name), "rb").read()
+        px = np.asarray(Image.open(os.path.join(SRC, name)))
+        ppm[name] = {"header_hex": raw[:len(raw) - px.nbytes].hex(), "shape": list(px.shape),
+                     "pixels_sha256": hashlib.sha256(np.ascontiguousarray(px).tobytes()).hexdigest(),
+                     "sha256": hashlib.sha256(raw).hexdigest()}
+    json.dump(ppm, open(os.path.join(DST, "ppm_fixtures.json"), "w"), indent=1, sort_keys=True)
     print({k: os.path.getsize(os.path.join(DST, k)) for k in sorted(os.listdir(DST))})
 
 

@@ -1,7 +1,8 @@
 """.caffemodel reader (csrc/caffemodel.cpp, flownet2_amd/caffemodel.py; reference: Net::CopyTrainedLayersFrom net.cpp:752-800,
 Blob::FromProto blob.cpp:459-508).  CPU tests: the committed fixture (written by the protobuf runtime with the REFERENCE's own
-descriptor, tests/golden/make_caffemodel_fixture.py) read back bit for bit by the product reader and by the oracle twin; where
-/root/reference exists, fresh messages are serialised on the fly as well (unpacked encodings, chunked data, truncation)."""
+descriptor, tests/golden/make_caffemodel_fixture.py) read back bit for bit by the product reader and by the oracle twin; fresh messages
+are serialised on the fly by the protobuf runtime as well (unpacked encodings, chunked data, truncation), with the messages the fixture uses
+restated from caffe.proto in this file."""
 import ctypes as C
 import os
 import sys
@@ -111,11 +112,50 @@ def test_malformed_files_are_refused():
     assert caffemodel.read_caffemodel(b"") == {}
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/python/caffe/proto/caffe_pb2.py"), reason="reference tree not present")
+def caffe_messages():
+    """The caffe.proto messages the fixture uses (package caffe, proto2), restricted to the fields it sets: numbers, types and packing as in
+    caffe.proto (NetParameter.layer = 100, LayerParameter.convolution_param = 106, packed BlobProto.data / double_data and BlobShape.dim,
+    V1LayerParameter.type an enum with CONVOLUTION = 4).  Unknown-to-this-subset fields never occur in these messages."""
+    from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
+    F = descriptor_pb2.FieldDescriptorProto
+    fdp = descriptor_pb2.FileDescriptorProto(name="caffe_subset.proto", package="caffe", syntax="proto2")
+
+    def msg(name, *fields):
+        m = fdp.message_type.add(name=name)
+        for fname, num, typ, rep, extra in fields:
+            f = m.field.add(name=fname, number=num, type=typ, label=F.LABEL_REPEATED if rep else F.LABEL_OPTIONAL)
+            if extra.get("packed"):
+                f.options.packed = True
+            if "type_name" in extra:
+                f.type_name = extra["type_name"]
+        return m
+
+    msg("BlobShape", ("dim", 1, F.TYPE_INT64, True, {"packed": True}))
+    msg("BlobProto", ("num", 1, F.TYPE_INT32, False, {}), ("channels", 2, F.TYPE_INT32, False, {}), ("height", 3, F.TYPE_INT32, False, {}),
+        ("width", 4, F.TYPE_INT32, False, {}), ("data", 5, F.TYPE_FLOAT, True, {"packed": True}),
+        ("shape", 7, F.TYPE_MESSAGE, False, {"type_name": ".caffe.BlobShape"}), ("double_data", 8, F.TYPE_DOUBLE, True, {"packed": True}))
+    msg("ParamSpec", ("lr_mult", 3, F.TYPE_FLOAT, False, {}))
+    msg("ConvolutionParameter", ("num_output", 1, F.TYPE_UINT32, False, {}), ("kernel_size", 4, F.TYPE_UINT32, True, {}))
+    msg("LayerParameter", ("name", 1, F.TYPE_STRING, False, {}), ("type", 2, F.TYPE_STRING, False, {}), ("bottom", 3, F.TYPE_STRING, True, {}),
+        ("top", 4, F.TYPE_STRING, True, {}), ("param", 6, F.TYPE_MESSAGE, True, {"type_name": ".caffe.ParamSpec"}),
+        ("blobs", 7, F.TYPE_MESSAGE, True, {"type_name": ".caffe.BlobProto"}),
+        ("convolution_param", 106, F.TYPE_MESSAGE, False, {"type_name": ".caffe.ConvolutionParameter"}))
+    v1 = msg("V1LayerParameter", ("name", 4, F.TYPE_STRING, False, {}), ("type", 5, F.TYPE_ENUM, False, {"type_name": ".caffe.V1LayerParameter.LayerType"}),
+             ("blobs", 6, F.TYPE_MESSAGE, True, {"type_name": ".caffe.BlobProto"}))
+    lt = v1.enum_type.add(name="LayerType")
+    lt.value.add(name="NONE", number=0)
+    lt.value.add(name="CONVOLUTION", number=4)
+    msg("NetParameter", ("name", 1, F.TYPE_STRING, False, {}), ("layers", 2, F.TYPE_MESSAGE, True, {"type_name": ".caffe.V1LayerParameter"}),
+        ("layer", 100, F.TYPE_MESSAGE, True, {"type_name": ".caffe.LayerParameter"}))
+    pool = descriptor_pool.DescriptorPool()
+    pool.Add(fdp)
+    return {n: message_factory.GetMessageClass(pool.FindMessageTypeByName("caffe." + n)) for n in ("NetParameter", "BlobProto")}
+
+
 def test_against_the_protobuf_runtime_with_the_reference_descriptor():
     sys.path.insert(0, GOLD)
     import make_caffemodel_fixture as mk
-    M = mk.reference_messages()
+    M = caffe_messages()
     net, arrays = mk.build(M["NetParameter"])
     assert net.SerializeToString() == RAW                                  # the committed fixture is what the script writes
     # a message protobuf would merge: data in two packed chunks + one unpacked element, shape.dim unpacked

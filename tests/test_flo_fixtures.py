@@ -1,12 +1,14 @@
 """.flo I/O against the reference-held fixtures (data/FlyingChairs_examples/*-gt.flo, util/output.cpp:16-65,
 scripts/run-flownet.py:100-126) and BASELINE.json configs[0]: FlowNetS deploy on one FlyingChairs pair -> .flo.
 
-The fixture digests and the first pair are committed under tests/golden/chairs (tests/golden/make_flo_fixtures.py made them
-from the reference tree); where /root/reference exists every reference file itself is read, re-written and byte-compared."""
+The fixture digests, the ground truth of every pair and the first image pair are committed under tests/golden/chairs
+(tests/golden/make_flo_fixtures.py made them from the reference tree); every reference file is rebuilt from them byte for byte, read,
+re-written and byte-compared."""
 import glob
 import hashlib
 import json
 import os
+import struct
 import subprocess
 import sys
 
@@ -17,8 +19,8 @@ from flownet2_amd import flo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHAIRS = os.path.join(ROOT, "tests", "golden", "chairs")
-REF_DIR = "/root/reference/data/FlyingChairs_examples"
 FIX = json.load(open(os.path.join(CHAIRS, "flo_fixtures.json")))
+PPM = json.load(open(os.path.join(CHAIRS, "ppm_fixtures.json")))
 
 
 def sha(path):
@@ -50,32 +52,38 @@ def test_writer_reproduces_reference_fixture_bytes(tmp_path):
     assert [float(back[-1, -1, 0]), float(back[-1, -1, 1])] == e["last_uv"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference tree not present (GPU box)")
 def test_every_reference_flo_roundtrips_byte_exact(tmp_path):
-    files = sorted(glob.glob(os.path.join(REF_DIR, "*-gt.flo")))
-    assert len(files) == 9
-    for f in files:
-        e = FIX["files"][os.path.basename(f)]
+    """Each reference *-gt.flo rebuilt from the committed flow (tests/golden/chairs/all-gt.npz) has the reference file's sha256; read back and
+    re-written by flo.read_flo / flo.write_flo it stays byte-identical."""
+    flows = np.load(os.path.join(CHAIRS, "all-gt.npz"))
+    assert sorted(k + "-gt.flo" for k in flows.files) == sorted(FIX["files"])
+    for name in sorted(FIX["files"]):
+        e = FIX["files"][name]
+        f = str(tmp_path / name)
+        open(f, "wb").write(b"PIEH" + struct.pack("<ii", e["width"], e["height"]) + flows[name[:-len("-gt.flo")]].astype("<f4").tobytes())
         assert sha(f) == e["sha256"]
         raw = open(f, "rb").read()
         assert raw[:4] == b"PIEH" and np.frombuffer(raw, "<i4", 2, 4).tolist() == [512, 384]
         a = flo.read_flo(f)
         assert a.shape == (384, 512, 2) and a.dtype == np.float32
         assert abs(float(np.abs(a.astype(np.float64)).mean()) - e["mean_abs"]) < 1e-12
-        out = str(tmp_path / os.path.basename(f))
+        out = str(tmp_path / ("w-" + name))
         flo.write_flo(out, a)
         assert open(out, "rb").read() == raw
         flo.write_flo(out, a.transpose(2, 0, 1))                                    # blob layout (run-flownet.py:98 transposes it back)
         assert open(out, "rb").read() == raw
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference tree not present (GPU box)")
 def test_committed_pair_equals_reference_ppm():
+    """The committed PNGs hold the pixels of the reference's 0000000-img{0,1}.ppm: with the PPM header of tests/golden/chairs/ppm_fixtures.json
+    they rebuild the reference file byte for byte."""
     from PIL import Image
     for k in ("img0", "img1"):
-        a = np.asarray(Image.open(os.path.join(REF_DIR, "0000000-%s.ppm" % k)))
-        b = np.asarray(Image.open(os.path.join(CHAIRS, "0000000-%s.png" % k)))
-        assert a.shape == (384, 512, 3) and np.array_equal(a, b)
+        e = PPM["0000000-%s.ppm" % k]
+        b = np.ascontiguousarray(np.asarray(Image.open(os.path.join(CHAIRS, "0000000-%s.png" % k))))
+        assert b.shape == (384, 512, 3) and list(b.shape) == e["shape"] and b.dtype == np.uint8
+        assert hashlib.sha256(b.tobytes()).hexdigest() == e["pixels_sha256"]
+        assert hashlib.sha256(bytes.fromhex(e["header_hex"]) + b.tobytes()).hexdigest() == e["sha256"]
 
 
 @pytest.mark.gpu
