@@ -549,7 +549,14 @@ FN2_API int fn2_conv_mfma_supported(int Cin, int Hin, int Win, int Cout, int ker
   if (pad < 0 || pad > 4 || pad > kernel - 1) return 0;
   if ((long long)Cin * Hin * Win >= (1ll << 28)) return 0;
   const int Hout = (Hin + 2 * pad - kernel) / stride + 1, Wout = (Win + 2 * pad - kernel) / stride + 1;
-  return Hout >= 1 && Wout >= 1;
+  if (Hout < 1 || Wout < 1) return 0;
+  // and a tile variant that takes it: only the 1x1 tiles block Cout by 32, the others by 64 (a Convolution{5, 2, 2} with 96 outputs
+  // used to be routed DIRECT by fn2_conv_route and then failed at launch with "no kernel variant")
+  cv::Args a{};
+  a.Win = Win; a.Cout = Cout;
+  for (int i = 0; i < cv::kNumVariants; ++i)
+    if (cv::variant_applies(cv::kVariants[i], a, kernel, stride)) return 1;
+  return 0;
 }
 
 FN2_API int fn2_debug_set_conv_variant(int v) { cv::g_forced_variant = v; return FN2_OK; }
