@@ -520,6 +520,12 @@ class _OwnForwardConv(torch.autograd.Function):
         # relu_chain (round 6, set by the graph builder for a layer pair A -> B where B is A's ONLY consumer): bit 0 on A = "my top_diff arrives
         # already multiplied by my ReLU derivative" (B did it), bit 1 on B = "fold the ReLU derivative of the layer in front into my data gradient"
         ctx.relu_chain, ctx.chain_cell = (int(relu_chain[0]), relu_chain[1]) if relu_chain else (0, None)
+        # ... and both ends must be in the graph: a consumer whose producer took another path (no relu_chain handed to it) would fold a ReLU
+        # derivative the producer's own backward applies a second time
+        if ctx.relu_chain & 1:
+            ctx.chain_cell["armed"] = True
+        elif ctx.relu_chain & 2 and not ctx.chain_cell.get("armed"):
+            raise RuntimeError("relu_chain: the layer in front of this one is not a chain producer (it would undo its ReLU twice)")
         # the activated output is needed for the ReLU mask: a slice of a Concat blob is kept as the BLOB (a saved view comes back from autograd
         # as a plain strided tensor that has forgotten its base: reading it in place needs the blob and the offset)
         ctx.save_for_backward(x, weight, (into[0] if into is not None else y) if act else None)
@@ -711,8 +717,15 @@ def conv_backward(x, w, y, g, stride, pad, slope, transposed, need_x, need_w, ne
         if x.is_cuda:       # counted like the forward's last resort: `library_conv_fallbacks: 0` in the bench line covers backward too
             _note_fallback("%s backward{stride %d, pad %d}%s%s" % ("Deconvolution" if transposed else "Convolution", stride, pad,
                                                                    " data" if lib_x else "", " weight" if lib_w else ""), x, w)
-        gxl, gwl, _ = torch.ops.aten.convolution_backward(d, x, w, None, [stride, stride], [pad, pad], [1, 1], transposed, [0, 0], 1,
-                                                          [lib_x, lib_w, False])
+        # deterministic library solvers (MIOpen's DETERMINISTIC attribute): with its default solvers the weight gradients of the small-channel
+        # first layers (FlowNet-SD's / the fusion net's conv0, 6 / 11 inputs) differed from run to run
+        cd, was = torch.backends.cudnn, torch.backends.cudnn.deterministic
+        cd.deterministic = True
+        try:
+            gxl, gwl, _ = torch.ops.aten.convolution_backward(d, x, w, None, [stride, stride], [pad, pad], [1, 1], transposed, [0, 0], 1,
+                                                              [lib_x, lib_w, False])
+        finally:
+            cd.deterministic = was
         gx, gw = (gxl if lib_x else gx), (gwl if lib_w else gw)
     return gx, gw, db
 

@@ -77,13 +77,13 @@ def _conv(x, P, name, stride, pad, act=True, backend=None, relu_chain=None):
     """Convolution (+ ReLU{negative_slope 0.1}).  With a backend that has conv_bias_leaky_relu the library runs the
     bias-free convolution and bias + activation are one in-place pass (csrc/bias_act.hip) instead of two."""
     w = P[name + ".w"]
-    if _TRACE_CONV:
-        y = _conv_routed(x, P, name, stride, pad, act, backend)
-        print("conv route %-16s in %-22s k%d s%d act=%d -> %s" % (name, tuple(x.shape), w.shape[2], stride, act, _LAST_ROUTE[0]))
-        return y
     if relu_chain is not None:
-        return conv_forward(x, w, P[name + ".b"], stride, pad, act, backend, relu_chain=relu_chain)
-    return _conv_routed(x, P, name, stride, pad, act, backend)
+        y = conv_forward(x, w, P[name + ".b"], stride, pad, act, backend, relu_chain=relu_chain)
+    else:
+        y = _conv_routed(x, P, name, stride, pad, act, backend)
+    if _TRACE_CONV:
+        print("conv route %-16s in %-22s k%d s%d act=%d -> %s" % (name, tuple(x.shape), w.shape[2], stride, act, _LAST_ROUTE[0]))
+    return y
 
 
 _TRACE_CONV = __import__("os").environ.get("FN2_TRACE_CONV") == "1"
@@ -522,6 +522,16 @@ def loss_targets_ahead(gt_flow, backend, divisors=None):
     sizes = [(H // divisors[s], W // divisors[s]) for s in LOSS_WEIGHTS]
     tgts, ev = backend.downsample_ahead(gt, sizes)
     return {"targets": dict(zip(LOSS_WEIGHTS, tgts)), "event": ev, "sizes": dict(zip(LOSS_WEIGHTS, sizes))}
+
+
+FINAL_FLOW_GT_SCALE = {"SD": 1.0 / SD_FLOW_SCALE, "fusion": 1.0}     # pixels -> the units of the final flow of flownet_sd_core / fusion_core
+
+
+def final_flow_loss(flow, gt_flow, backend, scale):
+    """Training loss of a core that returns only its final flow (flownet_sd_core, fusion_core): Downsample(GT * scale) to that flow's size
+    -> L1Loss{l2_per_location, normalize_by_num_entries}, the loss layer multiscale_loss uses per scale."""
+    tgt = backend.downsample(gt_flow * scale, flow.shape[2], flow.shape[3])
+    return backend.l1_loss(flow, tgt, l2_per_location=True, normalize_by_num_entries=True)
 
 
 def multiscale_loss(flows, gt_flow, backend, targets=None):

@@ -1,9 +1,10 @@
-"""fp64 evaluation of the FlowNetC TRAINING step's loss and parameter gradients -- the comparator of BASELINE config 4 at its own size.
+"""fp64 evaluation of the TRAINING step's loss and parameter gradients of a FlowNet core (FlowNetC: the comparator of BASELINE config 4 at
+its own size; FlowNetS, FlowNet-SD and the fusion net: train_reference).
 
 TEST INFRASTRUCTURE (only tests/, __graft_entry__.smoke() and bench.py's checker legs import it; the product path never does).
 
-What it is: the graph of flownet2_amd.nets.flownet_c_core + multiscale_loss -- the very function the training step runs -- evaluated in
-torch.float64 with autograd, through a backend that owns NONE of the product's kernels:
+What it is: the graph of flownet2_amd.nets.flownet_c_core + multiscale_loss (or of another core and its loss) -- the very function the
+training step runs -- evaluated in torch.float64 with autograd, through a backend that owns NONE of the product's kernels:
   * Convolution / Deconvolution / ReLU: torch's float64 conv2d / conv_transpose2d / leaky_relu (im2col + DGEMM: the reference's own
     algorithm, ConvolutionLayer::Forward_gpu / Backward_gpu, conv_layer.cu:8-60, base_conv_layer.cpp:325-393, at twice the precision);
   * Correlation: the sum over channels of shifted products, displacement by displacement, and its analytic gradient
@@ -97,9 +98,10 @@ def backend64():
 
 
 class record_relu_branches:
-    """Context manager around a forward pass of nets.flownet_c_core in ANY backend: records, in execution order, which side of the kink
-    every leaky-ReLU output of the graph is on (the activated outputs of nets._conv / nets._deconv with act = True, and the plain
-    F.leaky_relu calls of the graph itself: the correlation's ReLU).  `branches` is the list flownetc_train_reference(masks=...) takes.
+    """Context manager around a forward pass of a FlowNet core (nets.flownet_c_core / flownet_s_core / flownet_sd_core / fusion_core) in ANY
+    backend: records, in execution order, which side of the kink every leaky-ReLU output of the graph is on (the activated outputs of
+    nets._conv / nets._deconv with act = True, of the producers that write into a Concat blob, and the plain F.leaky_relu calls of the graph
+    itself: the correlation's ReLU).  `branches` is the list train_reference(masks=...) takes.
 
     Why: a leaky ReLU is piecewise linear.  An fp32 and an fp64 evaluation of the same net disagree about the SIGN of the few
     pre-activations that are within rounding of zero (about one in 10^6: a handful among the 5 M outputs of conv3_1 at batch 8), and each
@@ -187,22 +189,36 @@ class record_relu_branches:
         return False
 
 
-def flownetc_train_reference(P, img0, img1, gt, device=None, mean=0.43, masks=None, dtype=torch.float64):
-    """loss (float) and {parameter name: float64 gradient on the CPU} of one FlowNetC training step exactly as bench.py --mode train
-    states it: pre-processing im / 255 - mean, nets.flownet_c_core, nets.multiscale_loss against `gt` (NaN = no ground truth).
-    P: {name: fp32 tensor}; img0 / img1: raw [N, 3, H, W]; gt: [N, 2, H, W].
+PREFIX = {"C": "", "S": "", "SD": "netsd_", "fusion": "fuse_"}      # parameter-name prefix of each core (nets.init_params_flownet2 tables)
+
+
+def train_reference(kind, P, inputs, gt, device=None, mean=0.43, masks=None, dtype=torch.float64):
+    """loss (float) and {parameter name: float64 gradient on the CPU} of one training step of a FlowNet core, evaluated on torch's own
+    operators in `dtype`:
+      * "C": inputs = (img0, img1) raw [N, 3, H, W] 0..255, pre-processed im / 255 - mean, nets.flownet_c_core + nets.multiscale_loss --
+        exactly as bench.py --mode train states the step;
+      * "S": inputs = (x,) the [N, 6 | 12, H, W] blob nets.flownet_s_core reads (pre-processed), nets.multiscale_loss on its flow dict;
+      * "SD" / "fusion": inputs = (x,) the [N, 6 | 11, H, W] blob of nets.flownet_sd_core / nets.fusion_core.  These return their FINAL flow
+        only (SD: 1/4 resolution in units of SD_FLOW_SCALE px; fusion: full resolution in pixels), so the loss is ONE
+        L1Loss{l2_per_location, normalize_by_num_entries} against Downsample(gt * scale) at that flow's size (nets.final_flow_loss,
+        scale = nets.FINAL_FLOW_GT_SCALE[kind]).  Every parameter still gets a gradient: the coarser predict_flow heads feed the finer
+        levels through the upsample_flow deconvolutions and the refinement Concats.
+    P: {name: fp32 tensor}; SD / fusion read the netsd_ / fuse_ entries (nets.init_params_flownet2) through nets._Prefixed, the others take
+    P as it is.  Gradients are keyed by the full parameter name.  gt: [N, 2, H, W] in pixels (NaN = no ground truth).
     masks = record_relu_branches(...).branches of another run: every leaky ReLU takes the branch recorded there instead of the sign of
-    its own input (y = x * (1 | slope) by the recorded mask): the fp64 value and gradient of the piecewise-linear function that run evaluated.
+    its own input (y = x or x * slope by the recorded mask): the fp64 value and gradient of the piecewise-linear function that run evaluated.
     dtype = torch.float32 turns the same torch graph into the LIBRARY-fp32 yardstick (torch's fp32 conv2d / conv_transpose2d = MIOpen on the
     GPU box, none of the product's kernels): how far a stock fp32 implementation sits from the fp64 graph on the same inputs."""
     import torch.nn.functional as F
     from flownet2_amd import nets
-    dev = torch.device(device) if device is not None else img0.device
-    P64 = {k: v.detach().to(device=dev, dtype=dtype).requires_grad_(True) for k, v in P.items()}
-    i0, i1 = (im.detach().to(device=dev, dtype=dtype) for im in (img0, img1))
+    assert kind in PREFIX, kind
+    prefix = PREFIX[kind]
+    dev = torch.device(device) if device is not None else inputs[0].device
+    P64 = {k: v.detach().to(device=dev, dtype=dtype).requires_grad_(True) for k, v in P.items() if k.startswith(prefix)}
+    ins = [t.detach().to(device=dev, dtype=dtype) for t in inputs]
     g = gt.detach().to(device=dev, dtype=dtype)
     be = backend64()
-    pre = [(im * (1.0 / 255.0)) - mean for im in (i0, i1)]
+    Pc = nets._Prefixed(P64, prefix) if prefix else P64
     lr, oc, od = F.leaky_relu, nets._conv, nets._deconv
     todo = dict(masks) if masks is not None else None          # by layer name ("relu": the correlation's): the two runs may order them differently
     if masks is not None:
@@ -222,16 +238,32 @@ def flownetc_train_reference(P, img0, img1, gt, device=None, mean=0.43, masks=No
         name = current[0] or "relu"
         m = todo.pop(name)
         assert tuple(m.shape) == tuple(x.shape), (name, tuple(m.shape), tuple(x.shape))
-        return x * torch.where(m.to(x.device), 1.0, float(negative_slope)).to(x.dtype)
+        # leaky_relu's own formula on the recorded branch (a factor tensor from torch.where(m, 1.0, slope) would be float32: slope 0.1f)
+        return torch.where(m.to(x.device), x, x * float(negative_slope))
     if todo is not None:
         F.leaky_relu, nets._conv, nets._deconv = pinned, named(oc), named(od)
     try:
-        loss = nets.multiscale_loss(nets.flownet_c_core(P64, pre[0], pre[1], be), g, be)
+        if kind == "C":
+            assert len(ins) == 2, "C: inputs = (img0, img1)"
+            pre = [(im * (1.0 / 255.0)) - mean for im in ins]
+            loss = nets.multiscale_loss(nets.flownet_c_core(Pc, pre[0], pre[1], be), g, be)
+        else:
+            assert len(ins) == 1, "%s: inputs = (x,)" % kind
+            if kind == "S":
+                loss = nets.multiscale_loss(nets.flownet_s_core(Pc, ins[0], be), g, be)
+            else:
+                core = nets.flownet_sd_core if kind == "SD" else nets.fusion_core
+                loss = nets.final_flow_loss(core(Pc, ins[0], be), g, be, nets.FINAL_FLOW_GT_SCALE[kind])
     finally:
         F.leaky_relu, nets._conv, nets._deconv = lr, oc, od
-    assert not todo, "recorded ReLU branches left over: the two graphs differ"
+    assert not todo, "recorded ReLU branches left over: the two graphs differ (%s)" % sorted(todo)
     loss.backward()
     return float(loss.detach()), {k: v.grad.detach().cpu() for k, v in P64.items() if v.grad is not None}
+
+
+def flownetc_train_reference(P, img0, img1, gt, device=None, mean=0.43, masks=None, dtype=torch.float64):
+    """train_reference("C", ...): the comparator of BASELINE config 4."""
+    return train_reference("C", P, (img0, img1), gt, device=device, mean=mean, masks=masks, dtype=dtype)
 
 
 def relu_sign_flips(branches_a, branches_b):

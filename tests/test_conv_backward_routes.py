@@ -7,8 +7,9 @@ operand, and matches fp64 (torch's convolution_backward); the three output forms
 into a channel slice of a sentinel-filled blob, a channel slice of top_diff) give the same bits.  Then the masked epilogue (ReLUBackward of
 the layer in front folded into the TCONV route), the weight gradients (a / b swap of a Deconvolution, channel slices, accumulate; the stem's
 fused weight + bias gradient), the autograd mirror (functional.conv_mfma_relu / deconv_gemm_relu with Concat-like blobs and the data-gradient
-pack cache across a fused optimizer step), and on the host: the case lists cover every route, and every layer of the FlowNetC training
-graph at 448x320 batch 8 has an own backward."""
+pack cache across a fused optimizer step), and on the host: the case lists cover every route, every layer of the FlowNetC training
+graph at 448x320 batch 8 has an own backward, and so has every layer of the FlowNetS / FlowNet-SD / fusion training graphs but the ones
+tests/test_train_parity_family.py allow-lists."""
 import ctypes as C
 
 import numpy as np
@@ -204,6 +205,74 @@ def test_flownetc_training_graph_has_an_own_backward_for_every_layer():
             assert ops.conv_backward_data_route(d, tr) != NONE, name
         assert ops.conv_backward_weights_supported(d, tr), name
     assert ops.conv_backward_weights_bias_fused(ops.conv_desc(*layers[0][2:]), False)
+
+
+def family_training_layers(case, B, H=320, W=448):
+    """(name, kind, N, Cin, Hb, Wb, Cout, k, s, p) of every Convolution / Deconvolution of the FlowNetS ("S6", "S12"), FlowNet-SD ("SD") and
+    fusion ("fusion") training graphs (tests/test_train_parity_family.py): FlowNetS from nets.layer_table like FlowNetC (one tower); SD and
+    fusion from their tables and the OUTPUT resolution divisor of every layer (nets._SD_RES / _FUSE_RES): a convolution's bottom is at
+    divisor / stride, a deconvolution's at twice its divisor."""
+    if case in ("S6", "S12"):
+        out, r, after_deconv = [], 1, False
+        for (name, kind, ci, co, k, s, p) in nets.layer_table("S", 6 if case == "S6" else 12):
+            if kind == "conv" and after_deconv:
+                r, after_deconv = r // 2, False
+            out.append((name, kind, B, ci, H // r, W // r, co, k, s, p))
+            if kind == "conv":
+                r *= s
+            else:
+                after_deconv = True
+        return out
+    table, res = (nets._SD_TABLE, nets._SD_RES) if case == "SD" else (nets._FUSE_TABLE, nets._FUSE_RES)
+    return [(name, kind, B, ci, H // (res[name] // s if kind == "conv" else 2 * res[name]), W // (res[name] // s if kind == "conv" else 2 * res[name]),
+             co, k, s, p) for (name, kind, ci, co, k, s, p) in table]
+
+
+def library_parts(layers):
+    """{layer: parts of its training step that no own kernel computes} by descriptor: "forward" (the library's autograd then computes both
+    gradients of the layer), else "data" (every layer but the first: its bottom is the input blob) and / or "weight"."""
+    L = _lib.lib()
+    gaps = {}
+    for i, (name, kind, n, ci, h, w, co, k, s, p) in enumerate(layers):
+        d = ops.conv_desc(n, ci, h, w, co, k, s, p)
+        tr = kind == "deconv"
+        if tr and ci == 2 and co == 2:           # upsample_flow*: the 2-channel head kernel, forward and backward (fn2_upsample_flow_deconv_*)
+            assert L.fn2_deconv_route(C.byref(d), 0) == 3, name
+            continue
+        if not tr and co == 2:                   # predict_flow*: the flow-head kernels (fn2_predict_flow_conv_*)
+            assert L.fn2_conv_route(C.byref(d), 0) == 5 and L.fn2_predict_flow_conv_backward_supported(n, ci, h, w) == 1, name
+            continue
+        # the forward a training graph runs: nets.conv_forward (stem / Winograd / small-map / direct) or, for a Deconvolution, deconv_gemm_relu
+        # (GEMM + col2im, or the small-map kernel: fn2_deconv_route's two routes; nets takes them from 64 input channels on)
+        if (L.fn2_deconv_route(C.byref(d), 0) in (1, 2) and ci >= 64) if tr else L.fn2_conv_route(C.byref(d), 0) != 0:
+            parts = tuple(part for part, ok in (("data", i == 0 or ops.conv_backward_data_route(d, tr) != NONE),
+                                                ("weight", ops.conv_backward_weights_supported(d, tr))) if not ok)
+        else:
+            parts = ("forward",)
+        if parts:
+            gaps[name] = parts
+    return gaps
+
+
+def test_family_training_graphs_have_an_own_backward_for_every_layer_but_the_allow_listed():
+    """FlowNetS (6 and 12 input channels), FlowNet-SD and the fusion net at the sizes of tests/test_train_parity_family.py: every layer has an
+    own forward, data-gradient (all but the first) and weight-gradient route, except the layers that file lists -- exactly those."""
+    from test_train_parity_family import CASES, LIBRARY_LAYERS
+    flops_of = {"S6": lambda H, W: nets.conv_flops("S", H, W, 6), "S12": lambda H, W: nets.conv_flops("S", H, W, 12),
+                "SD": lambda H, W: nets._table_flops(nets._SD_TABLE, nets._SD_RES, H, W),
+                "fusion": lambda H, W: nets._table_flops(nets._FUSE_TABLE, nets._FUSE_RES, H, W)}
+    found = {}
+    for case, (B, H, W) in CASES.items():
+        layers = family_training_layers(case, B, H, W)
+        flops = 0.0         # the derivation reproduces the layer sizes the FLOP model counts with
+        for (name, kind, n, ci, h, w, co, k, s, p) in layers:
+            if kind == "conv":
+                flops += 2.0 * n * ((h + 2 * p - k) // s + 1) * ((w + 2 * p - k) // s + 1) * co * ci * k * k
+            else:
+                flops += 2.0 * n * h * w * ci * co * k * k
+        assert flops == B * flops_of[case](H, W), case
+        found.update({(case, name): parts for name, parts in library_parts(layers).items()})
+    assert found == {key: parts for key, (parts, _why) in LIBRARY_LAYERS.items()}
 
 
 def test_weight_gradient_support_needs_16_channels_on_both_sides():
