@@ -150,12 +150,22 @@ __global__ void __launch_bounds__(kWarpGatherThreads) warp_bwd_gather(const floa
     auto add_source = [&](int sp) {
       const int sy = sp / W, sx = sp - sy * W;
       const WarpTap t = warp_taps(sx, sy, fl[sp], fl[wh + sp], H, W);
-      float w = 0.f;                       // taps of this source that land on this cell, TL..BR order
-#pragma unroll
-      for (int k = 0; k < 4; ++k) if (t.o[k] == pix) w += t.w[k];
       const float* gsrc = warped_diff + ((size_t)n * C + c0) * wh + sp;
+      float w = 0.f;                       // taps of this source that land on this cell, TL..BR order
+      int hits = 0;
+      bool zero = false;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) if (c0 + j < c1) acc[j] += gsrc[(size_t)j * wh] * w;
+      for (int k = 0; k < 4; ++k) if (t.o[k] == pix) { w += t.w[k]; ++hits; zero |= t.w[k] == 0.f; }
+      // a clamped right / bottom tap of weight 0 that coincides with a weighted one (last column / row): the reference adds it as
+      // a product of its own (:197-200), so an infinite g makes the cell NaN there; for a finite g that term is a zero
+      const bool zero_term = hits > 1 && zero;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (c0 + j < c1) {
+          const float gv = gsrc[(size_t)j * wh];
+          acc[j] += gv * w;
+          if (zero_term) acc[j] += gv * 0.f;
+        }
     };
     // collect the candidate sources: lists of the cells (y, x), (y, x-1), (y-1, x), (y-1, x-1)
     // (the four list heads are loaded together and the lists walked side by side: one memory latency per list LEVEL instead of one per

@@ -70,12 +70,17 @@ def correlation1d(b0: torch.Tensor, b1: torch.Tensor, pad, K, md, s1, s2, single
     return torch.stack(outs, 1)
 
 
-def flow_warp(image: torch.Tensor, flow: torch.Tensor, fill=0.0) -> torch.Tensor:
-    """Appendix A.3: bilinear sample at (x+u, y+v), right/bottom neighbour clamped, fill outside."""
+def flow_warp(image: torch.Tensor, flow: torch.Tensor, fill=0.0, fp32_positions=False) -> torch.Tensor:
+    """Appendix A.3: bilinear sample at (x+u, y+v), right/bottom neighbour clamped, fill outside.
+    fp32_positions: x + u and y + v are rounded to fp32 first, as flow_warp_layer.cu:73-74 does; everything after that
+    stays in image.dtype (no gradient reaches the flow through the rounding)."""
     N, C, H, W = image.shape
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=image.dtype), torch.arange(W, dtype=image.dtype), indexing="ij")
-    x2 = xs[None] + flow[:, 0]
-    y2 = ys[None] + flow[:, 1]
+    if fp32_positions:
+        x2, y2 = (t.to(image.dtype) for t in _positions_fp32(flow))
+    else:
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=image.dtype), torch.arange(W, dtype=image.dtype), indexing="ij")
+        x2 = xs[None] + flow[:, 0]
+        y2 = ys[None] + flow[:, 1]
     inb = (x2 >= 0) & (y2 >= 0) & (x2 < W) & (y2 < H)
     x2c = torch.where(inb, x2, torch.zeros_like(x2))
     y2c = torch.where(inb, y2, torch.zeros_like(y2))
@@ -93,6 +98,78 @@ def flow_warp(image: torch.Tensor, flow: torch.Tensor, fill=0.0) -> torch.Tensor
 
     out = (1 - a) * (1 - b) * g(yt, xl) + a * (1 - b) * g(yt, xr) + (1 - a) * b * g(yb, xl) + a * b * g(yb, xr)
     return torch.where(inb[:, None], out, torch.full_like(out, fill))
+
+
+def _positions_fp32(flow):
+    """x2 = fp32(x + u), y2 = fp32(y + v): the sample positions of flow_warp_layer.cu:73-74 (and :184-185), [N,H,W] each."""
+    f = torch.as_tensor(flow).detach().to(torch.float32)
+    H, W = f.shape[2:]
+    xs = torch.arange(W, dtype=torch.float32).view(1, 1, W)
+    ys = torch.arange(H, dtype=torch.float32).view(1, H, 1)
+    return xs + f[:, 0], ys + f[:, 1]
+
+
+def flow_warp_backward(image, flow, g, propagate_image=True, propagate_flow=True):
+    """fp64 statement of flow_warp_backward_kernel_no_smem (flow_warp_layer.cu:169-229).  Sample positions are rounded to fp32 as
+    the reference does (:184-185); everything after them is fp64.
+
+    image gradient: every in-image source pixel adds g * w_k to each of its four taps (:197-200), clamped right / bottom taps that
+                    coincide with another tap included (each is a term of its own: an infinite g on a tap of weight 0 gives NaN);
+    flow gradient:  du = sum_c g_c * (gy * (TR - TL) + (1 - gy) * (BR - BL)),  gy = iyB - y2   (:203-214)
+                    dv = sum_c g_c * (gx * (BL - TL) + (1 - gx) * (BR - TR)),  gx = ixR - x2   (:216-227)
+                    -- at the clamped last row / column this is the reference's formula, not the derivative of the forward;
+    pixels whose sample falls outside the image contribute nothing and get a flow gradient of 0.
+
+    Returns (di, df, di_abs, di_terms, df_abs, df_terms) as float64 tensors: the gradients, and for each element the fp64 sum of
+    the |terms| that were added into it and their number -- what an elementwise rounding-error bound needs.  In df_abs the factor
+    (1 - gy) counts as |1 - gy| + |gy| (and (1 - gx) likewise): fp32 forms it from gy, which is rounded by up to u|gy| when y2 is
+    just above an integer, so the absolute error of 1 - gy is not relative to its own size."""
+    image = torch.as_tensor(image).detach().to(torch.float64)
+    g = torch.as_tensor(g).detach().to(torch.float64)
+    N, C, H, W = image.shape
+    HW = H * W
+    x2, y2 = _positions_fp32(flow)
+    inb = (x2 >= 0) & (y2 >= 0) & (x2 < W) & (y2 < H)
+    x2 = torch.where(inb, x2.double(), torch.zeros((), dtype=torch.float64))
+    y2 = torch.where(inb, y2.double(), torch.zeros((), dtype=torch.float64))
+    xl, yt = x2.floor().long(), y2.floor().long()                     # (int) of a non-negative position
+    xr, yb = torch.clamp(xl + 1, max=W - 1), torch.clamp(yt + 1, max=H - 1)
+    a, b = x2 - xl, y2 - yt
+    zero = torch.zeros((), dtype=torch.float64)
+    mask = inb[:, None]
+
+    di = torch.zeros((N, C, HW), dtype=torch.float64)
+    di_abs = torch.zeros_like(di)
+    di_terms = torch.zeros((N, HW), dtype=torch.float64)
+    if propagate_image:
+        for yy, xx, w in ((yt, xl, (1 - a) * (1 - b)), (yt, xr, a * (1 - b)), (yb, xl, (1 - a) * b), (yb, xr, a * b)):
+            idx = (yy * W + xx).reshape(N, HW)
+            term = torch.where(mask, g * w[:, None], zero).reshape(N, C, HW)     # where, not *: an outside g never reaches a cell
+            ic = idx[:, None].expand(N, C, HW)
+            di.scatter_add_(2, ic, term)
+            di_abs.scatter_add_(2, ic, term.abs())
+            di_terms.scatter_add_(1, idx, inb.reshape(N, HW).double())
+    di_terms = di_terms[:, None].expand(N, C, HW)
+
+    df = torch.zeros((N, 2, H, W), dtype=torch.float64)
+    df_abs = torch.zeros_like(df)
+    df_terms = torch.zeros_like(df)
+    if propagate_flow:
+        flat = image.reshape(N, C, HW)
+
+        def tap(yy, xx):
+            return torch.gather(flat, 2, (yy * W + xx).reshape(N, 1, HW).expand(N, C, HW)).reshape(N, C, H, W)
+
+        TL, TR, BL, BR = tap(yt, xl), tap(yt, xr), tap(yb, xl), tap(yb, xr)
+        gy = (yb - y2)[:, None]
+        gx = (xr - x2)[:, None]
+        for k, (gk, d0, d1) in enumerate(((gy, TR - TL, BR - BL), (gx, BL - TL, BR - TR))):
+            # g * (t0 + t1) as the reference groups it (:207-211): an infinite g meets the channel's temp once
+            df[:, k] = torch.where(mask, g * (gk * d0 + (1 - gk) * d1), zero).sum(1)
+            # fp32 gy = iyB - y2 is rounded (by up to u|gy|) before 1 - gy is formed from it: the second factor counts |1-gy| + |gy|
+            df_abs[:, k] = torch.where(mask, g.abs() * (gk.abs() * d0.abs() + ((1 - gk).abs() + gk.abs()) * d1.abs()), zero).sum(1)
+            df_terms[:, k] = torch.where(inb, 2.0 * C, 0.0)
+    return (di.reshape(N, C, H, W), df, di_abs.reshape(N, C, H, W), di_terms.reshape(N, C, H, W), df_abs, df_terms)
 
 
 def _tri(t):
