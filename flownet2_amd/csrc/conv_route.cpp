@@ -3,8 +3,10 @@
 // The reference has one ConvolutionLayer / DeconvolutionLayer for every geometry (im2col + GEMM per sample: conv_layer.cu:8-23,
 // deconv_layer.cu:8-26, base_conv_layer.cpp:255-396); this library has a kernel family per geometry class (direct 5x5/2 .. 7x7/2 and 1x1,
 // Winograd F(2x2,3x3), the small-map kernel with its deterministic K split, the Deconvolution as GEMM + col2im or as parity classes).
-// Which one serves a layer is decided HERE, from the descriptor alone -- the Python mirror (flownet2_amd/functional.py) and the Caffe
-// adapter (csrc/caffe_adapter) ask the same function, so a Caffe user of libflownet2_hip.so gets the routing the benchmarks ran with.
+// Which one serves a layer is decided HERE, from the descriptor alone -- the Python mirror (flownet2_amd/functional.py: conv_mfma_relu,
+// deconv_relu, conv_backward) and the Caffe adapter (csrc/caffe_adapter) make the same call sequence, forward and backward: route -> pack
+// (once per weight version) -> workspace -> one dispatch call.  Python holds no routing rule and no per-family dispatch of its own, so a
+// Caffe user of libflownet2_hip.so gets the routing, the operands and the kernels the tests and the benchmarks ran with.
 // The thresholds are measurements: profiles/r02_conv_bench_*.txt, r04_conv_plane_bench_flownetc.txt, scripts/probes/small_layer_routes.py.
 #include "fn2_common.hpp"
 

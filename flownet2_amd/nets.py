@@ -95,38 +95,23 @@ def _conv_routed(x, P, name, stride, pad, act, backend):
 
 
 def conv_forward(x, w, b, stride, pad, act, backend, slope=None, relu_chain=None):
-    """Convolution{w, stride, pad} + bias (+ ReLU{NEG_SLOPE} when act) on explicit tensors: the routing every graph of this file and the
-    Convolution layer of the prototxt executor (flownet2_amd.layers.ConvolutionLayer) share -- same kernels, same bits."""
-    P = {"x.w": w, "x.b": b}
-    name = "x"
+    """Convolution{w, stride, pad} + bias (+ ReLU{NEG_SLOPE} when act) on explicit tensors: the call every graph of this file and the
+    Convolution layer of the prototxt executor (flownet2_amd.layers.ConvolutionLayer) share -- same kernels, same bits.  The backend routes
+    (functional.conv_mfma_relu: the library's fn2_conv_route); what it declines is the counted library convolution's."""
     slope = NEG_SLOPE if slope is None else slope
+    y = None
+    if backend is not None and hasattr(backend, "conv_mfma_relu"):
+        y = backend.conv_mfma_relu(x, w, b, stride, pad, slope, act, relu_chain=relu_chain)
+    if y is not None:
+        _LAST_ROUTE[0] = "fn2 %s" % backend.conv_route_name(x.shape, w, stride, pad, act) if _TRACE_CONV and hasattr(backend, "conv_route_name") else "own kernel"
+        return y
+    if relu_chain is not None:
+        raise RuntimeError("relu_chain: no own kernel takes this layer (its consumer was told the stem kernel would)")
     _LAST_ROUTE[0] = "library conv2d"
-    if w.shape[2] == 7 and w.shape[1] % 4 == 0 and backend is not None and hasattr(backend, "conv_mfma_relu"):
-        # the 12-channel stems of FlowNet2's stacked nets are whole channel quads: the direct MFMA kernel does them in one pass
-        # (the register-resident stem kernel needs two passes with partial sums through memory)
-        y = backend.conv_mfma_relu(x, w, P[name + ".b"], stride, pad, slope, act)
-        if y is not None:
-            _LAST_ROUTE[0] = "fn2 MFMA conv"
-            return y
-    if act and stride == 2 and pad == 3 and w.shape[2] == 7 and backend is not None and hasattr(backend, "conv_k7s2_relu"):
-        y = (backend.conv_k7s2_relu(x, w, P[name + ".b"], slope) if relu_chain is None      # conv1 + ReLU1 in one kernel (csrc/conv_stem.hip)
-             else backend.conv_k7s2_relu(x, w, P[name + ".b"], slope, relu_chain=relu_chain))
-        if y is None and relu_chain is not None:
-            raise RuntimeError("relu_chain: the stem kernel does not take this layer (its consumer was told it would)")
-        if y is not None:
-            _LAST_ROUTE[0] = "stem kernel"
-            return y
-    if relu_chain is not None and _LAST_ROUTE[0] != "stem kernel":
-        raise RuntimeError("relu_chain: only the stem layer is a chain producer on this route")
-    if w.shape[2] in (1, 3, 5) and backend is not None and hasattr(backend, "conv_mfma_relu"):
-        y = backend.conv_mfma_relu(x, w, P[name + ".b"], stride, pad, slope, act)    # Winograd / direct MFMA convolution (1x1: a plain MFMA GEMM), bias + ReLU fused
-        if y is not None:
-            _LAST_ROUTE[0] = "fn2 MFMA conv"
-            return y
     conv2d = getattr(backend, "lib_conv2d", None) or (lambda xx, ww, bb, s, p: F.conv2d(xx, ww, bb, stride=s, padding=p))
     if act and backend is not None and hasattr(backend, "conv_bias_leaky_relu"):
-        return backend.conv_bias_leaky_relu(conv2d(x, w, None, stride, pad), P[name + ".b"], slope)
-    y = conv2d(x, w, P[name + ".b"], stride, pad)
+        return backend.conv_bias_leaky_relu(conv2d(x, w, None, stride, pad), b, slope)
+    y = conv2d(x, w, b, stride, pad)
     return F.leaky_relu(y, slope) if act else y
 
 
@@ -142,41 +127,22 @@ def _const(device, values):
     return _CONSTS[key]
 
 
-_WT_CACHE: Dict[int, tuple] = {}      # id(weight tensor) -> (weak reference to it, its _version, transposed copy)
-
-
-def _transposed_deconv_weight(w):
-    """weight [Cin, Cout, 4, 4] -> [Cout*16, Cin] contiguous (the A operand of the deconvolution GEMM).  Cached per
-    parameter tensor OBJECT (the entry dies with the tensor, so a new tensor that reuses the id or the storage address
-    never sees it) and rebuilt when the tensor is modified in place (torch bumps `_version`) or -- for a tensor that requires
-    grad -- when an optimizer has stepped since (functional._cached: fused optimizers write without touching `_version`)."""
-    from . import functional as Fn
-    return Fn._cached(_WT_CACHE, id(w), w, lambda: w.detach().reshape(w.shape[0], w.shape[1] * 16).t().contiguous())
-
-
 def _deconv(x, P, name, act=True, backend=None):
     return deconv_forward(x, P[name + ".w"], P[name + ".b"], act, backend)
 
 
 def deconv_forward(x, w, b, act=True, backend=None, slope=None):
-    """Deconvolution{4, 2, 1} + bias (+ ReLU): the routing shared with flownet2_amd.layers.DeconvolutionLayer."""
-    P = {"x.w": w, "x.b": b}
-    name = "x"
+    """Deconvolution{4, 2, 1} + bias (+ ReLU): the call shared with flownet2_amd.layers.DeconvolutionLayer.  The backend routes
+    (functional.deconv_relu: the library's fn2_deconv_route); what it declines is the counted library deconvolution's."""
     slope = NEG_SLOPE if slope is None else slope
-    if act and backend is not None and hasattr(backend, "deconv_mfma_relu") and w.shape[0] >= 64:
-        y = backend.deconv_mfma_relu(x, w, P[name + ".b"], slope, True)      # one MFMA kernel, a parity class per wave (csrc/conv_plane.hip)
-        if y is not None:
-            return y
-    if act and backend is not None and hasattr(backend, "deconv_gemm_relu") and w.shape[0] >= 64:
-        training = torch.is_grad_enabled() and (w.requires_grad or x.requires_grad)
-        y = backend.deconv_gemm_relu(x, None if training else _transposed_deconv_weight(w), P[name + ".b"], w.shape[1], 4, 2, 1, slope,
-                                     weight=w)
+    if backend is not None and hasattr(backend, "deconv_relu"):
+        y = backend.deconv_relu(x, w, b, slope, act)
         if y is not None:
             return y
     deconv2d = getattr(backend, "lib_conv_transpose2d", None) or (lambda xx, ww, bb, s, p: F.conv_transpose2d(xx, ww, bb, stride=s, padding=p))
     if act and backend is not None and hasattr(backend, "conv_bias_leaky_relu"):
-        return backend.conv_bias_leaky_relu(deconv2d(x, P[name + ".w"], None, 2, 1), P[name + ".b"], slope)
-    y = deconv2d(x, P[name + ".w"], P[name + ".b"], 2, 1)
+        return backend.conv_bias_leaky_relu(deconv2d(x, w, None, 2, 1), b, slope)
+    y = deconv2d(x, w, b, 2, 1)
     return F.leaky_relu(y, slope) if act else y
 
 
@@ -196,8 +162,7 @@ def _conv_into_concat(x, P, name, stride, pad, extra_channels, backend, relu_cha
         k = w.shape[2]
         ho, wo = (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1
         blob = torch.empty((x.shape[0], w.shape[0] + extra_channels, ho, wo), device=x.device, dtype=x.dtype)
-        y = (backend.conv_mfma_relu(x, w, P[name + ".b"], stride, pad, NEG_SLOPE, True, out=blob, out_c0=0) if relu_chain is None
-             else backend.conv_mfma_relu(x, w, P[name + ".b"], stride, pad, NEG_SLOPE, True, out=blob, out_c0=0, relu_chain=relu_chain))
+        y = backend.conv_mfma_relu(x, w, P[name + ".b"], stride, pad, NEG_SLOPE, True, out=blob, out_c0=0, relu_chain=relu_chain)
         if y is not None:
             return blob, (y if (training and y.requires_grad) else blob[:, :w.shape[0]])
     if relu_chain is not None:
@@ -219,15 +184,7 @@ def _any_requires_grad(P) -> bool:
 def _stage_deconv(P, x, dname, blob, cs, cd, backend, allow_copy=True):
     """ReLU(deconv(x)) written into channels [cs, cs + cd) of a refinement stage's Concat blob.  Returns what the kernel wrapper
     returned (with autograd: the slice view that carries the graph), or None after the copy fallback."""
-    d = None
-    w = P[dname + ".w"]
-    training = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)
-    if hasattr(backend, "deconv_mfma_relu"):
-        d = backend.deconv_mfma_relu(x, w, P[dname + ".b"], NEG_SLOPE, True, out=blob, out_c0=cs)
-    if d is None and hasattr(backend, "deconv_gemm_relu") and w.shape[0] >= 64:
-        # GEMM (weight^T x bottom), then our col2im + bias + ReLU pass straight into the blob
-        d = backend.deconv_gemm_relu(x, None if training else _transposed_deconv_weight(w), P[dname + ".b"], cd, 4, 2, 1, NEG_SLOPE,
-                                     weight=w if training else None, out=blob, out_c0=cs)
+    d = backend.deconv_relu(x, P[dname + ".w"], P[dname + ".b"], NEG_SLOPE, True, out=blob, out_c0=cs) if hasattr(backend, "deconv_relu") else None
     if d is None and allow_copy:
         blob[:, cs:cs + cd].copy_(_deconv(x, P, dname, backend=backend))
     return d
@@ -311,12 +268,13 @@ def _stem_chain(P, x, backend):
     gradient (the transposed 5x5 / 2 convolution) and conv1's bias gradient comes out of its weight-gradient kernel: no pass over the largest
     activation of the net (147 MB at batch 8 @448x320: read twice, written once) between the two.  Returns the (producer, consumer) handles
     for the two layers, or (None, None)."""
-    if not (RELU_CHAIN[0] and CONCAT_IN_PLACE_TRAINING[0] and torch.is_grad_enabled() and x.is_cuda and hasattr(backend, "relu_chain_supported")):
+    if not (RELU_CHAIN[0] and CONCAT_IN_PLACE_TRAINING[0] and torch.is_grad_enabled() and x.is_cuda and hasattr(backend, "relu_chain_supported")
+            and hasattr(backend, "conv_route_name")):
         return None, None
     w1, w2 = P["conv1.w"], P["conv2.w"]
     if not (w1.requires_grad and w2.requires_grad and P["conv1.b"].requires_grad) or x.requires_grad:
         return None, None
-    if w1.shape[2] != 7 or w1.shape[1] % 4 == 0 or x.shape[3] % 8 != 0:       # (conv1 must take the stem kernel: whole blobs)
+    if backend.conv_route_name(x.shape, w1, 2, 3) != "stem":                  # (conv1 must take the stem kernel: whole blobs)
         return None, None
     c1_shape = (x.shape[0], w1.shape[0], (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1)
     if not backend.relu_chain_supported(c1_shape, w2, 2, 2):

@@ -488,21 +488,23 @@ def conv_k7s2_relu_forward(x, weight, bias=None, negative_slope=0.1):
     return out
 
 
-CONV_ROUTES = {0: None, 1: "direct", 2: "wino", 3: "plane", 4: None, 5: None}     # 4 / 5: stem / flow head -- the graphs call those kernels by name (conv_k7s2_relu, predict_flow_conv)
+CONV_ROUTE_NONE, CONV_ROUTE_DIRECT, CONV_ROUTE_WINOGRAD, CONV_ROUTE_PLANE, CONV_ROUTE_STEM, CONV_ROUTE_HEAD = range(6)        # FN2_CONV_ROUTE_*
+DECONV_ROUTE_NONE, DECONV_ROUTE_GEMM, DECONV_ROUTE_PLANE, DECONV_ROUTE_HEAD = range(4)        # FN2_DECONV_ROUTE_*
+CONV_FWD_ROUTES = {0: None, 1: "direct", 2: "wino", 3: "plane", 4: "stem", 5: "head"}
+DECONV_FWD_ROUTES = {0: None, 1: "gemm", 2: "plane", 3: "head"}
+CONV_ROUTES = {0: None, 1: "direct", 2: "wino", 3: "plane", 4: None, 5: None}     # conv_route(): the three general families only (4 / 5: stem / flow head)
 DECONV_ROUTES = {0: None, 1: "gemm", 2: "plane", 3: None}      # 3: the 2-channel upsample_flow head (upsample_flow_deconv)
 
 
 def conv_route(N, Cin, Hin, Win, Cout, kernel, stride, pad, force=False):
     """Which kernel family the LIBRARY picks for Convolution{kernel, stride, pad} Cin -> Cout on [N, Cin, Hin, Win] (fn2_conv_route,
     csrc/conv_route.cpp -- the same decision the Caffe adapter gets): "wino", "plane", "direct" or None."""
-    d = _lib.ConvDesc(int(N), int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad))
-    return CONV_ROUTES[int(_lib.lib().fn2_conv_route(C.byref(d), 1 if force else 0))]
+    return CONV_ROUTES[conv_forward_route(conv_desc(N, Cin, Hin, Win, Cout, kernel, stride, pad), force)]
 
 
 def deconv_route(N, Cin, Hin, Win, Cout, kernel=4, stride=2, pad=1):
     """fn2_deconv_route: "gemm" (weight^T x bottom on the 1x1 kernel + col2im), "plane" (parity classes, small maps) or None."""
-    d = _lib.ConvDesc(int(N), int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad))
-    return DECONV_ROUTES[int(_lib.lib().fn2_deconv_route(C.byref(d), 0))]
+    return DECONV_ROUTES[deconv_forward_route(conv_desc(N, Cin, Hin, Win, Cout, kernel, stride, pad))]
 
 
 BWD_ROUTES = {0: None, 1: "wino", 2: "tconv", 3: "plane", 4: "direct", 5: "deconv_plane"}
@@ -511,6 +513,64 @@ BWD_ROUTES = {0: None, 1: "wino", 2: "tconv", 3: "plane", 4: "direct", 5: "decon
 def conv_desc(N, Cin, Hin, Win, Cout, kernel, stride, pad):
     """fn2_conv_desc: bottom [N, Cin, Hin, Win] of a Convolution{kernel, stride, pad} (Cin -> Cout) or of a Deconvolution{4, 2, 1}."""
     return _lib.ConvDesc(int(N), int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad))
+
+
+def conv_forward_route(desc, force=False) -> int:
+    """Which own kernel serves the forward pass of this Convolution (fn2_conv_route; 0 = none, names: CONV_FWD_ROUTES)."""
+    return int(_lib.lib().fn2_conv_route(C.byref(desc), 1 if force else 0))
+
+
+def deconv_forward_route(desc) -> int:
+    """Which own kernel serves the forward pass of this Deconvolution{4, 2, 1} (fn2_deconv_route; 0 = none, names: DECONV_FWD_ROUTES)."""
+    return int(_lib.lib().fn2_deconv_route(C.byref(desc), 0))
+
+
+def conv_pack_weights(weight, desc, route, transposed=False):
+    """The layer's weight blob ([Cout, Cin, k, k]; Deconvolution: [Cin, Cout, 4, 4]) -> the operand its forward kernel reads
+    (fn2_conv_pack_weights / fn2_deconv_pack_weights: once per weight update)."""
+    w = _chk(weight, "weight")
+    L = _lib.lib()
+    floats, pack = (L.fn2_deconv_packed_weight_floats, L.fn2_deconv_pack_weights) if transposed else (L.fn2_conv_packed_weight_floats, L.fn2_conv_pack_weights)
+    n = int(floats(C.byref(desc), int(route)))
+    k = desc.kernel
+    if n == 0 or tuple(w.shape) != ((desc.Cin, desc.Cout, k, k) if transposed else (desc.Cout, desc.Cin, k, k)):
+        raise ValueError("conv_pack_weights: route %d has no operand for a weight of shape %s" % (route, tuple(w.shape)))
+    packed = torch.empty(n, device=w.device, dtype=torch.float32)
+    check(pack(C.byref(desc), int(route), _ptr(w), _ptr(packed), _stream()))
+    return packed
+
+
+def conv_forward(x, packed, bias, desc, route, transposed=False, relu=True, negative_slope=0.1, out=None, out_c0=0, in_c0=0):
+    """act(Convolution(x[:, in_c0:in_c0+Cin]) + bias) -> out[:, out_c0:out_c0+Cout] (a new blob if out is None) on the kernel `route` names
+    (fn2_conv_forward; transposed: the Deconvolution{4, 2, 1}, top 2H x 2W, fn2_deconv_forward).  packed = conv_pack_weights(weight, desc,
+    route, transposed).  Returns the top blob."""
+    x = _chk(x, "bottom[0]")
+    N, Ctot, H, W = x.shape
+    k, s, p = desc.kernel, desc.stride, desc.pad
+    if (N, H, W) != (desc.N, desc.Hin, desc.Win) or in_c0 < 0 or in_c0 + desc.Cin > Ctot:
+        raise ValueError(f"conv_forward: bottom blob {tuple(x.shape)} does not hold the layer's [{desc.N},{desc.Cin},{desc.Hin},{desc.Win}] at channel {in_c0}")
+    Ho, Wo = (2 * H, 2 * W) if transposed else ((H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1)
+    if out is None:
+        out = torch.empty((N, desc.Cout, Ho, Wo), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, "top[0]")
+        if not out.is_contiguous() or out.shape[0] != N or tuple(out.shape[2:]) != (Ho, Wo) or out_c0 < 0 or out_c0 + desc.Cout > out.shape[1]:
+            raise ValueError(f"conv_forward: top blob {tuple(out.shape)} does not match [{N},>={out_c0 + desc.Cout},{Ho},{Wo}]")
+    b = _chk(bias, "bias", ndim=1) if bias is not None else None
+    pw = _chk(packed, "packed weight", ndim=None)
+    L = _lib.lib()
+    if pw.numel() != int((L.fn2_deconv_packed_weight_floats if transposed else L.fn2_conv_packed_weight_floats)(C.byref(desc), int(route))):
+        raise ValueError("conv_forward: the operand has %d floats, not what route %d reads for this layer" % (pw.numel(), route))
+    need = int((L.fn2_deconv_workspace_bytes if transposed else L.fn2_conv_workspace_bytes)(C.byref(desc), int(route)))
+    if transposed and route == DECONV_ROUTE_GEMM:
+        # the column matrix lives for this call only (the per-stream scratch never shrinks: it would pin the largest one for good)
+        ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
+    else:
+        ws = _plane_workspace(x.device, need) if need else None         # the K-split scratch of the small-map routes
+    check((L.fn2_deconv_forward if transposed else L.fn2_conv_forward)(
+        C.byref(desc), int(route), _ptr(x), Ctot, int(in_c0), _ptr(pw), _ptr(b), _ptr(out), out.shape[1], int(out_c0),
+        int(bool(relu)), C.c_float(float(negative_slope)), _ptr(ws), need, _stream()))
+    return out
 
 
 def conv_backward_data_route(desc, transposed=False) -> int:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-variant timing of the small-map deconvolution kernel (csrc/conv_plane.hip, MODE 1) on the refinement layers, next to the GEMM +
-col2im route (functional.deconv_gemm_relu) and the library's transposed convolution.
+col2im route (ops.conv_forward on FN2_DECONV_ROUTE_GEMM) and the library's transposed convolution.
     python scripts/deconv_bench.py [--net C|2] [--layers deconv5,...] [--ksplit 1,2,4]"""
 import argparse
 import os
@@ -12,7 +12,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import flownet2_amd  # noqa: E402
-from flownet2_amd import functional as Fn, nets, ops  # noqa: E402
+from flownet2_amd import functional as Fn, ops  # noqa: E402
 
 LAYERS = {"C": [("deconv5", 8, 1024, 5, 7, 512), ("deconv4", 8, 1026, 10, 14, 256), ("deconv3", 8, 770, 20, 28, 128), ("deconv2", 8, 386, 40, 56, 64)],
           "2": [("deconv5", 4, 1024, 6, 12, 512), ("deconv4", 4, 1026, 12, 24, 256), ("deconv3", 4, 770, 24, 48, 128), ("deconv2", 4, 386, 48, 96, 64)]}
@@ -48,8 +48,11 @@ def main():
         gf = 2.0 * N * H * W * Cin * Cout * 16 / 1e9
         want = F.leaky_relu(F.conv_transpose2d(x, w, b, stride=2, padding=1), 0.1)
         t_lib = timeit(lambda: Fn.conv_bias_leaky_relu(F.conv_transpose2d(x, w, None, stride=2, padding=1), b, 0.1), a.iters)
-        wt = nets._transposed_deconv_weight(w)
-        t_gemm = timeit(lambda: Fn.deconv_gemm_relu(x, wt, b, Cout), a.iters)
+        desc = ops.conv_desc(N, Cin, H, W, Cout, 4, 2, 1)
+        t_gemm = float("nan")
+        if ops.conv_mfma_supported(Cin, H, W, Cout * 16, 1, 1, 0):
+            pg = ops.conv_pack_weights(w, desc, ops.DECONV_ROUTE_GEMM, True)
+            t_gemm = timeit(lambda: ops.conv_forward(x, pg, b, desc, ops.DECONV_ROUTE_GEMM, True), a.iters)
         print(f"{name:8s} [{N},{Cin},{H},{W}]->{Cout}  {gf:6.2f} GF | MIOpen+bias/act {t_lib:7.1f} us {gf / t_lib * 1e3:6.1f} TF | GEMM+col2im {t_gemm:7.1f} us {gf / t_gemm * 1e3:6.1f} TF",
               flush=True)
         if not ops.deconv_plane_supported(N, Cin, H, W, Cout):

@@ -14,7 +14,7 @@ g = torch.Generator(device="cuda").manual_seed(1)
 a = torch.rand(B, 3, H, W, device="cuda", generator=g); b = torch.rand(B, 3, H, W, device="cuda", generator=g)
 gt = torch.randn(B, 2, H, W, device="cuda", generator=g)
 
-NAMES = ["conv_mfma_relu", "conv_k7s2_relu", "deconv_gemm_relu", "deconv_mfma_relu", "predict_flow_conv", "upsample_flow_deconv", "correlation",
+NAMES = ["conv_mfma_relu", "deconv_relu", "predict_flow_conv", "upsample_flow_deconv", "correlation",
          "conv_bias_leaky_relu", "l1_loss_multi", "downsample"]
 rec = None
 

@@ -26,9 +26,9 @@ def record(log):
                 if name == "conv_mfma_relu" and k.get("out") is not None:       # written into a Concat blob: only its own channel slice is defined yet
                     c0 = k.get("out_c0", 0)
                     t = t[:, c0:c0 + a[1].shape[0]]
-                if name in ("deconv_gemm_relu", "upsample_flow_deconv") and k.get("out") is not None:
+                if name in ("deconv_relu", "upsample_flow_deconv") and k.get("out") is not None and t.shape[1] == k["out"].shape[1]:
                     c0 = k.get("out_c0", 0)
-                    t = t[:, c0:c0 + (a[3] if name == "deconv_gemm_relu" else 2)]
+                    t = t[:, c0:c0 + a[1].shape[1]]
                 log.append((label_of(a, k), t.detach().clone()))
             return r
         setattr(mod, name, g)
@@ -36,8 +36,7 @@ def record(log):
     wrap(nets, "_conv_routed", lambda a, k: "conv " + a[2])
     wrap(nets, "_deconv", lambda a, k: "deconv " + a[2])
     wrap(nets, "_conv_into_concat", lambda a, k: "conv_into " + a[2])
-    for nm in ("correlation", "flow_warp", "resample", "channel_norm", "predict_flow_conv", "upsample_flow_deconv", "deconv_gemm_relu", "conv_gemm_relu",
-               "conv_mfma_relu", "conv_k7s2_relu"):
+    for nm in ("correlation", "flow_warp", "resample", "channel_norm", "predict_flow_conv", "upsample_flow_deconv", "deconv_relu", "conv_mfma_relu"):
         wrap(Fn, nm, lambda a, k, nm=nm: nm + " " + "x".join(str(v) for v in a[0].shape))
     return saved
 

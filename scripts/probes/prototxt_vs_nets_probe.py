@@ -22,14 +22,14 @@ def record(log):
             r = f(*a, **k)
             if torch.is_tensor(r):
                 t = r
-                if k.get("out") is not None:
+                if k.get("out") is not None and r.shape[1] == k["out"].shape[1]:
                     c0 = k.get("out_c0", 0)
-                    n = a[1].shape[0] if name == "conv_mfma_relu" else (a[3] if name == "deconv_gemm_relu" else 2)
+                    n = a[1].shape[0] if name == "conv_mfma_relu" else a[1].shape[1]      # (a Deconvolution blob is [Cin, Cout, 4, 4])
                     t = r[:, c0:c0 + n]
                 log.append((name + " " + "x".join(str(v) for v in a[0].shape), t.detach().clone()))
             return r
         setattr(mod, name, g)
-    for nm in ("conv_mfma_relu", "conv_k7s2_relu", "conv_gemm_relu", "deconv_gemm_relu", "predict_flow_conv", "upsample_flow_deconv", "lib_conv2d",
+    for nm in ("conv_mfma_relu", "deconv_relu", "predict_flow_conv", "upsample_flow_deconv", "lib_conv2d",
                "lib_conv_transpose2d", "correlation", "correlation_relu_into", "resample", "flow_warp", "channel_norm", "scale_shift"):
         wrap(Fn, nm)
     return saved

@@ -55,7 +55,7 @@ for name, N, Cin, H, W, Cout, k, s, p in (B4 if "--b4" in sys.argv else C8 if "-
     b = torch.randn(Cout, device="cuda", generator=g) * 0.1
     gf = 2.0 * N * Cout * ((H + 2 * p - k) // s + 1) * ((W + 2 * p - k) // s + 1) * Cin * k * k / 1e9
     with torch.no_grad():
-        kind = Fn._conv_mfma_pick(x, w, s, p)
+        kind = ops.conv_route(N, Cin, H, W, Cout, k, s, p)
         t_own = timeit(lambda: Fn.conv_mfma_relu(x, w, b, s, p, 0.1, True))
         if k == 3:
             t_lib = timeit(lambda: lib_gemm_conv(x, w, b, s, p))
@@ -70,7 +70,9 @@ for name, N, Cin, H, W, Cout, k, s, p in (B4 if "--b4" in sys.argv else C8 if "-
                     continue
                 if alt == "direct" and not ops.conv_mfma_supported(Cin, H, W, Cout, k, s, p):
                     continue
-                alts[alt] = timeit(lambda: Fn._conv_mfma_run(alt, x, w, b, s, p, 0.1, True))
+                desc, route = ops.conv_desc(N, Cin, H, W, Cout, k, s, p), {"direct": ops.CONV_ROUTE_DIRECT, "wino": ops.CONV_ROUTE_WINOGRAD, "plane": ops.CONV_ROUTE_PLANE}[alt]
+                pk = ops.conv_pack_weights(w, desc, route)
+                alts[alt] = timeit(lambda: ops.conv_forward(x, pk, b, desc, route))
             except flownet2_amd.Fn2Error:
                 pass
         ks_txt = ""

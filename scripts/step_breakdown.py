@@ -69,8 +69,8 @@ def main():
         return "%-12s %-20s k%ds%d %7.2f GF  %s" % (name, tuple(x.shape), w.shape[2], args[3], gf, "into concat blob" if y[0] is not None else "-> " + nets._LAST_ROUTE[0])
 
     nets._conv_into_concat = timed(into_label, nets._conv_into_concat)
-    Fn.deconv_mfma_relu = timed(lambda args, k, y: "%-12s %-20s -> %d  %s" % ("deconv_mfma", tuple(args[0].shape), args[1].shape[1], "own kernel" if y is not None else "(declined)"),
-                                Fn.deconv_mfma_relu)
+    Fn.deconv_relu = timed(lambda args, k, y: "%-12s %-20s -> %d  %s" % ("deconv_relu", tuple(args[0].shape), args[1].shape[1], "own kernel" if y is not None else "(declined)"),
+                           Fn.deconv_relu)
     for nm in ("predict_flow_conv", "upsample_flow_deconv", "correlation_relu_into", "resample", "flow_warp", "channel_norm"):
         if hasattr(Fn, nm):
             setattr(Fn, nm, timed(lambda args, k, y, nm=nm: "%-12s %s" % (nm, tuple(args[0].shape)), getattr(Fn, nm)))

@@ -6,7 +6,7 @@ the weight blob (rotation, channel swap, Cp padding); the result equals, bit for
 operand, and matches fp64 (torch's convolution_backward); the three output forms (room for the Cp computed channels, the workspace + 2-D copy
 into a channel slice of a sentinel-filled blob, a channel slice of top_diff) give the same bits.  Then the masked epilogue (ReLUBackward of
 the layer in front folded into the TCONV route), the weight gradients (a / b swap of a Deconvolution, channel slices, accumulate; the stem's
-fused weight + bias gradient), the autograd mirror (functional.conv_mfma_relu / deconv_gemm_relu with Concat-like blobs and the data-gradient
+fused weight + bias gradient), the autograd mirror (functional.conv_mfma_relu / deconv_relu with Concat-like blobs and the data-gradient
 pack cache across a fused optimizer step), and on the host: the case lists cover every route, every layer of the FlowNetC training
 graph at 448x320 batch 8 has an own backward, and so has every layer of the FlowNetS / FlowNet-SD / fusion training graphs but the ones
 tests/test_train_parity_family.py allow-lists."""
@@ -231,6 +231,7 @@ def family_training_layers(case, B, H=320, W=448):
 def library_parts(layers):
     """{layer: parts of its training step that no own kernel computes} by descriptor: "forward" (the library's autograd then computes both
     gradients of the layer), else "data" (every layer but the first: its bottom is the input blob) and / or "weight"."""
+    from flownet2_amd import functional as Fn
     L = _lib.lib()
     gaps = {}
     for i, (name, kind, n, ci, h, w, co, k, s, p) in enumerate(layers):
@@ -242,9 +243,9 @@ def library_parts(layers):
         if not tr and co == 2:                   # predict_flow*: the flow-head kernels (fn2_predict_flow_conv_*)
             assert L.fn2_conv_route(C.byref(d), 0) == 5 and L.fn2_predict_flow_conv_backward_supported(n, ci, h, w) == 1, name
             continue
-        # the forward a training graph runs: nets.conv_forward (stem / Winograd / small-map / direct) or, for a Deconvolution, deconv_gemm_relu
-        # (GEMM + col2im, or the small-map kernel: fn2_deconv_route's two routes; nets takes them from 64 input channels on)
-        if (L.fn2_deconv_route(C.byref(d), 0) in (1, 2) and ci >= 64) if tr else L.fn2_conv_route(C.byref(d), 0) != 0:
+        # the forward a training graph runs: functional.conv_mfma_relu (stem / Winograd / small-map / direct) or, for a Deconvolution,
+        # deconv_relu (GEMM + col2im, or the small-map kernel) -- the library's route minus what those two decline
+        if (Fn.deconv_forward_route(d) if tr else Fn.conv_forward_route(d)) != NONE:
             parts = tuple(part for part, ok in (("data", i == 0 or ops.conv_backward_data_route(d, tr) != NONE),
                                                 ("weight", ops.conv_backward_weights_supported(d, tr))) if not ok)
         else:
@@ -273,6 +274,32 @@ def test_family_training_graphs_have_an_own_backward_for_every_layer_but_the_all
         assert flops == B * flops_of[case](H, W), case
         found.update({(case, name): parts for name, parts in library_parts(layers).items()})
     assert found == {key: parts for key, (parts, _why) in LIBRARY_LAYERS.items()}
+
+
+def test_forward_routes_python_declines_although_the_library_has_one():
+    """functional.conv_forward_route / deconv_forward_route = the library's route minus a fixed list of layers (the graphs send those to
+    the flow-head entry points or to the counted library call): pinned here, independently of library_parts, which asks the same functions."""
+    from flownet2_amd import functional as Fn
+    L = _lib.lib()
+    dec = ops.conv_desc(2, 64, 10, 14, 32, 4, 2, 1)
+    assert L.fn2_deconv_route(C.byref(dec), 0) == 1 and Fn.deconv_forward_route(dec) == 1
+    assert Fn.deconv_forward_route(dec, act=False) == NONE                                   # a Deconvolution without ReLU
+    small = ops.conv_desc(2, 32, 10, 14, 32, 4, 2, 1)
+    assert L.fn2_deconv_route(C.byref(small), 0) == 1 and Fn.deconv_forward_route(small) == NONE        # fewer than 64 input channels
+    up = ops.conv_desc(2, 2, 10, 14, 2, 4, 2, 1)
+    assert L.fn2_deconv_route(C.byref(up), 0) == 3 and Fn.deconv_forward_route(up, act=False) == NONE == Fn.deconv_forward_route(up)      # HEAD
+    stem = ops.conv_desc(2, 3, 64, 128, 64, 7, 2, 3)
+    assert L.fn2_conv_route(C.byref(stem), 0) == 4 and Fn.conv_forward_route(stem) == 4
+    assert Fn.conv_forward_route(stem, act=False) == NONE and Fn.conv_forward_route(stem, whole_blobs=False) == NONE      # the stem: ReLU, whole blobs
+    head = ops.conv_desc(2, 194, 20, 28, 2, 3, 1, 1)
+    assert L.fn2_conv_route(C.byref(head), 0) == 5 and Fn.conv_forward_route(head) == NONE and Fn.conv_forward_route(head, act=False) == NONE
+    k4 = ops.conv_desc(2, 64, 16, 24, 64, 4, 2, 1)                                            # the direct kernel on 4x4 taps, 7x7 off channel quads
+    assert L.fn2_conv_route(C.byref(k4), 0) == 1 and Fn.conv_forward_route(k4) == NONE
+    k7 = ops.conv_desc(2, 3, 64, 100, 64, 7, 2, 3)
+    assert L.fn2_conv_route(C.byref(k7), 0) == 1 and Fn.conv_forward_route(k7) == NONE
+    quad = ops.conv_desc(2, 12, 64, 128, 64, 7, 2, 3)
+    assert L.fn2_conv_route(C.byref(quad), 0) == 1 and Fn.conv_forward_route(quad) == 1 and Fn.conv_forward_route(quad, act=False) == 1
+    assert Fn.conv_route_name((2, 3, 64, 128), torch.empty(64, 3, 7, 7), 2, 3) == "stem"
 
 
 def test_weight_gradient_support_needs_16_channels_on_both_sides():
@@ -501,7 +528,7 @@ def test_stem_fused_weight_and_bias_gradient(case):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# GPU: through autograd (functional.conv_mfma_relu / deconv_gemm_relu), output into a Concat-like blob, upstream gradient a channel slice
+# GPU: through autograd (functional.conv_mfma_relu / deconv_relu), output into a Concat-like blob, upstream gradient a channel slice
 
 AUTOGRAD = ["wino-odd-batch", "tconv-5x5-c128", "deconv-plane-10x14", "plane-5x7", "direct-1x1", "plane-deconv", "direct-deconv"]
 
@@ -510,7 +537,7 @@ def own_forward(name, x, w, b, blob, c0):
     from flownet2_amd import functional as Fn
     route, tr, N, Cin, H, W, Cout, k, s, p = DGRAD[name]
     if tr:
-        return Fn.deconv_gemm_relu(x, None, b, Cout, 4, 2, 1, 0.1, weight=w, out=blob, out_c0=c0)
+        return Fn.deconv_relu(x, w, b, 0.1, True, out=blob, out_c0=c0)
     return Fn.conv_mfma_relu(x, w, b, s, p, 0.1, True, out=blob, out_c0=c0)
 
 

@@ -616,7 +616,7 @@ def test_hip_packed_operand_of_a_strided_view_equals_the_oracle_bitwise():
 
 
 def test_small_conv_and_gemm_deconv_paths_match_library_convolutions():
-    """functional.conv_mfma_relu on a small map (the layers that went to im2col + a library GEMM until round 4) and deconv_gemm_relu
+    """functional.conv_mfma_relu on a small map (the layers that went to im2col + a library GEMM until round 4) and deconv_relu
     (own 1x1 MFMA kernel + our col2im pass) vs MIOpen's direct kernels; no call leaves the own kernels."""
     from flownet2_amd import functional as Fn
     x, w, b = dev(rand((2, 64, 10, 14), 64)), dev(rand((128, 64, 3, 3), 65, 0.05)), dev(rand((128,), 66))
@@ -631,21 +631,28 @@ def test_small_conv_and_gemm_deconv_paths_match_library_convolutions():
     assert Fn.LIBRARY_FALLBACKS[0] == before
     wd = dev(rand((64, 32, 4, 4), 67, 0.05)); bd = dev(rand((32,), 68))
     ref = torch.nn.functional.leaky_relu(torch.nn.functional.conv_transpose2d(x, wd, bd, stride=2, padding=1), 0.1)
-    got = Fn.deconv_gemm_relu(x, wd.reshape(64, 32 * 16).t().contiguous(), bd, 32)
+    got = Fn.deconv_relu(x, wd, bd)
     assert_close(host(got), host(ref), 1e-5, "deconv via GEMM + col2im")
 
 
-def test_deconv_weight_cache_follows_the_parameter():
-    """nets caches the transposed deconvolution weight per tensor object and rebuilds it after in-place updates."""
-    from flownet2_amd import nets
-    w = dev(rand((64, 8, 4, 4), 70))
-    t0 = nets._transposed_deconv_weight(w)
-    assert nets._transposed_deconv_weight(w) is t0
+def test_deconv_weight_cache_follows_the_parameter(monkeypatch):
+    """functional caches the packed deconvolution operand per tensor object and rebuilds it after in-place updates."""
+    from flownet2_amd import functional as Fn
+    packs, pack = [], ops.conv_pack_weights
+    monkeypatch.setattr(ops, "conv_pack_weights", lambda w, *a, **k: packs.append(w.clone()) or pack(w, *a, **k))
+    ref = lambda w: torch.nn.functional.leaky_relu(torch.nn.functional.conv_transpose2d(x, w, b, stride=2, padding=1), 0.1)
+    x, w, b = dev(rand((2, 64, 10, 14), 69)), dev(rand((64, 32, 4, 4), 70, 0.05)), dev(rand((32,), 72))
+    y0 = Fn.deconv_relu(x, w, b)
+    assert len(packs) == 1 and torch.equal(Fn.deconv_relu(x, w, b), y0) and len(packs) == 1       # packed once, reused
+    assert_close(host(y0), host(ref(w)), 1e-5, "deconv")
     w.mul_(2.0)
-    t1 = nets._transposed_deconv_weight(w)
-    assert t1 is not t0 and torch.equal(t1, w.reshape(64, 128).t())
-    w2 = dev(rand((64, 8, 4, 4), 71))
-    assert torch.equal(nets._transposed_deconv_weight(w2), w2.reshape(64, 128).t())
+    y1 = Fn.deconv_relu(x, w, b)
+    assert len(packs) == 2 and torch.equal(packs[1], w) and not torch.equal(y1, y0)             # rebuilt from the written tensor
+    assert_close(host(y1), host(ref(w)), 1e-5, "deconv after an in-place update")
+    w2 = dev(rand((64, 32, 4, 4), 71, 0.05))
+    y2 = Fn.deconv_relu(x, w2, b)
+    assert len(packs) == 3 and torch.equal(packs[2], w2)                                          # another tensor object: its own pack
+    assert_close(host(y2), host(ref(w2)), 1e-5, "deconv, second weight")
 
 
 @pytest.mark.parametrize("case", [((2, 2, 320, 448), (5, 7)), ((1, 2, 320, 448), (10, 14)), ((1, 3, 97, 130), (3, 4))])
