@@ -22,6 +22,34 @@ bool valid(const fn2_conv_desc* d) {
          d->Hin + 2 * d->pad >= d->kernel && d->Win + 2 * d->pad >= d->kernel;
 }
 
+// Does the kernel family `route` names take this layer?  Not "is it the route fn2_conv_route returns": that depends on the flags and on
+// batch-invariant mode, and a caller may pack for one answer and run after the mode changed.  What must never happen is a family function
+// that takes no kernel / stride argument (Winograd: 3x3 / 1; the heads) running a layer of another geometry into a top blob of another size.
+bool conv_route_applies(const fn2_conv_desc* d, int route) {
+  const int k = d->kernel, s = d->stride, p = d->pad;
+  switch (route) {
+    case FN2_CONV_ROUTE_WINOGRAD: return k == 3 && s == 1 && fn2_conv_wino_supported(d->Cin, d->Hin, d->Win, d->Cout, p) != 0;
+    case FN2_CONV_ROUTE_PLANE:
+      return k == 3 ? fn2_conv_plane_supported(d->N, d->Cin, d->Hin, d->Win, d->Cout, s, p) != 0
+                    : (k == 5 && s == 2 && p == 2 && fn2_conv_plane_k_supported(d->N, d->Cin, d->Hin, d->Win, d->Cout, 5, 2, 2) != 0);
+    case FN2_CONV_ROUTE_DIRECT: return fn2_conv_mfma_supported(d->Cin, d->Hin, d->Win, d->Cout, k, s, p) != 0;
+    case FN2_CONV_ROUTE_STEM: return k == 7 && s == 2 && p == 3 && fn2_conv_k7s2_relu_supported(d->Cin, d->Hin, d->Win, d->Cout) != 0;
+    case FN2_CONV_ROUTE_HEAD: return k == 3 && s == 1 && p == 1 && d->Cout == 2;
+    default: return false;
+  }
+}
+
+bool deconv_route_applies(const fn2_conv_desc* d, int route) {
+  if (d->kernel != 4 || d->stride != 2 || d->pad != 1) return false;
+  switch (route) {
+    case FN2_DECONV_ROUTE_GEMM:
+      return (d->Cout * 16) % 32 == 0 && (d->Hin * d->Win) % 4 == 0 && fn2_conv_mfma_supported(d->Cin, d->Hin, d->Win, d->Cout * 16, 1, 1, 0) != 0;
+    case FN2_DECONV_ROUTE_PLANE: return fn2_deconv_plane_supported(d->N, d->Cin, d->Hin, d->Win, d->Cout) != 0;
+    case FN2_DECONV_ROUTE_HEAD: return d->Cin == 2 && d->Cout == 2;
+    default: return false;
+  }
+}
+
 }  // namespace
 
 FN2_API int fn2_conv_route(const fn2_conv_desc* d, int flags) {
@@ -89,6 +117,12 @@ FN2_API int fn2_conv_forward(const fn2_conv_desc* d, int route, const float* bot
                              const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
                              int relu, float negative_slope, void* workspace, size_t workspace_bytes, void* stream) {
   if (!valid(d)) return fn2::fail(FN2_ERR_INVALID_ARG, "conv_forward: bad descriptor");
+  if (!conv_route_applies(d, route))
+    return fn2::fail(FN2_ERR_UNSUPPORTED, "conv_forward: no own kernel for Convolution{kernel %d, stride %d, pad %d} %d -> %d on %d x %d (route %d)",
+                     d->kernel, d->stride, d->pad, d->Cin, d->Cout, d->Hin, d->Win, route);
+  if (!bottom || !packed_weight || !top) return fn2::fail(FN2_ERR_INVALID_ARG, "conv_forward: NULL blob");
+  if (bottom_c0 < 0 || bottom_c0 + d->Cin > bottom_channels || top_c0 < 0 || top_c0 + d->Cout > top_channels)
+    return fn2::fail(FN2_ERR_INVALID_ARG, "conv_forward: channel slice outside its blob");
   switch (route) {
     case FN2_CONV_ROUTE_WINOGRAD:
       return fn2_conv_wino_forward(bottom, packed_weight, bias, top, d->N, d->Cin, d->Hin, d->Win, bottom_channels, bottom_c0, d->Cout, top_channels,
@@ -167,6 +201,12 @@ FN2_API int fn2_deconv_forward(const fn2_conv_desc* d, int route, const float* b
                                const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
                                int relu, float negative_slope, void* workspace, size_t workspace_bytes, void* stream) {
   if (!valid(d)) return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_forward: bad descriptor");
+  if (!deconv_route_applies(d, route))
+    return fn2::fail(FN2_ERR_UNSUPPORTED, "deconv_forward: no own kernel for Deconvolution{kernel %d, stride %d, pad %d} %d -> %d on %d x %d (route %d)",
+                     d->kernel, d->stride, d->pad, d->Cin, d->Cout, d->Hin, d->Win, route);
+  if (!bottom || !packed_weight || !top) return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_forward: NULL blob");
+  if (bottom_c0 < 0 || bottom_c0 + d->Cin > bottom_channels || top_c0 < 0 || top_c0 + d->Cout > top_channels)
+    return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_forward: channel slice outside its blob");
   if (route == FN2_DECONV_ROUTE_GEMM) {
     if (!workspace || workspace_bytes < fn2_deconv_workspace_bytes(d, route))
       return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_forward: workspace of %zu bytes needed for the column matrix", fn2_deconv_workspace_bytes(d, route));

@@ -8,7 +8,7 @@
 //   * GEMM view: M = output positions (16 consecutive x of one row), N = 16 output channels, K = (c, ky, kx);
 //     a wave owns ONE N tile and keeps its whole weight slice in registers (14 VGPRs per input channel);
 //   * K order (c, ky, kx padded to 8): k-step = (c, ky, half h), lane group kk <-> kx = 4h + kk, so every A operand
-//     is one ds_read_b32 at  lane base + immediate;  the 8th tap has weight 0;
+//     is one ds_read_b32 at  lane base + immediate;  the 8th tap has weight 0 and reads as 0;
 //   * the input rows of a workgroup (2 RB + 5 rows x CIN channels x (32 tiles + 8) columns) are staged once by 16-byte
 //     LDS-DMA in natural pixel order; out-of-image rows / columns come back 0 from the buffer descriptor = zero padding;
 //   * the MFMA result layout gives every lane 4 consecutive x of one output channel: bias + leaky ReLU + one 16-byte store;
@@ -107,8 +107,13 @@ conv_k7s2_relu(const float* __restrict__ in, const float* __restrict__ weight, c
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-          for (int u = 0; u < NTL; ++u)
-            acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(r0[c * CS + ky * RS + 4 * h + 32 * u], w[c][ky][h], acc[u], 0, 0, 0);
+          for (int u = 0; u < NTL; ++u) {
+            // the 8th tap (h = 1, kk = 3) is one column right of the window: its weight is 0, and its A operand must be 0 too -- 0 x NaN and
+            // 0 x Inf are NaN, and the reference never reads that pixel (finite inputs: 0 x a = +-0 either way, no bit changes)
+            float av = r0[c * CS + ky * RS + 4 * h + 32 * u];
+            if (h == 1) av = kk == 3 ? 0.f : av;
+            acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, w[c][ky][h], acc[u], 0, 0, 0);
+          }
     float* orow = out + (((size_t)n * a.Cout + co0 + nn) * a.Hout + y) * a.Wout;
 #pragma unroll
     for (int u = 0; u < NTL; ++u) {

@@ -37,9 +37,11 @@ def test_oracle_exports_cpu_twins():
             # (tile-variant hooks; ksplit is a launch-geometry query whose value the twins take as an argument)
             continue
         if name in ("fn2_conv_route", "fn2_deconv_route", "fn2_conv_forward", "fn2_deconv_forward") or name.startswith(("fn2_conv_pack", "fn2_deconv_pack", "fn2_conv_backward_data", "fn2_conv_backward_weights")):
-            # descriptor-level dispatchers (csrc/conv_route.cpp): no twins of their own -- every kernel they route to has its twin, and
-            # tests/test_conv_backward_routes.py pins what they add (operand packing, Cp padding, channel slices, masked epilogue, a / b roles)
-            # route by route against those twins bit for bit and against fp64
+            # descriptor-level dispatchers (csrc/conv_route.cpp): no twins of their own -- every kernel they route to has its twin, and two
+            # files pin what the dispatchers add, route by route, against those twins bit for bit and against fp64:
+            # tests/test_conv_forward_routes.py the forward half (fn2_conv_route / fn2_deconv_route, the forward pack functions, fn2_conv_forward /
+            # fn2_deconv_forward: operands, the GEMM view, flags, channel slices, refusals), tests/test_conv_backward_routes.py the backward half
+            # (operand packing, Cp padding, channel slices, masked epilogue, a / b roles)
             continue
         if name.startswith("fn2_hdf5_"):
             # the HDF5 file format is libhdf5's (a third-party dependency of the reference, absent from its tree): the reader is pinned on
