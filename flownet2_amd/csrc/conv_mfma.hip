@@ -20,22 +20,12 @@
 //     global_load_dwordx{MW} per lane straight into registers, prefetched NBUFA - 1 k-steps ahead; no LDS for weights.
 //   * wave tile = MW channel groups x NP patches (MW * NP accumulator tiles), workgroup = WM x WNX x WNY waves.
 //   * epilogue: the MFMA result layout hands every lane 4 consecutive x of one output channel: bias + leaky ReLU + 16-byte store.
-#include "fn2_common.hpp"
-#include "autotune.hpp"
-
-#include <mutex>
-#include <type_traits>
-#include <unordered_map>
+#include "mfma_tile.hpp"
 
 namespace fn2 {
 namespace cv {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
-
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
-constexpr int up_mod(int v, int r, int m) { return v + ((r - v % m) + m) % m; }   // smallest >= v with == r (mod m)
+using namespace mfma;
 
 struct Args {
   const float* in; const float* wp; const float* bias; float* out;
@@ -54,54 +44,21 @@ struct Args {
 // P16 (1x1 kernels only): the M tile is 16 CONSECUTIVE pixels of one row instead of a 4x4 patch -- the launcher flattens every plane into
 // one row of H * W pixels (a 1x1 convolution has no spatial window), so no tile hangs over an image edge: the plain-GEMM form.
 template <int KS_, int S_, int MW_, int NP_, int WM_, int WNX_, int WNY_, int CQ_, int P16_ = 0, int PIN_ = 0>
-struct Cfg {
+struct Cfg : Window<((P16_ ? 1 : 4) * WNY_ - 1) * S_ + KS_,                  // window rows per channel: (TH - 1) * S + KS
+                    ((P16_ ? 16 : 4) * NP_ * WNX_ - 1) * S_ + KS_ + 4,       // window columns incl. the left margin (pad <= PADL): (TW - 1) * S + KS + PADL
+                    CQ_, WM_ * WNX_ * WNY_> {
   static constexpr int KS = KS_, S = S_, MW = MW_, NP = NP_, WM = WM_, WNX = WNX_, WNY = WNY_, CQ = CQ_, P16 = P16_;
   static constexpr int PIN = PIN_;      // 1: operand reads pinned one behind each patch's MFMAs, a k-step ahead (else the compiler's order)
   static constexpr int NW = WM * WNX * WNY, THREADS = 64 * NW;
   static constexpr int PADL = 4;                                     // window columns left of S * x0 (16-byte aligned start)
   static constexpr int TW = (P16 ? 16 : 4) * NP * WNX, TH = (P16 ? 1 : 4) * WNY;   // output pixels of a workgroup tile
   static_assert(!P16 || (KS == 1 && S == 1), "row tiles are for 1x1 kernels");
-  static constexpr int WR = (TH - 1) * S + KS;                       // window rows per channel
-  static constexpr int WC = (TW - 1) * S + KS + PADL;                // window columns incl. the left margin (pad <= PADL)
-  static constexpr int RS = up_mod(cdiv(WC, 4) * 4, 4, 16);          // row stride (dwords)
-  static constexpr int CS = up_mod(WR * RS, 16, 32);                 // channel stride
-  static constexpr int SLOTS_C = CS / 4;                             // 16-byte slots per channel
-  static constexpr int SLOTS = 4 * CQ * SLOTS_C;                     // per chunk
-  static constexpr int NRUN = cdiv(SLOTS, 64);                       // 1 KiB LDS-DMA runs per chunk
-  static constexpr int RPW = cdiv(NRUN, NW);                         // runs per wave
-  static constexpr int BUF = NRUN * 256;                             // dwords per window buffer (whole runs)
+  static_assert(Cfg::WR == (TH - 1) * S + KS && Cfg::WC == (TW - 1) * S + KS + PADL, "window of the tile");
   static constexpr int KSC = CQ * KS * KS;                           // k-steps per chunk
-  static constexpr int NBUFA = (KSC % 6 == 0) ? 6 : (KSC % 5 == 0) ? 5 : (KSC % 7 == 0) ? 7 : (KSC % 4 == 0) ? 4 : 3;   // weight-operand ring
+  static constexpr int NBUFA = ring_depth(KSC);                      // weight-operand ring
   static_assert(KSC % NBUFA == 0, "ring phase must repeat per chunk");
-  static_assert(2 * BUF * 4 <= 160 * 1024, "LDS");
+  static_assert(2 * Cfg::BUF * 4 <= 160 * 1024, "LDS");
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int MW> struct WVec;
-template <> struct WVec<1> { using T = float; };
-template <> struct WVec<2> { using T = f32x2; };
-template <> struct WVec<4> { using T = f32x4; };
-
-template <int MW>
-__device__ __forceinline__ float wget(const typename WVec<MW>::T& v, int j) {
-  if constexpr (MW == 1) return v; else return v[j];
-}
-
-// LDS-DMA of one chunk's window: run r = i * NW + wave -> 1 KiB at dst + 1024 r (a __device__ function, not a lambda: the
-// host pass of a __global__ template cannot see the amdgcn builtins inside a lambda body)
-template <class K>
-__device__ __forceinline__ void stage_chunk(__amdgpu_buffer_rsrc_t rs, const unsigned (&voff)[K::RPW], unsigned dst, int wave, unsigned soff) {
-#pragma unroll
-  for (int i = 0; i < K::RPW; ++i) {
-    const int r = i * K::NW + wave;
-    if (r < K::NRUN)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(uintptr_t)(dst + 1024u * (unsigned)r), 16, voff[i], soff, 0, 0);
-  }
-}
 
 // One workgroup tile: channel group g (of 16 * MW * WM channels), pixel tile (bx, by) of sample n.
 template <class K>
@@ -116,22 +73,9 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
 
   // ---- LDS-DMA plan: run r = i * NW + wave, slot s = 64 r + lane -> (channel, window row, group of 4 columns)
   const size_t plane = (size_t)a.Hin * a.Win;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.in + ((size_t)n * a.in_ctot + a.in_c0) * plane), 0, (unsigned)(4u * a.Cin * plane), 0x00020000);
-  constexpr unsigned OOB = 0x7ffffff0u;
+  const __amdgpu_buffer_rsrc_t rs = nchw_rsrc(a.in, n, a.in_ctot, a.in_c0, a.Cin, plane);
   unsigned voff[K::RPW];
-#pragma unroll
-  for (int i = 0; i < K::RPW; ++i) {
-    const int s = (i * K::NW + wave) * 64 + lane;
-    voff[i] = OOB;
-    if (s < K::SLOTS) {
-      const int c = s / K::SLOTS_C, rem = s % K::SLOTS_C;
-      const int row = rem / (K::RS / 4), gq = rem % (K::RS / 4);
-      const int yi = S * y0 - a.pad + row, xi = S * x0 - K::PADL + 4 * gq;
-      if (row < K::WR && 4 * gq < K::WC && yi >= 0 && yi < a.Hin && xi >= 0 && xi < a.Win)
-        voff[i] = 4u * (unsigned)(c * plane + (size_t)yi * a.Win + xi);
-    }
-  }
+  window_plan<K>(voff, wave, lane, S * y0 - a.pad, S * x0 - K::PADL, a.Hin, a.Win, plane);
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
   const unsigned chunk_bytes = 4u * 4u * K::CQ * (unsigned)plane;
   auto stage = [&](int chunk, int buf) { stage_chunk<K>(rs, voff, lds_base + 4u * (unsigned)(buf * K::BUF), wave, (unsigned)chunk * chunk_bytes); };
@@ -143,8 +87,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
   using WV = typename WVec<MW>::T;
   // packed weights: [Cout/64][ksteps][64 lanes][4]; this wave's channel groups: 16 * MW * (g * WM + wm) ...
   const int cg0 = (g * K::WM + wm) * MW;                      // first 16-channel group of this wave
-  const float* wl = a.wp + ((size_t)(cg0 / 4) * a.ksteps * 64 + lane) * 4 + (cg0 % 4);
-  auto wload = [&](int ks) -> WV { return *reinterpret_cast<const WV*>(wl + (size_t)ks * 256); };
+  const float* wl = weight_lane(a.wp, cg0, a.ksteps, lane);
 
   f32x4 acc[MW][NP];
 #pragma unroll
@@ -155,7 +98,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
   WV wreg[K::NBUFA];
   stage(0, 0);
 #pragma unroll
-  for (int i = 0; i < K::NBUFA - 1; ++i) wreg[i] = wload(i);
+  for (int i = 0; i < K::NBUFA - 1; ++i) wreg[i] = weight_load<MW>(wl, i);
 
   for (int c = 0; c < a.nchunks; ++c) {
     const int buf = c & 1;
@@ -178,7 +121,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < K::KSC; ++ks) {
-        wreg[(ks + K::NBUFA - 1) % K::NBUFA] = wload(ks0 + ks + K::NBUFA - 1);
+        wreg[(ks + K::NBUFA - 1) % K::NBUFA] = weight_load<MW>(wl, ks0 + ks + K::NBUFA - 1);
         const WV w = wreg[ks % K::NBUFA];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
@@ -191,7 +134,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
     } else {
 #pragma unroll
     for (int ks = 0; ks < K::KSC; ++ks) {
-      wreg[(ks + K::NBUFA - 1) % K::NBUFA] = wload(ks0 + ks + K::NBUFA - 1);      // the packed array carries NBUFA spare k-steps
+      wreg[(ks + K::NBUFA - 1) % K::NBUFA] = weight_load<MW>(wl, ks0 + ks + K::NBUFA - 1);      // the packed array carries NBUFA spare k-steps
       const int cq = ks / (KS * KS), ky = (ks / KS) % KS, kx = ks % KS;
       float b[NP];
 #pragma unroll
@@ -217,26 +160,14 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         const int x = K::P16 ? x0 + 16 * (NP * wnx + p) + 4 * (lane >> 4) : x0 + 4 * (NP * wnx + p);
-        f32x4 v = acc[j][p];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float s = v[r] + bv;
-          if (a.relu) s = s > 0.f ? s : s * a.slope;
-          v[r] = s;
-        }
-        if (x + 3 < a.Wout) *reinterpret_cast<f32x4*>(orow + x) = v;
-        else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (x + r < a.Wout) orow[x + r] = v[r];
-        }
+        store_row4(orow, x, a.Wout, acc[j][p], bv, a.relu, a.slope);
       }
     }
   }
 }
 
-// Task list: (sample, tile row, tile column, channel group), channel group fastest, cut into 8 contiguous ranges, one per XCD
-// (block b runs on XCD b % 8): the workgroups that share an input window run next to each other on one XCD, whose L2 serves
-// the re-reads.
+// Task list: (sample, tile row, tile column, channel group), channel group fastest (the workgroups that share an input window are
+// neighbours: xcd_task)
 __device__ __forceinline__ void decode_tile(const Args& a, unsigned t, int& g, int& bx, int& by, int& n) {
   g = t % a.ng; t /= a.ng;
   bx = t % a.tx; t /= a.tx;
@@ -247,9 +178,8 @@ __device__ __forceinline__ void decode_tile(const Args& a, unsigned t, int& g, i
 template <class K>
 __global__ void __launch_bounds__(256, 2)
 conv_mfma(Args a) {
-  const unsigned per_xcd = (a.total + 7) / 8;
-  const unsigned t = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  if (blockIdx.x / 8 >= per_xcd || t >= a.total) return;
+  unsigned t;
+  if (!xcd_task(blockIdx.x, a.total, t)) return;
   int g, bx, by, n;
   decode_tile(a, t, g, bx, by, n);
   conv_body<K>(a, g, bx, by, n);
@@ -269,9 +199,8 @@ conv_mfma_tail(Args a) {
     decode_tile(a, t, g, bx, by, n);
     conv_body<K>(a, g, bx, by, n);
   } else {
-    const unsigned b = blockIdx.x - a.nbig, nsm = 2 * (a.total - a.nbig), per_xcd = (nsm + 7) / 8;
-    const unsigned u = (b % 8) * per_xcd + b / 8;
-    if (b / 8 >= per_xcd || u >= nsm) return;
+    unsigned u;
+    if (!xcd_task(blockIdx.x - a.nbig, 2 * (a.total - a.nbig), u)) return;
     decode_tile(a, a.nbig + u / 2, g, bx, by, n);
     conv_body<KH>(a, 2 * g + (int)(u & 1), bx, by, n);
   }
@@ -393,11 +322,7 @@ static int launch(const Args& base, hipStream_t st) {
   a.total = (unsigned)tiles_of(a); a.nbig = a.total;
   const unsigned grid = 8 * ((a.total + 7) / 8);
   constexpr size_t lds = sizeof(float) * 2 * K::BUF;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  set_dynamic_lds_once<&conv_mfma<K>>((int)lds);
   hipLaunchKernelGGL((conv_mfma<K>), dim3(grid), dim3(K::THREADS), lds, st, a);
   return check_launch("conv_mfma_forward");
 }
@@ -417,11 +342,7 @@ static int launch_tail(const Args& base, hipStream_t st) {
     const unsigned nsm = 2 * (a.total - a.nbig);
     const unsigned grid = a.nbig + 8 * ((nsm + 7) / 8);
     constexpr size_t lds = sizeof(float) * 2 * K::BUF;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_tail<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
+    set_dynamic_lds_once<&conv_mfma_tail<K>>((int)lds);
     hipLaunchKernelGGL((conv_mfma_tail<K>), dim3(grid), dim3(K::THREADS), lds, st, a);
     return check_launch("conv_mfma_forward");
   }
@@ -568,13 +489,11 @@ FN2_API int fn2_conv_mfma_forward(const float* bottom, const float* packed_weigh
                                   int relu, float negative_slope, void* stream) {
   if (N < 0) return fail(FN2_ERR_INVALID_ARG, "conv_mfma: bad batch");
   if (N == 0) return FN2_OK;
-  if (!bottom || !packed_weight || !top) return fail(FN2_ERR_INVALID_ARG, "conv_mfma: null blob");
-  if (!fn2_conv_mfma_supported(Cin, Hin, Win, Cout, kernel, stride, pad))
-    return fail(FN2_ERR_UNSUPPORTED, "conv_mfma: unsupported geometry (Cin %d, %dx%d, Cout %d, k %d s %d p %d)", Cin, Hin, Win, Cout, kernel, stride, pad);
-  if (bottom_c0 < 0 || bottom_c0 + Cin > bottom_channels || top_c0 < 0 || top_c0 + Cout > top_channels)
-    return fail(FN2_ERR_INVALID_ARG, "conv_mfma: channel slice outside the blob");
-  if (((reinterpret_cast<uintptr_t>(bottom) | reinterpret_cast<uintptr_t>(top) | reinterpret_cast<uintptr_t>(packed_weight)) & 15) != 0)
-    return fail(FN2_ERR_UNSUPPORTED, "conv_mfma: blobs must be 16-byte aligned");
+  if (const int rc = mfma::check_conv_args("conv_mfma", bottom, packed_weight, top, Cin, bottom_channels, bottom_c0, Cout, top_channels, top_c0, [&] {
+        return fn2_conv_mfma_supported(Cin, Hin, Win, Cout, kernel, stride, pad) ? FN2_OK
+            : fail(FN2_ERR_UNSUPPORTED, "conv_mfma: unsupported geometry (Cin %d, %dx%d, Cout %d, k %d s %d p %d)", Cin, Hin, Win, Cout, kernel, stride, pad);
+      }))
+    return rc;
   cv::Args a{};
   a.in = bottom; a.wp = packed_weight; a.bias = bias; a.out = top;
   a.N = N; a.Cin = Cin; a.Hin = Hin; a.Win = Win; a.in_ctot = bottom_channels; a.in_c0 = bottom_c0;
@@ -582,44 +501,15 @@ FN2_API int fn2_conv_mfma_forward(const float* bottom, const float* packed_weigh
   a.out_ctot = top_channels; a.out_c0 = top_c0; a.pad = pad;
   a.ksteps = cv::ksteps_for(Cin, kernel) + cv::kSpare;
   a.slope = negative_slope; a.relu = relu;
-  if ((a.Wout % 4) != 0 && ((size_t)a.Wout * sizeof(float)) % 16 != 0) { /* scalar tail stores handle it */ }
-  int best = -1;
-  bool tail = false;
-  if (cv::g_forced_variant >= 0) {
-    tail = cv::g_forced_variant >= 1000;
-    best = cv::g_forced_variant % 1000;
-    if (best >= cv::kNumVariants || !cv::variant_applies(cv::kVariants[best], a, kernel, stride) || (tail && !cv::kVariants[best].fn_tail))
-      return fail(FN2_ERR_UNSUPPORTED, "conv_mfma: forced variant %d does not apply", cv::g_forced_variant);
-  } else {
-    hipStream_t st = as_stream(stream);
-    int picked = -1;
-    if (autotune_enabled(st)) {
-      // candidates 2 i / 2 i + 1 = plain / split-tail launch of variant i; all of them write the same bits
-      static TuneCache cache("conv_mfma", cv::kNumVariants);
-      auto usable = [&](int c) -> bool {
-        const cv::Variant& v = cv::kVariants[c / 2];
-        return cv::variant_applies(v, a, kernel, stride) && (!(c & 1) || (v.fn_tail && cv::variant_cost(v, a, true) < 1e29));
-      };
-      const TuneKey key{N, Cin, Hin, Win, Cout, kernel, stride, pad, bottom_channels == Cin, top_channels == Cout};
-      picked = autotune_pick(cache, key, 2 * cv::kNumVariants, st, [&](int c) -> int {
-        const cv::Variant& v = cv::kVariants[c / 2];
-        if (!cv::variant_applies(v, a, kernel, stride)) return FN2_ERR_UNSUPPORTED;
-        if (c & 1) return (v.fn_tail && cv::variant_cost(v, a, true) < 1e29) ? v.fn_tail(a, st) : FN2_ERR_UNSUPPORTED;
-        return v.fn(a, st);
-      }, usable);
-    }
-    if (picked >= 0) { best = picked / 2; tail = (picked & 1) != 0; }
-    else {
-      double bc = 0;
-      for (int i = 0; i < cv::kNumVariants; ++i) {
-        if (!cv::variant_applies(cv::kVariants[i], a, kernel, stride)) continue;
-        for (int t = 0; t < (cv::kVariants[i].fn_tail ? 2 : 1); ++t) {
-          const double c = cv::variant_cost(cv::kVariants[i], a, t == 1);
-          if (best < 0 || c < bc) { best = i; bc = c; tail = t == 1; }
-        }
-      }
-    }
-  }
-  if (best < 0) return fail(FN2_ERR_UNSUPPORTED, "conv_mfma: no kernel variant for this geometry");
-  return tail ? cv::kVariants[best].fn_tail(a, as_stream(stream)) : cv::kVariants[best].fn(a, as_stream(stream));
+  hipStream_t st = as_stream(stream);
+  static TuneCache cache("conv_mfma", cv::kNumVariants);
+  const TuneKey key{N, Cin, Hin, Win, Cout, kernel, stride, pad, bottom_channels == Cin, top_channels == Cout};
+  mfma::Pick p;
+  if (const int rc = mfma::pick_variant(p, "conv_mfma", cv::g_forced_variant, cv::kNumVariants, true, cache, key, st,
+                                        [&](int i) { return cv::variant_applies(cv::kVariants[i], a, kernel, stride); },
+                                        [&](int i, bool tail) { return cv::variant_cost(cv::kVariants[i], a, tail); },
+                                        [&](int i, bool tail) { return tail ? cv::kVariants[i].fn_tail(a, st) : cv::kVariants[i].fn(a, st); },
+                                        [&](int i) { return cv::kVariants[i].fn_tail != nullptr; }))
+    return rc;
+  return p.tail ? cv::kVariants[p.variant].fn_tail(a, st) : cv::kVariants[p.variant].fn(a, st);
 }

@@ -30,18 +30,12 @@
 //     a k-ordered fma chain (channel quad, tap row, tap column, channel within the quad), the parts added in part order; part p
 //     covers the 2-quad units [p * U / ksplit, (p + 1) * U / ksplit), U = ceil(quads / 2) -- restated by the oracle twins
 //     fn2_conv_plane_forward_cpu / fn2_deconv_plane_forward_cpu.
-#include "fn2_common.hpp"
-#include "autotune.hpp"
+#include "mfma_tile.hpp"
 
 namespace fn2 {
 namespace cp {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
-
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
-inline int up_mod(int v, int r, int m) { return v + ((r - v % m) + m) % m; }
+using namespace mfma;
 
 constexpr int kNPR = 12;            // at most this many 64-slot DMA runs per (sample, channel) plane
 constexpr int kLdsBytes = 160 * 1024;
@@ -92,20 +86,6 @@ struct Cfg {
 __device__ __forceinline__ int fastdiv(int q, int d, unsigned m) { return d == 1 ? q : (int)__umulhi((unsigned)q, m); }
 inline unsigned magic_for(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int MW> struct WVec;
-template <> struct WVec<1> { using T = float; };
-template <> struct WVec<2> { using T = f32x2; };
-template <> struct WVec<4> { using T = f32x4; };
-template <int MW>
-__device__ __forceinline__ float wget(const typename WVec<MW>::T& v, int j) {
-  if constexpr (MW == 1) return v; else return v[j];
-}
-
 // LDS-DMA of one chunk: planes (sample il, channel ch of the chunk) wave, wave + NW, ..., every plane as npr runs of 64 slots
 // (a __device__ function: the host pass of a __global__ template cannot see amdgcn builtins inside a lambda)
 template <class K>
@@ -132,10 +112,9 @@ __global__ void __launch_bounds__(K::THREADS)
 conv_plane(Args a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int S = K::S, MW = K::MW, NP = K::NP, TAP = K::TAP;
-  // ---- task: channel block fastest (the blocks that share an input window are neighbours on one XCD: block b runs on XCD b % 8)
-  const unsigned per_xcd = (a.total + 7) / 8;
-  unsigned t = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  if (blockIdx.x / 8 >= per_xcd || t >= a.total) return;
+  // ---- task: channel block fastest (the blocks that share an input window are neighbours on one XCD: xcd_task)
+  unsigned t;
+  if (!xcd_task(blockIdx.x, a.total, t)) return;
   // (readfirstlane: the quotients are wave-uniform, but the compiler divides on the vector ALU; without it the buffer descriptor
   // built from them lives in VGPRs and every LDS-DMA becomes a waterfall loop)
   const int g = __builtin_amdgcn_readfirstlane((int)(t % a.ng)); t /= a.ng;
@@ -165,12 +144,11 @@ conv_plane(Args a) {
   const unsigned plane_bytes = 4u * (unsigned)plane, img_bytes = plane_bytes * (unsigned)a.in_ctot;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.in + ((size_t)n0 * a.in_ctot + a.in_c0) * plane), 0,
-      (unsigned)(img_bytes * (unsigned)(nimg - 1) + plane_bytes * (unsigned)a.Cin), 0x00020000);
-  constexpr unsigned OOB = 0x7ffffff0u;
+      (unsigned)(img_bytes * (unsigned)(nimg - 1) + plane_bytes * (unsigned)a.Cin), kRsrcWord3);
   unsigned voff[kNPR];
 #pragma unroll
   for (int j = 0; j < kNPR; ++j) {
-    voff[j] = OOB;
+    voff[j] = kOOB;
     if (j < a.npr) {
       const int last = a.slots_c - 64;
       const int d = K::VEC * ((64 * j < last ? 64 * j : last) + lane);
@@ -198,8 +176,7 @@ conv_plane(Args a) {
   }
   using WV = typename WVec<MW>::T;
   const int cg0 = (g * K::WM + wm) * MW;
-  const float* wl = a.wp + (size_t)cls * a.class_stride + ((size_t)(cg0 / 4) * a.ksteps * 64 + lane) * 4 + (cg0 % 4) + (size_t)chunk0 * K::KSC * 256;
-  auto wload = [&](int ks) -> WV { return *reinterpret_cast<const WV*>(wl + (size_t)ks * 256); };
+  const float* wl = weight_lane(a.wp + (size_t)cls * a.class_stride, cg0, a.ksteps, lane) + (size_t)chunk0 * K::KSC * 256;
 
   f32x4 acc[MW][NP];
 #pragma unroll
@@ -210,7 +187,7 @@ conv_plane(Args a) {
   WV wreg[K::NBUFA];
   stage_chunk<K>(rs, voff, a, lds_base, wave, (unsigned)chunk0 * chunk_bytes, plane_bytes, img_bytes, nimg);
 #pragma unroll
-  for (int i = 0; i < K::NBUFA - 1; ++i) wreg[i] = wload(i);
+  for (int i = 0; i < K::NBUFA - 1; ++i) wreg[i] = weight_load<MW>(wl, i);
 
   for (int c = 0; c < nchunks; ++c) {
     const int buf = c & 1;
@@ -244,7 +221,7 @@ conv_plane(Args a) {
 #pragma unroll
       for (int kx = 0; kx < TAP; ++kx) {
         const int ks = st * TAP + kx;
-        wreg[(ks + K::NBUFA - 1) % K::NBUFA] = wload(ks0 + ks + K::NBUFA - 1);
+        wreg[(ks + K::NBUFA - 1) % K::NBUFA] = weight_load<MW>(wl, ks0 + ks + K::NBUFA - 1);
         const WV w = wreg[ks % K::NBUFA];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
@@ -273,14 +250,7 @@ conv_plane(Args a) {
       const int co = 16 * (cg0 + j) + (lane & 15);
       const float bv = (final_pass && a.bias) ? a.bias[co] : 0.f;
       f32x4 v = acc[j][p];
-      if (final_pass) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float s = v[r] + bv;
-          if (a.relu) s = s > 0.f ? s : s * a.slope;
-          v[r] = s;
-        }
-      }
+      if (final_pass) v = bias_relu4(v, bv, a.relu, a.slope);
       if constexpr (K::MODE == 0) {
         float* o = dst + ((size_t)(n0 + il) * ctot + c0 + co) * a.P + pix;
         if (pix + 3 < a.P && (a.P & 3) == 0) *reinterpret_cast<f32x4*>(o) = v;
@@ -430,11 +400,7 @@ static bool plan(const Variant& v, Args& a) {
 template <class K>
 static int launch(const Args& a, hipStream_t st) {
   const size_t lds = sizeof(float) * 2 * (size_t)a.buf;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_plane<K>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    attr_set = true;
-  }
+  set_dynamic_lds_once<&conv_plane<K>>(kLdsBytes);
   hipLaunchKernelGGL((conv_plane<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), lds, st, a);
   return check_launch("conv_plane_forward");
 }
@@ -500,34 +466,22 @@ static int forward(Args a, int mode, int stride, int ks, void* workspace, size_t
     if (v.mode != mode || v.s != stride || v.ks != ks || !plan(v, t)) return FN2_ERR_UNSUPPORTED;
     return v.fn(t, st);
   };
-  int best = -1;
-  if (g_forced_variant >= 0) {
-    best = g_forced_variant;
-    if (best >= kNumVariants) return fail(FN2_ERR_UNSUPPORTED, "%s: no variant %d", what, best);
-  } else {
-    if (autotune_enabled(st)) {
-      static TuneCache cache_conv("conv_plane", kNumVariants), cache_deconv("deconv_plane", kNumVariants);
-      auto usable = [&](int i) -> bool {
-        Args t = a;
-        return kVariants[i].mode == mode && kVariants[i].s == stride && kVariants[i].ks == ks && plan(kVariants[i], t);
-      };
-      const TuneKey key{a.N, a.Cin, a.Hin, a.Win, a.Cout, stride + 16 * ks, a.pad, a.ksplit, a.in_ctot == a.Cin, a.out_ctot == a.Cout};
-      best = autotune_pick(mode == 0 ? cache_conv : cache_deconv, key, kNumVariants, st, run, usable);
-    }
-    if (best < 0) {
-      double bc = 0;
-      for (int i = 0; i < kNumVariants; ++i) {
-        Args t = a;
-        if (kVariants[i].mode != mode || kVariants[i].s != stride || kVariants[i].ks != ks || !plan(kVariants[i], t)) continue;
-        const double c = variant_cost(kVariants[i], t);
-        if (best < 0 || c < bc) { best = i; bc = c; }
-      }
-    }
-  }
-  if (best < 0) return fail(FN2_ERR_UNSUPPORTED, "%s: no kernel variant for this geometry", what);
-  const int rc = run(best);
-  if (rc == FN2_ERR_UNSUPPORTED) return fail(FN2_ERR_UNSUPPORTED, "%s: variant %d does not apply to this geometry", what, best);
-  if (rc != FN2_OK) return rc;
+  auto applies = [&](int i) -> bool {
+    Args t = a;
+    return kVariants[i].mode == mode && kVariants[i].s == stride && kVariants[i].ks == ks && plan(kVariants[i], t);
+  };
+  auto cost = [&](int i, bool) -> double {
+    Args t = a;
+    plan(kVariants[i], t);
+    return variant_cost(kVariants[i], t);
+  };
+  static TuneCache cache_conv("conv_plane", kNumVariants), cache_deconv("deconv_plane", kNumVariants);
+  const TuneKey key{a.N, a.Cin, a.Hin, a.Win, a.Cout, stride + 16 * ks, a.pad, a.ksplit, a.in_ctot == a.Cin, a.out_ctot == a.Cout};
+  Pick p;
+  if (const int rc = pick_variant(p, what, g_forced_variant, kNumVariants, false, mode == 0 ? cache_conv : cache_deconv, key, st, applies, cost,
+                                  [&](int i, bool) { return run(i); }, [](int) { return false; }))
+    return rc;
+  if (const int rc = run(p.variant)) return rc;
   if (a.ksplit > 1) {
     const long long total = (long long)a.N * a.Cout * Po;
     if (total >= (1ll << 31)) return fail(FN2_ERR_UNSUPPORTED, "%s: blob too large for the part reduction", what);

@@ -8,6 +8,7 @@
 // (once per weight version) -> workspace -> one dispatch call.  Python holds no routing rule and no per-family dispatch of its own, so a
 // Caffe user of libflownet2_hip.so gets the routing, the operands and the kernels the tests and the benchmarks ran with.
 // The thresholds are measurements: profiles/r02_conv_bench_*.txt, r04_conv_plane_bench_flownetc.txt, scripts/probes/small_layer_routes.py.
+#include "conv_internal.hpp"
 #include "fn2_common.hpp"
 
 namespace {
@@ -364,13 +365,6 @@ FN2_API int fn2_conv_backward_data_computed_channels(const fn2_conv_desc* d, int
   return (route == FN2_BWD_ROUTE_NONE || route != g.route) ? 0 : g.Cp;
 }
 
-namespace fn2 {
-int tconv_forward_masked(const float* bottom, const float* packed_weight, const float* bias, float* top,
-                         int N, int Cin, int Hin, int Win, int bottom_channels, int bottom_c0,
-                         int Cout, int Hout, int Wout, int top_channels, int top_c0, int kernel, int pad,
-                         int relu, float negative_slope, const float* mask, int mask_channels, int mask_c0, float mask_slope, void* stream);
-}
-
 FN2_API int fn2_conv_backward_data_masked_supported(const fn2_conv_desc* d, int transposed, int route) {
   const Bwd g = bwd_geom(d, transposed);
   return route == FN2_BWD_ROUTE_TCONV && route == g.route && g.Cp == g.Cb;
@@ -467,11 +461,6 @@ FN2_API size_t fn2_conv_backward_weights_workspace_bytes(const fn2_conv_desc* d,
   if (stem_class(d, transposed)) return fn2_conv_k7s2_wgrad_workspace_bytes(d->N, d->Cin, d->Hin, d->Win, d->Cout);
   const WG w = wg_geom(d, transposed);
   return fn2_conv_wgrad_workspace_bytes(d->N, w.Ca, w.Ha, w.Wa, w.Cb, w.Hb, w.Wb, d->kernel, d->stride, d->pad);
-}
-
-namespace fn2 {
-int conv_k7s2_wgrad_bias(const float* top_diff, const float* bottom, float* weight_diff, float* bias_diff, int N, int Cin, int Hin, int Win, int Cout,
-                         int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 }
 
 // weight_diff AND bias_diff of a layer from one pass over top_diff where a kernel has that form (the stem: csrc/conv_stem_wgrad.hip sums

@@ -14,13 +14,15 @@
 //   * the MFMA result layout gives every lane 4 consecutive x of one output channel: bias + leaky ReLU + one 16-byte store;
 //   * 12 input channels (the stems of FlowNet2's stacked nets) run as two 6-channel passes over the same output.
 #include "fn2_common.hpp"
+#include "mfma_tile.hpp"
 
 #include <type_traits>
 
 namespace fn2 {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
+using mfma::f32x4;
+using mfma::kOOB;
+using mfma::kRsrcWord3;
+using mfma::lds_ptr_t;
 
 struct StemArgs {
   int N, Hin, Win, Hout, Wout, Cout;
@@ -56,14 +58,14 @@ conv_k7s2_relu(const float* __restrict__ in, const float* __restrict__ weight, c
   // ---- stage the input window: slot s -> (c, row, group of 4 columns) ----
   const size_t plane = (size_t)a.Hin * a.Win;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(in + ((size_t)n * a.Ctot + a.c0) * plane), 0, (unsigned)(4u * CIN * plane), 0x00020000);
+      const_cast<float*>(in + ((size_t)n * a.Ctot + a.c0) * plane), 0, (unsigned)(4u * CIN * plane), kRsrcWord3);
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
 #pragma unroll
   for (int i = 0; i < (NRUN + 3) / 4; ++i) {
     const int run = i * 4 + wave;
     if (run < NRUN) {
       const int s = run * 64 + lane;
-      unsigned voff = 0x7ffffff0u;
+      unsigned voff = kOOB;
       if (s < SLOTS) {
         const int c = s / (ROWS * (RS / 4)), rem = s % (ROWS * (RS / 4));
         const int row = rem / (RS / 4), gq = rem % (RS / 4);

@@ -19,13 +19,17 @@
 //     layout.  Summation order (restated by the oracle twin fn2_conv_k7s2_wgrad_cpu): per part one fma chain over the part's pixels in
 //     (unit, row, x) order; the parts are added in 16 contiguous segments (part by part inside a segment, then the segment sums in order); the
 //     number of parts is a function of the geometry only (fn2_conv_k7s2_wgrad_ksplit).
+#include "conv_internal.hpp"
 #include "fn2_common.hpp"
+#include "mfma_tile.hpp"
 
 namespace fn2 {
+using mfma::f32x4;
+using mfma::kOOB;
+using mfma::kRsrcWord3;
+using mfma::lds_ptr_t;
 namespace sw {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
 using lds_vf = const volatile __attribute__((address_space(3))) float*;
 
 constexpr int kCout = 64, kR = 2, kXT = 32;
@@ -34,7 +38,6 @@ constexpr int kDSlots = kCout * (kDS / 4);        // 16-byte slots of the top_di
 constexpr int kWC = 2 * kXT + 16;                 // window columns: bottom x = 2 x0 - 4 .. 2 x0 + 75 (70 are read; 80 == 16 (mod 64 banks): the tap
                                                   // rows ky, ky + 1, ky + 2 of one operand read sit on disjoint banks)
 constexpr int kWR = 2 * (kR - 1) + 7;             // window rows: bottom y = 2 y0 - 3 .. 2 y0 + 5
-constexpr unsigned kOOB = 0x7ffffff0u;
 
 template <int CIN> struct Geo {
   static constexpr int TAPS = CIN * 49, NT = (TAPS + 15) / 16;
@@ -93,9 +96,9 @@ __device__ __forceinline__ void stage_unit(const Args& a, int u, unsigned dst, i
   unit_decode(a, u, n, y0, x0);
   const size_t planeD = (size_t)a.Ho * a.Wo, planeB = (size_t)a.H * a.W;
   const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.d + (size_t)n * kCout * planeD), 0,
-                                                                        (unsigned)(4u * kCout * planeD), 0x00020000);
+                                                                        (unsigned)(4u * kCout * planeD), kRsrcWord3);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.b + (size_t)n * CIN * planeB), 0,
-                                                                        (unsigned)(4u * CIN * planeB), 0x00020000);
+                                                                        (unsigned)(4u * CIN * planeB), kRsrcWord3);
   const unsigned originD = (unsigned)(y0 * a.Wo + x0);
 #pragma unroll
   for (int i = 0; i < G::RPW_D; ++i) {
@@ -296,11 +299,6 @@ FN2_API size_t fn2_conv_k7s2_wgrad_workspace_bytes(int N, int Cin, int Hin, int 
   sw::Args a{};
   sw::fill(a, N, Hin, Win);
   return sizeof(float) * (size_t)a.parts * sw::kCout * (((Cin * 49 + 15) / 16) * 16);
-}
-
-namespace fn2 {
-int conv_k7s2_wgrad_bias(const float* top_diff, const float* bottom, float* weight_diff, float* bias_diff, int N, int Cin, int Hin, int Win, int Cout,
-                         int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 }
 
 FN2_API int fn2_conv_k7s2_wgrad(const float* top_diff, const float* bottom, float* weight_diff, int N, int Cin, int Hin, int Win, int Cout,

@@ -17,14 +17,16 @@
 // Every part writes its accumulator tiles as they are (16-byte stores, MFMA layout); wgrad_finalize adds the parts in part order and
 // scatters into the weight layout.  Summation order (restated by the oracle twin fn2_conv_wgrad_cpu): per part one fma chain over the
 // part's pixels in (n, y, x) order, parts added in part order; ksplit is a function of the layer geometry only (conv_wgrad_geom.hpp).
-#include "fn2_common.hpp"
+#include "mfma_tile.hpp"
 #include "conv_wgrad_geom.hpp"
 
 namespace fn2 {
 namespace wg {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
+using mfma::f32x4;
+using mfma::kOOB;
+using mfma::lds_ptr_t;
+using mfma::wait_vmcnt;
 
 struct Args {
   const float* a; const float* b; float* slab;
@@ -34,13 +36,6 @@ struct Args {
   unsigned total;            // workgroups: nblk_a * nblk_b * ksplit
   long long slab_part;       // floats per part
 };
-
-constexpr unsigned kOOB = 0x7ffffff0u;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 struct Chunk { int n, y, rvalid, x0; };
 
@@ -52,9 +47,9 @@ __device__ __forceinline__ void stage_chunk(const Args& a, const Chunk& c, int c
                                             const unsigned (&pb_off)[K::RPW_B], const unsigned (&pb_rc)[K::RPW_B]) {
   const size_t planeA = (size_t)a.Ha * a.Wa, planeB = (size_t)a.Hb * a.Wb;
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.a + ((size_t)c.n * a.a_ctot + a.a_c0 + ca0) * planeA), 0, (unsigned)(4u * K::CA * planeA), 0x00020000);
+      const_cast<float*>(a.a + ((size_t)c.n * a.a_ctot + a.a_c0 + ca0) * planeA), 0, (unsigned)(4u * K::CA * planeA), mfma::kRsrcWord3);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.b + ((size_t)c.n * a.b_ctot + a.b_c0 + cb0) * planeB), 0, (unsigned)(4u * K::CB * planeB), 0x00020000);
+      const_cast<float*>(a.b + ((size_t)c.n * a.b_ctot + a.b_c0 + cb0) * planeB), 0, (unsigned)(4u * K::CB * planeB), mfma::kRsrcWord3);
   const unsigned originA = (unsigned)(c.y * a.Wa + c.x0);
 #pragma unroll
   for (int i = 0; i < K::RPW_A; ++i) {
@@ -132,9 +127,8 @@ __global__ void __launch_bounds__(256, K::WG_PER_CU) conv_wgrad(Args a) {
   const int wm = wave % K::WM, wn = wave / K::WM;
 
   // ---- task: (K part, channel block); the blocks of one part share its pixels -> contiguous on one XCD (block b runs on XCD b % 8)
-  const unsigned per_xcd = (a.total + 7) / 8;
-  const unsigned t = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  if (blockIdx.x / 8 >= per_xcd || t >= a.total) return;
+  unsigned t;
+  if (!mfma::xcd_task(blockIdx.x, a.total, t)) return;
   const int nblk = a.nblk_a * a.nblk_b;
   const int part = (int)(t / (unsigned)nblk), blk = (int)(t % (unsigned)nblk);
   const int ca0 = (blk / a.nblk_b) * K::CA, cb0 = (blk % a.nblk_b) * K::CB;
@@ -298,11 +292,7 @@ __global__ void __launch_bounds__(256) pad_width(const float* __restrict__ in, f
 
 template <class K>
 static int launch(const Args& a, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad<K>), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-    attr_set = true;
-  }
+  mfma::set_dynamic_lds_once<&conv_wgrad<K>>(K::LDS_BYTES);
   hipLaunchKernelGGL((conv_wgrad<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), K::LDS_BYTES, st, a);
   return check_launch("conv_wgrad");
 }

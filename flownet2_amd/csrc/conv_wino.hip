@@ -18,18 +18,12 @@
 // Numerics: exact fp32 products and k-ordered fma chains per position; the transforms add rounding of a few ulp of the largest
 // patch element (measured against the reference's Convolution layer and fp64 in tests/test_conv_wino.py).  The oracle twin
 // (oracle/fn2_oracle.c: fn2_conv_wino_forward_cpu) performs the same operations in the same order: bit-identical.
-#include "fn2_common.hpp"
-#include "autotune.hpp"
+#include "mfma_tile.hpp"
 
 namespace fn2 {
 namespace wino {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
-
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
-constexpr int up_mod(int v, int r, int m) { return v + ((r - v % m) + m) % m; }
+using namespace mfma;
 
 struct Args {
   const float* in; const float* up; const float* bias; float* out;
@@ -109,8 +103,6 @@ __device__ __forceinline__ void stage_chunk_tab(__amdgpu_buffer_rsrc_t rsU, __am
   }
 }
 
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 // Operands of one k-step (channel quad) of one tile block as they come out of LDS: U for the 16 positions, and the 4x4 input patch
 // d[i][0..3] of row i as a dword, the ALIGNED 8-byte pair m[i] = (d[i][1], d[i][2]) and a dword (window columns dcol + 1 .. dcol + 4, dcol
 // even).  The inner columns are transformed with packed-fp32 instructions on the pairs (two additions per lane and instruction); the
@@ -181,16 +173,14 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
   const int x0 = bx * K::TW, y0 = by * K::TH;
 
   const size_t plane = (size_t)a.Hin * a.Win;
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.in + ((size_t)n * a.in_ctot + a.in_c0) * plane), 0, (unsigned)(4u * a.Cin * plane), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsW = nchw_rsrc(a.in, n, a.in_ctot, a.in_c0, a.Cin, plane);
   const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.up + (size_t)g * K::WM * K::MW * a.kquads * 1024), 0, (unsigned)(4096u * a.kquads * K::WM * K::MW), 0x00020000);
-  constexpr unsigned OOB = 0x7ffffff0u;
+      const_cast<float*>(a.up + (size_t)g * K::WM * K::MW * a.kquads * 1024), 0, (unsigned)(4096u * a.kquads * K::WM * K::MW), kRsrcWord3);
   unsigned voff[K::RPW];
 #pragma unroll
   for (int i = 0; i < K::RPW; ++i) {
     const int r = i * K::NW + wave;
-    voff[i] = OOB;
+    voff[i] = kOOB;
     if (r < K::URUN) voff[i] = 4096u * (unsigned)((r / (4 * K::CQ)) * a.kquads) + 16u * (unsigned)((r % (4 * K::CQ)) * 64 + lane);   // slab r / (4 CQ) of the WM channel groups
     else if (r < K::NRUN) {
       const int s = (r - K::URUN) * 64 + lane;
@@ -232,7 +222,7 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
     const float* dp0 = smem + dbase;
     float vA[16], vB[16];
     WOps LA, LB;
-    wait_vm0();
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (a.nchunks > 1) stage_chunk<K>(rsU, rsW, voff, lds_base + 4u * (unsigned)K::BUF, wave, chunk_u, chunk_w);
     wino_load<K>(LA, ub0, dp0);
@@ -246,7 +236,7 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
       wino_transform(LB, vB);
       __builtin_amdgcn_sched_barrier(0);
       if (more) {
-        wait_vm0();
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if (c + 2 < a.nchunks)
         {
@@ -272,7 +262,7 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
   } else {
   for (int c = 0; c < a.nchunks; ++c) {
     const int buf = c & 1;
-    wait_vm0();                              // this wave's part of chunk c (issued one chunk ago) has landed
+    wait_vmcnt<0>();                              // this wave's part of chunk c (issued one chunk ago) has landed
     __builtin_amdgcn_s_barrier();            // ... and everybody's; everybody is also done reading the other buffer
     if (c + 1 < a.nchunks)
       stage_chunk<K>(rsU, rsW, voff, lds_base + 4u * (unsigned)((buf ^ 1) * K::BUF), wave, (unsigned)(c + 1) * chunk_u, (unsigned)(c + 1) * chunk_w);
@@ -339,20 +329,8 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
       if (oy + h >= a.Hout) continue;
       float* orow = oplane + (size_t)(oy + h) * a.Wout;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float s = y[h][e] + bv;
-        if (a.relu) s = s > 0.f ? s : s * a.slope;
-        y[h][e] = s;
-      }
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int x = ox + 4 * half;
-        if (x + 3 < a.Wout) *reinterpret_cast<f32x4*>(orow + x) = f32x4{y[h][4 * half], y[h][4 * half + 1], y[h][4 * half + 2], y[h][4 * half + 3]};
-        else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) if (x + e < a.Wout) orow[x + e] = y[h][4 * half + e];
-        }
-      }
+      for (int half = 0; half < 2; ++half)
+        store_row4(orow, ox + 4 * half, a.Wout, f32x4{y[h][4 * half], y[h][4 * half + 1], y[h][4 * half + 2], y[h][4 * half + 3]}, bv, a.relu, a.slope);
     }
   }
   }
@@ -379,9 +357,8 @@ __device__ __forceinline__ void decode_tile(const Args& a, unsigned t, int& g, i
 template <class K>
 __global__ void __launch_bounds__(K::THREADS, (K::NW == 4 && K::MT == 1 && K::MW == 1) ? 3 : 2)      // 3 workgroups of 4 waves per CU: <= 168 VGPRs
 conv_wino(Args a) {
-  const unsigned per_xcd = (a.total + 7) / 8;
-  const unsigned t = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  if (blockIdx.x / 8 >= per_xcd || t >= a.total) return;
+  unsigned t;
+  if (!xcd_task(blockIdx.x, a.total, t)) return;
   int g, bx, by, n;
   decode_tile(a, t, g, bx, by, n);
   wino_body<K>(a, g, bx, by, n);
@@ -399,9 +376,8 @@ conv_wino_tail(Args a) {
     decode_tile(a, t, g, bx, by, n);
     wino_body<K>(a, g, bx, by, n);
   } else {
-    const unsigned b = blockIdx.x - a.nbig, nsm = 2 * (a.total - a.nbig), per_xcd = (nsm + 7) / 8;
-    const unsigned u = (b % 8) * per_xcd + b / 8;
-    if (b / 8 >= per_xcd || u >= nsm) return;
+    unsigned u;
+    if (!xcd_task(blockIdx.x - a.nbig, 2 * (a.total - a.nbig), u)) return;
     decode_tile(a, a.nbig + u / 2, g, bx, by, n);
     wino_body<KH>(a, g, 2 * bx + (int)(u & 1), by, n);
   }
@@ -459,11 +435,7 @@ static int launch(const Args& base, hipStream_t st) {
   if (tiles_of(a) > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "conv_wino: grid too large");
   a.total = (unsigned)tiles_of(a); a.nbig = a.total;
   constexpr size_t lds = sizeof(float) * K::LDS_FLOATS;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  set_dynamic_lds_once<&conv_wino<K>>((int)lds);
   hipLaunchKernelGGL((conv_wino<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), lds, st, a);
   return check_launch("conv_wino_forward");
 }
@@ -480,11 +452,7 @@ static int launch_tail(const Args& base, hipStream_t st) {
     const unsigned nsm = 2 * (a.total - a.nbig);
     using KH = Cfg<K::TGY, K::TGX, K::MT / 2, K::WNY, K::WNX, K::WM, K::MW>;
     constexpr size_t lds = sizeof(float) * (K::LDS_FLOATS > KH::LDS_FLOATS ? K::LDS_FLOATS : KH::LDS_FLOATS);
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_tail<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
+    set_dynamic_lds_once<&conv_wino_tail<K>>((int)lds);
     hipLaunchKernelGGL((conv_wino_tail<K>), dim3(a.nbig + 8 * ((nsm + 7) / 8)), dim3(K::THREADS), lds, st, a);
     return check_launch("conv_wino_forward");
   }
@@ -562,52 +530,26 @@ FN2_API int fn2_conv_wino_forward(const float* bottom, const float* packed_weigh
                                   int Cout, int top_channels, int top_c0, int pad, int relu, float negative_slope, void* stream) {
   if (N < 0) return fail(FN2_ERR_INVALID_ARG, "conv_wino: bad batch");
   if (N == 0) return FN2_OK;
-  if (!bottom || !packed_weight || !top) return fail(FN2_ERR_INVALID_ARG, "conv_wino: null blob");
-  if (!fn2_conv_wino_supported(Cin, Hin, Win, Cout, pad))
-    return fail(FN2_ERR_UNSUPPORTED, "conv_wino: unsupported geometry (Cin %d, %dx%d, Cout %d, pad %d)", Cin, Hin, Win, Cout, pad);
-  if (bottom_c0 < 0 || bottom_c0 + Cin > bottom_channels || top_c0 < 0 || top_c0 + Cout > top_channels)
-    return fail(FN2_ERR_INVALID_ARG, "conv_wino: channel slice outside the blob");
-  if (((reinterpret_cast<uintptr_t>(bottom) | reinterpret_cast<uintptr_t>(top) | reinterpret_cast<uintptr_t>(packed_weight)) & 15) != 0)
-    return fail(FN2_ERR_UNSUPPORTED, "conv_wino: blobs must be 16-byte aligned");
+  if (const int rc = mfma::check_conv_args("conv_wino", bottom, packed_weight, top, Cin, bottom_channels, bottom_c0, Cout, top_channels, top_c0, [&] {
+        return fn2_conv_wino_supported(Cin, Hin, Win, Cout, pad) ? FN2_OK
+            : fail(FN2_ERR_UNSUPPORTED, "conv_wino: unsupported geometry (Cin %d, %dx%d, Cout %d, pad %d)", Cin, Hin, Win, Cout, pad);
+      }))
+    return rc;
   wino::Args a{};
   a.in = bottom; a.up = packed_weight; a.bias = bias; a.out = top;
   a.N = N; a.Cin = Cin; a.Hin = Hin; a.Win = Win; a.in_ctot = bottom_channels; a.in_c0 = bottom_c0;
   a.Cout = Cout; a.Hout = Hin + 2 * pad - 2; a.Wout = Win + 2 * pad - 2; a.out_ctot = top_channels; a.out_c0 = top_c0;
   a.kquads = wino::kquads_for(Cin);
   a.slope = negative_slope; a.relu = relu;
-  int best = -1;
-  bool tail = false;
-  if (wino::g_forced_variant >= 0) {
-    tail = wino::g_forced_variant >= 1000;
-    best = wino::g_forced_variant % 1000;
-    if (best >= wino::kNumVariants || !wino::variant_applies(wino::kVariants[best], a) || (tail && !wino::kVariants[best].fn_tail))
-      return fail(FN2_ERR_UNSUPPORTED, "conv_wino: forced variant %d does not apply", wino::g_forced_variant);
-  } else {
-    hipStream_t st = as_stream(stream);
-    int picked = -1;
-    if (autotune_enabled(st)) {
-      static TuneCache cache("conv_wino", wino::kNumVariants);
-      auto usable = [&](int c) -> bool {
-        const wino::Variant& v = wino::kVariants[c / 2];
-        return wino::variant_applies(v, a) && (!(c & 1) || (v.fn_tail && wino::variant_cost(v, a, true) < 1e29));
-      };
-      const TuneKey key{N, Cin, Hin, Win, Cout, pad, bottom_channels == Cin, top_channels == Cout, 0, 0};
-      picked = autotune_pick(cache, key, 2 * wino::kNumVariants, st, [&](int c) -> int {
-        const wino::Variant& v = wino::kVariants[c / 2];
-        if (!wino::variant_applies(v, a)) return FN2_ERR_UNSUPPORTED;
-        if (c & 1) return (v.fn_tail && wino::variant_cost(v, a, true) < 1e29) ? v.fn_tail(a, st) : FN2_ERR_UNSUPPORTED;
-        return v.fn(a, st);
-      }, usable);
-    }
-    if (picked >= 0) { best = picked / 2; tail = (picked & 1) != 0; }
-    else {
-      double bc = 0;
-      for (int i = 0; i < wino::kNumVariants; ++i)
-        for (int t = 0; t < (wino::kVariants[i].fn_tail ? 2 : 1); ++t) {
-          const double c = wino::variant_cost(wino::kVariants[i], a, t == 1);
-          if (best < 0 || c < bc) { best = i; bc = c; tail = t == 1; }
-        }
-    }
-  }
-  return tail ? wino::kVariants[best].fn_tail(a, as_stream(stream)) : wino::kVariants[best].fn(a, as_stream(stream));
+  hipStream_t st = as_stream(stream);
+  static TuneCache cache("conv_wino", wino::kNumVariants);
+  const TuneKey key{N, Cin, Hin, Win, Cout, pad, bottom_channels == Cin, top_channels == Cout, 0, 0};
+  mfma::Pick p;
+  if (const int rc = mfma::pick_variant(p, "conv_wino", wino::g_forced_variant, wino::kNumVariants, true, cache, key, st,
+                                        [&](int i) { return wino::variant_applies(wino::kVariants[i], a); },
+                                        [&](int i, bool tail) { return wino::variant_cost(wino::kVariants[i], a, tail); },
+                                        [&](int i, bool tail) { return tail ? wino::kVariants[i].fn_tail(a, st) : wino::kVariants[i].fn(a, st); },
+                                        [&](int i) { return wino::kVariants[i].fn_tail != nullptr; }))
+    return rc;
+  return p.tail ? wino::kVariants[p.variant].fn_tail(a, st) : wino::kVariants[p.variant].fn(a, st);
 }

@@ -20,11 +20,16 @@
 // the same quad swizzle, double buffered) and each chunk costs 24 ds_read_b32 + 24 MFMAs per wave.
 // The 64 x 4 x 32 output block goes through LDS and leaves as 128-byte rows.  No atomics: deterministic.
 #include "correlation.hpp"
+#include "mfma_tile.hpp"
 
 namespace fn2 {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
+using mfma::cdiv;
+using mfma::f32x2;
+using mfma::f32x4;
+using mfma::kOOB;
+using mfma::kRsrcWord3;
+using mfma::lds_ptr_t;
+using mfma::up_mod;
 
 namespace bwd {
 
@@ -34,8 +39,6 @@ constexpr int kKC = 16;       // channels per staged chunk = one MFMA N tile
 constexpr int kCQ = 64;       // channels per workgroup
 constexpr int kNCH = kCQ / kKC;
 
-constexpr int up_mod(int v, int r, int m) { return v + ((r - v % m) + m) % m; }
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 template <int S2, int R>
@@ -89,8 +92,7 @@ corr_bwd_mfma(const float* __restrict__ other, const float* __restrict__ top_dif
   const int plane = g.H * g.W;
   const float* src_n = other + ((size_t)n * g.C + (size_t)cq * kCQ) * plane;     // the 64 channels of this workgroup
   const float* g_n = top_diff + (size_t)n * K::D * K::D * plane;
-  const __amdgpu_buffer_rsrc_t g_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g_n), 0, 4u * K::D * K::D * (unsigned)plane, 0x00020000);
-  constexpr unsigned OOB = 0x7ffffff0u;
+  const __amdgpu_buffer_rsrc_t g_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g_n), 0, 4u * K::D * K::D * (unsigned)plane, kRsrcWord3);
 
   // lane roles inside the 16x16x4 fragments
   const int kk = lane >> 4;                     // contraction column of the k-step (both operands)
@@ -99,7 +101,7 @@ corr_bwd_mfma(const float* __restrict__ other, const float* __restrict__ top_dif
 
   // ---- staging plan: thread = one pixel of the 4 staged rows, 16 channels (as the forward's B region) ----
   const bool stager_wave = wave < K::SWAVES;
-  unsigned voff = OOB;
+  unsigned voff = kOOB;
   int laddr = -1, wsw = 0;
   int srow = 0, scol = 0;
   if (stager_wave) {
@@ -153,13 +155,13 @@ corr_bwd_mfma(const float* __restrict__ other, const float* __restrict__ top_dif
           xx = S2 * (jw - R + 4 * b + kk) + px;
         }
         const bool ok = q >= -R && q <= R && o >= -R && o <= R && yy >= 0 && yy < g.H && xx >= 0 && xx < g.W;
-        const unsigned off = ok ? 4u * (unsigned)(((q + R) * K::D + (o + R)) * plane + yy * g.W + xx) : OOB;
+        const unsigned off = ok ? 4u * (unsigned)(((q + R) * K::D + (o + R)) * plane + yy * g.W + xx) : kOOB;
         Gv[b][ks] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(g_rs, off, 0, 0));
       }
     }
 
     // ---- staging offsets of the 4 rows r0 .. r0+3 of the other map ----
-    voff = OOB;
+    voff = kOOB;
     if (stager_wave && srow < 4) {
       const int ir = r0 + srow, yb = S2 * ir + py, xb = S2 * (jS - R) + scol;
       if (ir >= 0 && yb < g.H && xb >= 0 && xb < g.W) voff = 4u * (unsigned)(yb * g.W + xb);
@@ -167,7 +169,7 @@ corr_bwd_mfma(const float* __restrict__ other, const float* __restrict__ top_dif
     auto load_chunk = [&](int c16) {
       if (laddr >= 0) {
         const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_n + (size_t)c16 * kKC * plane), 0, chunk_bytes, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_n + (size_t)c16 * kKC * plane), 0, chunk_bytes, kRsrcWord3);
 #pragma unroll
         for (int kc = 0; kc < kKC; ++kc)
           sv[kc] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, kc * plane_bytes, 0));
@@ -260,7 +262,6 @@ constexpr int NRUN = cdiv(SLOTS, 64);         // 19
 constexpr int RPW = cdiv(NRUN, kWaves);       // 3
 constexpr int BUF = NRUN * 256;
 constexpr int LDS_FLOATS = cmax(2 * BUF, K::OUT_FLOATS);
-using lds_ptr_t = __attribute__((address_space(3))) void*;
 
 __device__ __forceinline__ void stage(__amdgpu_buffer_rsrc_t rs, const unsigned (&voff)[RPW], unsigned dst, int wave, unsigned soff) {
 #pragma unroll
@@ -273,7 +274,6 @@ __device__ __forceinline__ void stage(__amdgpu_buffer_rsrc_t rs, const unsigned 
 template <int WHICH>
 __device__ __forceinline__ void gather_g(float (&Gv)[K::NB][4], __amdgpu_buffer_rsrc_t g_rs, const Args& g, int plane, int r0, int i0, int jw, int pi, int pj, int kk,
                                          int py, int px) {
-  constexpr unsigned OOB = 0x7ffffff0u;
 #pragma unroll
   for (int b = 0; b < K::NB; ++b) {
 #pragma unroll
@@ -291,7 +291,7 @@ __device__ __forceinline__ void gather_g(float (&Gv)[K::NB][4], __amdgpu_buffer_
         xx = S2 * (jw - R + 4 * b + kk) + px;
       }
       const bool ok = q >= -R && q <= R && o >= -R && o <= R && yy >= 0 && yy < g.H && xx >= 0 && xx < g.W;
-      const unsigned off = ok ? 4u * (unsigned)(((q + R) * K::D + (o + R)) * plane + yy * g.W + xx) : OOB;
+      const unsigned off = ok ? 4u * (unsigned)(((q + R) * K::D + (o + R)) * plane + yy * g.W + xx) : kOOB;
       Gv[b][ks] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(g_rs, off, 0, 0));
     }
   }
@@ -318,10 +318,9 @@ corr_bwd_dma(const float* __restrict__ other, const float* __restrict__ top_diff
   if (i0 >= Hc) return;
   const int plane = g.H * g.W;
   const float* src_n = other + ((size_t)n * g.C + (size_t)cq * kCQ) * plane;
-  const __amdgpu_buffer_rsrc_t s_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_n), 0, 4u * kCQ * (unsigned)plane, 0x00020000);
+  const __amdgpu_buffer_rsrc_t s_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_n), 0, 4u * kCQ * (unsigned)plane, kRsrcWord3);
   const __amdgpu_buffer_rsrc_t g_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(top_diff + (size_t)n * K::D * K::D * plane), 0, 4u * K::D * K::D * (unsigned)plane, 0x00020000);
-  constexpr unsigned OOB = 0x7ffffff0u;
+      const_cast<float*>(top_diff + (size_t)n * K::D * K::D * plane), 0, 4u * K::D * K::D * (unsigned)plane, kRsrcWord3);
 
   const int kk = lane >> 4, pi = (lane & 15) >> 2, pj = lane & 3, ch = lane & 15;
 
@@ -350,7 +349,7 @@ corr_bwd_dma(const float* __restrict__ other, const float* __restrict__ top_diff
     const int r0 = i0 - R + 4 * a;
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
-      voff[i] = OOB;
+      voff[i] = kOOB;
       if (srow[i] >= 0) {
         const int ir = r0 + srow[i], yb = S2 * ir + py;
         if (ir >= 0 && yb < g.H) voff[i] = vxc[i] + 4u * (unsigned)(yb * g.W);
@@ -449,7 +448,6 @@ namespace g3 {
 constexpr int kAbl = FN2_G3_ABL;
 constexpr int R = 10, S2 = 2, D = 21;
 using K = Cfg<S2, R>;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
 constexpr int BSL = K::BPX / 4 + 1;             // 19 slots per channel of the staged row (one pad slot): stride 76 dwords
 constexpr int BCS = 4 * BSL;
 constexpr int BSLOTS = kCQ * BSL;               // 1216 = 19 whole runs
@@ -476,9 +474,8 @@ template <int WHICH>
 __device__ __forceinline__ void stage(const float* bsrc, unsigned bbytes, const float* gsrc, unsigned gbytes,
                                       const unsigned (&vb)[G<WHICH>::RPW], const int (&gpi)[G<WHICH>::RPW], unsigned dst, int wave, int r, int i0) {
   using T = G<WHICH>;
-  constexpr unsigned OOB = 0x7ffffff0u;
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bsrc), 0, bbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gsrc), 0, gbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bsrc), 0, bbytes, kRsrcWord3);
+  const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gsrc), 0, gbytes, kRsrcWord3);
 #pragma unroll
   for (int i = 0; i < T::RPW; ++i) {
     const int run = i * kWaves + wave;
@@ -486,7 +483,7 @@ __device__ __forceinline__ void stage(const float* bsrc, unsigned bbytes, const 
       if constexpr (!(kAbl & 2)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_ptr_t)(uintptr_t)(dst + 1024u * (unsigned)run), 16, vb[i], 0, 0, 0);
     } else if (run < T::NRUN && !(kAbl & 1)) {
       const int q = WHICH == 0 ? r - i0 - gpi[i] : i0 + gpi[i] - r;          // displacement row of this slab row
-      const unsigned v = (gpi[i] >= 0 && q >= -R && q <= R) ? vb[i] : OOB;
+      const unsigned v = (gpi[i] >= 0 && q >= -R && q <= R) ? vb[i] : kOOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsG, (lds_ptr_t)(uintptr_t)(dst + 1024u * (unsigned)run), 16, v, 0, 0, 0);
     }
   }
@@ -515,7 +512,6 @@ corr_bwd_g3(const float* __restrict__ other, const float* __restrict__ top_diff,
   const int plane = g.H * g.W;
   const float* src_n = other + ((size_t)n * g.C + (size_t)cq * kCQ) * plane;
   const float* td_n = top_diff + (size_t)n * D * D * plane;
-  constexpr unsigned OOB = 0x7ffffff0u;
 
   const int kk = lane >> 4, pi = (lane & 15) >> 2, pj = lane & 3, ch = lane & 15;
   const int rlo = i0 - R < 0 ? 0 : i0 - R, rhi = i0 + 3 + R > Hc - 1 ? Hc - 1 : i0 + 3 + R;
@@ -527,7 +523,7 @@ corr_bwd_g3(const float* __restrict__ other, const float* __restrict__ top_diff,
 #pragma unroll
   for (int i = 0; i < T::RPW; ++i) {
     const int s = (i * kWaves + wave) * 64 + lane;
-    vb[i] = OOB; gpi[i] = -1;
+    vb[i] = kOOB; gpi[i] = -1;
     if (s < BSLOTS) {
       const int c = s / BSL, gq = s % BSL;
       const int xb = S2 * (jS - R) + 4 * gq;
@@ -638,7 +634,6 @@ corr_bwd_g3(const float* __restrict__ other, const float* __restrict__ top_diff,
 }
 }  // namespace g3
 
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Fourth generation (round 6).  Ablation builds of generation 3 (scripts/probes/corr_bwd_variants.sh, profiles/r06_corr_bwd_notes.md):
 // without any staging the kernel takes 45 us per bottom, without the other map's rows 61-64 (they come from L2: free), without the G slab
@@ -659,7 +654,6 @@ corr_bwd_g3(const float* __restrict__ other, const float* __restrict__ top_diff,
 namespace g4 {
 constexpr int R = 10, S2 = 2, D = 21;
 using K = Cfg<S2, R>;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
 constexpr int BSL = K::BPX / 4 + 1;             // 19 slots per channel of the staged row (one pad slot): stride 76 dwords
 constexpr int BCS = 4 * BSL;
 constexpr int BSLOTS = kCQ * BSL;               // 1216 = 19 whole runs
@@ -697,7 +691,6 @@ __device__ __forceinline__ void g4_body(const float* __restrict__ other, const f
   const int plane = g.H * g.W;
   const float* src_n = other + ((size_t)n * g.C + (size_t)cq * kCQ) * plane;
   const float* td_n = top_diff + (size_t)n * D * D * plane;
-  constexpr unsigned OOB = 0x7ffffff0u;
 
   const int kk = lane >> 4, pi = (lane & 15) >> 2, pj = lane & 3, ch = lane & 15;
   const int rlo = i0 - R < 0 ? 0 : i0 - R, rhi = i0 + 3 + R > Hc - 1 ? Hc - 1 : i0 + 3 + R;
@@ -708,7 +701,7 @@ __device__ __forceinline__ void g4_body(const float* __restrict__ other, const f
 #pragma unroll
   for (int i = 0; i < BRPW; ++i) {
     const int s = (i * kWaves + wave) * 64 + lane;
-    vbB[i] = OOB;
+    vbB[i] = kOOB;
     if (s < BSLOTS) {
       const int c = s / BSL, gq = s % BSL;
       const int xb = S2 * (jS - R) + 4 * gq;
@@ -718,7 +711,7 @@ __device__ __forceinline__ void g4_body(const float* __restrict__ other, const f
 #pragma unroll
   for (int i = 0; i < GRPW; ++i) {
     const int sg = (i * kWaves + wave) * 64 + lane;
-    vbG[i] = OOB; gpi[i] = -1;
+    vbG[i] = kOOB; gpi[i] = -1;
     if (sg < GSLOTS) {
       const int spi = sg / (D * GSLS), oo = (sg / GSLS) % D, gq = sg % GSLS;
       if (WHICH == 0) {
@@ -765,7 +758,7 @@ __device__ __forceinline__ void g4_body(const float* __restrict__ other, const f
   auto stage_b = [&](int rr, int slot) {
     const int yb = S2 * rr + py;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_n + (size_t)yb * g.W), 0,
-                                                                        src_bytes - 4u * (unsigned)(yb * g.W), 0x00020000);
+                                                                        src_bytes - 4u * (unsigned)(yb * g.W), kRsrcWord3);
     const unsigned dst = lds_base + 4u * (unsigned)(slot * BBUF);
 #pragma unroll
     for (int i = 0; i < BRPW; ++i) {
@@ -777,14 +770,14 @@ __device__ __forceinline__ void g4_body(const float* __restrict__ other, const f
     const int yb = S2 * rr + py;
     // (the base may point below the blob for displacement rows that do not exist: those lanes are masked)
     const long long goff = WHICH == 0 ? (long long)(rr - i0 + R - 3) * D * plane : (long long)(i0 - rr + R) * D * plane + (long long)yb * g.W;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(td_n + goff), 0, (unsigned)((long long)td_bytes - 4 * goff), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(td_n + goff), 0, (unsigned)((long long)td_bytes - 4 * goff), kRsrcWord3);
     const unsigned dst = g_base + 4u * (unsigned)(slot * GBUF);
 #pragma unroll
     for (int i = 0; i < GRPW; ++i) {
       const int run = i * kWaves + wave;
       if (run < GRUN && !(kAbl4 & 1)) {
         const int q = WHICH == 0 ? rr - i0 - gpi[i] : i0 + gpi[i] - rr;          // displacement row of this slab row
-        const unsigned v = (gpi[i] >= 0 && q >= -R && q <= R) ? vbG[i] : OOB;
+        const unsigned v = (gpi[i] >= 0 && q >= -R && q <= R) ? vbG[i] : kOOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(uintptr_t)(dst + 1024u * (unsigned)run), 16, v, 0, 0, 0);
       }
     }

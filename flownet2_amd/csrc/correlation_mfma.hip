@@ -27,19 +27,24 @@
 // Scheduling: decode_task below (live tasks first, dead tasks last, lists balanced over the 8 XCDs).
 #include <algorithm>
 #include "correlation.hpp"
+#include "mfma_tile.hpp"
 
 #include <type_traits>
 
 namespace fn2 {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using mfma::cdiv;
+using mfma::f32x2;
+using mfma::f32x4;
+using mfma::kOOB;
+using mfma::kRsrcWord3;
+using mfma::lds_ptr_t;
+using mfma::up_mod;
+using mfma::wait_vmcnt;
 
 constexpr int kWaves = 8;
 constexpr int kThreads = kWaves * 64;
 constexpr int kKC = 16;   // channel granularity of the MFMA paths (two 8-channel chunks per loop trip)
 
-constexpr int up_mod(int v, int r, int m) { return v + ((r - v % m) + m) % m; }   // smallest >= v with == r (mod m)
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 template <int S2, int R>
@@ -195,7 +200,7 @@ __device__ __forceinline__ void epilogue(const Acc& acc, float* smem, float* __r
   if (x < g.W && STORE) {
     const unsigned plane = (unsigned)g.H * (unsigned)g.W;
     const __amdgpu_buffer_rsrc_t rsT = __builtin_amdgcn_make_buffer_rsrc(
-        top + ((size_t)k.n * g.ctot + g.c0) * plane, 0, 4u * K::D * K::D * plane, 0x00020000);
+        top + ((size_t)k.n * g.ctot + g.c0) * plane, 0, 4u * K::D * K::D * plane, kRsrcWord3);
     const unsigned hw4 = 4u * plane, w4 = 4u * (unsigned)g.W;
     constexpr int STEP = kThreads / K::SPANPX;
     int rowid = tid / K::SPANPX, rmi = 0, rni = 0, oo = rowid;
@@ -258,21 +263,12 @@ struct GCfg {
   static_assert(RPW >= 1 && RPW <= 15, "vmcnt immediates below");
 };
 
-using lds_ptr_t = __attribute__((address_space(3))) void*;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 15, "");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int S2, int R, int LO, int HI, int ABL, typename Acc>
 __device__ __forceinline__ void k_loop_glds(Acc& acc, float* smem, const float* a_n, const float* b_n, const MfmaArgs& g,
                                             unsigned lds_base, int lane, int wave, int px, int Jw, int py, int i0, int i2_0, int jS) {
   using K = Cfg<S2, R>;
   using G = GCfg<S2, R>;
   const int plane = g.H * g.W;
-  constexpr unsigned OOB = 0x7ffffff0u;
 
   // ---- run plan of this wave.  Slot i < RB: second-map run i * 8 + wave, slot RB + i: first-map run i * 8 + wave.
   // The slot -> map assignment is static so the issue code is straight-line (it is interleaved with MFMAs below);
@@ -282,7 +278,7 @@ __device__ __forceinline__ void k_loop_glds(Acc& acc, float* smem, const float* 
 #pragma unroll
   for (int i = 0; i < G::RB; ++i) {
     const int rho = i * kWaves + wave;
-    voff[i] = OOB; ldst[i] = 4 * G::CHUNK;
+    voff[i] = kOOB; ldst[i] = 4 * G::CHUNK;
     if (rho < G::NBR) {
       const int grp = (rho * 64) / G::GROUP;                   // uniform
       const int rem = rho * 64 - grp * G::GROUP + lane;
@@ -297,7 +293,7 @@ __device__ __forceinline__ void k_loop_glds(Acc& acc, float* smem, const float* 
 #pragma unroll
   for (int i = 0; i < G::RA; ++i) {
     const int ra = i * kWaves + wave;
-    voff[G::RB + i] = OOB; ldst[G::RB + i] = 4 * G::CHUNK;
+    voff[G::RB + i] = kOOB; ldst[G::RB + i] = 4 * G::CHUNK;
     if (ra < G::NAR) {
       const int ch = ra >> 1, half = ra & 1;
       const int row = 2 * half + (lane >> 5), col = lane & 31;
@@ -308,11 +304,11 @@ __device__ __forceinline__ void k_loop_glds(Acc& acc, float* smem, const float* 
     }
   }
   const unsigned chunk_bytes = 4u * G::KC * (unsigned)plane;
-  // Descriptors span the whole sample; the chunk is selected by the scalar offset.  OOB (2 GiB - 16) is beyond any
+  // Descriptors span the whole sample; the chunk is selected by the scalar offset.  kOOB (2 GiB - 16) is beyond any
   // supported sample (C * H * W < 2^28 floats), so such lanes read 0.0f = the zero padding.
   const unsigned sample_bytes = 4u * (unsigned)g.C * (unsigned)plane;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a_n), 0, sample_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_n), 0, sample_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a_n), 0, sample_bytes, kRsrcWord3);
+  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_n), 0, sample_bytes, kRsrcWord3);
 
   // one LDS-DMA run: M0 = destination, 64 lanes x 4 B
   auto run = [&](int i, unsigned slot_bytes, unsigned soff) {
@@ -515,7 +511,6 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
   using K = Cfg<2, R>;
   using H = HCfg<R>;
   const int plane = g.H * g.W;
-  constexpr unsigned OOB = 0x7ffffff0u;
 
   // ---- run plan: run rho = i * WAVES + wave; lane -> one 16-byte slot (4 pixels of one row and channel) ----
   unsigned voff[H::RPW];
@@ -524,7 +519,7 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
 #pragma unroll
   for (int i = 0; i < H::RPW; ++i) {
     const int rho = i * H::WAVES + wave;
-    voff[i] = OOB; ldst[i] = 0; isB[i] = rho < H::NBR;
+    voff[i] = kOOB; ldst[i] = 0; isB[i] = rho < H::NBR;
     if (rho < H::NBR) {
       const int sl = rho * 64 + lane;                        // slot index in [ch][row][group]
       const int ch = sl / (4 * H::BQ), rem = sl % (4 * H::BQ);
@@ -545,8 +540,8 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
   const bool full = wave < H::NFULL;                         // this wave issues RPW (else RPW - 1) runs per chunk
   const unsigned chunk_bytes = 4u * H::KC * (unsigned)plane;
   const unsigned sample_bytes = 4u * (unsigned)g.C * (unsigned)plane;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a_n), 0, sample_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_n), 0, sample_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a_n), 0, sample_bytes, kRsrcWord3);
+  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_n), 0, sample_bytes, kRsrcWord3);
   auto run = [&](int i, unsigned slot_bytes, unsigned soff) {
     if (i == H::RPW - 1 && !full) return;                    // wave-uniform
     if constexpr (PROJ == 3) { if (i & 1) return; }          // profiling: half the staging traffic, all the MFMAs
@@ -568,7 +563,6 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
   constexpr int NT = (LO <= HI) ? HI - LO + 1 : 0;
   constexpr int KS = H::KC / 4;
   static_assert(KS == 2, "half-iteration schedule below");
-  using f32x2 = __attribute__((ext_vector_type(2))) float;
 
   struct Ops { f32x2 a[KS]; f32x2 b[KS][NT > 0 ? NT : 1]; };
   auto read_ops = [&](Ops& o, const float* buf) {
@@ -723,7 +717,7 @@ corr_fwd_pair(const float* __restrict__ b0, const float* __restrict__ b1, float*
   // Output rows of this task: rowid = (rmi * 4 + rni) * D + oo  <->  top[n, (qq = 4a + rni - rmi, oo), y = 2 (4I + rmi) + py,
   // 32-pixel span].  8 threads x 16 bytes per row, 32 rows per pass; offsets are 32-bit inside the sample's output (buffer store).
   const __amdgpu_buffer_rsrc_t rsT = __builtin_amdgcn_make_buffer_rsrc(
-      top + top_n * plane, 0, (unsigned)(4u * K::D * K::D * (unsigned)plane), 0x00020000);
+      top + top_n * plane, 0, (unsigned)(4u * K::D * K::D * (unsigned)plane), kRsrcWord3);
   // Dead tasks write zeros for the rows that exist; live tasks look the row's offset up in a table
   // the workgroup builds once (the decode, its range tests and the offset arithmetic cost ~25 VALU instructions per row and thread before --
   // VALU time is matrix-pipe time for the workgroups still in their K loops, and the epilogue + DMA plan were 1.4 VALU instructions per MFMA

@@ -36,15 +36,19 @@
 #include <vector>
 
 #include "correlation.hpp"
+#include "mfma_tile.hpp"
 
 namespace fn2 {
+using mfma::f32x2;
+using mfma::f32x4;
+using mfma::kOOB;
+using mfma::kRsrcWord3;
+using mfma::lds_ptr_t;
+using mfma::wait_vmcnt;
 namespace cu3 {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
 
 constexpr int R = 10, D = 2 * R + 1, NBT = 6;         // displacement radius in class units, displacements per axis, N tiles around a patch
 constexpr int CONS = 4, WAVES = 5, THREADS = WAVES * 64;
@@ -57,7 +61,6 @@ constexpr int OROWS = 16 * D;                           // (mi, ni, o) rows of t
 constexpr int IMGF = OROWS * (8 * MAXPATCH + 1);        // floats of the largest output image; the row table sits behind it
 constexpr int LDS_FLOATS = NSLOT * SLOTF;
 static_assert(IMGF + OROWS <= LDS_FLOATS, "image + row table fit the ring");
-constexpr unsigned OOB = 0x7ffffff0u;                   // beyond any supported sample: reads as 0.0f = the zero padding
 constexpr unsigned NOROW = 0xffffffffu;
 
 struct Args {
@@ -78,12 +81,6 @@ struct Args {
   unsigned seg[MAXSEG][SEGW];
   unsigned combo[MAXCOMBO / 2];     // 16 bits each: py | I << 1 | a << 6 | seg << 9; live combos [0, TH), then dead ones [TH, TH + TD)
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 15, "");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 __device__ __forceinline__ void wg_barrier() {
   // "memory": the consumers' loop contains no store the compiler can see (the LDS is written by the loader's DMA), and s_barrier is
@@ -194,7 +191,7 @@ __device__ __forceinline__ void load_task(const float* a_n, const float* b_n, co
   unsigned voff[MAXRUNS];
 #pragma unroll
   for (int i = 0; i < MAXRUNS; ++i) {
-    voff[i] = OOB;
+    voff[i] = kOOB;
     if (i < na) {                                           // [k-step 2][channel 4][row 4][2 na slots of 16 bytes]
       const unsigned q = (unsigned)(i * 64 + lane);
       const unsigned rr = (q * magic_a) >> 16, xs = q - rr * (unsigned)(2 * na);     // rr = (k-step * 4 + channel) * 4 + row
@@ -211,8 +208,8 @@ __device__ __forceinline__ void load_task(const float* a_n, const float* b_n, co
   }
   const unsigned chunk_bytes = 32u * (unsigned)plane;       // 8 channels
   const unsigned sample_bytes = 4u * (unsigned)g.C * (unsigned)plane;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a_n), 0, sample_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_n), 0, sample_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a_n), 0, sample_bytes, kRsrcWord3);
+  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_n), 0, sample_bytes, kRsrcWord3);
   auto issue = [&](int c, int slot) {
     if constexpr (ABL & 2) return;
     const unsigned soff = (unsigned)c * chunk_bytes;
@@ -286,7 +283,7 @@ corr_fwd_units(const float* __restrict__ b0, const float* __restrict__ b1, float
   const size_t top_n = (size_t)n * g.ctot + g.c0;
   // Output rows of this task: rowid = (rmi * 4 + rni) * D + oo  <->  top[n, (qq = 4a + rni - rmi, oo), y = 2 (4I + rmi) + py, 8 np px from 8 p0];
   // offsets are 32-bit inside the sample's output (buffer store).
-  const __amdgpu_buffer_rsrc_t rsT = __builtin_amdgcn_make_buffer_rsrc(top + top_n * plane, 0, (unsigned)(4u * D * D * (unsigned)plane), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsT = __builtin_amdgcn_make_buffer_rsrc(top + top_n * plane, 0, (unsigned)(4u * D * D * (unsigned)plane), kRsrcWord3);
   const unsigned hw4 = 4u * (unsigned)plane, w4b = 4u * (unsigned)g.W;
   auto row_offset = [&](int rowid) -> unsigned {
     const int blk = rowid / D, oo = rowid - blk * D, rmi = blk >> 2, rni = blk & 3;

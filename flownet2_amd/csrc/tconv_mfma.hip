@@ -20,18 +20,13 @@
 // consecutive output pixels, bias + ReLU, two 16-byte stores; the top blob may be a channel slice of a Concat blob.
 // Summation order per output element (restated by the oracle twin fn2_tconv_forward_cpu): channel quads ascending, within a quad the
 // taps (ky, kx) of the element's class ascending, within a tap the 4 channels -- the same for every tile variant (same bits).
-#include "fn2_common.hpp"
-#include "autotune.hpp"
+#include "conv_internal.hpp"
+#include "mfma_tile.hpp"
 
 namespace fn2 {
 namespace tc {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using lds_ptr_t = __attribute__((address_space(3))) void*;
-
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
-constexpr int up_mod(int v, int r, int m) { return v + ((r - v % m) + m) % m; }
+using namespace mfma;
 
 struct Args {
   const float* in; const float* wp; const float* bias; float* out;
@@ -56,53 +51,23 @@ template <int KS, int PAD> struct Par {
 };
 
 template <int KS_, int PAD_, int MW_, int NP_, int WM_, int WNX_, int WNY_, int CQ_>
-struct Cfg {
+struct Cfg : Window<4 * WNY_ + Par<KS_, PAD_>::dmax() - Par<KS_, PAD_>::dmin(),      // window rows: input rows i0 + DMIN .. i0 + TH - 1 + DMAX
+                    4 * NP_ * WNX_ + 4 + Par<KS_, PAD_>::dmax(),                     // window columns: input columns j0 - PADL .. j0 + TW - 1 + DMAX
+                    CQ_, WM_ * WNX_ * WNY_> {
   static constexpr int KS = KS_, PAD = PAD_, MW = MW_, NP = NP_, WM = WM_, WNX = WNX_, WNY = WNY_, CQ = CQ_;
   using P = Par<KS, PAD>;
   static constexpr int NW = WM * WNX * WNY, THREADS = 64 * NW;
   static constexpr int DMIN = P::dmin(), DMAX = P::dmax(), ND = DMAX - DMIN + 1;
   static constexpr int PADL = 4;                                     // window column 0 <-> input column j0 - PADL (16-byte aligned)
   static constexpr int TW = 4 * NP * WNX, TH = 4 * WNY;              // class positions of a workgroup tile (2 TW x 2 TH output pixels)
-  static constexpr int WR = TH + ND - 1;                             // window rows: input rows i0 + DMIN .. i0 + TH - 1 + DMAX
-  static constexpr int WC = TW + PADL + DMAX;                        // window columns: input columns j0 - PADL .. j0 + TW - 1 + DMAX
-  static constexpr int RS = up_mod(cdiv(WC, 4) * 4, 4, 16);
-  static constexpr int CS = up_mod(WR * RS, 16, 32);
-  static constexpr int SLOTS_C = CS / 4;
-  static constexpr int SLOTS = 4 * CQ * SLOTS_C;
-  static constexpr int NRUN = cdiv(SLOTS, 64);
-  static constexpr int RPW = cdiv(NRUN, NW);
-  static constexpr int BUF = NRUN * 256;
+  static_assert(Cfg::WR == TH + ND - 1 && Cfg::WC == TW + PADL + DMAX, "window of the tile");
   static constexpr int KSC = CQ * KS * KS;
-  static constexpr int NBUFA = (KSC % 6 == 0) ? 6 : (KSC % 5 == 0) ? 5 : (KSC % 7 == 0) ? 7 : (KSC % 4 == 0) ? 4 : 3;
+  static constexpr int NBUFA = ring_depth(KSC);
   static_assert(KSC % NBUFA == 0, "ring phase must repeat per chunk");
   static_assert(-DMIN <= PADL, "left margin");
-  static_assert(2 * BUF * 4 <= 80 * 1024, "LDS (two workgroups per CU)");
+  static_assert(2 * Cfg::BUF * 4 <= 80 * 1024, "LDS (two workgroups per CU)");
   static_assert(NW == 4, "256 threads");
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int MW> struct WVec;
-template <> struct WVec<1> { using T = float; };
-template <> struct WVec<2> { using T = f32x2; };
-template <> struct WVec<4> { using T = f32x4; };
-template <int MW>
-__device__ __forceinline__ float wget(const typename WVec<MW>::T& v, int j) {
-  if constexpr (MW == 1) return v; else return v[j];
-}
-
-template <class K>
-__device__ __forceinline__ void stage_chunk(__amdgpu_buffer_rsrc_t rs, const unsigned (&voff)[K::RPW], unsigned dst, int wave, unsigned soff) {
-#pragma unroll
-  for (int i = 0; i < K::RPW; ++i) {
-    const int r = i * K::NW + wave;
-    if (r < K::NRUN)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(uintptr_t)(dst + 1024u * (unsigned)r), 16, voff[i], soff, 0, 0);
-  }
-}
 
 template <class K>
 __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by, int n) {
@@ -116,22 +81,9 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
 
   // ---- LDS-DMA plan: slot s = 64 (i NW + wave) + lane -> (channel of the chunk, window row, group of 4 window columns)
   const size_t plane = (size_t)a.Hin * a.Win;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.in + ((size_t)n * a.in_ctot + a.in_c0) * plane), 0, (unsigned)(4u * a.Cin * plane), 0x00020000);
-  constexpr unsigned OOB = 0x7ffffff0u;
+  const __amdgpu_buffer_rsrc_t rs = nchw_rsrc(a.in, n, a.in_ctot, a.in_c0, a.Cin, plane);
   unsigned voff[K::RPW];
-#pragma unroll
-  for (int i = 0; i < K::RPW; ++i) {
-    const int s = (i * K::NW + wave) * 64 + lane;
-    voff[i] = OOB;
-    if (s < K::SLOTS) {
-      const int c = s / K::SLOTS_C, rem = s % K::SLOTS_C;
-      const int row = rem / (K::RS / 4), gq = rem % (K::RS / 4);
-      const int yi = i0 + K::DMIN + row, xi = j0 - K::PADL + 4 * gq;
-      if (row < K::WR && 4 * gq < K::WC && yi >= 0 && yi < a.Hin && xi >= 0 && xi < a.Win)
-        voff[i] = 4u * (unsigned)(c * plane + (size_t)yi * a.Win + xi);
-    }
-  }
+  window_plan<K>(voff, wave, lane, i0 + K::DMIN, j0 - K::PADL, a.Hin, a.Win, plane);
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
   const unsigned chunk_bytes = 4u * 4u * K::CQ * (unsigned)plane;
   auto stage = [&](int chunk, int buf) { stage_chunk<K>(rs, voff, lds_base + 4u * (unsigned)(buf * K::BUF), wave, (unsigned)chunk * chunk_bytes); };
@@ -141,8 +93,7 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
   const int bbase = kq * K::CS + (4 * wny + pi - K::DMIN) * K::RS + (4 * NP * wnx + pj) + K::PADL;   // + d_of(ky) * RS + d_of(kx)
   using WV = typename WVec<MW>::T;
   const int cg0 = (g * K::WM + wm) * MW;
-  const float* wl = a.wp + ((size_t)(cg0 / 4) * a.ksteps * 64 + lane) * 4 + (cg0 % 4);
-  auto wload = [&](int ks) -> WV { return *reinterpret_cast<const WV*>(wl + (size_t)ks * 256); };
+  const float* wl = weight_lane(a.wp, cg0, a.ksteps, lane);
 
   f32x4 acc[4][MW][NP];
 #pragma unroll
@@ -155,7 +106,7 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
   WV wreg[K::NBUFA];
   stage(0, 0);
 #pragma unroll
-  for (int i = 0; i < K::NBUFA - 1; ++i) wreg[i] = wload(i);
+  for (int i = 0; i < K::NBUFA - 1; ++i) wreg[i] = weight_load<MW>(wl, i);
 
   for (int c = 0; c < a.nchunks; ++c) {
     const int buf = c & 1;
@@ -175,7 +126,7 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int ks = 0; ks < K::KSC; ++ks) {
-      wreg[(ks + K::NBUFA - 1) % K::NBUFA] = wload(ks0 + ks + K::NBUFA - 1);      // the packed array carries spare k-steps
+      wreg[(ks + K::NBUFA - 1) % K::NBUFA] = weight_load<MW>(wl, ks0 + ks + K::NBUFA - 1);      // the packed array carries spare k-steps
       const int ky = (ks / KS) % KS, kx = ks % KS;
       const int cls = 2 * P::par_of(ky) + P::par_of(kx);
       const WV w = wreg[ks % K::NBUFA];
@@ -205,13 +156,7 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
         for (int p = 0; p < NP; ++p) {
           const int X0 = 2 * (j0 + 4 * (NP * wnx + p));
           const f32x4 e = acc[2 * py][j][p], o = acc[2 * py + 1][j][p];
-          float v[8] = {e[0], o[0], e[1], o[1], e[2], o[2], e[3], o[3]};
-#pragma unroll
-          for (int r = 0; r < 8; ++r) {
-            float s = v[r] + bv;
-            if (a.relu) s = s > 0.f ? s : s * a.slope;
-            v[r] = s;
-          }
+          f32x4 v[2] = {bias_relu4(f32x4{e[0], o[0], e[1], o[1]}, bv, a.relu, a.slope), bias_relu4(f32x4{e[2], o[2], e[3], o[3]}, bv, a.relu, a.slope)};
           if (a.mask) {
             const float* mrow = a.mask + (((size_t)n * a.mask_ctot + a.mask_c0 + co) * a.Hout + Y) * a.Wout;
             float m[8];
@@ -224,15 +169,10 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
               for (int r = 0; r < 8; ++r) m[r] = X0 + r < a.Wout ? mrow[X0 + r] : 1.f;
             }
 #pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] *= m[r] > 0.f ? 1.f : a.mask_slope;      // the expression of bias_leaky_relu_bwd: the same bits
+            for (int r = 0; r < 8; ++r) v[r >> 2][r & 3] *= m[r] > 0.f ? 1.f : a.mask_slope;      // the expression of bias_leaky_relu_bwd: the same bits
           }
-          if (X0 + 7 < a.Wout) {
-            *reinterpret_cast<f32x4*>(orow + X0) = f32x4{v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(orow + X0 + 4) = f32x4{v[4], v[5], v[6], v[7]};
-          } else {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) if (X0 + r < a.Wout) orow[X0 + r] = v[r];
-          }
+          store4(orow, X0, a.Wout, v[0]);
+          store4(orow, X0 + 4, a.Wout, v[1]);
         }
       }
     }
@@ -242,9 +182,8 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
 template <class K>
 __global__ void __launch_bounds__(256, 2)
 tconv_mfma(Args a) {
-  const unsigned per_xcd = (a.total + 7) / 8;
-  unsigned t = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  if (blockIdx.x / 8 >= per_xcd || t >= a.total) return;
+  unsigned t;
+  if (!xcd_task(blockIdx.x, a.total, t)) return;
   const int g = t % a.ng; t /= a.ng;
   const int bx = t % a.tx; t /= a.tx;
   const int by = t % a.ty;
@@ -267,11 +206,7 @@ static int launch(const Args& base, hipStream_t st) {
   if (tiles > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "tconv: grid too large");
   a.total = (unsigned)tiles;
   constexpr size_t lds = sizeof(float) * 2 * K::BUF;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_mfma<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  set_dynamic_lds_once<&tconv_mfma<K>>((int)lds);
   hipLaunchKernelGGL((tconv_mfma<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), lds, st, a);
   return check_launch("tconv_forward");
 }
@@ -297,7 +232,7 @@ static bool variant_applies(const Variant& v, const Args& a, int KS, int pad) {
 }
 
 // workgroups over 512 slots (two per CU) x accumulator tiles of a wave, mild penalty for small wave tiles
-static double variant_cost(const Variant& v, const Args& a) {
+static double variant_cost(const Variant& v, const Args& a, bool /*tail*/) {
   const int Hc = cdiv(a.Hout, 2), Wc = cdiv(a.Wout, 2);
   const long long wgs = (long long)a.N * cdiv(Wc, 4 * v.np * v.wnx) * cdiv(Hc, 4 * v.wny) * (a.Cout / (16 * v.mw * v.wm));
   const double rounds = (double)((wgs + 511) / 512);
@@ -326,13 +261,6 @@ FN2_API int fn2_tconv_supported(int Cin, int Hin, int Win, int Cout, int Hout, i
 FN2_API int fn2_debug_set_tconv_variant(int v) { tc::g_forced_variant = v; return FN2_OK; }
 FN2_API int fn2_tconv_num_variants(void) { return tc::kNumVariants; }
 
-namespace fn2 {
-int tconv_forward_masked(const float* bottom, const float* packed_weight, const float* bias, float* top,
-                         int N, int Cin, int Hin, int Win, int bottom_channels, int bottom_c0,
-                         int Cout, int Hout, int Wout, int top_channels, int top_c0, int kernel, int pad,
-                         int relu, float negative_slope, const float* mask, int mask_channels, int mask_c0, float mask_slope, void* stream);
-}
-
 FN2_API int fn2_tconv_forward(const float* bottom, const float* packed_weight, const float* bias, float* top,
                               int N, int Cin, int Hin, int Win, int bottom_channels, int bottom_c0,
                               int Cout, int Hout, int Wout, int top_channels, int top_c0, int kernel, int pad,
@@ -347,13 +275,11 @@ int fn2::tconv_forward_masked(const float* bottom, const float* packed_weight, c
                               int relu, float negative_slope, const float* mask, int mask_channels, int mask_c0, float mask_slope, void* stream) {
   if (N < 0) return fail(FN2_ERR_INVALID_ARG, "tconv: bad batch");
   if (N == 0) return FN2_OK;
-  if (!bottom || !packed_weight || !top) return fail(FN2_ERR_INVALID_ARG, "tconv: null blob");
-  if (!tc::geometry_ok(Cin, Hin, Win, Cout, Hout, Wout, kernel, pad))
-    return fail(FN2_ERR_UNSUPPORTED, "tconv: unsupported geometry (Cin %d, %dx%d, Cout %d, out %dx%d, k %d p %d)", Cin, Hin, Win, Cout, Hout, Wout, kernel, pad);
-  if (bottom_c0 < 0 || bottom_c0 + Cin > bottom_channels || top_c0 < 0 || top_c0 + Cout > top_channels)
-    return fail(FN2_ERR_INVALID_ARG, "tconv: channel slice outside the blob");
-  if (((reinterpret_cast<uintptr_t>(bottom) | reinterpret_cast<uintptr_t>(top) | reinterpret_cast<uintptr_t>(packed_weight)) & 15) != 0)
-    return fail(FN2_ERR_UNSUPPORTED, "tconv: blobs must be 16-byte aligned");
+  if (const int rc = mfma::check_conv_args("tconv", bottom, packed_weight, top, Cin, bottom_channels, bottom_c0, Cout, top_channels, top_c0, [&] {
+        return tc::geometry_ok(Cin, Hin, Win, Cout, Hout, Wout, kernel, pad) ? FN2_OK
+            : fail(FN2_ERR_UNSUPPORTED, "tconv: unsupported geometry (Cin %d, %dx%d, Cout %d, out %dx%d, k %d p %d)", Cin, Hin, Win, Cout, Hout, Wout, kernel, pad);
+      }))
+    return rc;
   tc::Args a{};
   a.in = bottom; a.wp = packed_weight; a.bias = bias; a.out = top;
   a.N = N; a.Cin = Cin; a.Hin = Hin; a.Win = Win; a.in_ctot = bottom_channels; a.in_c0 = bottom_c0;
@@ -366,29 +292,13 @@ int fn2::tconv_forward_masked(const float* bottom, const float* packed_weight, c
   }
   a.mask = mask; a.mask_ctot = mask_channels; a.mask_c0 = mask_c0; a.mask_slope = mask_slope;
   hipStream_t st = as_stream(stream);
-  int best = -1;
-  if (tc::g_forced_variant >= 0) {
-    best = tc::g_forced_variant;
-    if (best >= tc::kNumVariants || !tc::variant_applies(tc::kVariants[best], a, kernel, pad))
-      return fail(FN2_ERR_UNSUPPORTED, "tconv: forced variant %d does not apply", best);
-  } else {
-    if (autotune_enabled(st)) {
-      static TuneCache cache("tconv", tc::kNumVariants);
-      const TuneKey key{N, Cin, Hin, Win, Cout, Hout, Wout, kernel * 16 + pad, bottom_channels == Cin, top_channels == Cout};
-      auto usable = [&](int c) -> bool { return tc::variant_applies(tc::kVariants[c], a, kernel, pad); };
-      best = autotune_pick(cache, key, tc::kNumVariants, st, [&](int c) -> int {
-        return usable(c) ? tc::kVariants[c].fn(a, st) : FN2_ERR_UNSUPPORTED;
-      }, usable);
-    }
-    if (best < 0) {
-      double bc = 0;
-      for (int i = 0; i < tc::kNumVariants; ++i) {
-        if (!tc::variant_applies(tc::kVariants[i], a, kernel, pad)) continue;
-        const double c = tc::variant_cost(tc::kVariants[i], a);
-        if (best < 0 || c < bc) { best = i; bc = c; }
-      }
-    }
-  }
-  if (best < 0) return fail(FN2_ERR_UNSUPPORTED, "tconv: no kernel variant for this geometry");
-  return tc::kVariants[best].fn(a, st);
+  static TuneCache cache("tconv", tc::kNumVariants);
+  const TuneKey key{N, Cin, Hin, Win, Cout, Hout, Wout, kernel * 16 + pad, bottom_channels == Cin, top_channels == Cout};
+  mfma::Pick p;
+  if (const int rc = mfma::pick_variant(p, "tconv", tc::g_forced_variant, tc::kNumVariants, false, cache, key, st,
+                                        [&](int i) { return tc::variant_applies(tc::kVariants[i], a, kernel, pad); },
+                                        [&](int i, bool tail) { return tc::variant_cost(tc::kVariants[i], a, tail); },
+                                        [&](int i, bool) { return tc::kVariants[i].fn(a, st); }, [](int) { return false; }))
+    return rc;
+  return tc::kVariants[p.variant].fn(a, st);
 }

@@ -30,6 +30,7 @@ DGRAD = {
     "tconv-5x5": (TCONV, False, 2, 64, 16, 24, 96, 5, 2, 2),              # conv2 / conv3 class
     "tconv-5x5-c128": (TCONV, False, 2, 64, 16, 24, 128, 5, 2, 2),        # (the same with a forward kernel: the 96-output one has none)
     "tconv-3x3-odd": (TCONV, False, 2, 128, 17, 32, 64, 3, 2, 1),         # odd bottom height
+    "tconv-3x3-9x7": (TCONV, False, 1, 64, 9, 7, 8, 3, 2, 1),             # odd bottom width: the mask read and the store take their scalar tails
     "deconv-plane-10x14": (DECONV_PLANE, False, 2, 64, 10, 14, 128, 3, 2, 1),   # conv5 / conv6 class: top 5x7
     "deconv-plane-6x10": (DECONV_PLANE, False, 2, 64, 6, 10, 128, 3, 2, 1),
     "plane-5x7": (PLANE, False, 2, 40, 5, 7, 64, 3, 1, 1),                # Cp 64

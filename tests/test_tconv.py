@@ -21,7 +21,8 @@ def torch_tconv64(x, w, b, k, p, out_hw):
 
 # (N, Cin, Hin, Win, Cout, kernel, pad, extra output rows / columns)
 CASES = [(2, 13, 5, 8, 64, 4, 1, 0), (1, 20, 7, 12, 128, 5, 2, 1), (2, 9, 6, 16, 64, 3, 1, 1), (1, 64, 3, 4, 64, 4, 1, 0),
-         (1, 33, 9, 20, 64, 5, 2, 0), (3, 8, 4, 8, 192, 3, 1, 0)]
+         (1, 33, 9, 20, 64, 5, 2, 0), (3, 8, 4, 8, 192, 3, 1, 0),
+         (1, 8, 5, 4, 64, 3, 1, 0)]      # output 9x7: the odd width ends inside the 8 pixels of a lane (scalar-tail stores)
 
 
 def out_size(case):
