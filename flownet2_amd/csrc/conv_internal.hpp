@@ -15,4 +15,12 @@ int tconv_forward_masked(const float* bottom, const float* packed_weight, const 
 int conv_k7s2_wgrad_bias(const float* top_diff, const float* bottom, float* weight_diff, float* bias_diff, int N, int Cin, int Hin, int Win, int Cout,
                          int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
+// csrc/conv_bf16x3.hip: the direct convolution in split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3 beside FN2_CONV_ROUTE_DIRECT); which layers
+// it takes: fn2_conv_bf16x3_supported.  The operand holds the three bf16 planes of the weights (0 floats: no operand for these channels).
+size_t conv_bf16x3_packed_floats(int Cout, int Cin, int kernel);
+int conv_bf16x3_pack_weights(const float* weight, float* packed, int Cout, int Cin, int kernel, void* stream);
+int conv_bf16x3_forward(const float* bottom, const float* packed_weight, const float* bias, float* top, int N, int Cin, int Hin, int Win,
+                        int bottom_channels, int bottom_c0, int Cout, int top_channels, int top_c0, int kernel, int stride, int pad,
+                        int relu, float negative_slope, void* stream);
+
 }  // namespace fn2

@@ -40,6 +40,12 @@ bool conv_route_applies(const fn2_conv_desc* d, int route) {
   }
 }
 
+// the combined value FN2_CONV_ROUTE_DIRECT | FN2_CONV_ARITH_BF16X3 on a layer the split-bf16 kernel takes (csrc/conv_bf16x3.hip); the
+// arithmetic bit on any other base route, or on any other layer, names no kernel
+bool split_route(const fn2_conv_desc* d, int route) {
+  return route == (FN2_CONV_ROUTE_DIRECT | FN2_CONV_ARITH_BF16X3) && fn2_conv_bf16x3_supported(d) != 0;
+}
+
 bool deconv_route_applies(const fn2_conv_desc* d, int route) {
   if (d->kernel != 4 || d->stride != 2 || d->pad != 1) return false;
   switch (route) {
@@ -82,12 +88,14 @@ FN2_API int fn2_conv_route(const fn2_conv_desc* d, int flags) {
       fn2_conv_plane_k_supported(d->N, Cin, H, W, Cout, 5, 2, 2) && (N == d->N || fn2_conv_plane_k_supported(N, Cin, H, W, Cout, 5, 2, 2)))
     return FN2_CONV_ROUTE_PLANE;       // conv3 of the encoders when one sample is the whole batch: the direct kernel has no K split to fill the chip with
   if (wino_ok) return FN2_CONV_ROUTE_WINOGRAD;      // too large for the small-map kernel, too small to fill the chip: still 2.25x fewer multiplies
-  if (fn2_conv_mfma_supported(Cin, H, W, Cout, k, s, p)) return FN2_CONV_ROUTE_DIRECT;
+  if (fn2_conv_mfma_supported(Cin, H, W, Cout, k, s, p))      // FN2_ROUTE_BF16X3: the same layers, in split-bf16 arithmetic where that kernel takes them
+    return ((flags & FN2_ROUTE_BF16X3) && fn2_conv_bf16x3_supported(d)) ? (FN2_CONV_ROUTE_DIRECT | FN2_CONV_ARITH_BF16X3) : FN2_CONV_ROUTE_DIRECT;
   return FN2_CONV_ROUTE_NONE;
 }
 
 FN2_API size_t fn2_conv_packed_weight_floats(const fn2_conv_desc* d, int route) {
   if (!valid(d)) return 0;
+  if (split_route(d, route)) return fn2::conv_bf16x3_packed_floats(d->Cout, d->Cin, d->kernel);
   if (route == FN2_CONV_ROUTE_WINOGRAD) return fn2_conv_wino_packed_floats(d->Cout, d->Cin);
   if (route == FN2_CONV_ROUTE_DIRECT || route == FN2_CONV_ROUTE_PLANE) return fn2_conv_mfma_packed_floats(d->Cout, d->Cin, d->kernel);
   if (route == FN2_CONV_ROUTE_STEM || route == FN2_CONV_ROUTE_HEAD) return (size_t)d->Cout * d->Cin * d->kernel * d->kernel;    // these kernels read the blob as it is
@@ -96,6 +104,7 @@ FN2_API size_t fn2_conv_packed_weight_floats(const fn2_conv_desc* d, int route) 
 
 FN2_API int fn2_conv_pack_weights(const fn2_conv_desc* d, int route, const float* weight, float* packed, void* stream) {
   if (!valid(d) || !weight || !packed) return fn2::fail(FN2_ERR_INVALID_ARG, "conv_pack_weights: bad descriptor or NULL blob");
+  if (split_route(d, route)) return fn2::conv_bf16x3_pack_weights(weight, packed, d->Cout, d->Cin, d->kernel, stream);
   if (route == FN2_CONV_ROUTE_WINOGRAD) return fn2_conv_wino_pack_weights(weight, packed, d->Cout, d->Cin, stream);
   if (route == FN2_CONV_ROUTE_DIRECT || route == FN2_CONV_ROUTE_PLANE) return fn2_conv_mfma_pack_weights(weight, packed, d->Cout, d->Cin, d->kernel, stream);
   if (route == FN2_CONV_ROUTE_STEM || route == FN2_CONV_ROUTE_HEAD) {
@@ -118,6 +127,9 @@ FN2_API int fn2_conv_forward(const fn2_conv_desc* d, int route, const float* bot
                              const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
                              int relu, float negative_slope, void* workspace, size_t workspace_bytes, void* stream) {
   if (!valid(d)) return fn2::fail(FN2_ERR_INVALID_ARG, "conv_forward: bad descriptor");
+  if (split_route(d, route))        // (its own argument checks: null blobs, channel slices, alignment -- all before anything is launched)
+    return fn2::conv_bf16x3_forward(bottom, packed_weight, bias, top, d->N, d->Cin, d->Hin, d->Win, bottom_channels, bottom_c0, d->Cout, top_channels,
+                                    top_c0, d->kernel, d->stride, d->pad, relu, negative_slope, stream);
   if (!conv_route_applies(d, route))
     return fn2::fail(FN2_ERR_UNSUPPORTED, "conv_forward: no own kernel for Convolution{kernel %d, stride %d, pad %d} %d -> %d on %d x %d (route %d)",
                      d->kernel, d->stride, d->pad, d->Cin, d->Cout, d->Hin, d->Win, route);

@@ -430,6 +430,27 @@ def set_route_force(on: bool = True):
     _ROUTE_FORCE[0] = bool(on)
 
 
+_CONV_ARITHMETICS = ("fp32", "bf16x3")
+_CONV_ARITH = ["fp32"]
+
+
+def set_conv_arithmetic(name: str = "fp32"):
+    """Arithmetic of the convolution FORWARD: "fp32" (exact fp32 products, the default) or "bf16x3" -- split-bf16 arithmetic (six bf16 piece
+    products per multiply, fp32 accumulation: include/flownet2_hip.h, FN2_CONV_ARITH_BF16X3) on the layers fn2_conv_route hands to that
+    kernel, the direct 5x5 / 2 layers; every other layer, and every backward route, stays exact fp32.  Initial value: $FN2_CONV_ARITH."""
+    if name not in _CONV_ARITHMETICS:
+        raise ValueError("conv arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
+    _CONV_ARITH[0] = name
+
+
+def conv_arithmetic() -> str:
+    return _CONV_ARITH[0]
+
+
+if os.environ.get("FN2_CONV_ARITH"):
+    set_conv_arithmetic(os.environ["FN2_CONV_ARITH"])
+
+
 def _channel_slice(x):
     """(blob, first channel): x itself, or -- when x is a channel-slice view `blob[:, c0:c0+C]` of a contiguous NCHW blob (a skip
     tensor that was written straight into its Concat blob) -- that blob and the offset, so that the kernels read it in place."""
@@ -770,7 +791,7 @@ def _needs_grad(*ts):
 def conv_forward_route(desc, act=True, whole_blobs=True) -> int:
     """The own kernel conv_mfma_relu runs this Convolution on (0 = none): the library's choice (fn2_conv_route, csrc/conv_route.cpp: thresholds,
     batch-invariant mode -- the one the Caffe adapter's Convolution gets) minus the layers this module does not serve."""
-    route = ops.conv_forward_route(desc, force=_ROUTE_FORCE[0])
+    route = ops.conv_forward_route(desc, force=_ROUTE_FORCE[0], bf16x3=_CONV_ARITH[0] == "bf16x3")
     stem = route == ops.CONV_ROUTE_STEM
     if route == ops.CONV_ROUTE_HEAD:                      # the predict_flow heads: predict_flow_conv, with an autograd function of its own
         return ops.CONV_ROUTE_NONE
@@ -791,9 +812,13 @@ def deconv_forward_route(desc, act=True) -> int:
 
 def conv_route_name(x_shape, w, stride, pad, act=True, whole_blobs=True):
     """Name (ops.CONV_FWD_ROUTES) of the kernel conv_mfma_relu runs this layer on for a CUDA bottom of this shape, None = declined: "stem"
-    is the one relu_chain producer; the FN2_TRACE_CONV print of nets.py."""
+    is the one relu_chain producer; the FN2_TRACE_CONV print of nets.py.  A layer run in split-bf16 arithmetic: "direct+bf16x3"."""
     desc = _layer_desc(w, stride, pad, False, x_shape=x_shape)
-    return ops.CONV_FWD_ROUTES[conv_forward_route(desc, act, whole_blobs)] if desc is not None else None
+    if desc is None:
+        return None
+    route = conv_forward_route(desc, act, whole_blobs)
+    name = ops.CONV_FWD_ROUTES[route & ~ops.CONV_ARITH_BF16X3]
+    return name + "+bf16x3" if name and route & ops.CONV_ARITH_BF16X3 else name
 
 
 def conv_mfma_relu(x, weight, bias, stride, pad, negative_slope=0.1, act=True, out=None, out_c0=0, relu_chain=None):

@@ -499,7 +499,26 @@ typedef struct fn2_conv_desc {
 enum { FN2_CONV_ROUTE_NONE = 0, FN2_CONV_ROUTE_DIRECT = 1, FN2_CONV_ROUTE_WINOGRAD = 2, FN2_CONV_ROUTE_PLANE = 3, FN2_CONV_ROUTE_STEM = 4,
        FN2_CONV_ROUTE_HEAD = 5 };
 enum { FN2_DECONV_ROUTE_NONE = 0, FN2_DECONV_ROUTE_GEMM = 1, FN2_DECONV_ROUTE_PLANE = 2, FN2_DECONV_ROUTE_HEAD = 3 };
-enum { FN2_ROUTE_FORCE = 1 };
+enum { FN2_ROUTE_FORCE = 1, FN2_ROUTE_BF16X3 = 2 };
+/* Arithmetic of a route, carried beside it in the route value (not a route of its own).  FN2_CONV_ARITH_BF16X3: split-bf16 arithmetic on the
+ * bf16 matrix cores (csrc/conv_bf16x3.hip), opt-in.  Every fp32 activation and weight v is cut into three bf16 pieces h = rne(v),
+ * m = rne(v - h), l = rne(v - h - m) (h + m + l == v); of the nine piece products of x * w the six leading ones -- hh, hm, mh, hl, lh, mm,
+ * each exact in fp32 -- are summed in fp32 in a fixed order (k-steps of 8 input channels x 4 taps; in a k-step mm, lh, hl, mh, hm, hh on one
+ * accumulator).  The result is bit-reproducible from run to run, does not depend on the batch (a sample has the bits it has alone) or on
+ * the tile variant, and meets the fp64 bound of the exact direct kernel; it is NOT bit-identical to that kernel (another summation order,
+ * three products of relative size < 2^-24 dropped).  Non-finite inputs: Inf splits into (inf, nan, nan), so an output whose window covers
+ * an Inf or a NaN is non-finite and may be NaN where the exact kernel gives Inf; outputs whose window covers none are unaffected.
+ * With FN2_ROUTE_BF16X3 in `flags` the route function returns FN2_CONV_ROUTE_DIRECT | FN2_CONV_ARITH_BF16X3 where it would have returned
+ * DIRECT and the split kernel takes the layer (Convolution{5, 2, 2}, Cout % 64 == 0, Win % 4 == 0), and exactly what it returns without the
+ * flag everywhere else, so a whole net can run with the flag on.  The four functions that take a route accept the combined value: the
+ * operand then holds the three bf16 planes of the weights in MFMA operand order (another size than the exact operand), no workspace.  The
+ * bit on any other base route, or on a layer the split kernel does not take, is refused on the host: FN2_ERR_UNSUPPORTED, 0 from the size
+ * queries.  Backward routes are exact fp32 whatever the forward ran in. */
+enum { FN2_CONV_ARITH_BF16X3 = 0x100 };
+int fn2_conv_bf16x3_supported(const fn2_conv_desc* desc);
+/* Test / profiling hooks of the split kernel: number of tile variants, forced variant (-1 = autotuned / cost model). */
+int fn2_conv_bf16x3_num_variants(void);
+int fn2_debug_set_conv_bf16x3_variant(int variant);
 int fn2_conv_route(const fn2_conv_desc* desc, int flags);
 size_t fn2_conv_packed_weight_floats(const fn2_conv_desc* desc, int route);
 int fn2_conv_pack_weights(const fn2_conv_desc* desc, int route, const float* weight, float* packed, void* stream);

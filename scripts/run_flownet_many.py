@@ -66,6 +66,8 @@ def main():
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection depend on the batch size (faster library "
                     "calls; a pair's bits then depend on the batch it was computed in)")
     ap.add_argument("--gpu", type=int, default=None, help="device index (default: LOCAL_RANK)")
+    ap.add_argument("--conv-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -74,6 +76,8 @@ def main():
     dev = torch.device("cuda", a.gpu if a.gpu is not None else int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
     torch.cuda.set_device(dev)
     Fn.set_batch_invariant(not a.no_batch_invariant)
+    if a.conv_arith:
+        Fn.set_conv_arithmetic(a.conv_arith)
     entries = [l.split() for l in open(a.listfile) if l.strip()]
     mine = parallel.shard(entries)
     P, mean = RF.load_params(a.net, a.weights, dev)
