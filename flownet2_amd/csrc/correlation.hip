@@ -151,41 +151,53 @@ __global__ void __launch_bounds__(256) corr_bwd_generic(const float* __restrict_
   }
 }
 
-// Set by the tests / bench through fn2_debug_set_correlation_impl: 0 = auto, 1 = force generic.
+// Set by the tests / bench through fn2_debug_set_correlation_impl(1): force the generic kernels.
 static int g_force_generic = 0;
 
 }  // namespace fn2
 
 using namespace fn2;
 
-namespace fn2 { extern int g_corr_units; extern int g_corr_units_lds; extern int g_corr_units_abl; extern int g_corr_ablation; extern int g_corr_force_dword; extern int g_corr_proj; extern int g_corr_skip_dead; extern int g_corr_simd_plan; extern int g_corr1d_force_generic; extern int g_corr1d_no_mfma; extern unsigned long long* g_corr_dbg; namespace bwd { extern int g_corr_bwd_first_gen; extern int g_corr_bwd_gen; extern int g_corr_bwd_separate; } }
-
 FN2_API int fn2_debug_set_correlation_trace(void* device_buffer) {
   fn2::g_corr_dbg = reinterpret_cast<unsigned long long*>(device_buffer);
   return FN2_OK;
 }
 
-// impl: 0 = automatic, 1 = generic kernels, 3 = general (dword LDS-DMA) MFMA forward even where the paired-parity kernel applies,
-// 5 / 6 = first / second generation of the MFMA backward, 7 / 8 / 9 = profiling builds of the paired-parity forward (3/8 of the MFMAs, no
-// MFMAs, half the staging: wrong results), 13 = paired-parity forward without the SIMD plan, 14 = no zero-fill workgroups (profiling, wrong
-// output), 64 + bits = ablation of the general MFMA forward (FN2_ABLATION builds: 1 no MFMA, 2 no staging loads, 4 no stores);
-// 19 = corr_fwd_pair (second generation) where the unit kernel applies, 20 + policy = the unit kernel with a task policy
-// (correlation_units.hip: 0 automatic, k = tasks per image row, + 16 image order), 60 + policy = the same with 16 KB of extra LDS (two workgroups per CU)
+// Test / profiling hook: which correlation kernels run.  Every hook goes back to its automatic value, then the one code applies; a value
+// that is no code changes nothing and is FN2_ERR_INVALID_ARG.  The codes keep their numbers (scripts and profile notes cite them;
+// flownet2_amd/ops.py names them).
 FN2_API int fn2_debug_set_correlation_impl(int impl) {
-  fn2::g_corr_units = impl == 19 ? 0 : (impl >= 20 && impl < 52) ? 1 + (impl - 20) : 1;
-  fn2::g_corr_units_lds = impl == 60 ? 16384 : impl == 61 ? 65536 : 0;          // 60 / 61: two / one workgroup per CU (extra dynamic LDS)
-  fn2::g_corr_units_abl = (impl >= 100 && impl < 164) ? impl - 100 : 0;
-  g_force_generic = (impl == 1);
-  fn2::g_corr1d_force_generic = (impl == 1);
-  fn2::g_corr1d_no_mfma = (impl == 17);                      // Correlation1D: the LDS-tiled VALU forward instead of the MFMA one
-  fn2::g_corr_force_dword = (impl == 3);
-  fn2::g_corr_proj = impl == 7 ? 1 : impl == 8 ? 2 : impl == 9 ? 3 : 0;   // profiling builds of the paired-parity forward: 7 = 3/8 of the MFMAs (bf16 x 3 projection), 8 = none (wrong results)
-  fn2::bwd::g_corr_bwd_first_gen = (impl == 5);
-  fn2::bwd::g_corr_bwd_gen = (impl == 6) ? 2 : (impl == 15) ? 3 : 0;      // 15 = third generation (G through LDS, one slab ahead) where the fourth applies;        // 6 = second-generation MFMA backward (LDS-DMA staging, gathered G)       // 5 = first-generation (register-staged) MFMA backward where the LDS-DMA one applies
-  fn2::bwd::g_corr_bwd_separate = (impl == 16);           // 16 = one backward launch per bottom where the merged launch applies
-  fn2::g_corr_skip_dead = (impl == 14);                  // 14 (profiling, wrong output): no zero-fill workgroups
-  fn2::g_corr_simd_plan = (impl != 13);                  // 13 = corr_fwd_pair without the SIMD plan (wave w takes patch column w)
-  fn2::g_corr_ablation = (impl >= 64 && impl < 100) ? impl - 64 : 0;
+  int generic = 0, force_dword = 0, first_gen = 0, simd_plan = 1, separate = 0, no_mfma_1d = 0;
+  int units = 1, units_lds = 0, ablation = 0, units_abl = 0;
+  switch (impl) {
+    case 0: break;                                   // automatic
+    case 1: generic = 1; break;                      // generic kernels (Correlation and Correlation1D)
+    case 3: force_dword = 1; break;                  // general dword LDS-DMA MFMA forward even where the paired-parity kernel applies
+    case 5: first_gen = 1; break;                    // corr_bwd_mfma (register-staged backward) where the G-ring kernel applies
+    case 13: simd_plan = 0; break;                   // corr_fwd_pair without the SIMD plan (wave w takes patch column w)
+    case 16: separate = 1; break;                    // one backward launch per bottom where the merged launch applies
+    case 17: no_mfma_1d = 1; break;                  // Correlation1D: the LDS-tiled VALU forward instead of the MFMA one
+    case 19: units = 0; break;                       // corr_fwd_pair where the unit kernel applies
+    case 20 ... 51: units = 1 + (impl - 20); break;  // unit kernel with a task policy (correlation_units.hip: 0 automatic, k = tasks per image row, + 16 image order)
+    case 60: units_lds = 16384; break;               // unit kernel with 16 KB of extra LDS: two workgroups per CU
+    case 61: units_lds = 65536; break;               // unit kernel with 64 KB of extra LDS: one workgroup per CU
+#ifdef FN2_ABLATION
+    case 64 ... 99: ablation = impl - 64; break;     // ablation of corr_fwd_glds: bit 0 no MFMA, 1 no staging loads, 2 no stores (wrong results)
+    case 100 ... 163: units_abl = impl - 100; break; // ablation of corr_fwd_units (wrong results)
+#endif
+    default: return fail(FN2_ERR_INVALID_ARG, "fn2_debug_set_correlation_impl: %d is not a correlation implementation code", impl);
+  }
+  g_force_generic = generic;
+  fn2::g_corr1d_force_generic = generic;
+  fn2::g_corr1d_no_mfma = no_mfma_1d;
+  fn2::g_corr_force_dword = force_dword;
+  fn2::g_corr_simd_plan = simd_plan;
+  fn2::g_corr_units = units;
+  fn2::g_corr_units_lds = units_lds;
+  fn2::g_corr_ablation = ablation;
+  fn2::g_corr_units_abl = units_abl;
+  fn2::bwd::g_corr_bwd_first_gen = first_gen;
+  fn2::bwd::g_corr_bwd_separate = separate;
   return FN2_OK;
 }
 
@@ -224,7 +236,7 @@ FN2_API int fn2_correlation_forward_fused(const fn2_corr_params* p, const float*
   if (N == 0) return FN2_OK;
   if (!bottom0 || !bottom1 || !top) return fail(FN2_ERR_INVALID_ARG, "correlation_forward: NULL blob pointer");
   hipStream_t st = as_stream(stream);
-  const bool plain = fn2::g_corr_force_dword == 0 && fn2::g_corr_proj == 0 && fn2::g_corr_ablation == 0 && fn2::g_corr_skip_dead == 0 && fn2::g_corr_simd_plan != 0;
+  const bool plain = fn2::g_corr_force_dword == 0 && fn2::g_corr_ablation == 0 && fn2::g_corr_simd_plan != 0;
   if (!g_force_generic && plain && corr_fwd_units_supported(g, bottom0, bottom1, top)) return corr_fwd_units_launch(g, bottom0, bottom1, top, st);
   if (!g_force_generic && corr_fwd_mfma_supported(g)) return corr_fwd_mfma_launch(g, bottom0, bottom1, top, st);
   const long long total = (long long)N * g.topC * g.topH * g.topW;

@@ -23,7 +23,23 @@ int corr_fwd_units_launch(const CorrGeom& g, const float* b0, const float* b1, f
 int corr_fwd_units_plan_words(int N, int H, int W, int policy, unsigned* out, int max_words);
 bool corr_bwd_mfma_supported(const CorrGeom& g);
 int corr_bwd_mfma_launch(const CorrGeom& g, int which, const float* other, const float* top_diff, float* out, hipStream_t st);
-// both bottom diffs in ONE launch (round 6); FN2_ERR_UNSUPPORTED (no error text) where it does not apply
+// both bottom diffs in ONE launch; FN2_ERR_UNSUPPORTED (no error text) where it does not apply
 int corr_bwd_mfma_launch_both(const CorrGeom& g, const float* b0, const float* b1, const float* top_diff, float* d0, float* d1, hipStream_t st);
+
+
+// Test / profiling hooks, set together by fn2_debug_set_correlation_impl (correlation.hip); each is defined beside the launch code that reads it.
+extern int g_corr_force_dword;         // correlation_mfma.hip: corr_fwd_glds even where corr_fwd_pair applies
+extern int g_corr_simd_plan;           // correlation_mfma.hip: 0 = corr_fwd_pair without the SIMD plan
+extern int g_corr_ablation;            // correlation_mfma.hip: ablation bits of corr_fwd_glds (FN2_ABLATION builds)
+extern unsigned long long* g_corr_dbg; // correlation_mfma.hip: per-workgroup trace buffer (FN2_ABLATION builds; fn2_debug_set_correlation_trace)
+extern int g_corr_units;               // correlation_units.hip: 0 = corr_fwd_pair where both apply, 1 + policy = the unit kernel
+extern int g_corr_units_lds;           // correlation_units.hip: extra dynamic LDS per workgroup, bytes
+extern int g_corr_units_abl;           // correlation_units.hip: ablation bits of corr_fwd_units (FN2_ABLATION builds)
+extern int g_corr1d_force_generic;     // correlation1d.hip: generic 1-D kernels
+extern int g_corr1d_no_mfma;           // correlation1d.hip: the LDS-tiled VALU forward instead of the MFMA one
+namespace bwd {
+extern int g_corr_bwd_first_gen;       // correlation_bwd_mfma.hip: corr_bwd_mfma where the G-ring kernel applies
+extern int g_corr_bwd_separate;        // correlation_bwd_mfma.hip: one launch per bottom where the merged launch applies
+}  // namespace bwd
 
 }  // namespace fn2

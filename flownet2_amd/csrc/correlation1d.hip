@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(256) corr1d_bwd(const float* __restrict__ b0, 
 using namespace fn2;
 
 // test hook (fn2_debug_set_correlation_impl(1) also forces the generic 1-D kernels)
-namespace fn2 { int g_corr1d_force_generic = 0; int g_corr1d_no_mfma = 0; }      // (impl 2: the LDS-tiled VALU kernel instead of the MFMA one)
+namespace fn2 { int g_corr1d_force_generic = 0; int g_corr1d_no_mfma = 0; }      // (impl 17: the LDS-tiled VALU kernel instead of the MFMA one)
 
 FN2_API int fn2_correlation1d_out_shape(const fn2_corr_params* p, int C, int H, int W, int* topC, int* topH, int* topW) {
   Corr1dGeom g;

@@ -479,6 +479,8 @@ corr_fwd_glds(const float* __restrict__ b0, const float* __restrict__ b1, float*
 //   * twice the MFMA run (24) per barrier, half the waves to synchronise.
 // First-map rows are only 32 dwords, so their 16-byte slots are XOR-swizzled (row bit 1 -> slot bit 2, channel
 // bit 0 -> slot bit 1) on the SOURCE side of the DMA and in the read address alike.
+// (A profiling build that issued only every second LDS-DMA run ran 46.3 us against 47.3: the staging volume is not what holds this
+// kernel back.  That build and two that dropped MFMAs were last held by commit 4caa9de.)
 template <int R>
 struct HCfg {
   using K = Cfg<2, R>;
@@ -500,12 +502,7 @@ struct HCfg {
   static_assert(CHB % 64 == 32, "channel stride must flip bank bit 5");
 };
 
-// PROJ (profiling only, wrong results): 0 = the kernel; 1 = only 3 of every 8 MFMAs issue -- the matrix-pipe time a split-bf16
-// (bf16 x 3, 6 products per fp32 product on v_mfma_f32_16x16x16_bf16: 48 cycles per 16 channels against 128) variant would have
-// on the same staging, LDS traffic and epilogue, with the operand split taken as free; 2 = no MFMA at all (the data-movement
-// floor of this structure); 3 = all the MFMAs, every second LDS-DMA run (half the staging traffic: 46.3 us against 47.3, i.e. the
-// staging volume is NOT what holds this kernel back).  The operands are kept alive by empty asm statements, so the LDS reads stay.
-template <int R, int LO, int HI, int PROJ = 0, typename Acc>
+template <int R, int LO, int HI, typename Acc>
 __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, const float* a_n, const float* b_n, const MfmaArgs& g,
                                             unsigned lds_base, int lane, int wave, int Jw, int py, int i0, int i2_0, int jS) {
   using K = Cfg<2, R>;
@@ -544,13 +541,11 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_n), 0, sample_bytes, kRsrcWord3);
   auto run = [&](int i, unsigned slot_bytes, unsigned soff) {
     if (i == H::RPW - 1 && !full) return;                    // wave-uniform
-    if constexpr (PROJ == 3) { if (i & 1) return; }          // profiling: half the staging traffic, all the MFMAs
     lds_ptr_t lp = (lds_ptr_t)(uintptr_t)(slot_bytes + (unsigned)ldst[i]);
     if (isB[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, lp, 16, voff[i], soff, 0, 0);
     else        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, lp, 16, voff[i], soff, 0, 0);
   };
   auto wait_landed = [&]() {                                  // everything but the newest chunk's runs has landed
-    if constexpr (PROJ == 3) { wait_vmcnt<H::RPW / 2>(); return; }
     if (full) wait_vmcnt<H::RPW>(); else wait_vmcnt<H::RPW - 1>();
   };
 
@@ -579,12 +574,6 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
   auto mfma_step = [&](const Ops& o, int r, int j) {
     if constexpr (NT > 0) {
       const int t = j >> 1;
-      if constexpr (PROJ != 0) {
-        if (PROJ == 2 || (PROJ == 1 && (j + 2 * NT * r) % 8 >= 3)) {
-          asm volatile("" ::"v"(o.a[r].x), "v"(o.a[r].y), "v"(o.b[r][t].x), "v"(o.b[r][t].y));
-          return;
-        }
-      }
       if (j & 1) acc1[LO + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[r].y, o.b[r][t].y, acc1[LO + t], 0, 0, 0);
       else       acc0[LO + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[r].x, o.b[r][t].x, acc0[LO + t], 0, 0, 0);
     }
@@ -621,7 +610,7 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
     }
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (READ && NT > 0 && PROJ == 0) {
+    if constexpr (READ && NT > 0) {
       // The operand reads of chunk c + 1 go BETWEEN the MFMAs of k-step 1, one group (the two first-map operands, then two second-map
       // tiles at a time) behind each of the first MFMAs.  Issued in one block in front of them (rounds 1-2) they are ~100 cycles in which
       // this wave feeds nothing to the matrix pipe: hidden while three waves share the SIMD, exposed once the workgroups of a CU have
@@ -676,7 +665,7 @@ __device__ __forceinline__ void k_loop_pair(Acc& acc0, Acc& acc1, float* smem, c
   chunk_step(F{}, F{}, c + 1, slot, o1, o0);
 }
 
-template <int R, int PROJ = 0>
+template <int R>
 __global__ void __launch_bounds__(256, 3)
 corr_fwd_pair(const float* __restrict__ b0, const float* __restrict__ b1, float* __restrict__ top, MfmaArgs g,
               unsigned long long* __restrict__ dbg, SimdPlan plan) {
@@ -753,7 +742,7 @@ corr_fwd_pair(const float* __restrict__ b0, const float* __restrict__ b1, float*
   {
     const int sel = tile_range_sel<2, R>(jw, Wc);
     wave_sel = sel;
-#define FN2_KLOOP(LO_, HI_) k_loop_pair<R, LO_, HI_, PROJ>(acc0, acc1, smem, a_n, b_n, g, lds_base, lane, wave, Jw, k.py, i0, i2_0, jS)
+#define FN2_KLOOP(LO_, HI_) k_loop_pair<R, LO_, HI_>(acc0, acc1, smem, a_n, b_n, g, lds_base, lane, wave, Jw, k.py, i0, i2_0, jS)
     switch (sel) {
       case 0: FN2_KLOOP(0, K::HI_MIN + 0); break;
       case 1: FN2_KLOOP(0, K::HI_MIN + 1); break;
@@ -841,7 +830,6 @@ corr_fwd_pair(const float* __restrict__ b0, const float* __restrict__ b1, float*
 #endif
 }
 
-int g_corr_skip_dead = 0;     // profiling hook (fn2_debug_set_correlation_impl(14)): launch no zero-fill workgroups
 int g_corr_simd_plan = 1;      // profiling / test hook (fn2_debug_set_correlation_impl(13) switches the SIMD plan of corr_fwd_pair off)
 
 // Tile units of wave Jw of a span (the specialised N-tile ranges of tile_range_sel).
@@ -902,7 +890,6 @@ static void build_simd_plan(const MfmaArgs& g, SimdPlan& plan) {
 }
 
 int g_corr_force_dword = 0;   // test hook: run the general (dword LDS-DMA) kernel even where the paired one applies
-int g_corr_proj = 0;          // profiling hook (fn2_debug_set_correlation_impl(7 / 8)): the PROJ = 1 / 2 builds of corr_fwd_pair
 
 template <int S2, int R>
 static int launch(const CorrGeom& cg, const float* b0, const float* b1, float* top, hipStream_t st) {
@@ -926,7 +913,6 @@ static int launch(const CorrGeom& cg, const float* b0, const float* b1, float* t
   if (NL + ND > (1ll << 30)) return fail(FN2_ERR_UNSUPPORTED, "correlation: problem too large for the MFMA path");
   g.LP = (int)((NL + 7) / 8);
   g.DP = (int)((ND + 7) / 8);
-  if (g_corr_skip_dead) g.DP = 0;          // profiling only (wrong output): what the zero-fill workgroups cost
   const unsigned grid = 8u * (unsigned)(g.LP + g.DP);
   if constexpr (S2 == 2 && R == 10) {
     const bool aligned = cg.W % 4 == 0 &&
@@ -935,41 +921,13 @@ static int launch(const CorrGeom& cg, const float* b0, const float* b1, float* t
       const size_t lds3 = sizeof(float) * HCfg<R>::LDS_FLOATS;
       SimdPlan plan;
       build_simd_plan<R>(g, plan);
-      static bool attr3_set = false;
-      if (!attr3_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_fwd_pair<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-        attr3_set = true;
-      }
-      if (g_corr_proj == 3) {
-        static bool attrq_set = false;
-        if (!attrq_set) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_fwd_pair<R, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-          attrq_set = true;
-        }
-        hipLaunchKernelGGL((corr_fwd_pair<R, 3>), dim3(grid), dim3(HCfg<R>::THREADS), lds3, st, b0, b1, top, g, g_corr_dbg, plan);
-        return check_launch("correlation_forward (mfma, paired parities, projection build)");
-      }
-      if (g_corr_proj == 1 || g_corr_proj == 2) {
-        static bool attrp_set = false;
-        if (!attrp_set) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_fwd_pair<R, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_fwd_pair<R, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-          attrp_set = true;
-        }
-        if (g_corr_proj == 1) hipLaunchKernelGGL((corr_fwd_pair<R, 1>), dim3(grid), dim3(HCfg<R>::THREADS), lds3, st, b0, b1, top, g, g_corr_dbg, plan);
-        else                  hipLaunchKernelGGL((corr_fwd_pair<R, 2>), dim3(grid), dim3(HCfg<R>::THREADS), lds3, st, b0, b1, top, g, g_corr_dbg, plan);
-        return check_launch("correlation_forward (mfma, paired parities, projection build)");
-      }
+      mfma::set_dynamic_lds_once<&corr_fwd_pair<R>>((int)lds3);
       hipLaunchKernelGGL((corr_fwd_pair<R>), dim3(grid), dim3(HCfg<R>::THREADS), lds3, st, b0, b1, top, g, g_corr_dbg, plan);
       return check_launch("correlation_forward (mfma, paired parities)");
     }
   }
   const size_t lds2 = sizeof(float) * GCfg<S2, R>::LDS_FLOATS;
-  static bool attr2_set = false;
-  if (!attr2_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&corr_fwd_glds<S2, R, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-    attr2_set = true;
-  }
+  mfma::set_dynamic_lds_once<&corr_fwd_glds<S2, R, 0>>((int)lds2);
 #ifdef FN2_ABLATION
   if (S2 == 2 && R == 10 && g_corr_ablation) {     // profiling builds, fn2_debug_set_correlation_impl(64 + bits)
     switch (g_corr_ablation) {

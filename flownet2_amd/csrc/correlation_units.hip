@@ -584,7 +584,6 @@ static Plan plan_for(int N, int H, int W, int policy) {
 
 }  // namespace cu3
 
-extern unsigned long long* g_corr_dbg;
 int g_corr_units_abl = 0;      // FN2_ABLATION builds: ablation bits of corr_fwd_units
 int g_corr_units = 1;          // test / profiling hook (fn2_debug_set_correlation_impl): 0 = corr_fwd_pair where both apply, 1 + policy = this kernel
 int g_corr_units_lds = 0;      // profiling hook: extra dynamic LDS per workgroup (bytes) -- fewer workgroups per CU

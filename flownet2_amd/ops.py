@@ -103,9 +103,37 @@ def correlation1d_backward(p: CorrParams, bottom0, bottom1, top_diff, need0=True
     return d0, d1
 
 
+# codes of fn2_debug_set_correlation_impl (csrc/correlation.hip); every other value is FN2_ERR_INVALID_ARG
+CORR_IMPL_AUTO = 0                # automatic choice
+CORR_IMPL_GENERIC = 1             # generic (thread per element) kernels, Correlation and Correlation1D
+CORR_IMPL_FWD_DWORD = 3           # general dword LDS-DMA MFMA forward even where the paired-parity kernel applies
+CORR_IMPL_BWD_GEN1 = 5            # register-staged MFMA backward (corr_bwd_mfma) even where the G-ring kernel applies
+CORR_IMPL_FWD_PAIR_NO_PLAN = 13   # paired-parity forward (corr_fwd_pair) without the SIMD plan
+CORR_IMPL_BWD_PER_BOTTOM = 16     # one backward launch per bottom where the merged launch applies
+CORR_IMPL_1D_TILED = 17           # Correlation1D: the LDS-tiled VALU forward instead of the MFMA one
+CORR_IMPL_FWD_PAIR = 19           # paired-parity forward where the unit kernel applies
+CORR_IMPL_UNITS = 20              # + task policy (0 .. 31): the unit kernel with that policy
+CORR_IMPL_UNITS_LDS_16K = 60      # unit kernel with 16 KB of extra LDS (two workgroups per CU)
+CORR_IMPL_UNITS_LDS_64K = 61      # unit kernel with 64 KB of extra LDS (one workgroup per CU)
+CORR_IMPL_ABL_GLDS = 64           # + bits (0 .. 35): ablation of the general MFMA forward, FN2_ABLATION builds only
+CORR_IMPL_ABL_UNITS = 100         # + bits (0 .. 63): ablation of the unit kernel, FN2_ABLATION builds only
+
+
 def set_correlation_impl(impl):
-    """Test hook: 0 / False = automatic choice, 1 / True = generic kernels, 3 = the general (dword LDS-DMA) MFMA forward
-    even where the paired-parity kernel applies."""
+    """Test / profiling hook: which correlation kernels run.  `impl` is one of the CORR_IMPL_* codes above (False / True are
+    CORR_IMPL_AUTO / CORR_IMPL_GENERIC):
+      CORR_IMPL_AUTO (0)              automatic choice
+      CORR_IMPL_GENERIC (1)           generic kernels
+      CORR_IMPL_FWD_DWORD (3)         general dword LDS-DMA forward
+      CORR_IMPL_BWD_GEN1 (5)          register-staged backward
+      CORR_IMPL_FWD_PAIR_NO_PLAN (13) paired-parity forward without the SIMD plan
+      CORR_IMPL_BWD_PER_BOTTOM (16)   one backward launch per bottom
+      CORR_IMPL_1D_TILED (17)         Correlation1D tiled VALU forward
+      CORR_IMPL_FWD_PAIR (19)         paired-parity forward where the unit kernel applies
+      CORR_IMPL_UNITS + policy (20 .. 51)   unit kernel with a task policy
+      CORR_IMPL_UNITS_LDS_16K / _64K (60, 61)   unit kernel with extra LDS
+      CORR_IMPL_ABL_GLDS + bits (64 .. 99), CORR_IMPL_ABL_UNITS + bits (100 .. 163)   ablations, FN2_ABLATION builds only
+    Any other value raises Fn2Error (FN2_ERR_INVALID_ARG) and changes nothing."""
     check(_lib.lib().fn2_debug_set_correlation_impl(int(impl)))
 
 

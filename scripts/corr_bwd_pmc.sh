@@ -1,6 +1,6 @@
 #!/bin/bash
-# SQ counter passes over the correlation BACKWARD kernel (round 6: corr_bwd_g4_both; FN2_CORR_IMPL=15 / 16 for the per-bottom kernels of
-# generations 3 / 4), each set in its own rocprofv3 run.
+# SQ counter passes over the correlation BACKWARD kernel (corr_bwd_g4_both; FN2_CORR_IMPL=16 for the per-bottom
+# launches corr_bwd_g4<0> / <1>), each set in its own rocprofv3 run.
 export TMPDIR=/tmp
 R=gpurun_out/pmc_bwd
 mkdir -p $R
@@ -12,7 +12,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
 done
 python - <<'PY'
 import csv, glob, collections
-for which in ("corr_bwd_g4_both", "corr_bwd_g4<0>", "corr_bwd_g4<1>", "corr_bwd_g3<0>", "corr_bwd_g3<1>"):
+for which in ("corr_bwd_g4_both", "corr_bwd_g4<0>", "corr_bwd_g4<1>"):
     rows = []
     for f in sorted(glob.glob("gpurun_out/pmc_bwd/*/c_counter_collection.csv")):
         acc = collections.defaultdict(list)

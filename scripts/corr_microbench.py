@@ -14,7 +14,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--shape", default="8,256,40,56")
 ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--generic", action="store_true")
-ap.add_argument("--impl", type=int, default=0, help="fn2_debug_set_correlation_impl value (3 = general dword LDS-DMA MFMA kernel)")
+ap.add_argument("--impl", type=int, default=0, help="ops.CORR_IMPL_* code (3 = general dword LDS-DMA MFMA forward, 5 = register-staged backward, 16 = one backward launch per bottom)")
 ap.add_argument("--backward", action="store_true")
 ap.add_argument("--ablation", type=int, default=0, help="FN2_ABLATION builds: 1 no MFMA, 2 no loads, 4 no stores (bit-or)")
 a = ap.parse_args()
@@ -26,11 +26,9 @@ p = ops.corr_params(20, 1, 20, 1, 2)
 out = torch.empty(N, 441, H, W, device="cuda")
 ops.set_correlation_impl(a.generic)
 if a.ablation:
-    from flownet2_amd import _lib
-    _lib.lib().fn2_debug_set_correlation_impl(64 + a.ablation)
+    ops.set_correlation_impl(ops.CORR_IMPL_ABL_GLDS + a.ablation)
 elif a.impl:
-    from flownet2_amd import _lib
-    _lib.lib().fn2_debug_set_correlation_impl(a.impl)
+    ops.set_correlation_impl(a.impl)
 for _ in range(5):
     ops.correlation_forward(p, x, y, out=out)
 torch.cuda.synchronize()

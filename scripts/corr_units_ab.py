@@ -5,9 +5,8 @@ rounds of N back-to-back launches per variant, order reversed every other round)
 import json, os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from flownet2_amd import ops, _lib
+from flownet2_amd import ops
 
-L = _lib.lib()
 P = ops.corr_params(20, 1, 20, 1, 2)
 
 
@@ -21,14 +20,14 @@ def check(impls):
     for shape in [(8, 256, 40, 56), (4, 256, 48, 96), (1, 256, 56, 128), (2, 64, 16, 24), (3, 32, 11, 20), (1, 32, 5, 8), (16, 32, 9, 12), (5, 96, 30, 44), (8, 64, 40, 56), (8, 128, 24, 32), (2, 64, 40, 56), (1, 64, 40, 56), (4, 192, 40, 56)]:
         x, y = mk(shape)
         N, C, H, W = shape
-        L.fn2_debug_set_correlation_impl(19)
+        ops.set_correlation_impl(19)
         want = ops.correlation_forward(P, x, y)
         if shape[1] % 32 != 0:
             continue
         wide = torch.full((N, 441 + 40, H, W), 7.0, device="cuda")
         want_f = ops.correlation_forward(P, x, y, out=wide.clone(), out_c0=13, relu=True, negative_slope=0.1)
         for i in impls:
-            L.fn2_debug_set_correlation_impl(i)
+            ops.set_correlation_impl(i)
             got = torch.full_like(want, float("nan"))
             ops.correlation_forward(P, x, y, out=got)
             got_f = ops.correlation_forward(P, x, y, out=wide.clone(), out_c0=13, relu=True, negative_slope=0.1)
@@ -40,7 +39,7 @@ def check(impls):
                 nanc = int(torch.isnan(got).sum())
                 print("MISMATCH impl %d shape %s: max abs %.3e, nan %d, differing %d / %d" % (i, shape, float(torch.nan_to_num(d).abs().max()), nanc,
                                                                                            int((got.view(torch.int32) != want.view(torch.int32)).sum()), got.numel()), flush=True)
-    L.fn2_debug_set_correlation_impl(0)
+    ops.set_correlation_impl(0)
     print("bit-identity vs corr_fwd_pair: %s" % ("OK" if bad == 0 else "%d FAILURES" % bad), flush=True)
     return bad
 
@@ -58,17 +57,17 @@ def timing(impls, shape, rounds=6, iters=1500):
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / n * 1e3
-    L.fn2_debug_set_correlation_impl(impls[0])
+    ops.set_correlation_impl(impls[0])
     t0 = time.time()
     while time.time() - t0 < 1.0:
         run(500)
     res = {i: [] for i in impls}
     for rnd in range(rounds):
         for i in (impls if rnd % 2 == 0 else impls[::-1]):
-            L.fn2_debug_set_correlation_impl(i)
+            ops.set_correlation_impl(i)
             run(200)
             res[i].append(run(iters))
-    L.fn2_debug_set_correlation_impl(0)
+    ops.set_correlation_impl(0)
     fl = 2.0 * C * 441 * N * H * W
     rows = {}
     for i in impls:

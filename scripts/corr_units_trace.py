@@ -25,30 +25,30 @@ def run(n):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-impls = [int(v) for v in sys.argv[1].split(",")] if len(sys.argv) > 1 else [20, 19, 201, 202, 203]
+impls = [int(v) for v in sys.argv[1].split(",")] if len(sys.argv) > 1 else [20, 19]
 t0 = time.time()
 while time.time() - t0 < 1.0:
     run(500)
 res = {i: [] for i in impls}
 for rnd in range(4):
     for i in (impls if rnd % 2 == 0 else impls[::-1]):
-        L.fn2_debug_set_correlation_impl(i)
+        ops.set_correlation_impl(i)
         run(200)
         res[i].append(run(1000))
 names = {1: "no MFMA", 2: "no DMA", 4: "no stores", 8: "no loop barriers", 16: "no operand reads"}
 for i in impls:
-    what = "corr_fwd_pair" if i == 19 else "units" if i == 20 else "units, policy %d flags %d" % ((i - 200) >> 3, (i - 200) & 7) if i >= 200 else "units without " + ", ".join(v for k, v in names.items() if (i - 100) & k)
+    what = "corr_fwd_pair" if i == 19 else "units" if i == 20 else "units, policy %d" % (i - 20) if i < 52 else "units without " + ", ".join(v for k, v in names.items() if (i - 100) & k)
     print("impl %3d %-60s median %.2f us (min %.2f)" % (i, what, statistics.median(res[i]), min(res[i])), flush=True)
 
 # ---- per-wave trace of one launch of the real kernel ----
 TR = int(os.environ.get("TRACE_IMPL", "20"))
-L.fn2_debug_set_correlation_impl(TR)
+ops.set_correlation_impl(TR)
 run(300)
 dbg = torch.zeros(6 * 5 * 4096, dtype=torch.int64, device="cuda")
 L.fn2_debug_set_correlation_trace(C.c_void_p(dbg.data_ptr()))
 ops.correlation_forward(p, x, y, out=out); torch.cuda.synchronize()
 L.fn2_debug_set_correlation_trace(None)
-L.fn2_debug_set_correlation_impl(0)
+ops.set_correlation_impl(0)
 raw = dbg.cpu().numpy().reshape(-1, 5, 6)
 blk = np.nonzero(raw[:, 0, 0] != 0)[0]
 d = raw[blk]                                                   # [block][wave][start, loop end, end, info]

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Correlation backward (corr_bwd_g3) ablation builds, rebuilt ON the GPU box and timed one after the other at config A:
+# Correlation backward (corr_bwd_g4_both; FN2_CORR_IMPL=16: corr_bwd_g4<0> / <1>) ablation builds (FN2_G4_ABL), rebuilt ON the GPU box and timed one after the other at config A:
 #   bash scripts/probes/corr_bwd_variants.sh <tag>   -> gpurun_out/<tag>/corr_bwd_variants.txt
 set -u
 TAG=${1:-corrbwd}
@@ -21,14 +21,10 @@ run() {
   [ -n "$f" ] && python -c "
 import csv,sys
 for r in csv.DictReader(open('$f')):
-    if 'corr_bwd' in r['Name']: print('  %-22s calls %s  avg %.2f us' % (r['Name'].split('(')[0].replace('void fn2::bwd::g3::',''), r['Calls'], float(r['AverageNs'])/1e3))
+    if 'corr_bwd' in r['Name']: print('  %-22s calls %s  avg %.2f us' % (r['Name'].split('(')[0].replace('void fn2::bwd::g4::',''), r['Calls'], float(r['AverageNs'])/1e3))
 " >> $OUT
   rm -rf $R/t_$2
 }
-if [ "${FN2_GEN:-4}" = "3" ]; then
-  for v in 0 1 2 3 4 7; do build "-DFN2_G3_ABL=$v"; run "generation 3, ablation $v (1 no G DMA, 2 no other-map DMA, 4 no MFMA)" $v; done
-else
-  for v in 0 1 2 3 4 7 8 15; do build "-DFN2_G4_ABL=$v"; run "generation 4 (both bottoms, one launch), ablation $v (1 no G DMA, 2 no other-map DMA, 4 no MFMA, 8 no stores)" $v; done
-fi
+for v in 0 1 2 3 4 7 8 15; do build "-DFN2_G4_ABL=$v"; run "G-ring kernel, ablation $v (1 no G DMA, 2 no other-map DMA, 4 no MFMA, 8 no stores)" $v; done
 build ""
 cat $OUT

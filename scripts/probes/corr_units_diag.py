@@ -1,13 +1,13 @@
 import sys, os, torch, numpy as np
 sys.path.insert(0, os.getcwd())
-from flownet2_amd import ops, _lib
-L=_lib.lib(); P=ops.corr_params(20,1,20,1,2)
+from flownet2_amd import ops
+P=ops.corr_params(20,1,20,1,2)
 H,W=40,56
 shape=(1,32,H,W)
 g=torch.Generator(device="cuda").manual_seed(0)
 xr=torch.randn(*shape,device="cuda",generator=g); yr=torch.randn(*shape,device="cuda",generator=g)
 def run(impl,x,y):
-    L.fn2_debug_set_correlation_impl(impl); got=torch.full((1,441,H,W),float('nan'),device="cuda"); ops.correlation_forward(P,x,y,out=got); torch.cuda.synchronize(); return got
+    ops.set_correlation_impl(impl); got=torch.full((1,441,H,W),float('nan'),device="cuda"); ops.correlation_forward(P,x,y,out=got); torch.cuda.synchronize(); return got
 A=torch.zeros(*shape,device="cuda"); B=torch.zeros(*shape,device="cuda")
 pix=(torch.arange(H*W,device="cuda",dtype=torch.float32)+1).reshape(H,W)
 A[0,0]=pix*32; B[0,0]=1.0

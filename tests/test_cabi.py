@@ -95,6 +95,27 @@ def test_correlation1d_shape_function_matches_reference_reshape():
         ops.correlation1d_forward(ops.corr_params(1, 1, 1, 1, 1), x, x)
 
 
+def test_correlation_impl_selector_refuses_what_is_no_code():
+    """fn2_debug_set_correlation_impl (no GPU touched): the retired codes, a number that never was one, the ends of the ranges and -- in a
+    default build (flownet2_amd.build adds the ablation kernels only under FN2_ABLATION) -- the two ablation ranges are
+    FN2_ERR_INVALID_ARG with the value in the message; every surviving code is accepted."""
+    FN2_ERR_INVALID_ARG = -1
+    refused = [2, 6, 7, 8, 9, 14, 15, 164, -1] + ([] if os.environ.get("FN2_ABLATION") else [64, 100])
+    accepted = [ops.CORR_IMPL_AUTO, ops.CORR_IMPL_GENERIC, ops.CORR_IMPL_FWD_DWORD, ops.CORR_IMPL_BWD_GEN1, ops.CORR_IMPL_FWD_PAIR_NO_PLAN,
+                ops.CORR_IMPL_BWD_PER_BOTTOM, ops.CORR_IMPL_1D_TILED, ops.CORR_IMPL_FWD_PAIR, ops.CORR_IMPL_UNITS_LDS_16K, ops.CORR_IMPL_UNITS_LDS_64K]
+    accepted += [ops.CORR_IMPL_UNITS + policy for policy in range(32)]
+    assert sorted(accepted) == [0, 1, 3, 5, 13, 16, 17, 19] + list(range(20, 52)) + [60, 61]      # the numbers scripts and notes cite
+    try:
+        for code in refused:
+            with pytest.raises(flownet2_amd.Fn2Error, match=r"impl: %s is not " % re.escape(str(code))) as e:
+                ops.set_correlation_impl(code)
+            assert e.value.status == FN2_ERR_INVALID_ARG, code
+        for code in accepted:
+            ops.set_correlation_impl(code)
+    finally:
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
+
+
 def test_ops_refuse_cpu_tensors_no_fallback():
     x = torch.zeros(1, 3, 4, 4)
     with pytest.raises(ValueError, match="no CPU path"):

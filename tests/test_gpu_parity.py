@@ -69,7 +69,7 @@ CORR_CASES = [
 
 @pytest.mark.parametrize("case", CORR_CASES)
 @pytest.mark.parametrize("ctype", [oracle.MULTIPLY, oracle.SUBTRACT])
-@pytest.mark.parametrize("force_generic", [0, 1, 3])  # automatic (paired-parity / general MFMA kernels where they apply), generic, general (dword LDS-DMA) MFMA
+@pytest.mark.parametrize("force_generic", [ops.CORR_IMPL_AUTO, ops.CORR_IMPL_GENERIC, ops.CORR_IMPL_FWD_DWORD])  # automatic (paired-parity / general MFMA kernels where they apply), generic, general (dword LDS-DMA) MFMA
 def test_correlation_forward(case, ctype, force_generic):
     N, C, H, W, pad, K, md, s1, s2 = case
     b0, b1 = rand((N, C, H, W), 1), rand((N, C, H, W), 2)
@@ -78,7 +78,7 @@ def test_correlation_forward(case, ctype, force_generic):
     try:
         top = ops.correlation_forward(ops.corr_params(pad, K, md, s1, s2, ctype), dev(b0), dev(b1))
     finally:
-        ops.set_correlation_impl(False)
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
     assert_close(host(top), ref, 2e-6, "correlation forward")
 
 
@@ -141,13 +141,13 @@ def test_correlation1d_fast_forwards_agree_with_generic_and_oracle(case):
     b0, b1 = rand((N, C, H, W), 51), rand((N, C, H, W), 52)
     p = ops.corr_params(pad, K, md, s1, s2, oracle.MULTIPLY, False, sd)
     fast = ops.correlation1d_forward(p, dev(b0), dev(b1))
-    ops.set_correlation_impl(1)
+    ops.set_correlation_impl(ops.CORR_IMPL_GENERIC)
     try:
         generic = ops.correlation1d_forward(p, dev(b0), dev(b1))
-        ops.set_correlation_impl(17)
+        ops.set_correlation_impl(ops.CORR_IMPL_1D_TILED)
         tiled = ops.correlation1d_forward(p, dev(b0), dev(b1))
     finally:
-        ops.set_correlation_impl(0)
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
     ngw = (md // s2) + 1 if sd else 2 * (md // s2) + 1
     if s2 == 1 and ngw <= 113:
         assert torch.equal(fast, generic), "the MFMA forward has the bits of the sequential fmaf loop"
@@ -246,11 +246,11 @@ def test_correlation_full_size_properties():
     ch, chm = (q + 10) * 21 + (o + 10), (-q + 10) * 21 + (-o + 10)
     assert torch.allclose(topr[:, ch, 0:H - 2 * q, -2 * o:W], top[:, chm, 2 * q:H, 0:W + 2 * o], atol=2e-6)
     # (5) generic kernel and MFMA kernel agree on the full size
-    ops.set_correlation_impl(True)
+    ops.set_correlation_impl(ops.CORR_IMPL_GENERIC)
     try:
         topg = ops.correlation_forward(p, a, b)
     finally:
-        ops.set_correlation_impl(False)
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
     assert torch.allclose(topg, top, atol=2e-6)
     # (6) backward is the adjoint of forward: <corr(a,b), g> differentiated w.r.t. a and b
     gg = torch.randn(top.shape, device="cuda", generator=g)
@@ -901,16 +901,17 @@ def test_sweep_correlation_mfma_kernels_agree_with_generic(shape):
     b0, b1 = dev(rand(shape, 240)), dev(rand(shape, 241))
     p = ops.corr_params(20, 1, 20, 1, 2)
     outs = {}
-    for impl in (1, 0, 3):
+    for impl in (ops.CORR_IMPL_GENERIC, ops.CORR_IMPL_AUTO, ops.CORR_IMPL_FWD_DWORD):
         ops.set_correlation_impl(impl)
         try:
             outs[impl] = ops.correlation_forward(p, b0, b1)
         finally:
-            ops.set_correlation_impl(0)
-    scale = max(1.0, float(outs[1].abs().max()))
-    assert float((outs[0] - outs[1]).abs().max()) <= 2e-7 * scale
-    assert float((outs[3] - outs[1]).abs().max()) <= 2e-7 * scale
-    assert_close(host(outs[0]), oracle.correlation_forward(oracle.corr_params(20, 1, 20, 1, 2), host(b0), host(b1)), 2e-6, "vs oracle")
+            ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
+    generic = outs[ops.CORR_IMPL_GENERIC]
+    scale = max(1.0, float(generic.abs().max()))
+    assert float((outs[ops.CORR_IMPL_AUTO] - generic).abs().max()) <= 2e-7 * scale
+    assert float((outs[ops.CORR_IMPL_FWD_DWORD] - generic).abs().max()) <= 2e-7 * scale
+    assert_close(host(outs[ops.CORR_IMPL_AUTO]), oracle.correlation_forward(oracle.corr_params(20, 1, 20, 1, 2), host(b0), host(b1)), 2e-6, "vs oracle")
 
 
 @pytest.mark.parametrize("case", [(2, 13, 12, 16, 32), (1, 473, 8, 12, 64), (3, 16, 9, 20, 16)])
@@ -981,7 +982,7 @@ def test_correlation_fused_relu_and_channel_slice(case):
     b0, b1 = rand((N, Cc, H, W), 31), rand((N, Cc, H, W), 32)
     p = ops.corr_params(pad, K, md, s1, s2, t)
     try:
-        for impl in (0, 1, 3):               # automatic, generic kernel, general (dword LDS-DMA) MFMA kernel
+        for impl in (ops.CORR_IMPL_AUTO, ops.CORR_IMPL_GENERIC, ops.CORR_IMPL_FWD_DWORD):
             ops.set_correlation_impl(impl)
             plain = ops.correlation_forward(p, dev(b0), dev(b1))
             tc = plain.shape[1]
@@ -990,7 +991,7 @@ def test_correlation_fused_relu_and_channel_slice(case):
             assert torch.equal(out[:, 4:4 + tc], torch.nn.functional.leaky_relu(plain, 0.1)), impl
             assert bool((out[:, :4] == 5).all()) and bool((out[:, 4 + tc:] == 5).all())
     finally:
-        ops.set_correlation_impl(0)
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
     fp = C.POINTER(C.c_float)
     top = np.full(tuple(out.shape), 5.0, np.float32)
     po = oracle.corr_params(pad, K, md, s1, s2, t)
@@ -1001,44 +1002,70 @@ def test_correlation_fused_relu_and_channel_slice(case):
 
 
 @pytest.mark.parametrize("shape", [(2, 64, 24, 40), (1, 128, 16, 24), (2, 64, 11, 28), (8, 256, 40, 56), (1, 64, 9, 12), (3, 64, 30, 72), (1, 64, 4, 4)])
-def test_correlation_backward_generations_agree_bitwise(shape):
-    """Four generations of the MFMA backward.  1 (register-staged) and 2 (LDS-DMA staging, gathered G) perform the same
-    multiplications in the same order: identical bits.  3 (G through LDS, one contraction row per chunk) sums the same products
-    row by row: equal at rounding level, on ragged heights too.  4 (round 6: G ring three rows deep, the bottom-1 slab cut to the
-    sliding 36-dword window, operand reads pinned behind the MFMAs) performs generation 3's products in generation 3's order:
-    identical bits to it; all against the oracle on the small shapes."""
+def test_correlation_backward_kernels_agree(shape):
+    """The two MFMA backward kernels.  corr_bwd_mfma (register-staged, G gathered per patch row) and the G-ring kernel (G through LDS
+    three rows deep, one contraction row per chunk) multiply the same products; the second sums them row by row: equal at rounding level,
+    on ragged heights too.  The G-ring kernel gives the same bits however it is launched: both bottoms in one grid (the default), one
+    launch per bottom, a second run, one bottom alone.  Both kernels against the oracle on the small shapes."""
     N, C, H, W = shape
     p = ops.corr_params(20, 1, 20, 1, 2)
     b0, b1 = rand(shape, 41), rand(shape, 42)
     td = rand((N, 441, H, W), 43)
     try:
-        ops.set_correlation_impl(5)
+        ops.set_correlation_impl(ops.CORR_IMPL_BWD_GEN1)
         f0, f1 = ops.correlation_backward(p, dev(b0), dev(b1), dev(td))
-        ops.set_correlation_impl(6)
-        s0, s1 = ops.correlation_backward(p, dev(b0), dev(b1), dev(td))
-        ops.set_correlation_impl(15)
-        t0, t1 = ops.correlation_backward(p, dev(b0), dev(b1), dev(td))
-        ops.set_correlation_impl(16)                  # generation 4, one launch per bottom
+        ops.set_correlation_impl(ops.CORR_IMPL_BWD_PER_BOTTOM)      # G-ring kernel, one launch per bottom
         w0, w1 = ops.correlation_backward(p, dev(b0), dev(b1), dev(td))
-        ops.set_correlation_impl(0)                   # generation 4, both bottoms in one grid (the default)
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)                # G-ring kernel, both bottoms in one grid (the default)
         u0, u1 = ops.correlation_backward(p, dev(b0), dev(b1), dev(td))
         v0, v1 = ops.correlation_backward(p, dev(b0), dev(b1), dev(td))
         only0, _ = ops.correlation_backward(p, dev(b0), dev(b1), dev(td), need1=False)
         _, only1 = ops.correlation_backward(p, dev(b0), dev(b1), dev(td), need0=False)
     finally:
-        ops.set_correlation_impl(0)
-    assert torch.equal(f0, s0) and torch.equal(f1, s1)
-    assert torch.equal(t0, u0), float((t0 - u0).abs().max())
-    assert torch.equal(t1, u1), float((t1 - u1).abs().max())
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
+    assert torch.equal(w0, u0), float((w0 - u0).abs().max())
+    assert torch.equal(w1, u1), float((w1 - u1).abs().max())
     assert torch.equal(u0, v0) and torch.equal(u1, v1)
-    assert torch.equal(w0, u0) and torch.equal(w1, u1) and torch.equal(only0, u0) and torch.equal(only1, u1)
-    assert_close(host(t0), host(f0), 2e-6, "generation 3 vs 1, bottom 0 diff")
-    assert_close(host(t1), host(f1), 2e-6, "generation 3 vs 1, bottom 1 diff")
+    assert torch.equal(only0, u0) and torch.equal(only1, u1)
+    assert_close(host(u0), host(f0), 2e-6, "G-ring kernel vs corr_bwd_mfma, bottom 0 diff")
+    assert_close(host(u1), host(f1), 2e-6, "G-ring kernel vs corr_bwd_mfma, bottom 1 diff")
     if N * C * H * W <= 2 * 64 * 24 * 40:
         o0, o1 = oracle.correlation_backward(oracle.corr_params(20, 1, 20, 1, 2), b0, b1, td)
-        for got in ((s0, s1), (t0, t1)):
+        for got in ((f0, f1), (u0, u1)):
             assert_close(host(got[0]), o0, 3e-6, "bottom 0 diff")
             assert_close(host(got[1]), o1, 3e-6, "bottom 1 diff")
+
+
+@pytest.mark.parametrize("shape", [(1, 64, 9, 12), (2, 64, 11, 28)])
+def test_correlation_backward_unaligned_top_diff(shape):
+    """A top_diff that starts one float past a 16-byte boundary (aligned bottoms, W % 4 == 0) cannot take the 16-byte LDS-DMA of the
+    G-ring kernel: the register-staged kernel serves it with dword buffer loads.  Both diffs, and each alone, carry the bits that kernel
+    gives on an aligned copy of the same values; the first shape also against the oracle."""
+    N, C, H, W = shape
+    p = ops.corr_params(20, 1, 20, 1, 2)
+    b0, b1 = rand(shape, 44), rand(shape, 45)
+    td = rand((N, 441, H, W), 46)
+    n = td.size
+    td_off = torch.empty(n + 1, device="cuda")[1:].view(N, 441, H, W)
+    td_off.copy_(torch.from_numpy(td))
+    assert td_off.is_contiguous() and td_off.data_ptr() % 16 == 4
+    d_b0, d_b1, d_td = dev(b0), dev(b1), dev(td)
+    assert d_b0.data_ptr() % 16 == 0 and d_b1.data_ptr() % 16 == 0 and d_td.data_ptr() % 16 == 0
+    try:
+        ops.set_correlation_impl(ops.CORR_IMPL_BWD_GEN1)
+        f0, f1 = ops.correlation_backward(p, d_b0, d_b1, d_td)
+    finally:
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
+    u0, u1 = ops.correlation_backward(p, d_b0, d_b1, td_off)
+    only0, none1 = ops.correlation_backward(p, d_b0, d_b1, td_off, need1=False)
+    none0, only1 = ops.correlation_backward(p, d_b0, d_b1, td_off, need0=False)
+    assert none0 is None and none1 is None
+    assert torch.equal(u0, f0) and torch.equal(u1, f1)
+    assert torch.equal(only0, f0) and torch.equal(only1, f1)
+    if shape == (1, 64, 9, 12):
+        o0, o1 = oracle.correlation_backward(oracle.corr_params(20, 1, 20, 1, 2), b0, b1, td)
+        assert_close(host(u0), o0, 3e-6, "bottom 0 diff")
+        assert_close(host(u1), o1, 3e-6, "bottom 1 diff")
 
 
 @pytest.mark.parametrize("shape", [(2, 3, 64, 128), (1, 3, 7, 9), (3, 5, 10, 6)])
@@ -1063,14 +1090,14 @@ def test_correlation_simd_plan_changes_no_bit(shape):
     b0, b1 = dev(rand(shape, 244)), dev(rand(shape, 245))
     p = ops.corr_params(20, 1, 20, 1, 2)
     outs = {}
-    for impl in (0, 13):
+    for impl in (ops.CORR_IMPL_AUTO, ops.CORR_IMPL_FWD_PAIR_NO_PLAN):
         ops.set_correlation_impl(impl)
         try:
             outs[impl] = ops.correlation_forward(p, b0, b1)
         finally:
-            ops.set_correlation_impl(0)
-    assert torch.equal(outs[0], outs[13])
-    assert_close(host(outs[0]), oracle.correlation_forward(oracle.corr_params(20, 1, 20, 1, 2), host(b0), host(b1)), 2e-6, "vs oracle")
+            ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
+    assert torch.equal(outs[ops.CORR_IMPL_AUTO], outs[ops.CORR_IMPL_FWD_PAIR_NO_PLAN])
+    assert_close(host(outs[ops.CORR_IMPL_AUTO]), oracle.correlation_forward(oracle.corr_params(20, 1, 20, 1, 2), host(b0), host(b1)), 2e-6, "vs oracle")
 
 
 @pytest.mark.parametrize("shape", [(8, 32, 40, 56), (4, 64, 48, 96), (1, 32, 56, 128), (2, 64, 16, 24), (3, 32, 11, 20), (1, 32, 5, 8), (16, 32, 9, 12), (5, 96, 30, 44)])
@@ -1083,16 +1110,16 @@ def test_correlation_unit_kernel_is_bitwise_the_paired_parity_kernel(shape, poli
     N, C, H, W = shape
     b0, b1 = dev(rand(shape, 501)), dev(rand(shape, 502))
     p = ops.corr_params(20, 1, 20, 1, 2)
-    ops.set_correlation_impl(19)
+    ops.set_correlation_impl(ops.CORR_IMPL_FWD_PAIR)
     try:
         want = ops.correlation_forward(p, b0, b1)
         wide = torch.full((N, 441 + 9, H, W), 7.0, device="cuda")
         want_f = ops.correlation_forward(p, b0, b1, out=wide.clone(), out_c0=5, relu=True, negative_slope=0.1)
-        ops.set_correlation_impl(20 + policy)
+        ops.set_correlation_impl(ops.CORR_IMPL_UNITS + policy)
         got = ops.correlation_forward(p, b0, b1, out=torch.full_like(want, float("nan")))
         got_f = ops.correlation_forward(p, b0, b1, out=wide.clone(), out_c0=5, relu=True, negative_slope=0.1)
     finally:
-        ops.set_correlation_impl(0)
+        ops.set_correlation_impl(ops.CORR_IMPL_AUTO)
     assert torch.equal(got.view(torch.int32), want.view(torch.int32))
     assert torch.equal(got_f.view(torch.int32), want_f.view(torch.int32))
     assert_close(host(got), oracle.correlation_forward(oracle.corr_params(20, 1, 20, 1, 2), host(b0), host(b1)), 2e-6, "vs oracle")
