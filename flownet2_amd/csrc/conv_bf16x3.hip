@@ -30,15 +30,13 @@
 // LDS; variant 1 (16x8) 126 VGPRs, 72,896 bytes; no spills, two workgroups per CU (LDS), four waves per SIMD by registers.
 #include "conv_internal.hpp"
 #include "mfma_tile.hpp"
+#include "split_bf16.hpp"
 
 namespace fn2 {
 namespace cx {
 
 using namespace mfma;
-
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using namespace bf16x3;      // bf16x8, u32x4, piece2 / split8 (split_bf16.hpp)
 
 struct Args {
   const float* in; const u32x4* wp; const float* bias; float* out;
@@ -52,25 +50,6 @@ struct Args {
   unsigned total;     // tiles = workgroups
   float slope; int relu;
 };
-
-// (a, b) -> the bf16 pieces of both, packed (a in the low half), and what is left of a and b
-__device__ __forceinline__ unsigned piece2(float& a, float& b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);           // v_cvt_pk_bf16_f32: round to nearest even
-  const unsigned u = __builtin_bit_cast(unsigned, h);
-  a -= __builtin_bit_cast(float, u << 16);
-  b -= __builtin_bit_cast(float, u & 0xffff0000u);
-  return u;
-}
-
-// 8 fp32 values -> three 16-byte operands (h, m, l), element j in bits 16 (j % 2) of dword j / 2
-__device__ __forceinline__ void split8(float (&v)[8], u32x4& h, u32x4& m, u32x4& l) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h[i] = piece2(v[2 * i], v[2 * i + 1]);
-    m[i] = piece2(v[2 * i], v[2 * i + 1]);
-    l[i] = piece2(v[2 * i], v[2 * i + 1]);
-  }
-}
 
 template <int KS_, int S_, int MW_, int NP_, int WM_, int WNX_, int WNY_>
 struct Cfg : Window<(4 * WNY_ - 1) * S_ + KS_, (4 * NP_ * WNX_ - 1) * S_ + KS_ + 4, 2, WM_ * WNX_ * WNY_> {      // 2 channel quads = the 8 channels of a chunk

@@ -23,4 +23,12 @@ int conv_bf16x3_forward(const float* bottom, const float* packed_weight, const f
                         int bottom_channels, int bottom_c0, int Cout, int top_channels, int top_c0, int kernel, int stride, int pad,
                         int relu, float negative_slope, void* stream);
 
+// csrc/deconv_bf16x3.hip: the GEMM of the Deconvolution{4, 2, 1} in split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3 beside
+// FN2_DECONV_ROUTE_GEMM); which layers it takes: fn2_deconv_bf16x3_supported.  weight: Caffe's [Cin][Cout][4][4] blob; the operand holds
+// the three bf16 planes of weight^T; col: the column matrix [N][16 Cout][Hin Win] fn2_col2im_bias_relu_forward_into reads.
+size_t deconv_bf16x3_packed_floats(int Cin, int Cout);
+int deconv_bf16x3_pack_weights(const float* weight, float* packed, int Cin, int Cout, void* stream);
+int deconv_bf16x3_gemm(const float* bottom, const float* packed_weight, float* col, int N, int Cin, int Hin, int Win, int bottom_channels,
+                       int bottom_c0, int Cout, void* stream);
+
 }  // namespace fn2

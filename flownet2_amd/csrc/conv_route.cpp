@@ -8,6 +8,10 @@
 // (once per weight version) -> workspace -> one dispatch call.  Python holds no routing rule and no per-family dispatch of its own, so a
 // Caffe user of libflownet2_hip.so gets the routing, the operands and the kernels the tests and the benchmarks ran with.
 // The thresholds are measurements: profiles/r02_conv_bench_*.txt, r04_conv_plane_bench_flownetc.txt, scripts/probes/small_layer_routes.py.
+// FN2_ROUTE_BF16X3 asks for the split-bf16 arithmetic where a kernel of it takes the layer -- the DIRECT 5x5 / 2 convolutions
+// (csrc/conv_bf16x3.hip) and the GEMM of the Deconvolution{4, 2, 1} (csrc/deconv_bf16x3.hip: 0.80 / 0.81 / 0.75 of the exact route's time at
+// FlowNetC's deconv4 / 3 / 2, profiles/deconv_bf16x3_bench.md; faster at all three, so no class of the GEMM route is kept exact under the
+// flag) -- as a bit beside the route; without the flag every answer is the exact fp32 one.
 #include "conv_internal.hpp"
 #include "fn2_common.hpp"
 
@@ -46,11 +50,23 @@ bool split_route(const fn2_conv_desc* d, int route) {
   return route == (FN2_CONV_ROUTE_DIRECT | FN2_CONV_ARITH_BF16X3) && fn2_conv_bf16x3_supported(d) != 0;
 }
 
+// the layers of the GEMM route: weight^T x bottom on the 1x1 form of the direct kernel
+bool deconv_gemm_ok(const fn2_conv_desc* d) {
+  return (d->Cout * 16) % 32 == 0 && (d->Hin * d->Win) % 4 == 0 && fn2_conv_mfma_supported(d->Cin, d->Hin, d->Win, d->Cout * 16, 1, 1, 0) != 0;
+}
+
+// the combined value FN2_DECONV_ROUTE_GEMM | FN2_CONV_ARITH_BF16X3 on a layer of the GEMM route that the split-bf16 GEMM takes
+// (csrc/deconv_bf16x3.hip); the arithmetic bit on PLANE / HEAD / NONE, or on any other layer, names no kernel
+bool deconv_split_route(const fn2_conv_desc* d, int route) {
+  return route == (FN2_DECONV_ROUTE_GEMM | FN2_CONV_ARITH_BF16X3) && d->kernel == 4 && d->stride == 2 && d->pad == 1 && deconv_gemm_ok(d) &&
+         fn2_deconv_bf16x3_supported(d) != 0;
+}
+
 bool deconv_route_applies(const fn2_conv_desc* d, int route) {
   if (d->kernel != 4 || d->stride != 2 || d->pad != 1) return false;
+  if (deconv_split_route(d, route)) return true;
   switch (route) {
-    case FN2_DECONV_ROUTE_GEMM:
-      return (d->Cout * 16) % 32 == 0 && (d->Hin * d->Win) % 4 == 0 && fn2_conv_mfma_supported(d->Cin, d->Hin, d->Win, d->Cout * 16, 1, 1, 0) != 0;
+    case FN2_DECONV_ROUTE_GEMM: return deconv_gemm_ok(d);
     case FN2_DECONV_ROUTE_PLANE: return fn2_deconv_plane_supported(d->N, d->Cin, d->Hin, d->Win, d->Cout) != 0;
     case FN2_DECONV_ROUTE_HEAD: return d->Cin == 2 && d->Cout == 2;
     default: return false;
@@ -169,20 +185,20 @@ FN2_API int fn2_conv_forward(const fn2_conv_desc* d, int route, const float* bot
 
 // ---- Deconvolution{4, 2, 1}: Cin = bottom channels, Cout = top channels, top is [N, Cout, 2 Hin, 2 Win]; weight blob [Cin][Cout][4][4] ----
 FN2_API int fn2_deconv_route(const fn2_conv_desc* d, int flags) {
-  (void)flags;
   if (!valid(d) || d->kernel != 4 || d->stride != 2 || d->pad != 1) return FN2_DECONV_ROUTE_NONE;
   if (d->Cin == 2 && d->Cout == 2) return FN2_DECONV_ROUTE_HEAD;       // upsample_flow*: the 2-channel kernel (csrc/flow_head.hip)
-  const int M = d->Cout * 16;
   // weight^T x bottom as the 1x1 / GEMM form of the direct kernel + our col2im / bias / ReLU pass: 5-25 % faster than the parity-class kernel
-  // on every FlowNet map it takes (profiles/r02_deconv_bench_flownetc.txt); planes whose size is no multiple of 4 (deconv5: 5x7) are not its
-  const bool gemm_ok = M % 32 == 0 && (d->Hin * d->Win) % 4 == 0 && fn2_conv_mfma_supported(d->Cin, d->Hin, d->Win, M, 1, 1, 0) != 0;
-  if (gemm_ok) return FN2_DECONV_ROUTE_GEMM;
+  // on every FlowNet map it takes (profiles/r02_deconv_bench_flownetc.txt); planes whose size is no multiple of 4 (deconv5: 5x7) are not its.
+  // FN2_ROUTE_BF16X3: the same layers with the GEMM in split-bf16 arithmetic where that kernel takes them (profiles/deconv_bf16x3_bench.md)
+  if (deconv_gemm_ok(d))
+    return ((flags & FN2_ROUTE_BF16X3) && fn2_deconv_bf16x3_supported(d)) ? (FN2_DECONV_ROUTE_GEMM | FN2_CONV_ARITH_BF16X3) : FN2_DECONV_ROUTE_GEMM;
   if (fn2_deconv_plane_supported(d->N, d->Cin, d->Hin, d->Win, d->Cout)) return FN2_DECONV_ROUTE_PLANE;
   return FN2_DECONV_ROUTE_NONE;
 }
 
 FN2_API size_t fn2_deconv_packed_weight_floats(const fn2_conv_desc* d, int route) {
   if (!valid(d)) return 0;
+  if (deconv_split_route(d, route)) return fn2::deconv_bf16x3_packed_floats(d->Cin, d->Cout);
   if (route == FN2_DECONV_ROUTE_GEMM) return fn2_conv_mfma_packed_floats(d->Cout * 16, d->Cin, 1);
   if (route == FN2_DECONV_ROUTE_PLANE) return fn2_deconv_plane_packed_floats(d->Cin, d->Cout);
   if (route == FN2_DECONV_ROUTE_HEAD) return (size_t)d->Cin * d->Cout * 16;
@@ -191,6 +207,7 @@ FN2_API size_t fn2_deconv_packed_weight_floats(const fn2_conv_desc* d, int route
 
 FN2_API int fn2_deconv_pack_weights(const fn2_conv_desc* d, int route, const float* weight, float* packed, void* stream) {
   if (!valid(d) || !weight || !packed) return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_pack_weights: bad descriptor or NULL blob");
+  if (deconv_split_route(d, route)) return fn2::deconv_bf16x3_pack_weights(weight, packed, d->Cin, d->Cout, stream);
   const int M = d->Cout * 16;
   // GEMM operand [M = Cout 16][Cin] straight from the [Cin][Cout][4][4] blob through the strided view (base_conv_layer.cpp:375-384's weight^T)
   if (route == FN2_DECONV_ROUTE_GEMM) return fn2_conv_mfma_pack_weights_view(weight, packed, M, d->Cin, 1, M, d->Cin, 1, M, 0, stream);
@@ -205,7 +222,7 @@ FN2_API int fn2_deconv_pack_weights(const fn2_conv_desc* d, int route, const flo
 
 FN2_API size_t fn2_deconv_workspace_bytes(const fn2_conv_desc* d, int route) {
   if (!valid(d)) return 0;
-  if (route == FN2_DECONV_ROUTE_GEMM) return sizeof(float) * (size_t)d->N * d->Cout * 16 * d->Hin * d->Win;      // the column matrix
+  if (route == FN2_DECONV_ROUTE_GEMM || deconv_split_route(d, route)) return sizeof(float) * (size_t)d->N * d->Cout * 16 * d->Hin * d->Win;      // the column matrix
   if (route == FN2_DECONV_ROUTE_PLANE) return fn2_deconv_plane_workspace_bytes(d->N, d->Cin, d->Hin, d->Win, d->Cout);
   return 0;
 }
@@ -220,12 +237,15 @@ FN2_API int fn2_deconv_forward(const fn2_conv_desc* d, int route, const float* b
   if (!bottom || !packed_weight || !top) return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_forward: NULL blob");
   if (bottom_c0 < 0 || bottom_c0 + d->Cin > bottom_channels || top_c0 < 0 || top_c0 + d->Cout > top_channels)
     return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_forward: channel slice outside its blob");
-  if (route == FN2_DECONV_ROUTE_GEMM) {
+  if (route == FN2_DECONV_ROUTE_GEMM || route == (FN2_DECONV_ROUTE_GEMM | FN2_CONV_ARITH_BF16X3)) {
     if (!workspace || workspace_bytes < fn2_deconv_workspace_bytes(d, route))
       return fn2::fail(FN2_ERR_INVALID_ARG, "deconv_forward: workspace of %zu bytes needed for the column matrix", fn2_deconv_workspace_bytes(d, route));
     float* col = static_cast<float*>(workspace);
-    int rc = fn2_conv_mfma_forward(bottom, packed_weight, nullptr, col, d->N, d->Cin, d->Hin, d->Win, bottom_channels, bottom_c0, d->Cout * 16,
-                                   d->Cout * 16, 0, 1, 1, 0, 0, 0.f, stream);
+    // only the arithmetic of the GEMM differs between the two: the same column matrix, the same second pass
+    int rc = route != FN2_DECONV_ROUTE_GEMM
+                 ? fn2::deconv_bf16x3_gemm(bottom, packed_weight, col, d->N, d->Cin, d->Hin, d->Win, bottom_channels, bottom_c0, d->Cout, stream)
+                 : fn2_conv_mfma_forward(bottom, packed_weight, nullptr, col, d->N, d->Cin, d->Hin, d->Win, bottom_channels, bottom_c0, d->Cout * 16,
+                                         d->Cout * 16, 0, 1, 1, 0, 0, 0.f, stream);
     if (rc) return rc;
     return fn2_col2im_bias_relu_forward_into(col, bias, top, d->N, d->Cout, 2 * d->Hin, 2 * d->Win, 4, 1, 2, relu, negative_slope, top_channels, top_c0, stream);
   }

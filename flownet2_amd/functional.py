@@ -451,6 +451,26 @@ if os.environ.get("FN2_CONV_ARITH"):
     set_conv_arithmetic(os.environ["FN2_CONV_ARITH"])
 
 
+_DECONV_ARITH = ["fp32"]
+
+
+def set_deconv_arithmetic(name: str = "fp32"):
+    """Arithmetic of the Deconvolution{4, 2, 1} FORWARD, a switch of its own beside set_conv_arithmetic: "fp32" (the default) or "bf16x3" --
+    the weight^T x bottom GEMM of the layers fn2_deconv_route hands to the GEMM route in split-bf16 arithmetic (csrc/deconv_bf16x3.hip; the
+    col2im + bias + ReLU pass is unchanged); every other layer, and every backward route, stays exact fp32.  Initial value: $FN2_DECONV_ARITH."""
+    if name not in _CONV_ARITHMETICS:
+        raise ValueError("deconv arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
+    _DECONV_ARITH[0] = name
+
+
+def deconv_arithmetic() -> str:
+    return _DECONV_ARITH[0]
+
+
+if os.environ.get("FN2_DECONV_ARITH"):
+    set_deconv_arithmetic(os.environ["FN2_DECONV_ARITH"])
+
+
 def _channel_slice(x):
     """(blob, first channel): x itself, or -- when x is a channel-slice view `blob[:, c0:c0+C]` of a contiguous NCHW blob (a skip
     tensor that was written straight into its Concat blob) -- that blob and the offset, so that the kernels read it in place."""
@@ -806,7 +826,7 @@ def deconv_forward_route(desc, act=True) -> int:
     """The own kernel deconv_relu runs this Deconvolution{4, 2, 1} on (0 = none): fn2_deconv_route minus the layers this module does not serve."""
     if not act or desc.Cin < 64:                          # no fused ReLU asked for; fewer than 64 input channels
         return ops.DECONV_ROUTE_NONE
-    route = ops.deconv_forward_route(desc)
+    route = ops.deconv_forward_route(desc, bf16x3=_DECONV_ARITH[0] == "bf16x3")
     return ops.DECONV_ROUTE_NONE if route == ops.DECONV_ROUTE_HEAD else route      # (2 -> 2: upsample_flow_deconv, with an autograd function of its own)
 
 

@@ -552,9 +552,11 @@ def conv_forward_route(desc, force=False, bf16x3=False) -> int:
     return int(_lib.lib().fn2_conv_route(C.byref(desc), (ROUTE_FORCE if force else 0) | (ROUTE_BF16X3 if bf16x3 else 0)))
 
 
-def deconv_forward_route(desc) -> int:
-    """Which own kernel serves the forward pass of this Deconvolution{4, 2, 1} (fn2_deconv_route; 0 = none, names: DECONV_FWD_ROUTES)."""
-    return int(_lib.lib().fn2_deconv_route(C.byref(desc), 0))
+def deconv_forward_route(desc, bf16x3=False) -> int:
+    """Which own kernel serves the forward pass of this Deconvolution{4, 2, 1} (fn2_deconv_route; 0 = none, names: DECONV_FWD_ROUTES).
+    bf16x3: the layers of the GEMM route that the split-bf16 GEMM takes come back as DECONV_ROUTE_GEMM | CONV_ARITH_BF16X3, every other layer
+    as without it; conv_pack_weights and conv_forward (transposed=True) take that value as it is."""
+    return int(_lib.lib().fn2_deconv_route(C.byref(desc), ROUTE_BF16X3 if bf16x3 else 0))
 
 
 def conv_pack_weights(weight, desc, route, transposed=False):
@@ -594,7 +596,7 @@ def conv_forward(x, packed, bias, desc, route, transposed=False, relu=True, nega
     if pw.numel() != int((L.fn2_deconv_packed_weight_floats if transposed else L.fn2_conv_packed_weight_floats)(C.byref(desc), int(route))):
         raise ValueError("conv_forward: the operand has %d floats, not what route %d reads for this layer" % (pw.numel(), route))
     need = int((L.fn2_deconv_workspace_bytes if transposed else L.fn2_conv_workspace_bytes)(C.byref(desc), int(route)))
-    if transposed and route == DECONV_ROUTE_GEMM:
+    if transposed and (route & ~CONV_ARITH_BF16X3) == DECONV_ROUTE_GEMM:
         # the column matrix lives for this call only (the per-stream scratch never shrinks: it would pin the largest one for good)
         ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
     else:

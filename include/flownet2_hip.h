@@ -519,6 +519,21 @@ int fn2_conv_bf16x3_supported(const fn2_conv_desc* desc);
 /* Test / profiling hooks of the split kernel: number of tile variants, forced variant (-1 = autotuned / cost model). */
 int fn2_conv_bf16x3_num_variants(void);
 int fn2_debug_set_conv_bf16x3_variant(int variant);
+/* The same arithmetic for the GEMM of the Deconvolution{4, 2, 1} (csrc/deconv_bf16x3.hip): with FN2_ROUTE_BF16X3 fn2_deconv_route returns
+ * FN2_DECONV_ROUTE_GEMM | FN2_CONV_ARITH_BF16X3 where it would have returned GEMM and the split GEMM takes the layer (16 Cout % 32 == 0,
+ * Hin Win % 4 == 0: every layer of the GEMM route), and exactly what it returns without the flag everywhere else.  weight^T x bottom is then
+ * summed in k-steps of 32 input channels in ascending order (mm, lh, hl, mh, hm, hh on one accumulator, no K split); the column matrix in the
+ * workspace (fn2_deconv_workspace_bytes: as for GEMM) and the col2im + bias + ReLU pass are those of the GEMM route.  The operand holds the three
+ * bf16 planes of weight^T, [Cout][ceil(Cin / 32) + 1][3][64 lanes][8 bf16] (the last k-step a spare of zeros: the length then differs from the exact operand's
+ * for every layer); channels >= Cin of the last k-step carry zero weights and meet zero
+ * activations, never the neighbouring channels of a wider bottom blob.  The result meets the fp64 bound of the GEMM route (3e-6 x scale;
+ * measured 0.03 - 0.25 of it, tests/test_deconv_bf16x3.py).  The bit on PLANE / HEAD / NONE, or on a layer the kernel does not take:
+ * FN2_ERR_UNSUPPORTED, 0 from the size queries.  Measured on an MI355X at deconv4 / deconv3 / deconv2 of FlowNetC, batch 8 @448x320
+ * (profiles/deconv_bf16x3_bench.md): the whole call takes 0.80 / 0.81 / 0.75 of the exact route's time, the GEMM alone 0.78 / 0.80 / 0.72; the
+ * flow of a FlowNetC forward differs from the fp32 run by 4.3e-7 px in the mean (2.6e-6 px with the convolutions' split arithmetic on too). */
+int fn2_deconv_bf16x3_supported(const fn2_conv_desc* desc);
+int fn2_deconv_bf16x3_num_variants(void);
+int fn2_debug_set_deconv_bf16x3_variant(int variant);
 int fn2_conv_route(const fn2_conv_desc* desc, int flags);
 size_t fn2_conv_packed_weight_floats(const fn2_conv_desc* desc, int route);
 int fn2_conv_pack_weights(const fn2_conv_desc* desc, int route, const float* weight, float* packed, void* stream);

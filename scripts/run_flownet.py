@@ -93,7 +93,7 @@ def infer_prototxt(model, template_path, img0, img1, device):
 
 def _positionals(argv):
     """Positional arguments of either form: the values of the value-taking options are not positionals."""
-    takes_value = {"--gpu", "--weights", "--net", "--conv-arith"}
+    takes_value = {"--gpu", "--weights", "--net", "--conv-arith", "--deconv-arith"}
     out, skip = [], False
     for a in argv:
         if skip:
@@ -119,6 +119,8 @@ def main():
         ap.add_argument("--no-batch-invariant", action="store_true")
         ap.add_argument("--conv-arith", choices=["fp32", "bf16x3"], default=None,
                         help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
+        ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
+                        help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
         a = ap.parse_args()
         if not a.caffemodel.startswith("seed:") and not os.path.exists(a.caffemodel):
             raise SystemExit("caffemodel does not exist: " + a.caffemodel)                   # run-flownet.py:20
@@ -132,6 +134,8 @@ def main():
         Fn.set_batch_invariant(not a.no_batch_invariant)
         if a.conv_arith:
             Fn.set_conv_arithmetic(a.conv_arith)
+        if a.deconv_arith:
+            Fn.set_deconv_arithmetic(a.deconv_arith)
         i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
         flow = infer_prototxt(a.caffemodel, a.deployproto, i0, i1, dev)
         flo.write_flo(a.out, flow[0].cpu().numpy())
@@ -145,6 +149,8 @@ def main():
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection follow the work size (see run_flownet_many.py)")
     ap.add_argument("--conv-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
+    ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
     a = ap.parse_args()
     for f in (a.img0, a.img1):
         if not os.path.exists(f):
@@ -154,6 +160,8 @@ def main():
     Fn.set_batch_invariant(not a.no_batch_invariant)
     if a.conv_arith:
         Fn.set_conv_arithmetic(a.conv_arith)
+    if a.deconv_arith:
+        Fn.set_deconv_arithmetic(a.deconv_arith)
     P, mean = load_params(a.net, a.weights, dev)
     i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
     flow = infer(a.net, P, i0, i1, mean)

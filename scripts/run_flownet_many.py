@@ -68,6 +68,8 @@ def main():
     ap.add_argument("--gpu", type=int, default=None, help="device index (default: LOCAL_RANK)")
     ap.add_argument("--conv-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
+    ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -78,6 +80,8 @@ def main():
     Fn.set_batch_invariant(not a.no_batch_invariant)
     if a.conv_arith:
         Fn.set_conv_arithmetic(a.conv_arith)
+    if a.deconv_arith:
+        Fn.set_deconv_arithmetic(a.deconv_arith)
     entries = [l.split() for l in open(a.listfile) if l.strip()]
     mine = parallel.shard(entries)
     P, mean = RF.load_params(a.net, a.weights, dev)
