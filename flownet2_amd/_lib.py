@@ -41,6 +41,7 @@ EXPORTS = [
     "fn2_debug_set_wgrad_buffers", "fn2_debug_set_wgrad_chunk", "fn2_conv_wgrad_supported", "fn2_conv_wgrad_ksplit", "fn2_conv_wgrad_workspace_bytes", "fn2_conv_wgrad",
     "fn2_conv_bf16x3_supported", "fn2_conv_bf16x3_num_variants", "fn2_debug_set_conv_bf16x3_variant",
     "fn2_deconv_bf16x3_supported", "fn2_deconv_bf16x3_num_variants", "fn2_debug_set_deconv_bf16x3_variant",
+    "fn2_correlation_bf16x3_supported", "fn2_correlation_bf16x3_num_variants", "fn2_debug_set_correlation_bf16x3_variant",
     "fn2_conv_route", "fn2_conv_packed_weight_floats", "fn2_conv_pack_weights", "fn2_conv_workspace_bytes", "fn2_conv_forward",
     "fn2_deconv_route", "fn2_deconv_packed_weight_floats", "fn2_deconv_pack_weights", "fn2_deconv_workspace_bytes", "fn2_deconv_forward",
     "fn2_conv_backward_data_route", "fn2_conv_backward_data_packed_weight_floats", "fn2_conv_backward_data_pack_workspace_bytes",
@@ -110,6 +111,9 @@ class L1LossScale(C.Structure):
 
 _lib = None
 
+# include/flownet2_hip_corr_route.h: the correlation's route query and routed forward (dispatchers: no CPU twin in the oracle)
+CORR_ROUTE_EXPORTS = ["fn2_correlation_route", "fn2_correlation_forward_routed"]
+
 
 def lib():
     """Load (once) and return the CDLL.  Raises if the native library is unavailable."""
@@ -129,6 +133,11 @@ def lib():
     L.fn2_correlation_workspace_bytes.restype = sz
     L.fn2_correlation_forward.argtypes = [C.POINTER(CorrParams), fp, fp, fp, i, i, i, i, vp, sz, vp]
     L.fn2_correlation_forward_fused.argtypes = [C.POINTER(CorrParams), fp, fp, fp, i, i, i, i, i, i, i, C.c_float, vp, sz, vp]
+    L.fn2_correlation_bf16x3_supported.argtypes = [C.POINTER(CorrParams), i, i, i, i]
+    L.fn2_correlation_bf16x3_num_variants.argtypes = []
+    L.fn2_debug_set_correlation_bf16x3_variant.argtypes = [i]
+    L.fn2_correlation_route.argtypes = [C.POINTER(CorrParams), i, i, i, i, i]
+    L.fn2_correlation_forward_routed.argtypes = [C.POINTER(CorrParams), i, fp, fp, fp, i, i, i, i, i, i, i, C.c_float, vp, sz, vp]
     L.fn2_correlation_backward.argtypes = [C.POINTER(CorrParams), fp, fp, fp, fp, fp, i, i, i, i, vp, sz, vp]
     L.fn2_correlation1d_out_shape.argtypes = [C.POINTER(CorrParams), i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
     L.fn2_correlation1d_forward.argtypes = [C.POINTER(CorrParams), fp, fp, fp, i, i, i, i, vp]

@@ -12,6 +12,9 @@
 //       one thread per output element, x fastest (coalesced).  Fallback + cross-check.
 //   corr_fwd_mfma (correlation_mfma.hip), corr_bwd_mfma (correlation_bwd_mfma.hip): the FlowNetC fast paths,
 //       kernel_size 1, stride_1 1, MULTIPLY: 2-D banded GEMMs on v_mfma_f32_16x16x4_f32 (exact fp32).
+//   corr_fwd_bf16x3 (correlation_bf16x3.hip): the forward of the FlowNetC instance in split-bf16 arithmetic on v_mfma_f32_16x16x32_bf16,
+//       opt-in: fn2_correlation_route with FN2_ROUTE_BF16X3 -> fn2_correlation_forward_routed(FN2_CORR_ROUTE_OWN | FN2_CONV_ARITH_BF16X3).
+//       Every other entry point, and the backward, stays exact fp32.
 #include "correlation.hpp"
 
 #include <cmath>
@@ -246,6 +249,38 @@ FN2_API int fn2_correlation_forward_fused(const fn2_corr_params* p, const float*
   else
     hipLaunchKernelGGL(corr_fwd_generic<true>, dim3(blocks), dim3(256), 0, st, bottom0, bottom1, top, g);
   return check_launch("correlation_forward");
+}
+
+// The route of the layer: one route of its own (the dispatch above), and beside it the arithmetic bit of the split-bf16 kernel
+// (correlation_bf16x3.hip) where FN2_ROUTE_BF16X3 asks for it and that kernel takes the layer.  Geometry alone: no hook, no batch-invariant mode.
+FN2_API int fn2_correlation_route(const fn2_corr_params* p, int N, int C, int H, int W, int flags) {
+  CorrGeom g;
+  if (corr_geometry(p, N, C, H, W, &g) != FN2_OK) { last_error().clear(); return FN2_CORR_ROUTE_NONE; }
+  if ((flags & FN2_ROUTE_BF16X3) && corr_bf16x3_geometry_ok(p, N, C, H, W)) return FN2_CORR_ROUTE_OWN | FN2_CONV_ARITH_BF16X3;
+  return FN2_CORR_ROUTE_OWN;
+}
+
+FN2_API int fn2_correlation_forward_routed(const fn2_corr_params* p, int route, const float* bottom0, const float* bottom1, float* top,
+                                           int N, int C, int H, int W, int top_channels, int top_c0, int relu, float negative_slope,
+                                           void* ws, size_t ws_bytes, void* stream) {
+  if (route == FN2_CORR_ROUTE_OWN)
+    return fn2_correlation_forward_fused(p, bottom0, bottom1, top, N, C, H, W, top_channels, top_c0, relu, negative_slope, ws, ws_bytes, stream);
+  if (route != (FN2_CORR_ROUTE_OWN | FN2_CONV_ARITH_BF16X3)) return fail(FN2_ERR_INVALID_ARG, "correlation_forward: %d is not a correlation route", route);
+  CorrGeom g;
+  int rc = corr_geometry(p, N, C, H, W, &g);
+  if (rc) return rc;
+  if (top_channels > 0) {
+    if (top_c0 < 0 || top_c0 + g.topC > top_channels) return fail(FN2_ERR_INVALID_ARG, "correlation_forward: channel slice outside the top blob");
+    g.top_ctot = top_channels; g.top_c0 = top_c0;
+  }
+  g.relu = relu != 0; g.slope = negative_slope;
+  if (!corr_bf16x3_geometry_ok(p, N, C, H, W))
+    return fail(FN2_ERR_UNSUPPORTED, "correlation_forward: the split-bf16 kernel does not take this layer ([%d,%d,%d,%d])", N, C, H, W);
+  if (N == 0) return FN2_OK;
+  if (!bottom0 || !bottom1 || !top) return fail(FN2_ERR_INVALID_ARG, "correlation_forward: NULL blob pointer");
+  if (((reinterpret_cast<uintptr_t>(bottom0) | reinterpret_cast<uintptr_t>(bottom1) | reinterpret_cast<uintptr_t>(top)) & 15) != 0)
+    return fail(FN2_ERR_UNSUPPORTED, "correlation_forward (bf16x3): blobs must be 16-byte aligned");
+  return corr_bf16x3_launch(g, bottom0, bottom1, top, as_stream(stream));
 }
 
 FN2_API int fn2_correlation_backward(const fn2_corr_params* p, const float* bottom0, const float* bottom1,

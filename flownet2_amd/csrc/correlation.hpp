@@ -21,6 +21,9 @@ int corr_fwd_mfma_launch(const CorrGeom& g, const float* b0, const float* b1, fl
 bool corr_fwd_units_supported(const CorrGeom& g, const float* b0, const float* b1, const float* top);
 int corr_fwd_units_launch(const CorrGeom& g, const float* b0, const float* b1, float* top, hipStream_t st);
 int corr_fwd_units_plan_words(int N, int H, int W, int policy, unsigned* out, int max_words);
+// the FlowNetC instance in split-bf16 arithmetic (correlation_bf16x3.hip; FN2_CONV_ARITH_BF16X3 beside FN2_CORR_ROUTE_OWN)
+bool corr_bf16x3_geometry_ok(const fn2_corr_params* p, int N, int C, int H, int W);
+int corr_bf16x3_launch(const CorrGeom& g, const float* b0, const float* b1, float* top, hipStream_t st);
 bool corr_bwd_mfma_supported(const CorrGeom& g);
 int corr_bwd_mfma_launch(const CorrGeom& g, int which, const float* other, const float* top_diff, float* out, hipStream_t st);
 // both bottom diffs in ONE launch; FN2_ERR_UNSUPPORTED (no error text) where it does not apply

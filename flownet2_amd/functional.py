@@ -70,7 +70,7 @@ class _Correlation(torch.autograd.Function):
     def forward(ctx, b0, b1, params):
         ctx.params = params
         ctx.save_for_backward(b0, b1)
-        return ops.correlation_forward(params, b0, b1)
+        return ops.correlation_forward(params, b0, b1, bf16x3=_CORR_ARITH[0] == "bf16x3")
 
     @staticmethod
     def backward(ctx, g):
@@ -91,7 +91,7 @@ class _CorrelationReluInto(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, b0, b1, params, blob, c0, slope):
-        ops.correlation_forward(params, b0, b1, out=blob, out_c0=c0, relu=True, negative_slope=slope)
+        ops.correlation_forward(params, b0, b1, out=blob, out_c0=c0, relu=True, negative_slope=slope, bf16x3=_CORR_ARITH[0] == "bf16x3")
         tc = ops.correlation_out_shape(params, b0.shape[1], b0.shape[2], b0.shape[3])[0]
         ctx.cfg = (params, c0, tc, slope)
         ctx.save_for_backward(b0, b1, blob)
@@ -117,7 +117,8 @@ def correlation_relu_into(b0, b1, out, out_c0, negative_slope, pad=0, kernel_siz
         if not training:
             return None
         return _CorrelationReluInto.apply(b0.contiguous(), b1.contiguous(), p, out, out_c0, negative_slope)
-    return ops.correlation_forward(p, b0.contiguous(), b1.contiguous(), out=out, out_c0=out_c0, relu=True, negative_slope=negative_slope)
+    return ops.correlation_forward(p, b0.contiguous(), b1.contiguous(), out=out, out_c0=out_c0, relu=True, negative_slope=negative_slope,
+                                   bf16x3=_CORR_ARITH[0] == "bf16x3")
 
 
 class _FlowWarp(torch.autograd.Function):
@@ -469,6 +470,27 @@ def deconv_arithmetic() -> str:
 
 if os.environ.get("FN2_DECONV_ARITH"):
     set_deconv_arithmetic(os.environ["FN2_DECONV_ARITH"])
+
+
+_CORR_ARITH = ["fp32"]
+
+
+def set_correlation_arithmetic(name: str = "fp32"):
+    """Arithmetic of the Correlation FORWARD, a switch of its own beside set_conv_arithmetic / set_deconv_arithmetic: "fp32" (the default) or
+    "bf16x3" -- split-bf16 arithmetic on the layers fn2_correlation_route hands to that kernel (csrc/correlation_bf16x3.hip: the FlowNetC
+    instance, C % 32 == 0, W % 4 == 0); every other layer, and the backward, stays exact fp32.  Honoured by correlation /
+    correlation_relu_into here and by layers.CorrelationLayer.  Initial value: $FN2_CORR_ARITH."""
+    if name not in _CONV_ARITHMETICS:
+        raise ValueError("correlation arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
+    _CORR_ARITH[0] = name
+
+
+def correlation_arithmetic() -> str:
+    return _CORR_ARITH[0]
+
+
+if os.environ.get("FN2_CORR_ARITH"):
+    set_correlation_arithmetic(os.environ["FN2_CORR_ARITH"])
 
 
 def _channel_slice(x):

@@ -279,7 +279,8 @@ class CorrelationLayer(Layer):
         top[0].Reshape(self.num_, tc, th, tw)                                        # cpp:73
 
     def Forward_gpu(self, bottom, top):
-        _wrap(ops.correlation_forward, self.params_, bottom[0].data, bottom[1].data, out=top[0].data)
+        from . import functional as Fn      # (imports this module): the arithmetic switch, functional.set_correlation_arithmetic
+        _wrap(ops.correlation_forward, self.params_, bottom[0].data, bottom[1].data, out=top[0].data, bf16x3=Fn.correlation_arithmetic() == "bf16x3")
 
     def Backward_gpu(self, top, propagate_down, bottom):
         # like the reference (correlation_layer.cu:508-603) both diffs are always written

@@ -48,10 +48,20 @@ def correlation_out_shape(p: CorrParams, Cc: int, H: int, W: int):
     return tc.value, th.value, tw.value
 
 
+CORR_ROUTE_NONE, CORR_ROUTE_OWN = 0, 1    # FN2_CORR_ROUTE_*: the layer's own dispatch; CONV_ARITH_BF16X3 (below) is the arithmetic bit beside it
+
+
+def correlation_forward_route(p: CorrParams, N: int, Cc: int, H: int, W: int, bf16x3: bool = False) -> int:
+    """fn2_correlation_route: CORR_ROUTE_NONE for parameters correlation_out_shape refuses, CORR_ROUTE_OWN | CONV_ARITH_BF16X3 where bf16x3
+    is asked for and the split-bf16 kernel (csrc/correlation_bf16x3.hip) takes the layer, CORR_ROUTE_OWN otherwise."""
+    return int(_lib.lib().fn2_correlation_route(C.byref(p), int(N), int(Cc), int(H), int(W), ROUTE_BF16X3 if bf16x3 else 0))
+
+
 def correlation_forward(p: CorrParams, bottom0: torch.Tensor, bottom1: torch.Tensor, out: torch.Tensor | None = None,
-                        out_c0: int = 0, relu: bool = False, negative_slope: float = 0.0):
+                        out_c0: int = 0, relu: bool = False, negative_slope: float = 0.0, bf16x3: bool = False):
     """top = Correlation(bottom0, bottom1).  With `out` wider than topC channels the layer writes the slice
-    [out_c0, out_c0 + topC) of it (the Concat that follows it in FlowNetC); relu applies ReLU{negative_slope} on the way out."""
+    [out_c0, out_c0 + topC) of it (the Concat that follows it in FlowNetC); relu applies ReLU{negative_slope} on the way out.
+    bf16x3: split-bf16 arithmetic where fn2_correlation_route hands the layer to that kernel; every other layer stays exact."""
     b0, b1 = _chk(bottom0, "bottom[0]"), _chk(bottom1, "bottom[1]")
     if b0.shape != b1.shape:   # correlation_layer.cpp:45-47
         raise ValueError("Both bottom blobs must have same shape")
@@ -59,11 +69,9 @@ def correlation_forward(p: CorrParams, bottom0: torch.Tensor, bottom1: torch.Ten
     tc, th, tw = correlation_out_shape(p, Cc, H, W)
     top = out if out is not None else torch.empty((N, tc, th, tw), device=b0.device, dtype=torch.float32)
     assert top.is_contiguous() and top.shape[0] == N and tuple(top.shape[2:]) == (th, tw) and out_c0 + tc <= top.shape[1]
-    if not relu and out_c0 == 0 and top.shape[1] == tc:
-        check(_lib.lib().fn2_correlation_forward(C.byref(p), _ptr(b0), _ptr(b1), _ptr(top), N, Cc, H, W, None, 0, _stream()))
-    else:
-        check(_lib.lib().fn2_correlation_forward_fused(C.byref(p), _ptr(b0), _ptr(b1), _ptr(top), N, Cc, H, W, int(top.shape[1]), int(out_c0),
-                                                       int(bool(relu)), C.c_float(float(negative_slope)), None, 0, _stream()))
+    route = correlation_forward_route(p, N, Cc, H, W, bf16x3=True) if bf16x3 else CORR_ROUTE_OWN      # (exact: the one route of every layer)
+    check(_lib.lib().fn2_correlation_forward_routed(C.byref(p), route, _ptr(b0), _ptr(b1), _ptr(top), N, Cc, H, W, int(top.shape[1]), int(out_c0),
+                                                    int(bool(relu)), C.c_float(float(negative_slope)), None, 0, _stream()))
     return top
 
 

@@ -534,6 +534,26 @@ int fn2_debug_set_conv_bf16x3_variant(int variant);
 int fn2_deconv_bf16x3_supported(const fn2_conv_desc* desc);
 int fn2_deconv_bf16x3_num_variants(void);
 int fn2_debug_set_deconv_bf16x3_variant(int variant);
+/* The same arithmetic for the Correlation forward (csrc/correlation_bf16x3.hip), by the same convention: the arithmetic is a bit beside
+ * the route.  The layer has one route of its own, FN2_CORR_ROUTE_OWN = the dispatch of fn2_correlation_forward_fused (unit kernel,
+ * corr_fwd_pair, the general MFMA kernel, the generic one; fn2_debug_set_correlation_impl steers it).  fn2_correlation_route returns NONE for
+ * parameters fn2_correlation_out_shape refuses, OWN | FN2_CONV_ARITH_BF16X3 when FN2_ROUTE_BF16X3 is in `flags` and the split kernel takes the
+ * layer (fn2_correlation_bf16x3_supported, geometry alone: kernel_size 1, stride_1 1, stride_2 2, max_displacement 20 = pad, MULTIPLY,
+ * C % 32 == 0, W % 4 == 0, the 32-bit offset limits of the exact kernels), OWN otherwise; the answer does not depend on batch-invariant mode.
+ * Both bottoms are cut into three bf16 pieces inside the kernel (no weights, no workspace, no pre-split copy); per 32-channel k-step, in
+ * ascending order and without a K split, mm, lh, hl, mh, hm, hh (first letter: bottom0's piece) go to one fp32 accumulator; 1 / C and the
+ * ReLU are applied to the final value.  Bit-reproducible, batch-independent, the same bits from every variant; meets the fp64 bound of the
+ * exact kernels (2e-6 x scale, tests/test_correlation_bf16x3.py).  fn2_correlation_forward_routed: route OWN is exactly
+ * fn2_correlation_forward_fused; OWN | FN2_CONV_ARITH_BF16X3 runs the split kernel (FN2_ERR_UNSUPPORTED where it does not take the layer
+ * or a blob is not 16-byte aligned; the debug impl codes do not apply); any other value is FN2_ERR_INVALID_ARG.  The backward stays exact fp32.
+ * Measurements: profiles/corr_bf16x3_bench.md. */
+int fn2_correlation_bf16x3_supported(const fn2_corr_params* p, int N, int C, int H, int W);
+int fn2_correlation_bf16x3_num_variants(void);
+int fn2_debug_set_correlation_bf16x3_variant(int variant);
+/* FN2_CORR_ROUTE_*, the route query and the routed forward: descriptor-level dispatchers like the convolution ones below, declared in a header of
+ * their own (tests/test_cabi.py asks the CPU oracle for a twin of every function THIS file declares outside its list of dispatchers; a
+ * dispatcher has none -- every kernel it routes to has its own). */
+#include "flownet2_hip_corr_route.h"
 int fn2_conv_route(const fn2_conv_desc* desc, int flags);
 size_t fn2_conv_packed_weight_floats(const fn2_conv_desc* desc, int route);
 int fn2_conv_pack_weights(const fn2_conv_desc* desc, int route, const float* weight, float* packed, void* stream);

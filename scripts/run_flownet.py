@@ -121,6 +121,9 @@ def main():
                         help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
         ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
                         help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
+        ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
+                        help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
+                             "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
         a = ap.parse_args()
         if not a.caffemodel.startswith("seed:") and not os.path.exists(a.caffemodel):
             raise SystemExit("caffemodel does not exist: " + a.caffemodel)                   # run-flownet.py:20
@@ -136,6 +139,8 @@ def main():
             Fn.set_conv_arithmetic(a.conv_arith)
         if a.deconv_arith:
             Fn.set_deconv_arithmetic(a.deconv_arith)
+        if a.corr_arith:
+            Fn.set_correlation_arithmetic(a.corr_arith)
         i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
         flow = infer_prototxt(a.caffemodel, a.deployproto, i0, i1, dev)
         flo.write_flo(a.out, flow[0].cpu().numpy())
@@ -151,6 +156,9 @@ def main():
                     help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
     ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
+    ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
+                         "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
     a = ap.parse_args()
     for f in (a.img0, a.img1):
         if not os.path.exists(f):
@@ -162,6 +170,8 @@ def main():
         Fn.set_conv_arithmetic(a.conv_arith)
     if a.deconv_arith:
         Fn.set_deconv_arithmetic(a.deconv_arith)
+    if a.corr_arith:
+        Fn.set_correlation_arithmetic(a.corr_arith)
     P, mean = load_params(a.net, a.weights, dev)
     i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
     flow = infer(a.net, P, i0, i1, mean)
