@@ -271,3 +271,225 @@ def downsample(x: np.ndarray, Hout, Wout) -> np.ndarray:
                 r[(nansum / wsum) > 0.5] = np.nan
             out[:, :, dy, dx] = r
     return out
+
+
+# ---- elementwise fp64 statements of Resample / Downsample / ChannelNorm (tests/test_resample.py, test_downsample_channel_norm.py) ----
+# Positions and scale factors are rounded to fp32 exactly as the host functions and kernels round them (so that the statement picks
+# the same window and the same taps); coefficients, products, sums and the division are fp64.  Each statement also returns, per
+# output element, the quantities an elementwise rounding-error bound needs.
+
+_U = 2.0 ** -24
+_F32 = np.float32
+
+
+def _roundf(v):
+    """C roundf (half away from zero) of fp32 values, as int64."""
+    v = np.asarray(v, np.float64)
+    return (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int64)
+
+
+def resample_geometry(Hin, Win, Hout, Wout, kind="linear", antialias=True):
+    """fx, fy, ax, ay (fp32) and rx, ry as fn2_resample_forward_slices forms them (resample_layer.cu:146-147, :71-74, :179-185)."""
+    fx, fy = _F32(Win) / _F32(Wout), _F32(Hin) / _F32(Hout)
+    aa = bool((fx > 1) or (fy > 1)) and bool(antialias)
+    ax = _F32(1) / (fx if aa else _F32(1))
+    ay = _F32(1) / (fy if aa else _F32(1))
+    kw = _F32(4 if kind == "cubic" else 2)
+    rx = 2 if fx < 1 else int(np.ceil(kw / ax))
+    ry = 2 if fy < 1 else int(np.ceil(kw / ay))
+    return dict(fx=fx, fy=fy, ax=ax, ay=ay, rx=rx, ry=ry)
+
+
+def resample_positions(n_out, f_own, f_other):
+    """fp32(fp32(fp32(o * f_own) + fp32(f_other / 2)) - 0.5), uncontracted: x_in uses (fx, fy), y_in (fy, fx) -- the reference's swap."""
+    o = np.arange(n_out, dtype=_F32)
+    return (o * _F32(f_own) + _F32(f_other) / _F32(2)) - _F32(0.5)
+
+
+def _coeff32(t32, kind):
+    """The kernels' fp32 coefficient of an fp32 argument, operation by operation (resample.hip is compiled without contraction, and
+    numpy rounds every fp32 operation): bicubic_coeff / triangle_coeff of resample_layer.cu:14-33."""
+    t32 = np.asarray(t32, _F32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        if kind == "cubic":
+            x = np.abs(t32)
+            p1 = x * x * (_F32(1.5) * x - _F32(2.5)) + _F32(1)
+            p2 = x * (x * (_F32(-0.5) * x + _F32(2.5)) - _F32(4)) + _F32(2)
+            return np.where(x <= 1, p1, np.where(x < 2, p2, _F32(0)))
+        return np.where((t32 >= -1) & (t32 < 0), t32 + _F32(1), np.where((t32 >= 0) & (t32 <= 1), _F32(1) - t32, _F32(0)))
+
+
+def _axis_table(n_in, n_out, f_own, f_other, a, r, kind):
+    """Per output index of one axis: tap indices [n_out, 2r+1] (clamped into the image), their in-image mask, the fp64 coefficient
+    a * k(a * (pos - tap)) (0 for a tap outside), the part `e` of its fp32 error that is NOT relative to it (in absolute units), and
+    whether fp32 and fp64 disagree on an in-image tap's coefficient being 0 (a tap on a zero of the kernel: |t| = 1 or 2)."""
+    pos = resample_positions(n_out, f_own, f_other)
+    centre = _roundf(pos)
+    taps = centre[:, None] + np.arange(-r, r + 1)[None]
+    ok = (taps >= 0) & (taps < n_in)
+    a32, a = _F32(a), float(a)
+    t = a * (pos.astype(np.float64)[:, None] - taps)
+    k = _cub(t) if kind == "cubic" else _tri(t)
+    # the coefficient the kernels form from the same fp32 position: k32(fp32(a * fp32(pos - tap))).  e = |k32 - k| is the part of a
+    # weight's fp32 error that is not relative to the weight (the argument's two roundings, the cancellation of 1 - |t| and of the
+    # cubic polynomial near its zeros); `edge`: fp32 and fp64 disagree on whether the coefficient is 0.
+    with np.errstate(over="ignore", invalid="ignore"):
+        k32 = _coeff32(a32 * (pos.astype(_F32)[:, None] - taps.astype(_F32)), kind).astype(np.float64)
+    e = np.abs(k32 - k)
+    edge = (k32 == 0) != (k == 0)
+    w = np.where(ok, a * k, 0.0)
+    e = np.where(ok, a * e, 0.0)
+    live = ok & ((k != 0) | (k32 != 0))                              # a coefficient of exactly 0 adds +0 exactly: no rounding
+    return dict(idx=np.clip(taps, 0, n_in - 1), ok=ok, w=w, e=e, edge=(edge & ok).any(1), pos=pos, centre=centre, live=live.sum(1))
+
+
+def _sep(x, tab, weights, axis):
+    """sum_k weights[o, k] * x[..., tap(o, k), ...] along `axis` (taps outside the image contribute a 0 sample, NOT 0 * a clamped one).
+    Lines of finite samples go through one matrix product; a line with a NaN / Inf is gathered tap by tap, so that only the taps of
+    an output's own window can poison it."""
+    x = np.moveaxis(x, axis, -1)
+    n_out, K = tab["idx"].shape
+    w = np.where(tab["ok"], weights, 0.0)
+    M = np.zeros((n_out, x.shape[-1]))
+    np.add.at(M, (np.repeat(np.arange(n_out), K), tab["idx"].ravel()), w.ravel())
+    fin = np.isfinite(x).all(-1)
+    out = np.empty(x.shape[:-1] + (n_out,))
+    out[fin] = x[fin] @ M.T
+    if not fin.all():
+        out[~fin] = (np.where(tab["ok"], x[~fin][..., tab["idx"]], 0.0) * weights).sum(-1)       # [lines, n_out, K]
+    return np.moveaxis(out, -1, axis)
+
+
+def resample_statement(x, Hout, Wout, kind="linear", antialias=True, in_scale=1.0):
+    """Resample (resample_layer.cu:39-95) per output element in fp64 over the in-image taps of the kernel's own window.
+
+    fx, fy, ax, ay, rx, ry and the source positions are fp32 as the host function and the kernels form them; `in_scale` rounds every
+    tap to fp32(tap * in_scale) first (the folded Eltwise).
+
+    Returns a dict of float64 arrays -- per element [N,C,Hout,Wout]: ref, A = sum |w tap|, Ae = sum |e_w tap| (e_w: the part of a
+    weight's fp32 error that is not relative to the weight); hull() -> (min, max) of the window's taps, computed on demand;
+    per pixel [Hout,Wout]: ws = sum w, Aw = sum |w|, Awe = sum e_w, m = the number of in-image taps with a non-zero coefficient,
+    taps = the number of in-image taps, edge = fp32 and fp64 disagree on whether the weight of some in-image tap is 0 (a tap exactly
+    on the edge of the support), xr / yr = the window centres."""
+    x = np.ascontiguousarray(x, np.float32)
+    if in_scale != 1.0:
+        x = x * _F32(in_scale)
+    N, C, Hin, Win = x.shape
+    g = resample_geometry(Hin, Win, Hout, Wout, kind, antialias)
+    tx = _axis_table(Win, Wout, g["fx"], g["fy"], g["ax"], g["rx"], kind)          # x_in takes fy / 2 and y_in fx / 2: the reference's swap
+    ty = _axis_table(Hin, Hout, g["fy"], g["fx"], g["ay"], g["ry"], kind)
+    xd, xa = x.astype(np.float64), np.abs(x.astype(np.float64))
+    with np.errstate(invalid="ignore", over="ignore"):
+        sx = _sep(xd, tx, tx["w"], 3)
+        sxa, sxe = _sep(xa, tx, np.abs(tx["w"]), 3), _sep(xa, tx, tx["e"], 3)
+        num = _sep(sx, ty, ty["w"], 2)
+        A = _sep(sxa, ty, np.abs(ty["w"]), 2)
+        Ae = _sep(sxe, ty, np.abs(ty["w"]), 2) + _sep(sxa, ty, ty["e"], 2)
+    ws = ty["w"].sum(1)[:, None] * tx["w"].sum(1)[None]
+    Aw = np.abs(ty["w"]).sum(1)[:, None] * np.abs(tx["w"]).sum(1)[None]
+    Awe = (np.abs(ty["w"]).sum(1)[:, None] * tx["e"].sum(1)[None] + ty["e"].sum(1)[:, None] * np.abs(tx["w"]).sum(1)[None])
+    m = ty["live"][:, None] * tx["live"][None]
+    taps = ty["ok"].sum(1)[:, None] * tx["ok"].sum(1)[None]
+
+    def hull(fn, fill):
+        v = np.moveaxis(xd, 3, -1)
+        v = fn(np.where(tx["ok"], v[..., tx["idx"]], fill), -1)          # [N,C,Hin,Wout]
+        v = np.moveaxis(v, 2, -1)
+        v = fn(np.where(ty["ok"], v[..., ty["idx"]], fill), -1)          # [N,C,Wout,Hout]
+        return np.swapaxes(v, 2, 3)
+
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        ref = np.where(ws == 0, 0.0, num / np.where(ws == 0, 1.0, ws))
+    return dict(ref=ref, ws=ws, A=A, Aw=Aw, Ae=Ae, Awe=Awe, m=m, hull=lambda: (hull(np.min, np.inf), hull(np.max, -np.inf)),
+                edge=ty["edge"][:, None] | tx["edge"][None], taps=taps, geometry=g, xr=tx["centre"], yr=ty["centre"])
+
+
+def resample_nearest(x, Hout, Wout, in_scale=1.0):
+    """NEAREST (resample_layer.cu:117-123, the index clamped into the image): a bitwise statement, fp32 in and out."""
+    x = np.ascontiguousarray(x, np.float32)
+    if in_scale != 1.0:
+        x = x * _F32(in_scale)
+    Hin, Win = x.shape[2:]
+    g = resample_geometry(Hin, Win, Hout, Wout)
+    xr = np.clip(_roundf(resample_positions(Wout, g["fx"], g["fy"])), 0, Win - 1)
+    yr = np.clip(_roundf(resample_positions(Hout, g["fy"], g["fx"])), 0, Hin - 1)
+    return x[:, :, yr[:, None], xr[None]]
+
+
+def downsample_geometry(Hin, Win, Hout, Wout):
+    """widthScale, heightScale (fp32), the radii, and per output column / row botx / boty (fp32), the rounded centre and the clipped
+    tap range [x0, x1] / [y0, y1]: down_plan and downsample_thread_body (downsample_layer.cu:104-108, :27-31)."""
+    ws, hs = _F32(Win - 1) / _F32(Wout - 1), _F32(Hin - 1) / _F32(Hout - 1)
+    wr, hr = int(np.ceil(ws)), int(np.ceil(hs))
+    botx = (np.arange(Wout, dtype=_F32) / _F32(Wout - 1)) * _F32(Win - 1)
+    boty = (np.arange(Hout, dtype=_F32) / _F32(Hout - 1)) * _F32(Hin - 1)
+    ix, iy = _roundf(botx), _roundf(boty)
+    return dict(ws=ws, hs=hs, wr=wr, hr=hr, botx=botx, boty=boty,
+                x0=np.maximum(ix - wr, 0), x1=np.minimum(ix + wr, Win - 1), y0=np.maximum(iy - hr, 0), y1=np.minimum(iy + hr, Hin - 1))
+
+
+def downsample_weights(Hin, Win, Hout, Wout):
+    """fp64 tap weights of every output row / column from the fp32 positions and scales: wy [Hout,Hin], wx [Wout,Win] (0 outside the
+    window), and ey / ex = |w32 - w|, where w32 is the weight the kernels form in fp32 from the same position, operation by operation
+    (fmaxf(0, 1 - fabsf(tap - bot) / scale), :52): the rounding of tap - bot, of the division and the cancellation in 1 - q move a
+    weight by up to 2u q whatever its size -- the part of its error that is not relative to it."""
+    g = downsample_geometry(Hin, Win, Hout, Wout)
+
+    def axis(n_in, bot, lo, hi, scale):
+        t = np.arange(n_in)[None]
+        q = np.abs(t - bot.astype(np.float64)[:, None]) / float(scale)
+        inside = (t >= lo[:, None]) & (t <= hi[:, None])
+        w = np.where(inside, np.maximum(0.0, 1 - q), 0.0)
+        w32 = np.maximum(_F32(0), _F32(1) - np.abs(np.arange(n_in, dtype=_F32)[None] - bot[:, None]) / _F32(scale)).astype(np.float64)
+        return w, np.where(inside, np.abs(w32 - w), 0.0)
+
+    wy, ey = axis(Hin, g["boty"], g["y0"], g["y1"], g["hs"])
+    wx, ex = axis(Win, g["botx"], g["x0"], g["x1"], g["ws"])
+    return g, wy, wx, ey, ex
+
+
+def downsample_statement(x, Hout, Wout):
+    """Downsample (downsample_layer.cu:15-72) per output element in fp64: weights from the fp32 positions, NaN samples vote with their
+    weight and leave the sums.  Returns float64 arrays [N,C,Hout,Wout]: ref (NaN where the vote says so), A = sum |s| w / W,
+    Ae = sum |s| e_w / W and Ee = sum e_w / W (e_w: see downsample_weights), W = the valid weight, Wn = the NaN weight, r = Wn / W
+    (inf for an all-NaN window), voted = the NaN mask; and Wt = sum w [Hout,Wout].
+    value = the quotient without the vote.  The vote is Wn / W > 0.5: strict, over the valid weight only."""
+    x = np.ascontiguousarray(x, np.float32)
+    N, C, Hin, Win = x.shape
+    g, wy, wx, ey, ex = downsample_weights(Hin, Win, Hout, Wout)
+    isn = np.isnan(x)
+    s = np.where(isn, 0.0, x.astype(np.float64))
+
+    def both(a, my, mx):                                              # sum_{y,x} my[o,y] a[..,y,x] mx[p,x]
+        return np.einsum("oy,ncyp->ncop", my, np.einsum("ncyx,px->ncyp", a, mx, optimize=True), optimize=True)
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        val = both(s, wy, wx)
+        Wn = both(isn.astype(np.float64), wy, wx)
+        Wt = wy.sum(1)[:, None] * wx.sum(1)[None]
+        W = both((~isn).astype(np.float64), wy, wx)
+        sa = np.abs(s)
+        A = both(sa, wy, wx) / W
+        Ae = (both(sa, ey, wx) + both(sa, wy, ex)) / W
+        Ee = (ey.sum(1)[:, None] * wx.sum(1)[None] + wy.sum(1)[:, None] * ex.sum(1)[None])[None, None] / W
+        r = Wn / W
+        value = val / W
+        nan = r > 0.5
+        ref = np.where(nan, np.nan, value)
+    return dict(ref=ref, value=value, A=A, Ae=Ae, Ee=Ee, W=W, Wn=Wn, r=r, Wt=Wt, voted=nan, geometry=g)
+
+
+def channel_norm_statement(x, minus=None):
+    """sqrt(sum_c v^2) in fp64, v = the fp32 difference x - minus for the folded-subtraction form."""
+    v = np.asarray(x, np.float32)
+    if minus is not None:
+        v = v - np.asarray(minus, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.sqrt((v.astype(np.float64) ** 2).sum(1, keepdims=True))
+
+
+def channel_norm_backward_statement(x, top, top_diff):
+    """(g * x) / (top + 1e-9) in fp64 with g * x rounded to fp32 first (channel_norm_layer.cu:45)."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        gx = np.asarray(top_diff, np.float32) * np.asarray(x, np.float32)
+        return gx.astype(np.float64) / (np.asarray(top, np.float32).astype(np.float64) + 1e-9)

@@ -412,3 +412,19 @@ def test_packed_operand_of_a_strided_view_equals_packing_the_materialised_tensor
     got = oracle.conv_mfma_pack_weights_view(w, Cout, Cin, k, sco, sci, st_co, st_ci, flip)
     want = oracle.conv_mfma_pack_weights(expr(torch.from_numpy(w)).contiguous().numpy())
     assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("kind,code", [("linear", oracle.LINEAR), ("cubic", oracle.CUBIC), ("nearest", oracle.NEAREST)])
+@pytest.mark.parametrize("shape", [((12, 64), (12, 8)), ((64, 12), (8, 12)), ((8, 32), (32, 8)), ((32, 8), (8, 32)), ((7, 50), (20, 11))])
+@pytest.mark.parametrize("antialias", [True, False])
+def test_resample_mixed_ratios_vs_fp64_statement(kind, code, shape, antialias):
+    """Anisotropic and mixed up / down ratios (the swapped half-pixel offsets push the window off the image: empty windows and
+    wsum == 0 outputs) against the elementwise statement with fp32 positions and the bounds of tests/test_resample.py."""
+    import resample_bounds as TR
+    (Hin, Win), (Hout, Wout) = shape
+    x = _rand((2, 2, Hin, Win), 15)
+    out = oracle.resample_forward(x, Hout, Wout, code, antialias)
+    if kind == "nearest":
+        np.testing.assert_array_equal(out.view(np.uint32), R.resample_nearest(x, Hout, Wout).view(np.uint32))
+    else:
+        assert TR.check(out, x, Hout, Wout, code, antialias, f"oracle {kind} {shape} antialias={antialias}") <= 1.0
