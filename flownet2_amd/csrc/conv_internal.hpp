@@ -31,4 +31,14 @@ int deconv_bf16x3_pack_weights(const float* weight, float* packed, int Cin, int 
 int deconv_bf16x3_gemm(const float* bottom, const float* packed_weight, float* col, int N, int Cin, int Hin, int Win, int bottom_channels,
                        int bottom_c0, int Cout, void* stream);
 
+// csrc/tconv_bf16x3.hip: the data gradient of a Convolution{5, 2, 2} in split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3 beside
+// FN2_BWD_ROUTE_TCONV); which layers it takes: fn2_tconv_bf16x3_supported.  weight: the Convolution's own blob [Ct][Cb][k][k] (Ct = top_diff
+// channels, Cb = bottom_diff channels); the operand holds its three bf16 planes in k-step order.  mask: NULL, or the activated output of the
+// layer in front (bottom_diff is multiplied by its leaky-ReLU derivative on the way out).
+size_t tconv_bf16x3_packed_floats(int Cb, int Ct, int kernel, int pad);
+int tconv_bf16x3_pack_weights(const float* weight, float* packed, int Cb, int Ct, int kernel, int pad, void* stream);
+int tconv_bf16x3_masked(const float* top_diff, const float* packed_weight, float* bottom_diff, int N, int Ct, int Ht, int Wt, int top_channels, int top_c0,
+                        int Cb, int Hb, int Wb, int bottom_channels, int bottom_c0, int kernel, int pad,
+                        const float* mask, int mask_channels, int mask_c0, float mask_slope, void* stream);
+
 }  // namespace fn2

@@ -11,7 +11,9 @@
 // FN2_ROUTE_BF16X3 asks for the split-bf16 arithmetic where a kernel of it takes the layer -- the DIRECT 5x5 / 2 convolutions
 // (csrc/conv_bf16x3.hip) and the GEMM of the Deconvolution{4, 2, 1} (csrc/deconv_bf16x3.hip: 0.80 / 0.81 / 0.75 of the exact route's time at
 // FlowNetC's deconv4 / 3 / 2, profiles/deconv_bf16x3_bench.md; faster at all three, so no class of the GEMM route is kept exact under the
-// flag) -- as a bit beside the route; without the flag every answer is the exact fp32 one.
+// flag) -- as a bit beside the route; without the flag every answer is the exact fp32 one.  The data gradient has the same flag on a
+// function of its own, fn2_conv_backward_data_route_flags: the 5x5 / 2 / 2 class of the TCONV route (csrc/tconv_bf16x3.hip: 0.79 - 0.93 of the
+// exact kernel's time, profiles/dgrad_bf16x3_bench.md); its 3x3 / 2 / 1 class measured 2.13 x the exact kernel and stays exact under the flag.
 #include "conv_internal.hpp"
 #include "fn2_common.hpp"
 
@@ -324,13 +326,34 @@ __global__ void __launch_bounds__(256) rot180_swap(const float* __restrict__ w, 
   out[i] = ci < Cin ? w[((size_t)co * Cin + ci) * 9 + (8 - t)] : 0.f;
 }
 
+// A backward-data route value as a caller passes it -> the base route and the arithmetic.  The combined value FN2_BWD_ROUTE_TCONV |
+// FN2_CONV_ARITH_BF16X3 names the split-bf16 kernel (csrc/tconv_bf16x3.hip) on a TCONV layer that kernel takes; the arithmetic bit on any
+// other base route, on any other layer, or alone names no kernel (base NONE: sizes 0, calls refused).
+struct BwdRoute { int base; bool split; };
+BwdRoute bwd_route_of(const fn2_conv_desc* d, int transposed, int route, const Bwd& g) {
+  if (route == (FN2_BWD_ROUTE_TCONV | FN2_CONV_ARITH_BF16X3))
+    return (g.route == FN2_BWD_ROUTE_TCONV && fn2_tconv_bf16x3_supported(d, transposed)) ? BwdRoute{FN2_BWD_ROUTE_TCONV, true} : BwdRoute{FN2_BWD_ROUTE_NONE, false};
+  if (route & FN2_CONV_ARITH_BF16X3) return BwdRoute{FN2_BWD_ROUTE_NONE, false};
+  return BwdRoute{route, false};
+}
+
 }  // namespace
 
 FN2_API int fn2_conv_backward_data_route(const fn2_conv_desc* d, int transposed) { return bwd_geom(d, transposed).route; }
 
-FN2_API size_t fn2_conv_backward_data_packed_weight_floats(const fn2_conv_desc* d, int transposed, int route) {
+// FN2_ROUTE_BF16X3: the TCONV layers the split-bf16 kernel takes (5x5 / 2 / 2), in that arithmetic; everything else as without the flag
+FN2_API int fn2_conv_backward_data_route_flags(const fn2_conv_desc* d, int transposed, int flags) {
+  const int route = bwd_geom(d, transposed).route;
+  if ((flags & FN2_ROUTE_BF16X3) && route == FN2_BWD_ROUTE_TCONV && fn2_tconv_bf16x3_supported(d, transposed)) return route | FN2_CONV_ARITH_BF16X3;
+  return route;
+}
+
+FN2_API size_t fn2_conv_backward_data_packed_weight_floats(const fn2_conv_desc* d, int transposed, int route_arith) {
   const Bwd g = bwd_geom(d, transposed);
+  const BwdRoute br = bwd_route_of(d, transposed, route_arith, g);
+  const int route = br.base;
   if (route == FN2_BWD_ROUTE_NONE || route != g.route) return 0;
+  if (br.split) return fn2::tconv_bf16x3_packed_floats(g.Cb, g.Ct, d->kernel, d->pad);
   switch (route) {
     case FN2_BWD_ROUTE_WINOGRAD: return fn2_conv_wino_packed_floats(g.Cp, g.Ct);
     case FN2_BWD_ROUTE_TCONV: return fn2_conv_mfma_packed_floats(g.Cb, g.Ct, d->kernel);
@@ -340,7 +363,7 @@ FN2_API size_t fn2_conv_backward_data_packed_weight_floats(const fn2_conv_desc* 
 }
 
 FN2_API size_t fn2_conv_backward_data_pack_workspace_bytes(const fn2_conv_desc* d, int transposed, int route) {
-  const Bwd g = bwd_geom(d, transposed);
+  const Bwd g = bwd_geom(d, transposed);       // (the combined TCONV | BF16X3 value: no scratch, like TCONV)
   return (route == FN2_BWD_ROUTE_WINOGRAD && route == g.route) ? sizeof(float) * (size_t)g.Cp * g.Ct * 9 : 0;
 }
 
@@ -348,8 +371,10 @@ FN2_API int fn2_conv_backward_data_pack_weights(const fn2_conv_desc* d, int tran
                                                 void* workspace, size_t workspace_bytes, void* stream) {
   const Bwd g = bwd_geom(d, transposed);
   if (!weight || !packed) return fn2::fail(FN2_ERR_INVALID_ARG, "conv_backward_data_pack_weights: NULL blob");
-  if (route == FN2_BWD_ROUTE_NONE || route != g.route)
+  const BwdRoute br = bwd_route_of(d, transposed, route, g);
+  if (br.base == FN2_BWD_ROUTE_NONE || br.base != g.route)
     return fn2::fail(FN2_ERR_UNSUPPORTED, "conv_backward_data_pack_weights: route %d is not this layer's (%d)", route, g.route);
+  if (br.split) return fn2::tconv_bf16x3_pack_weights(weight, packed, g.Cb, g.Ct, d->kernel, d->pad, stream);
   const int k = d->kernel, Cin = d->Cin, Cout = d->Cout;
   switch (route) {
     case FN2_BWD_ROUTE_WINOGRAD: {
@@ -375,8 +400,9 @@ FN2_API int fn2_conv_backward_data_pack_weights(const fn2_conv_desc* d, int tran
   }
 }
 
-FN2_API size_t fn2_conv_backward_data_workspace_bytes(const fn2_conv_desc* d, int transposed, int route) {
+FN2_API size_t fn2_conv_backward_data_workspace_bytes(const fn2_conv_desc* d, int transposed, int route_arith) {
   const Bwd g = bwd_geom(d, transposed);
+  const int route = bwd_route_of(d, transposed, route_arith, g).base;
   if (route == FN2_BWD_ROUTE_NONE || route != g.route) return 0;
   size_t b = align256(bwd_kernel_workspace(d, transposed, g));
   if (g.Cp != g.Cb) b += sizeof(float) * (size_t)d->N * g.Cp * g.Hb * g.Wb;       // the padded result, copied into bottom_diff afterwards
@@ -385,20 +411,23 @@ FN2_API size_t fn2_conv_backward_data_workspace_bytes(const fn2_conv_desc* d, in
 
 // the same for a caller whose bottom_diff blob has room for `bottom_room` channels: with room for the computed channels
 // (fn2_conv_backward_data_computed_channels) only the kernel's own scratch is needed -- no padded copy
-FN2_API size_t fn2_conv_backward_data_workspace_bytes_with_room(const fn2_conv_desc* d, int transposed, int route, int bottom_room) {
+FN2_API size_t fn2_conv_backward_data_workspace_bytes_with_room(const fn2_conv_desc* d, int transposed, int route_arith, int bottom_room) {
   const Bwd g = bwd_geom(d, transposed);
+  const int route = bwd_route_of(d, transposed, route_arith, g).base;
   if (route == FN2_BWD_ROUTE_NONE || route != g.route) return 0;
   if (bottom_room >= g.Cp) return bwd_kernel_workspace(d, transposed, g);
   return fn2_conv_backward_data_workspace_bytes(d, transposed, route);
 }
 
-FN2_API int fn2_conv_backward_data_computed_channels(const fn2_conv_desc* d, int transposed, int route) {
+FN2_API int fn2_conv_backward_data_computed_channels(const fn2_conv_desc* d, int transposed, int route_arith) {
   const Bwd g = bwd_geom(d, transposed);
+  const int route = bwd_route_of(d, transposed, route_arith, g).base;
   return (route == FN2_BWD_ROUTE_NONE || route != g.route) ? 0 : g.Cp;
 }
 
-FN2_API int fn2_conv_backward_data_masked_supported(const fn2_conv_desc* d, int transposed, int route) {
+FN2_API int fn2_conv_backward_data_masked_supported(const fn2_conv_desc* d, int transposed, int route_arith) {
   const Bwd g = bwd_geom(d, transposed);
+  const int route = bwd_route_of(d, transposed, route_arith, g).base;
   return route == FN2_BWD_ROUTE_TCONV && route == g.route && g.Cp == g.Cb;
 }
 
@@ -411,19 +440,24 @@ FN2_API int fn2_conv_backward_data_masked(const fn2_conv_desc* d, int transposed
   const Bwd g = bwd_geom(d, transposed);
   if (top_c0 < 0 || top_c0 + g.Ct > top_channels || bottom_c0 < 0 || bottom_c0 + g.Cb > bottom_channels)
     return fn2::fail(FN2_ERR_INVALID_ARG, "conv_backward_data_masked: channel slice outside its blob");
+  if (bwd_route_of(d, transposed, route, g).split)
+    return fn2::tconv_bf16x3_masked(top_diff, packed, bottom_diff, d->N, g.Ct, g.Ht, g.Wt, top_channels, top_c0, g.Cb, g.Hb, g.Wb, bottom_channels, bottom_c0,
+                                    d->kernel, d->pad, bottom_data, data_channels, data_c0, negative_slope, stream);
   return fn2::tconv_forward_masked(top_diff, packed, nullptr, bottom_diff, d->N, g.Ct, g.Ht, g.Wt, top_channels, top_c0, g.Cb, g.Hb, g.Wb, bottom_channels,
                                    bottom_c0, d->kernel, d->pad, 0, 0.f, bottom_data, data_channels, data_c0, negative_slope, stream);
 }
 
-FN2_API int fn2_conv_backward_data(const fn2_conv_desc* d, int transposed, int route, const float* top_diff, int top_channels, int top_c0,
+FN2_API int fn2_conv_backward_data(const fn2_conv_desc* d, int transposed, int route_arith, const float* top_diff, int top_channels, int top_c0,
                                    const float* packed, float* bottom_diff, int bottom_channels, int bottom_c0, int bottom_room,
                                    void* workspace, size_t workspace_bytes, void* stream) {
   const Bwd g = bwd_geom(d, transposed);
+  const BwdRoute br = bwd_route_of(d, transposed, route_arith, g);
+  const int route = br.base;
   if (!top_diff || !packed || !bottom_diff) return fn2::fail(FN2_ERR_INVALID_ARG, "conv_backward_data: NULL blob");
   if (route == FN2_BWD_ROUTE_NONE || route != g.route)
     return fn2::fail(FN2_ERR_UNSUPPORTED, "conv_backward_data: no own kernel for %s{kernel %d, stride %d, pad %d} %d -> %d on %d x %d (route %d)",
                      transposed ? "Deconvolution" : "Convolution", d ? d->kernel : 0, d ? d->stride : 0, d ? d->pad : 0, d ? d->Cin : 0, d ? d->Cout : 0,
-                     d ? d->Hin : 0, d ? d->Win : 0, route);
+                     d ? d->Hin : 0, d ? d->Win : 0, route_arith);
   if (top_c0 < 0 || top_c0 + g.Ct > top_channels || bottom_c0 < 0 || bottom_room < g.Cb || bottom_c0 + bottom_room > bottom_channels)
     return fn2::fail(FN2_ERR_INVALID_ARG, "conv_backward_data: channel slice outside its blob");
   const size_t kws = bwd_kernel_workspace(d, transposed, g);
@@ -439,7 +473,11 @@ FN2_API int fn2_conv_backward_data(const fn2_conv_desc* d, int transposed, int r
       rc = fn2_conv_wino_forward(top_diff, packed, nullptr, out, N, g.Ct, g.Ht, g.Wt, top_channels, top_c0, g.Cp, oc, o0, 1, 0, 0.f, stream);
       break;
     case FN2_BWD_ROUTE_TCONV:
-      rc = fn2_tconv_forward(top_diff, packed, nullptr, out, N, g.Ct, g.Ht, g.Wt, top_channels, top_c0, g.Cb, g.Hb, g.Wb, oc, o0, d->kernel, d->pad, 0, 0.f, stream);
+      if (br.split)
+        rc = fn2::tconv_bf16x3_masked(top_diff, packed, out, N, g.Ct, g.Ht, g.Wt, top_channels, top_c0, g.Cb, g.Hb, g.Wb, oc, o0, d->kernel, d->pad,
+                                      nullptr, 0, 0, 1.f, stream);
+      else
+        rc = fn2_tconv_forward(top_diff, packed, nullptr, out, N, g.Ct, g.Ht, g.Wt, top_channels, top_c0, g.Cb, g.Hb, g.Wb, oc, o0, d->kernel, d->pad, 0, 0.f, stream);
       break;
     case FN2_BWD_ROUTE_DECONV_PLANE:
       rc = fn2_deconv_plane_forward(top_diff, packed, nullptr, out, N, g.Ct, g.Ht, g.Wt, top_channels, top_c0, g.Cb, oc, o0, 0, 0.f, workspace, kws, stream);

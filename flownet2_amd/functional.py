@@ -438,7 +438,8 @@ _CONV_ARITH = ["fp32"]
 def set_conv_arithmetic(name: str = "fp32"):
     """Arithmetic of the convolution FORWARD: "fp32" (exact fp32 products, the default) or "bf16x3" -- split-bf16 arithmetic (six bf16 piece
     products per multiply, fp32 accumulation: include/flownet2_hip.h, FN2_CONV_ARITH_BF16X3) on the layers fn2_conv_route hands to that
-    kernel, the direct 5x5 / 2 layers; every other layer, and every backward route, stays exact fp32.  Initial value: $FN2_CONV_ARITH."""
+    kernel, the direct 5x5 / 2 layers; every other layer stays exact fp32, and so does every backward route (the data gradient has a
+    switch of its own: set_conv_backward_arithmetic).  Initial value: $FN2_CONV_ARITH."""
     if name not in _CONV_ARITHMETICS:
         raise ValueError("conv arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
     _CONV_ARITH[0] = name
@@ -458,7 +459,8 @@ _DECONV_ARITH = ["fp32"]
 def set_deconv_arithmetic(name: str = "fp32"):
     """Arithmetic of the Deconvolution{4, 2, 1} FORWARD, a switch of its own beside set_conv_arithmetic: "fp32" (the default) or "bf16x3" --
     the weight^T x bottom GEMM of the layers fn2_deconv_route hands to the GEMM route in split-bf16 arithmetic (csrc/deconv_bf16x3.hip; the
-    col2im + bias + ReLU pass is unchanged); every other layer, and every backward route, stays exact fp32.  Initial value: $FN2_DECONV_ARITH."""
+    col2im + bias + ReLU pass is unchanged); every other layer, and every backward route, stays exact fp32 (the stride-2 data gradient has
+    a switch of its own: set_conv_backward_arithmetic).  Initial value: $FN2_DECONV_ARITH."""
     if name not in _CONV_ARITHMETICS:
         raise ValueError("deconv arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
     _DECONV_ARITH[0] = name
@@ -471,6 +473,27 @@ def deconv_arithmetic() -> str:
 if os.environ.get("FN2_DECONV_ARITH"):
     set_deconv_arithmetic(os.environ["FN2_DECONV_ARITH"])
 
+
+_DGRAD_ARITH = ["fp32"]
+
+
+def set_conv_backward_arithmetic(name: str):
+    """Arithmetic of the convolution DATA GRADIENT, a switch of its own beside the three forward ones: "fp32" (the default) or "bf16x3" --
+    split-bf16 arithmetic on the layers fn2_conv_backward_data_route_flags hands to that kernel (csrc/tconv_bf16x3.hip: the stride-2
+    5x5 / 2 / 2 class of the transposed-convolution route, conv2 / conv3 of the encoders, plain and with the ReLU derivative of the layer
+    in front folded in); every other data gradient, every weight and bias gradient and every forward stay as they are.  Initial value:
+    $FN2_DGRAD_ARITH."""
+    if name not in _CONV_ARITHMETICS:
+        raise ValueError("conv backward arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
+    _DGRAD_ARITH[0] = name
+
+
+def conv_backward_arithmetic() -> str:
+    return _DGRAD_ARITH[0]
+
+
+if os.environ.get("FN2_DGRAD_ARITH"):
+    set_conv_backward_arithmetic(os.environ["FN2_DGRAD_ARITH"])
 
 _CORR_ARITH = ["fp32"]
 
@@ -658,7 +681,7 @@ def relu_chain_supported(x_shape, w, stride, pad) -> bool:
     desc = _layer_desc(w, stride, pad, False, x_shape=x_shape)
     if desc is None or not w.is_cuda:
         return False
-    route = ops.conv_backward_data_route(desc, False)
+    route = ops.conv_backward_data_route(desc, False, bf16x3=_DGRAD_ARITH[0] == "bf16x3")
     return route != 0 and ops.conv_backward_data_masked_supported(desc, False, route)
 
 
@@ -800,7 +823,7 @@ def _own_bwd_data(d, w, stride, pad, transposed, x_shape=None):
     desc = _layer_desc(w, stride, pad, transposed, x_shape=x_shape, d_shape=d.shape)
     if desc is None:
         return None
-    route = ops.conv_backward_data_route(desc, transposed)
+    route = ops.conv_backward_data_route(desc, transposed, bf16x3=_DGRAD_ARITH[0] == "bf16x3")
     if route == 0:
         return None
     key = (desc.N, desc.Hin, desc.Win)       # the route (and with it the operand's layout) is a function of the layer geometry
@@ -815,7 +838,7 @@ def _own_bwd_data_masked(d, w, stride, pad, x, slope):
     desc = _layer_desc(w, stride, pad, False, x_shape=x.shape)
     if desc is None or not d.is_cuda:
         return None
-    route = ops.conv_backward_data_route(desc, False)
+    route = ops.conv_backward_data_route(desc, False, bf16x3=_DGRAD_ARITH[0] == "bf16x3")
     if route == 0 or not ops.conv_backward_data_masked_supported(desc, False, route):
         return None
     key = (desc.N, desc.Hin, desc.Win)

@@ -615,9 +615,23 @@ def conv_forward(x, packed, bias, desc, route, transposed=False, relu=True, nega
     return out
 
 
-def conv_backward_data_route(desc, transposed=False) -> int:
-    """Which own kernel computes bottom_diff of this layer (fn2_conv_backward_data_route; 0 = none, names: BWD_ROUTES)."""
-    return int(_lib.lib().fn2_conv_backward_data_route(C.byref(desc), int(bool(transposed))))
+def conv_backward_data_route(desc, transposed=False, bf16x3=False) -> int:
+    """Which own kernel computes bottom_diff of this layer (fn2_conv_backward_data_route; 0 = none, names: BWD_ROUTES).  bf16x3: the layers
+    the split-bf16 data-gradient kernel takes (csrc/tconv_bf16x3.hip: the 5x5 / 2 / 2 class of BWD_ROUTE_TCONV) come back as
+    BWD_ROUTE_TCONV | CONV_ARITH_BF16X3, every other layer as without it (fn2_conv_backward_data_route_flags); the pack, run and masked
+    wrappers below take that value."""
+    if not bf16x3:
+        return int(_lib.lib().fn2_conv_backward_data_route(C.byref(desc), int(bool(transposed))))
+    return int(_lib.lib().fn2_conv_backward_data_route_flags(C.byref(desc), int(bool(transposed)), ROUTE_BF16X3))
+
+
+def _check_dgrad_operand(what, packed, desc, tr, route):
+    """The operand must be the one packed for THIS route: the exact and the split-bf16 operand of a layer differ in size and layout."""
+    n = int(_lib.lib().fn2_conv_backward_data_packed_weight_floats(C.byref(desc), tr, int(route)))
+    if n == 0:
+        raise ValueError("%s: route %d is not this layer's" % (what, route))
+    if packed.numel() != n:
+        raise ValueError("%s: the operand has %d floats, route %d of this layer needs %d (packed for another route?)" % (what, packed.numel(), route, n))
 
 
 def conv_backward_data_pack_weights(weight, desc, transposed, route):
@@ -642,6 +656,7 @@ def conv_backward_data(top_diff, packed_weight, desc, transposed, route, top_c0=
     Cp = int(L.fn2_conv_backward_data_computed_channels(C.byref(desc), tr, int(route)))
     if Cp == 0:
         raise ValueError("conv_backward_data: route %d is not this layer's" % route)
+    _check_dgrad_operand("conv_backward_data", packed_weight, desc, tr, route)
     out = torch.empty((desc.N, Cp, desc.Hin, desc.Win), device=d.device, dtype=torch.float32)
     need = int(L.fn2_conv_backward_data_workspace_bytes_with_room(C.byref(desc), tr, int(route), Cp))      # (the blob has room: no padded copy in the scratch)
     ws = _plane_workspace(d.device, need) if need else None
@@ -684,6 +699,7 @@ def conv_backward_data_masked(top_diff, packed, desc, transposed, route, bottom_
     the kernel's epilogue (fn2_conv_backward_data_masked; the transposed-convolution route).  bottom_data = this layer's bottom blob, the
     activated output of the layer in front (may be a channel slice: data_c0)."""
     d, y = _chk(top_diff, "top_diff"), _chk(bottom_data, "bottom data")
+    _check_dgrad_operand("conv_backward_data_masked", packed, desc, int(bool(transposed)), route)
     out = torch.empty((desc.N, desc.Cin, desc.Hin, desc.Win), device=d.device, dtype=torch.float32)
     check(_lib.lib().fn2_conv_backward_data_masked(C.byref(desc), int(bool(transposed)), int(route), _ptr(d), d.shape[1], int(top_c0), _ptr(packed),
                                                    _ptr(out), desc.Cin, 0, _ptr(y), y.shape[1], int(data_c0), C.c_float(float(negative_slope)), _stream()))

@@ -513,7 +513,8 @@ enum { FN2_ROUTE_FORCE = 1, FN2_ROUTE_BF16X3 = 2 };
  * flag everywhere else, so a whole net can run with the flag on.  The four functions that take a route accept the combined value: the
  * operand then holds the three bf16 planes of the weights in MFMA operand order (another size than the exact operand), no workspace.  The
  * bit on any other base route, or on a layer the split kernel does not take, is refused on the host: FN2_ERR_UNSUPPORTED, 0 from the size
- * queries.  Backward routes are exact fp32 whatever the forward ran in. */
+ * queries.  Backward routes are exact fp32 whatever the forward ran in; the stride-2 data gradient has the same arithmetic behind a flag of
+ * its own (fn2_conv_backward_data_route_flags, below). */
 enum { FN2_CONV_ARITH_BF16X3 = 0x100 };
 int fn2_conv_bf16x3_supported(const fn2_conv_desc* desc);
 /* Test / profiling hooks of the split kernel: number of tile variants, forced variant (-1 = autotuned / cost model). */
@@ -610,6 +611,22 @@ int fn2_conv_backward_data_masked_supported(const fn2_conv_desc* desc, int trans
 int fn2_conv_backward_data_masked(const fn2_conv_desc* desc, int transposed, int route, const float* top_diff, int top_channels, int top_c0,
                                   const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0,
                                   const float* bottom_data, int data_channels, int data_c0, float negative_slope, void* stream);
+/* The split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3, above) for the data gradient of the stride-2 5x5 / 2 / 2 convolutions (conv2 / conv3 of the
+ * encoders; csrc/tconv_bf16x3.hip), a switch of its own beside the three forward ones.  fn2_conv_backward_data_route_flags: with
+ * FN2_ROUTE_BF16X3 in `flags` it returns FN2_BWD_ROUTE_TCONV | FN2_CONV_ARITH_BF16X3 where fn2_conv_backward_data_route returns TCONV and the
+ * split kernel takes the layer (fn2_tconv_bf16x3_supported: not transposed, kernel 5 / stride 2 / pad 2, Cin % 64 == 0, top_diff width % 4 == 0;
+ * the 3x3 / 2 / 1 class and the Deconvolution routes stay exact); in every other case, and for flags 0, exactly what
+ * fn2_conv_backward_data_route returns.  Every by-route backward-data function above accepts the combined value for such a layer: the
+ * operand is the Convolution's own blob split once into three bf16 planes, (Cin / 16) x (13 ceil(Cout / 16) + 1) x 768 floats -- NOT the
+ * exact operand's size -- no workspace, computed channels = Cin, the masked form included.  The bit on any other base route, on a layer the
+ * kernel does not take, or alone names no kernel: the size functions return 0 and the calls FN2_ERR_UNSUPPORTED, decided on the host before
+ * any launch.  Fixed summation order (chunks of 16 top_diff channels, pairs of the taps of the output pixel's parity class, the six piece
+ * products mm, lh, hl, mh, hm, hh on one fp32 accumulator): bit-reproducible, batch-invariant, the same bits from every tile variant; not
+ * the exact route's bits, but within its fp64 bound (1e-5 x scale, tests/test_dgrad_bf16x3.py).  Measurements: profiles/dgrad_bf16x3_bench.md. */
+int fn2_conv_backward_data_route_flags(const fn2_conv_desc* desc, int transposed, int flags);
+int fn2_tconv_bf16x3_supported(const fn2_conv_desc* desc, int transposed);
+int fn2_tconv_bf16x3_num_variants(void);
+int fn2_debug_set_tconv_bf16x3_variant(int variant);
 int fn2_conv_backward_weights_supported(const fn2_conv_desc* desc, int transposed);
 size_t fn2_conv_backward_weights_workspace_bytes(const fn2_conv_desc* desc, int transposed);
 int fn2_conv_backward_weights(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0,

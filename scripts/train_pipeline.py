@@ -67,7 +67,11 @@ def main():
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--no-prefetch", action="store_true")
     ap.add_argument("--prefetch-thread", action="store_true", help="draw on a background thread instead of a worker process")
+    ap.add_argument("--dgrad-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the convolution data gradient (default: $FN2_DGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
     a = ap.parse_args()
+    if a.dgrad_arith:
+        Fn.set_conv_backward_arithmetic(a.dgrad_arith)
     dev = torch.device("cuda")
     B, H, W, ch, cw = a.batch, a.height, a.width, a.crop_height, a.crop_width
     recs = synthetic_records(2 * B, H, W)
@@ -141,6 +145,7 @@ def main():
     print("coefficient draws: %s" % how)
     print("iteration (sum of the stages): %.3f ms" % sum(statistics.median(times[s_]) for s_ in stages))
     if not a.no_train:
+        print("data-gradient arithmetic: %s" % Fn.conv_backward_arithmetic())
         print("loss %.4f, NaN ground truth kept: %s" % (float(loss), bool(torch.isnan(t_flow[0].data).any())))
 
 

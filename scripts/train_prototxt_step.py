@@ -1,10 +1,17 @@
 #!/usr/bin/env python
 """Time of one FlowNetC TRAIN iteration through the prototxt executor (Net.ClearParamDiffs + ForwardBackward: Caffe-style Backward_gpu of every
 layer mirror) next to the same iteration through nets.py + autograd -- batch 8 @448x320, forward + backward only (no optimizer)."""
-import os, sys, time
+import argparse, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flownet2_amd import functional as Fn, net as fnet, nets, templates
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--dgrad-arith", choices=["fp32", "bf16x3"], default=None,
+                help="arithmetic of the convolution data gradient (default: $FN2_DGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
+args = ap.parse_args()
+if args.dgrad_arith:
+    Fn.set_conv_backward_arithmetic(args.dgrad_arith)
 
 N, H, W = 8, 320, 448
 P = {k: v.cuda() for k, v in nets.init_params("C", seed=0).items()}
@@ -41,5 +48,6 @@ def timeit(fn, n=20, warm=8):
 
 
 a, b = timeit(autograd_step), timeit(proto_step)
+print("data-gradient arithmetic: %s" % Fn.conv_backward_arithmetic())
 print("FlowNetC forward + backward, batch 8 @448x320: nets.py + autograd %.2f ms, prototxt Net.ForwardBackward %.2f ms (losses %.6f / %.6f)"
       % (a, b, float(autograd_step().detach()), float(proto_step())))
