@@ -87,7 +87,8 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
   using WV = typename WVec<MW>::T;
   // packed weights: [Cout/64][ksteps][64 lanes][4]; this wave's channel groups: 16 * MW * (g * WM + wm) ...
   const int cg0 = (g * K::WM + wm) * MW;                      // first 16-channel group of this wave
-  const float* wl = weight_lane(a.wp, cg0, a.ksteps, lane);
+  const float* wb = a.wp + (size_t)(cg0 / 4) * a.ksteps * 256 + (cg0 % 4);      // weight_lane, split for weight_fetch: the wave's base + the lane's bytes
+  const unsigned wlane = 16u * (unsigned)lane;
 
   f32x4 acc[MW][NP];
 #pragma unroll
@@ -95,18 +96,41 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
 #pragma unroll
     for (int p = 0; p < NP; ++p) acc[j][p] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // The weight ring runs R k-steps ahead and waits by hand (weight_fetch / ring_wait* / weight_landed, mfma_tile.hpp).  Order of the loads in
+  // flight at k-step ks of chunk c:  weights of k-steps ks .. R - 1 (issued before the chunk's top, only while ks < R) | the window DMA of
+  // chunk c + 1 (issued at the top; every wave issues at least DMA instructions of it) | the weights issued since.  A use may therefore leave
+  // R + DMA loads in flight while ks < R, and R from then on: the window has the ring's depth, R k-steps, to land before a wait reaches it
+  // -- with one counter and in-order returns, the first weight issued behind it cannot be waited for without it.  The last chunk issues no
+  // window and no weight beyond its own k-steps (nothing is in flight when the epilogue starts): its uses leave min(R, KSC - 1 - ks).
+  constexpr int R = K::NBUFA - 1, DMA = K::NRUN / K::NW;
+  static_assert(R + DMA <= 63, "vmcnt has 6 bits");
   WV wreg[K::NBUFA];
   stage(0, 0);
+  if (a.nchunks > 0) {
 #pragma unroll
-  for (int i = 0; i < K::NBUFA - 1; ++i) wreg[i] = weight_load<MW>(wl, i);
+    for (int i = 0; i < R; ++i) wreg[i] = weight_fetch<MW>(wb + (size_t)i * 256, wlane);
+  }
+  // the k-step's weight: fetch the one R k-steps ahead, wait for this one
+  auto weight_step = [&](int ks0, int ks, int rest) -> WV {
+    const float* wks = wb + (size_t)(ks0 + ks + R) * 256;
+    if (ks + R < K::KSC) wreg[(ks + R) % K::NBUFA] = weight_fetch<MW>(wks, wlane);
+    else wreg[(ks + R) % K::NBUFA] = weight_fetch_unless_last<MW>(rest, wks, wlane);
+    const int left = K::KSC - 1 - ks < R ? K::KSC - 1 - ks : R;
+    if (ks < R) ring_wait_either(rest, left, R + DMA);
+    else if (left < R) ring_wait_either(rest, left, R);
+    else ring_wait(R);
+    weight_landed(wreg[ks % K::NBUFA]);
+    return wreg[ks % K::NBUFA];
+  };
 
   for (int c = 0; c < a.nchunks; ++c) {
     const int buf = c & 1;
-    // in flight: the window of chunk c (issued a whole chunk ago) and, younger than it, the weight prefetch of the last NBUFA - 1
-    // k-steps; loads retire in order, so the window has landed once at most NBUFA - 1 loads remain -- no need to drain the ring
-    wait_vmcnt<K::NBUFA - 1>();
+    const int rest = a.nchunks - 1 - c;      // chunks still to come
+    // in flight: the window of chunk c (issued at the top of the chunk before) and, younger than it, the weight prefetch of the last R
+    // k-steps; loads retire in order, so the window has landed once at most R loads remain -- no need to drain the ring
+    wait_vmcnt<R>();
     __builtin_amdgcn_s_barrier();
-    if (c + 1 < a.nchunks) stage(c + 1, buf ^ 1);
+    if (rest) stage(c + 1, buf ^ 1);
     const float* win = smem + buf * K::BUF + bbase;
     const int ks0 = c * K::KSC;
     if constexpr (K::PIN) {
@@ -121,8 +145,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < K::KSC; ++ks) {
-        wreg[(ks + K::NBUFA - 1) % K::NBUFA] = weight_load<MW>(wl, ks0 + ks + K::NBUFA - 1);
-        const WV w = wreg[ks % K::NBUFA];
+        const WV w = weight_step(ks0, ks, rest);
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
 #pragma unroll
@@ -134,12 +157,11 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
     } else {
 #pragma unroll
     for (int ks = 0; ks < K::KSC; ++ks) {
-      wreg[(ks + K::NBUFA - 1) % K::NBUFA] = weight_load<MW>(wl, ks0 + ks + K::NBUFA - 1);      // the packed array carries NBUFA spare k-steps
+      const WV w = weight_step(ks0, ks, rest);
       const int cq = ks / (KS * KS), ky = (ks / KS) % KS, kx = ks % KS;
       float b[NP];
 #pragma unroll
       for (int p = 0; p < NP; ++p) b[p] = win[cq * 4 * K::CS + ky * K::RS + kx + PW * S * p];
-      const WV w = wreg[ks % K::NBUFA];
 #pragma unroll
       for (int j = 0; j < MW; ++j)
 #pragma unroll
@@ -148,6 +170,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
     }
   }
 
+  wait_vmcnt<0>();      // (nothing is in flight behind a last chunk)
   // ---- epilogue: lane (row block = lane >> 4, channel = lane & 15) holds 4 consecutive x of output row y0 + 4 wny + (lane >> 4)
   // (row tiles: pixels 4 (lane >> 4) .. + 3 of the 16-pixel tile, row y0 + wny)
   const int y = K::P16 ? y0 + wny : y0 + 4 * wny + (lane >> 4);

@@ -103,6 +103,62 @@ __device__ __forceinline__ typename WVec<MW>::T weight_load(const float* wl, int
   return *reinterpret_cast<const typename WVec<MW>::T*>(wl + (size_t)ks * 256);
 }
 
+// The weight ring with the kernel's OWN waits (conv_mfma.hip).  LDS-DMA window loads and the weight loads share the one vmcnt counter and
+// loads retire in order.  Left to the compiler, the ring's plain loads get re-clustered or waited for with vmcnt(0 .. 1) right behind the
+// window DMA of the next chunk, which drains that DMA a k-step after its issue instead of leaving it the ring's depth in k-steps to arrive
+// (profiles/NOTES_window_lead.md).  So the ring's loads are asm volatile (the compiler neither counts nor moves them) and every use waits by hand:
+//   weight_fetch       a k-step's operand of the wave: uniform `base` (SGPR pair) + the lane's byte offset
+//   ring_wait          s_waitcnt vmcnt(n), n = the loads YOUNGER than the operand that may stay in flight (a smaller n is always
+//                      correct, only slower).  n must fold to a constant (an unrolled loop's counter does; it does not compile otherwise)
+//   ring_wait_either   one of two such waits, chosen at run time (the last chunk has fewer loads behind the operand)
+//   weight_landed      ties the operand to the waits in front of it: the MFMAs that read it stay behind them.  The waits themselves name
+//                      no register and branch inside one asm block: the k loop stays one basic block for the compiler, which therefore
+//                      never copies an operand that is still in flight on the way into a branch.
+// A kernel that uses these leaves no ring load in flight when it reaches code whose registers the compiler allocates on its own.
+template <int MW>
+__device__ __forceinline__ typename WVec<MW>::T weight_fetch(const float* base, unsigned lane_bytes) {
+  typename WVec<MW>::T w;
+  if constexpr (MW == 1) asm volatile("global_load_dword %0, %1, %2" : "=v"(w) : "v"(lane_bytes), "s"(base));
+  else if constexpr (MW == 2) asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(w) : "v"(lane_bytes), "s"(base));
+  else asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(w) : "v"(lane_bytes), "s"(base));
+  return w;
+}
+
+template <class T>
+__device__ __forceinline__ void weight_landed(T& w) { asm volatile("" : "+v"(w)); }
+
+constexpr int vmcnt_clamp(int n) { return n < 63 ? n : 63; }      // the counter has 6 bits
+
+__device__ __forceinline__ void ring_wait(int n) { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(vmcnt_clamp(n))); }
+
+// vmcnt(n_last) in the last chunk (`rest`, the chunks still to come, is 0), else vmcnt(n_else)
+__device__ __forceinline__ void ring_wait_either(int rest, int n_last, int n_else) {
+  asm volatile(
+      "s_cmp_eq_u32 %0, 0\n\t"
+      "s_cbranch_scc1 .Lrwt_%=\n\t"
+      "s_waitcnt vmcnt(%2)\n\t"
+      "s_branch .Lrwe_%=\n"
+      ".Lrwt_%=:\n\t"
+      "s_waitcnt vmcnt(%1)\n"
+      ".Lrwe_%=:"
+      :
+      : "s"(rest), "i"(vmcnt_clamp(n_last)), "i"(vmcnt_clamp(n_else))
+      : "scc");
+}
+
+// weight_fetch unless this is the last chunk (rest == 0), which fetches nothing beyond its own k-steps
+template <int MW>
+__device__ __forceinline__ typename WVec<MW>::T weight_fetch_unless_last(int rest, const float* base, unsigned lane_bytes) {
+  typename WVec<MW>::T w;
+#define FN2_FETCH_UNLESS(INSN) \
+  asm volatile("s_cmp_eq_u32 %3, 0\n\ts_cbranch_scc1 .Lwfs_%=\n\t" INSN " %0, %1, %2\n.Lwfs_%=:" : "=v"(w) : "v"(lane_bytes), "s"(base), "s"(rest) : "scc")
+  if constexpr (MW == 1) FN2_FETCH_UNLESS("global_load_dword");
+  else if constexpr (MW == 2) FN2_FETCH_UNLESS("global_load_dwordx2");
+  else FN2_FETCH_UNLESS("global_load_dwordx4");
+#undef FN2_FETCH_UNLESS
+  return w;
+}
+
 // ------------------------------------------------------------------------------------------------ XCD task remap
 // Block b runs on XCD b % 8.  The task list is cut into 8 contiguous ranges, one per XCD, so that neighbouring tasks (which share
 // an input window) run on one XCD, whose L2 serves the re-reads.  false: this block has no task.
