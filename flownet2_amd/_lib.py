@@ -41,6 +41,7 @@ EXPORTS = [
     "fn2_debug_set_wgrad_buffers", "fn2_debug_set_wgrad_chunk", "fn2_conv_wgrad_supported", "fn2_conv_wgrad_ksplit", "fn2_conv_wgrad_workspace_bytes", "fn2_conv_wgrad",
     "fn2_conv_bf16x3_supported", "fn2_conv_bf16x3_num_variants", "fn2_debug_set_conv_bf16x3_variant",
     "fn2_deconv_bf16x3_supported", "fn2_deconv_bf16x3_num_variants", "fn2_debug_set_deconv_bf16x3_variant",
+    "fn2_conv_wino_bf16x3_supported", "fn2_conv_wino_bf16x3_num_variants", "fn2_debug_set_conv_wino_bf16x3_variant",
     "fn2_conv_backward_data_route_flags", "fn2_tconv_bf16x3_supported", "fn2_tconv_bf16x3_num_variants", "fn2_debug_set_tconv_bf16x3_variant",
     "fn2_correlation_bf16x3_supported", "fn2_correlation_bf16x3_num_variants", "fn2_debug_set_correlation_bf16x3_variant",
     "fn2_conv_route", "fn2_conv_packed_weight_floats", "fn2_conv_pack_weights", "fn2_conv_workspace_bytes", "fn2_conv_forward",
@@ -274,6 +275,9 @@ def lib():
     L.fn2_deconv_bf16x3_supported.argtypes = [dp]
     L.fn2_deconv_bf16x3_num_variants.argtypes = []
     L.fn2_debug_set_deconv_bf16x3_variant.argtypes = [i]
+    L.fn2_conv_wino_bf16x3_supported.argtypes = [dp]
+    L.fn2_conv_wino_bf16x3_num_variants.argtypes = []
+    L.fn2_debug_set_conv_wino_bf16x3_variant.argtypes = [i]
     L.fn2_conv_backward_data_route_flags.argtypes = [dp, i, i]
     L.fn2_tconv_bf16x3_supported.argtypes = [dp, i]
     L.fn2_tconv_bf16x3_num_variants.argtypes = []

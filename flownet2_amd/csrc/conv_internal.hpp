@@ -23,6 +23,15 @@ int conv_bf16x3_forward(const float* bottom, const float* packed_weight, const f
                         int bottom_channels, int bottom_c0, int Cout, int top_channels, int top_c0, int kernel, int stride, int pad,
                         int relu, float negative_slope, void* stream);
 
+// csrc/conv_wino_bf16x3.hip: the Winograd F(2x2, 3x3) convolution in split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3 beside
+// FN2_CONV_ROUTE_WINOGRAD); which layers it takes: fn2_conv_wino_bf16x3_supported.  The operand holds the three bf16 planes of U = G g G^T:
+// (Cout / 32) x (ceil(Cin / 16) + 1) x 12288 floats (0: no operand for these channels).
+size_t conv_wino_bf16x3_packed_floats(int Cout, int Cin);
+int conv_wino_bf16x3_pack_weights(const float* weight, float* packed, int Cout, int Cin, void* stream);
+int conv_wino_bf16x3_forward(const float* bottom, const float* packed_weight, const float* bias, float* top, int N, int Cin, int Hin, int Win,
+                             int bottom_channels, int bottom_c0, int Cout, int top_channels, int top_c0, int kernel, int stride, int pad,
+                             int relu, float negative_slope, void* stream);
+
 // csrc/deconv_bf16x3.hip: the GEMM of the Deconvolution{4, 2, 1} in split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3 beside
 // FN2_DECONV_ROUTE_GEMM); which layers it takes: fn2_deconv_bf16x3_supported.  weight: Caffe's [Cin][Cout][4][4] blob; the operand holds
 // the three bf16 planes of weight^T; col: the column matrix [N][16 Cout][Hin Win] fn2_col2im_bias_relu_forward_into reads.

@@ -14,6 +14,8 @@
 // flag) -- as a bit beside the route; without the flag every answer is the exact fp32 one.  The data gradient has the same flag on a
 // function of its own, fn2_conv_backward_data_route_flags: the 5x5 / 2 / 2 class of the TCONV route (csrc/tconv_bf16x3.hip: 0.79 - 0.93 of the
 // exact kernel's time, profiles/dgrad_bf16x3_bench.md); its 3x3 / 2 / 1 class measured 2.13 x the exact kernel and stays exact under the flag.
+// FN2_ROUTE_WINO_BF16X3, a flag of its own, asks for the same arithmetic on the WINOGRAD layers csrc/conv_wino_bf16x3.hip takes
+// (profiles/wino_bf16x3_bench.md); FN2_ROUTE_BF16X3 alone leaves every Winograd layer exact.
 #include "conv_internal.hpp"
 #include "fn2_common.hpp"
 
@@ -50,6 +52,11 @@ bool conv_route_applies(const fn2_conv_desc* d, int route) {
 // arithmetic bit on any other base route, or on any other layer, names no kernel
 bool split_route(const fn2_conv_desc* d, int route) {
   return route == (FN2_CONV_ROUTE_DIRECT | FN2_CONV_ARITH_BF16X3) && fn2_conv_bf16x3_supported(d) != 0;
+}
+
+// the combined value FN2_CONV_ROUTE_WINOGRAD | FN2_CONV_ARITH_BF16X3 on a layer the split-bf16 Winograd kernel takes (csrc/conv_wino_bf16x3.hip)
+bool wino_split_route(const fn2_conv_desc* d, int route) {
+  return route == (FN2_CONV_ROUTE_WINOGRAD | FN2_CONV_ARITH_BF16X3) && fn2_conv_wino_bf16x3_supported(d) != 0;
 }
 
 // the layers of the GEMM route: weight^T x bottom on the 1x1 form of the direct kernel
@@ -95,9 +102,11 @@ FN2_API int fn2_conv_route(const fn2_conv_desc* d, int flags) {
     return FN2_CONV_ROUTE_STEM;
   if (k == 3 && s == 1 && p == 1 && Cout == 2) return FN2_CONV_ROUTE_HEAD;
   const bool wino_ok = k == 3 && s == 1 && fn2_conv_wino_supported(Cin, H, W, Cout, p) != 0;
+  // FN2_ROUTE_WINO_BF16X3: the same layers, in split-bf16 arithmetic where that kernel takes them
+  const int wino = ((flags & FN2_ROUTE_WINO_BF16X3) && fn2_conv_wino_bf16x3_supported(d)) ? (FN2_CONV_ROUTE_WINOGRAD | FN2_CONV_ARITH_BF16X3) : FN2_CONV_ROUTE_WINOGRAD;
   // accumulator blocks of the Winograd kernel (16 channels x an 8x8-pixel block of tiles): from ~1000 on the launch fills the 1024 SIMDs and
   // it is the fastest kernel of a 3x3 / 1 layer (20x28 maps win by 1.6x, 12x24 maps lose)
-  if (wino_ok && (wino_first || (long long)N * ((o.H + 7) / 8) * ((o.W + 7) / 8) * (Cout / 16) >= 1000)) return FN2_CONV_ROUTE_WINOGRAD;
+  if (wino_ok && (wino_first || (long long)N * ((o.H + 7) / 8) * ((o.W + 7) / 8) * (Cout / 16) >= 1000)) return wino;
   const int maxpix = 8000;
   if (k == 3 && (force || o.H * o.W <= maxpix) && fn2_conv_plane_supported(N, Cin, H, W, Cout, s, p) &&
       (N == d->N || fn2_conv_plane_supported(d->N, Cin, H, W, Cout, s, p)))
@@ -105,7 +114,7 @@ FN2_API int fn2_conv_route(const fn2_conv_desc* d, int flags) {
   if (k == 5 && s == 2 && p == 2 && (long long)N * ((o.H + 3) / 4) * ((o.W + 3) / 4) * (Cout / 16) < 64 * 256 && o.H * o.W <= maxpix &&
       fn2_conv_plane_k_supported(d->N, Cin, H, W, Cout, 5, 2, 2) && (N == d->N || fn2_conv_plane_k_supported(N, Cin, H, W, Cout, 5, 2, 2)))
     return FN2_CONV_ROUTE_PLANE;       // conv3 of the encoders when one sample is the whole batch: the direct kernel has no K split to fill the chip with
-  if (wino_ok) return FN2_CONV_ROUTE_WINOGRAD;      // too large for the small-map kernel, too small to fill the chip: still 2.25x fewer multiplies
+  if (wino_ok) return wino;      // too large for the small-map kernel, too small to fill the chip: still 2.25x fewer multiplies
   if (fn2_conv_mfma_supported(Cin, H, W, Cout, k, s, p))      // FN2_ROUTE_BF16X3: the same layers, in split-bf16 arithmetic where that kernel takes them
     return ((flags & FN2_ROUTE_BF16X3) && fn2_conv_bf16x3_supported(d)) ? (FN2_CONV_ROUTE_DIRECT | FN2_CONV_ARITH_BF16X3) : FN2_CONV_ROUTE_DIRECT;
   return FN2_CONV_ROUTE_NONE;
@@ -114,6 +123,7 @@ FN2_API int fn2_conv_route(const fn2_conv_desc* d, int flags) {
 FN2_API size_t fn2_conv_packed_weight_floats(const fn2_conv_desc* d, int route) {
   if (!valid(d)) return 0;
   if (split_route(d, route)) return fn2::conv_bf16x3_packed_floats(d->Cout, d->Cin, d->kernel);
+  if (wino_split_route(d, route)) return fn2::conv_wino_bf16x3_packed_floats(d->Cout, d->Cin);
   if (route == FN2_CONV_ROUTE_WINOGRAD) return fn2_conv_wino_packed_floats(d->Cout, d->Cin);
   if (route == FN2_CONV_ROUTE_DIRECT || route == FN2_CONV_ROUTE_PLANE) return fn2_conv_mfma_packed_floats(d->Cout, d->Cin, d->kernel);
   if (route == FN2_CONV_ROUTE_STEM || route == FN2_CONV_ROUTE_HEAD) return (size_t)d->Cout * d->Cin * d->kernel * d->kernel;    // these kernels read the blob as it is
@@ -123,6 +133,7 @@ FN2_API size_t fn2_conv_packed_weight_floats(const fn2_conv_desc* d, int route) 
 FN2_API int fn2_conv_pack_weights(const fn2_conv_desc* d, int route, const float* weight, float* packed, void* stream) {
   if (!valid(d) || !weight || !packed) return fn2::fail(FN2_ERR_INVALID_ARG, "conv_pack_weights: bad descriptor or NULL blob");
   if (split_route(d, route)) return fn2::conv_bf16x3_pack_weights(weight, packed, d->Cout, d->Cin, d->kernel, stream);
+  if (wino_split_route(d, route)) return fn2::conv_wino_bf16x3_pack_weights(weight, packed, d->Cout, d->Cin, stream);
   if (route == FN2_CONV_ROUTE_WINOGRAD) return fn2_conv_wino_pack_weights(weight, packed, d->Cout, d->Cin, stream);
   if (route == FN2_CONV_ROUTE_DIRECT || route == FN2_CONV_ROUTE_PLANE) return fn2_conv_mfma_pack_weights(weight, packed, d->Cout, d->Cin, d->kernel, stream);
   if (route == FN2_CONV_ROUTE_STEM || route == FN2_CONV_ROUTE_HEAD) {
@@ -148,6 +159,9 @@ FN2_API int fn2_conv_forward(const fn2_conv_desc* d, int route, const float* bot
   if (split_route(d, route))        // (its own argument checks: null blobs, channel slices, alignment -- all before anything is launched)
     return fn2::conv_bf16x3_forward(bottom, packed_weight, bias, top, d->N, d->Cin, d->Hin, d->Win, bottom_channels, bottom_c0, d->Cout, top_channels,
                                     top_c0, d->kernel, d->stride, d->pad, relu, negative_slope, stream);
+  if (wino_split_route(d, route))
+    return fn2::conv_wino_bf16x3_forward(bottom, packed_weight, bias, top, d->N, d->Cin, d->Hin, d->Win, bottom_channels, bottom_c0, d->Cout, top_channels,
+                                         top_c0, d->kernel, d->stride, d->pad, relu, negative_slope, stream);
   if (!conv_route_applies(d, route))
     return fn2::fail(FN2_ERR_UNSUPPORTED, "conv_forward: no own kernel for Convolution{kernel %d, stride %d, pad %d} %d -> %d on %d x %d (route %d)",
                      d->kernel, d->stride, d->pad, d->Cin, d->Cout, d->Hin, d->Win, route);

@@ -474,6 +474,27 @@ if os.environ.get("FN2_DECONV_ARITH"):
     set_deconv_arithmetic(os.environ["FN2_DECONV_ARITH"])
 
 
+_WINO_ARITH = ["fp32"]
+
+
+def set_winograd_arithmetic(name: str = "fp32"):
+    """Arithmetic of the Winograd F(2x2, 3x3) FORWARD, a switch of its own beside the other four: "fp32" (the default) or "bf16x3" --
+    split-bf16 arithmetic on the Winograd layers fn2_conv_route hands to that kernel under FN2_ROUTE_WINO_BF16X3 (csrc/conv_wino_bf16x3.hip:
+    3x3 / 1 / 1, Win % 4 == 0, Cout % 64 == 0); every other layer, and every backward route, stays exact fp32.  Initial value:
+    $FN2_WINO_ARITH."""
+    if name not in _CONV_ARITHMETICS:
+        raise ValueError("winograd arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
+    _WINO_ARITH[0] = name
+
+
+def get_winograd_arithmetic() -> str:
+    return _WINO_ARITH[0]
+
+
+if os.environ.get("FN2_WINO_ARITH"):
+    set_winograd_arithmetic(os.environ["FN2_WINO_ARITH"])
+
+
 _DGRAD_ARITH = ["fp32"]
 
 
@@ -856,7 +877,7 @@ def _needs_grad(*ts):
 def conv_forward_route(desc, act=True, whole_blobs=True) -> int:
     """The own kernel conv_mfma_relu runs this Convolution on (0 = none): the library's choice (fn2_conv_route, csrc/conv_route.cpp: thresholds,
     batch-invariant mode -- the one the Caffe adapter's Convolution gets) minus the layers this module does not serve."""
-    route = ops.conv_forward_route(desc, force=_ROUTE_FORCE[0], bf16x3=_CONV_ARITH[0] == "bf16x3")
+    route = ops.conv_forward_route(desc, force=_ROUTE_FORCE[0], bf16x3=_CONV_ARITH[0] == "bf16x3", wino_bf16x3=_WINO_ARITH[0] == "bf16x3")
     stem = route == ops.CONV_ROUTE_STEM
     if route == ops.CONV_ROUTE_HEAD:                      # the predict_flow heads: predict_flow_conv, with an autograd function of its own
         return ops.CONV_ROUTE_NONE
@@ -877,7 +898,7 @@ def deconv_forward_route(desc, act=True) -> int:
 
 def conv_route_name(x_shape, w, stride, pad, act=True, whole_blobs=True):
     """Name (ops.CONV_FWD_ROUTES) of the kernel conv_mfma_relu runs this layer on for a CUDA bottom of this shape, None = declined: "stem"
-    is the one relu_chain producer; the FN2_TRACE_CONV print of nets.py.  A layer run in split-bf16 arithmetic: "direct+bf16x3"."""
+    is the one relu_chain producer; the FN2_TRACE_CONV print of nets.py.  A layer run in split-bf16 arithmetic: "direct+bf16x3" / "wino+bf16x3"."""
     desc = _layer_desc(w, stride, pad, False, x_shape=x_shape)
     if desc is None:
         return None

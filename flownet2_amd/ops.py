@@ -526,8 +526,8 @@ def conv_k7s2_relu_forward(x, weight, bias=None, negative_slope=0.1):
 
 CONV_ROUTE_NONE, CONV_ROUTE_DIRECT, CONV_ROUTE_WINOGRAD, CONV_ROUTE_PLANE, CONV_ROUTE_STEM, CONV_ROUTE_HEAD = range(6)        # FN2_CONV_ROUTE_*
 DECONV_ROUTE_NONE, DECONV_ROUTE_GEMM, DECONV_ROUTE_PLANE, DECONV_ROUTE_HEAD = range(4)        # FN2_DECONV_ROUTE_*
-ROUTE_FORCE, ROUTE_BF16X3 = 1, 2          # FN2_ROUTE_*: flags of fn2_conv_route
-CONV_ARITH_BF16X3 = 0x100                 # FN2_CONV_ARITH_BF16X3: split-bf16 arithmetic, a bit beside CONV_ROUTE_DIRECT in the route value (not a route)
+ROUTE_FORCE, ROUTE_BF16X3, ROUTE_WINO_BF16X3 = 1, 2, 4          # FN2_ROUTE_*: flags of fn2_conv_route
+CONV_ARITH_BF16X3 = 0x100                 # FN2_CONV_ARITH_BF16X3: split-bf16 arithmetic, a bit beside CONV_ROUTE_DIRECT / CONV_ROUTE_WINOGRAD in the route value (not a route)
 CONV_FWD_ROUTES = {0: None, 1: "direct", 2: "wino", 3: "plane", 4: "stem", 5: "head"}
 DECONV_FWD_ROUTES = {0: None, 1: "gemm", 2: "plane", 3: "head"}
 CONV_ROUTES = {0: None, 1: "direct", 2: "wino", 3: "plane", 4: None, 5: None}     # conv_route(): the three general families only (4 / 5: stem / flow head)
@@ -553,11 +553,13 @@ def conv_desc(N, Cin, Hin, Win, Cout, kernel, stride, pad):
     return _lib.ConvDesc(int(N), int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad))
 
 
-def conv_forward_route(desc, force=False, bf16x3=False) -> int:
+def conv_forward_route(desc, force=False, bf16x3=False, wino_bf16x3=False) -> int:
     """Which own kernel serves the forward pass of this Convolution (fn2_conv_route; 0 = none, names: CONV_FWD_ROUTES).  bf16x3: the layers
-    the split-bf16 kernel takes come back as CONV_ROUTE_DIRECT | CONV_ARITH_BF16X3, every other layer as without it; conv_pack_weights and
-    conv_forward take that value as it is."""
-    return int(_lib.lib().fn2_conv_route(C.byref(desc), (ROUTE_FORCE if force else 0) | (ROUTE_BF16X3 if bf16x3 else 0)))
+    the split-bf16 kernel takes come back as CONV_ROUTE_DIRECT | CONV_ARITH_BF16X3, every other layer as without it; wino_bf16x3, a flag of
+    its own: the Winograd layers the split-bf16 Winograd kernel takes (csrc/conv_wino_bf16x3.hip) come back as CONV_ROUTE_WINOGRAD |
+    CONV_ARITH_BF16X3.  conv_pack_weights and conv_forward take these values as they are."""
+    flags = (ROUTE_FORCE if force else 0) | (ROUTE_BF16X3 if bf16x3 else 0) | (ROUTE_WINO_BF16X3 if wino_bf16x3 else 0)
+    return int(_lib.lib().fn2_conv_route(C.byref(desc), flags))
 
 
 def deconv_forward_route(desc, bf16x3=False) -> int:

@@ -499,7 +499,7 @@ typedef struct fn2_conv_desc {
 enum { FN2_CONV_ROUTE_NONE = 0, FN2_CONV_ROUTE_DIRECT = 1, FN2_CONV_ROUTE_WINOGRAD = 2, FN2_CONV_ROUTE_PLANE = 3, FN2_CONV_ROUTE_STEM = 4,
        FN2_CONV_ROUTE_HEAD = 5 };
 enum { FN2_DECONV_ROUTE_NONE = 0, FN2_DECONV_ROUTE_GEMM = 1, FN2_DECONV_ROUTE_PLANE = 2, FN2_DECONV_ROUTE_HEAD = 3 };
-enum { FN2_ROUTE_FORCE = 1, FN2_ROUTE_BF16X3 = 2 };
+enum { FN2_ROUTE_FORCE = 1, FN2_ROUTE_BF16X3 = 2, FN2_ROUTE_WINO_BF16X3 = 4 };
 /* Arithmetic of a route, carried beside it in the route value (not a route of its own).  FN2_CONV_ARITH_BF16X3: split-bf16 arithmetic on the
  * bf16 matrix cores (csrc/conv_bf16x3.hip), opt-in.  Every fp32 activation and weight v is cut into three bf16 pieces h = rne(v),
  * m = rne(v - h), l = rne(v - h - m) (h + m + l == v); of the nine piece products of x * w the six leading ones -- hh, hm, mh, hl, lh, mm,
@@ -535,6 +535,27 @@ int fn2_debug_set_conv_bf16x3_variant(int variant);
 int fn2_deconv_bf16x3_supported(const fn2_conv_desc* desc);
 int fn2_deconv_bf16x3_num_variants(void);
 int fn2_debug_set_deconv_bf16x3_variant(int variant);
+/* The same arithmetic for the Winograd F(2x2, 3x3) forward (csrc/conv_wino_bf16x3.hip), behind a flag of its OWN: with FN2_ROUTE_WINO_BF16X3
+ * in `flags` fn2_conv_route returns FN2_CONV_ROUTE_WINOGRAD | FN2_CONV_ARITH_BF16X3 where it would have returned WINOGRAD and the split kernel
+ * takes the layer (fn2_conv_wino_bf16x3_supported, geometry alone: kernel 3 / stride 1 / pad 1, Win % 4 == 0, Cout % 64 == 0, any Cin, the
+ * 32-bit offset limits of the exact kernel) -- under FN2_ROUTE_FORCE and in batch-invariant mode too -- and exactly what it returns without the
+ * flag everywhere else; FN2_ROUTE_BF16X3 alone leaves every Winograd layer exact.  U = G g G^T and V = B^T d B are computed in fp32 as the
+ * exact kernel computes them, then cut into three bf16 pieces each (U once when packed, V once per workgroup and k-step in LDS); per Winograd
+ * position one fp32 accumulator takes, per k-step of 16 input channels in ascending order and without a K split, mm, lh, hl, mh, hm, hh (first
+ * letter: V's piece); A^T . A, bias and ReLU are applied to the final values.  Bit-reproducible, batch-independent, the same bits from every
+ * tile variant; not the exact kernel's bits, but within its fp64 bound (tests/test_wino_bf16x3.py).  Non-finite inputs as above: exactly the
+ * outputs whose 3x3 window covers an Inf or a NaN are non-finite.  The operand holds the three bf16 planes of U in MFMA operand order,
+ * [Cout / 32][ceil(Cin / 16) + 1][16 positions][3][64 lanes][8 bf16] = (Cout / 32) x (ceil(Cin / 16) + 1) x 12288 floats (the last k-step a spare
+ * of zeros; never the exact operand's length); channels >= Cin of the last k-step carry zero weights and meet zero activations, never the
+ * neighbouring channels of a wider bottom blob.  No workspace.  The bit on WINOGRAD for a layer the kernel does not take: FN2_ERR_UNSUPPORTED,
+ * 0 from the size queries, decided on the host before any launch.  The by-route backward functions refuse the bit on WINOGRAD: the data
+ * gradient stays exact.  Two tile variants (16x16 and 8x32 output pixels x 64 channels), 256 + 256 registers, 145 / 125 KB of LDS, no spills.
+ * Measured on an MI355X (profiles/wino_bf16x3_bench.md): NOT a speed-up -- 1.37 / 1.16 times the exact kernel's time at FlowNetC's conv3_1 /
+ * conv4_1 (batch 8 @448x320), 1.14 - 1.52 on five layers of FlowNet2 (batch 4 @768x384); no geometry class is faster, so none is left out:
+ * the flag exists so that the measurement can be reproduced.  fp64 error 0.03 - 0.10 of the exact kernel's bound (the exact kernel: 0.04 - 0.13). */
+int fn2_conv_wino_bf16x3_supported(const fn2_conv_desc* desc);
+int fn2_conv_wino_bf16x3_num_variants(void);
+int fn2_debug_set_conv_wino_bf16x3_variant(int variant);
 /* The same arithmetic for the Correlation forward (csrc/correlation_bf16x3.hip), by the same convention: the arithmetic is a bit beside
  * the route.  The layer has one route of its own, FN2_CORR_ROUTE_OWN = the dispatch of fn2_correlation_forward_fused (unit kernel,
  * corr_fwd_pair, the general MFMA kernel, the generic one; fn2_debug_set_correlation_impl steers it).  fn2_correlation_route returns NONE for

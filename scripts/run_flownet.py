@@ -93,7 +93,7 @@ def infer_prototxt(model, template_path, img0, img1, device):
 
 def _positionals(argv):
     """Positional arguments of either form: the values of the value-taking options are not positionals."""
-    takes_value = {"--gpu", "--weights", "--net", "--conv-arith", "--deconv-arith"}
+    takes_value = {"--gpu", "--weights", "--net", "--conv-arith", "--deconv-arith", "--wino-arith"}
     out, skip = [], False
     for a in argv:
         if skip:
@@ -121,6 +121,8 @@ def main():
                         help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
         ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
                         help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
+        ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
+                        help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0")
         ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
                         help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
                              "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
@@ -141,6 +143,8 @@ def main():
             Fn.set_deconv_arithmetic(a.deconv_arith)
         if a.corr_arith:
             Fn.set_correlation_arithmetic(a.corr_arith)
+        if a.wino_arith:
+            Fn.set_winograd_arithmetic(a.wino_arith)
         i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
         flow = infer_prototxt(a.caffemodel, a.deployproto, i0, i1, dev)
         flo.write_flo(a.out, flow[0].cpu().numpy())
@@ -156,6 +160,8 @@ def main():
                     help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
     ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
+    ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0")
     ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
                          "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
@@ -172,6 +178,8 @@ def main():
         Fn.set_deconv_arithmetic(a.deconv_arith)
     if a.corr_arith:
         Fn.set_correlation_arithmetic(a.corr_arith)
+    if a.wino_arith:
+        Fn.set_winograd_arithmetic(a.wino_arith)
     P, mean = load_params(a.net, a.weights, dev)
     i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
     flow = infer(a.net, P, i0, i1, mean)

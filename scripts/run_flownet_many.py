@@ -70,6 +70,8 @@ def main():
                     help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
     ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
+    ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0")
     ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
                          "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
@@ -87,6 +89,8 @@ def main():
         Fn.set_deconv_arithmetic(a.deconv_arith)
     if a.corr_arith:
         Fn.set_correlation_arithmetic(a.corr_arith)
+    if a.wino_arith:
+        Fn.set_winograd_arithmetic(a.wino_arith)
     entries = [l.split() for l in open(a.listfile) if l.strip()]
     mine = parallel.shard(entries)
     P, mean = RF.load_params(a.net, a.weights, dev)
