@@ -50,6 +50,8 @@ EXPORTS = [
     "fn2_conv_backward_data_pack_weights", "fn2_conv_backward_data_workspace_bytes", "fn2_conv_backward_data_workspace_bytes_with_room", "fn2_conv_backward_data_computed_channels", "fn2_conv_backward_data",
     "fn2_conv_backward_data_masked_supported", "fn2_conv_backward_data_masked", "fn2_conv_backward_weights_bias_fused", "fn2_conv_backward_weights_bias",
     "fn2_conv_backward_weights_supported", "fn2_conv_backward_weights_workspace_bytes", "fn2_conv_backward_weights", "fn2_conv_backward_bias",
+    "fn2_conv_wgrad_bf16x3_supported", "fn2_conv_wgrad_bf16x3_ksplit", "fn2_conv_wgrad_bf16x3_num_variants", "fn2_debug_set_conv_wgrad_bf16x3_variant",
+    "fn2_conv_backward_weights_arith", "fn2_conv_backward_weights_workspace_bytes_arith", "fn2_conv_backward_weights_arith_run",
     "fn2_im2col_forward", "fn2_col2im_bias_relu_forward", "fn2_col2im_bias_relu_forward_into",
     "fn2_datum_parse", "fn2_datum_float_data", "fn2_datum_serialize",
     "fn2_custom_data_sample_bytes", "fn2_custom_data_encode_sample", "fn2_custom_data_stage_records", "fn2_custom_data_decode_forward",
@@ -296,6 +298,14 @@ def lib():
     L.fn2_conv_backward_weights_workspace_bytes.argtypes = [dp, i]
     L.fn2_conv_backward_weights_workspace_bytes.restype = sz
     L.fn2_conv_backward_weights.argtypes = [dp, i, fp, i, i, fp, i, i, fp, i, vp, sz, vp]
+    L.fn2_conv_wgrad_bf16x3_supported.argtypes = [dp, i]
+    L.fn2_conv_wgrad_bf16x3_ksplit.argtypes = [dp, i]
+    L.fn2_conv_wgrad_bf16x3_num_variants.argtypes = []
+    L.fn2_debug_set_conv_wgrad_bf16x3_variant.argtypes = [i]
+    L.fn2_conv_backward_weights_arith.argtypes = [dp, i, i]
+    L.fn2_conv_backward_weights_workspace_bytes_arith.argtypes = [dp, i, i]
+    L.fn2_conv_backward_weights_workspace_bytes_arith.restype = sz
+    L.fn2_conv_backward_weights_arith_run.argtypes = [dp, i, i, fp, i, i, fp, i, i, fp, i, vp, sz, vp]
     L.fn2_conv_backward_data_workspace_bytes_with_room.argtypes = [dp, i, i, i]
     L.fn2_conv_backward_data_workspace_bytes_with_room.restype = sz
     L.fn2_conv_backward_data_masked_supported.argtypes = [dp, i, i]

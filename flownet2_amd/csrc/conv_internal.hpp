@@ -3,7 +3,11 @@
 
 #include <cstddef>
 
+#include "../../include/flownet2_hip.h"
+
 namespace fn2 {
+
+namespace wg { struct SlabMap; }
 
 // csrc/tconv_mfma.hip: fn2_tconv_forward with the output multiplied by the leaky-ReLU derivative of `mask` (NULL: no mask)
 int tconv_forward_masked(const float* bottom, const float* packed_weight, const float* bias, float* top,
@@ -49,5 +53,17 @@ int tconv_bf16x3_pack_weights(const float* weight, float* packed, int Cb, int Ct
 int tconv_bf16x3_masked(const float* top_diff, const float* packed_weight, float* bottom_diff, int N, int Ct, int Ht, int Wt, int top_channels, int top_c0,
                         int Cb, int Hb, int Wb, int bottom_channels, int bottom_c0, int kernel, int pad,
                         const float* mask, int mask_channels, int mask_c0, float mask_slope, void* stream);
+
+// csrc/conv_wgrad.hip: the finalize pass of the weight-gradient kernels (wgrad_finalize / wgrad_finalize_tiled) over a slab of `ksplit` parts of
+// `slab_part` floats in the tile layout `map` (conv_wgrad_geom.hpp): the parts added in part order, scattered into dw [Ca][Cb][T]
+int wgrad_finalize_parts(const float* slab, float* dw, const wg::SlabMap& map, int Ca, int Cb, int nblk_a, int nblk_b, int ksplit, long long slab_part,
+                         int accumulate, void* stream);
+
+// csrc/conv_wgrad_bf16x3.hip: the weight gradient of a Convolution{5, 2, 2} in split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3 of
+// fn2_conv_backward_weights_arith); which layers it takes: fn2_conv_wgrad_bf16x3_supported (0 bytes: not this layer).  Arguments as
+// fn2_conv_backward_weights.
+size_t conv_wgrad_bf16x3_workspace_bytes(const fn2_conv_desc* desc, int transposed);
+int conv_wgrad_bf16x3(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0, const float* top_diff,
+                      int top_channels, int top_c0, float* weight_diff, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 }  // namespace fn2

@@ -578,3 +578,29 @@ FN2_API int fn2_conv_backward_weights(const fn2_conv_desc* d, int transposed, co
   return fn2_conv_wgrad(a, b, weight_diff, d->N, w.Ca, w.Ha, w.Wa, ac, a0, w.Cb, w.Hb, w.Wb, bc, b0, d->kernel, d->stride, d->pad, accumulate,
                         workspace, workspace_bytes, stream);
 }
+
+// ---- weight gradient, by arithmetic (the split-bf16 kernel of csrc/conv_wgrad_bf16x3.hip beside the exact ones) ----
+// FN2_ROUTE_BF16X3: FN2_CONV_ARITH_BF16X3 for the layers the split kernel takes (Convolution{5, 2, 2}), 0 = the exact kernel everywhere else
+FN2_API int fn2_conv_backward_weights_arith(const fn2_conv_desc* d, int transposed, int flags) {
+  if (!(flags & FN2_ROUTE_BF16X3) || !valid(d)) return 0;
+  return fn2_conv_backward_weights_supported(d, transposed) && fn2_conv_wgrad_bf16x3_supported(d, transposed) ? FN2_CONV_ARITH_BF16X3 : 0;
+}
+
+FN2_API size_t fn2_conv_backward_weights_workspace_bytes_arith(const fn2_conv_desc* d, int transposed, int arith) {
+  if (arith == 0) return fn2_conv_backward_weights_workspace_bytes(d, transposed);
+  if (arith != FN2_CONV_ARITH_BF16X3 || !fn2_conv_backward_weights_arith(d, transposed, FN2_ROUTE_BF16X3)) return 0;
+  return fn2::conv_wgrad_bf16x3_workspace_bytes(d, transposed);
+}
+
+FN2_API int fn2_conv_backward_weights_arith_run(const fn2_conv_desc* d, int transposed, int arith, const float* bottom, int bottom_channels, int bottom_c0,
+                                                const float* top_diff, int top_channels, int top_c0, float* weight_diff, int accumulate,
+                                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (arith == 0)
+    return fn2_conv_backward_weights(d, transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels, top_c0, weight_diff, accumulate, workspace,
+                                     workspace_bytes, stream);
+  if (arith != FN2_CONV_ARITH_BF16X3) return fn2::fail(FN2_ERR_UNSUPPORTED, "conv_backward_weights_arith_run: unknown arithmetic 0x%x", arith);
+  if (!fn2_conv_backward_weights_arith(d, transposed, FN2_ROUTE_BF16X3))
+    return fn2::fail(FN2_ERR_UNSUPPORTED, "conv_backward_weights_arith_run: the split-bf16 weight gradient does not take this layer");
+  return fn2::conv_wgrad_bf16x3(d, transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels, top_c0, weight_diff, accumulate, workspace,
+                                workspace_bytes, stream);
+}

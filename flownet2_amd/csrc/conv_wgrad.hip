@@ -17,6 +17,7 @@
 // Every part writes its accumulator tiles as they are (16-byte stores, MFMA layout); wgrad_finalize adds the parts in part order and
 // scatters into the weight layout.  Summation order (restated by the oracle twin fn2_conv_wgrad_cpu): per part one fma chain over the
 // part's pixels in (n, y, x) order, parts added in part order; ksplit is a function of the layer geometry only (conv_wgrad_geom.hpp).
+#include "conv_internal.hpp"
 #include "mfma_tile.hpp"
 #include "conv_wgrad_geom.hpp"
 
@@ -365,6 +366,33 @@ static bool make_plan(Plan& p, int N, int Ca, int Ha, int Wa, int Cb, int Hb, in
 }
 
 }  // namespace wg
+
+// The finalize pass of a slab of `ksplit` parts of `slab_part` floats in the tile layout `map` (this file's kernels and
+// csrc/conv_wgrad_bf16x3.hip): the parts added in part order, scattered into dw [Ca][Cb][T]
+int wgrad_finalize_parts(const float* slab, float* dw, const wg::SlabMap& map, int Ca, int Cb, int nblk_a, int nblk_b, int ksplit, long long slab_part,
+                         int accumulate, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const long long quads = slab_part / 4;
+  const long long groups = (long long)nblk_a * nblk_b * 4 * map.MA * map.NB;
+  static const bool tiled = [] { const char* e = getenv("FN2_WGRAD_FINALIZE"); return !(e && e[0] == 'g'); }();      // "gather": the per-element kernel
+  static const long long g_tiled_min = [] { const char* e = getenv("FN2_WGRAD_TILED_MIN"); return e ? atoll(e) : 1024ll; }();
+  // (a group is T * 256 floats summed over ksplit parts by one workgroup: only where that still leaves >= 4 workgroups per CU (measured: 512 loses on conv4 / conv3_1, 1024 wins on deconv4) -- the layers
+  // with megabytes of weights and few parts; conv2's 64 parts x 32 groups are the per-element kernel's)
+  if (tiled && groups >= g_tiled_min && groups < (1ll << 31) && (map.T == 1 || map.T == 9 || map.T == 16 || map.T == 25)) {
+    const dim3 grid((unsigned)groups);
+    switch (map.T) {
+      case 1: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<1>), grid, dim3(256), 0, st, slab, dw, map, Ca, Cb, nblk_b, ksplit, slab_part, accumulate ? 1 : 0); break;
+      case 9: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<9>), grid, dim3(256), 0, st, slab, dw, map, Ca, Cb, nblk_b, ksplit, slab_part, accumulate ? 1 : 0); break;
+      case 16: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<16>), grid, dim3(256), 0, st, slab, dw, map, Ca, Cb, nblk_b, ksplit, slab_part, accumulate ? 1 : 0); break;
+      default: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<25>), grid, dim3(256), 0, st, slab, dw, map, Ca, Cb, nblk_b, ksplit, slab_part, accumulate ? 1 : 0); break;
+    }
+    return check_launch("conv_wgrad_finalize");
+  }
+  hipLaunchKernelGGL(wg::wgrad_finalize, dim3(blocks_for(quads, 256, 8192)), dim3(256), 0, st, slab, dw, map, Ca, Cb, nblk_b, quads, ksplit,
+                     slab_part, accumulate ? 1 : 0);
+  return check_launch("conv_wgrad_finalize");
+}
+
 }  // namespace fn2
 
 using namespace fn2;
@@ -432,23 +460,5 @@ FN2_API int fn2_conv_wgrad(const float* a, const float* b, float* dw,
   g.slab_part = (long long)p.slab_floats;
   const int rc = v.fn(g, st);
   if (rc != FN2_OK) return rc;
-  const long long quads = (long long)p.slab_floats / 4;
-  const long long groups = (long long)p.nblk_a * p.nblk_b * 4 * v.map.MA * v.map.NB;
-  static const bool tiled = [] { const char* e = getenv("FN2_WGRAD_FINALIZE"); return !(e && e[0] == 'g'); }();      // "gather": the per-element kernel
-  static const long long g_tiled_min = [] { const char* e = getenv("FN2_WGRAD_TILED_MIN"); return e ? atoll(e) : 1024ll; }();
-  // (a group is T * 256 floats summed over ksplit parts by one workgroup: only where that still leaves >= 4 workgroups per CU (measured: 512 loses on conv4 / conv3_1, 1024 wins on deconv4) -- the layers
-  // with megabytes of weights and few parts; conv2's 64 parts x 32 groups are the per-element kernel's)
-  if (tiled && groups >= g_tiled_min && groups < (1ll << 31) && (v.map.T == 1 || v.map.T == 9 || v.map.T == 16 || v.map.T == 25)) {
-    const dim3 grid((unsigned)groups);
-    switch (v.map.T) {
-      case 1: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<1>), grid, dim3(256), 0, st, slab, dw, v.map, Ca, Cb, p.nblk_b, p.ksplit, g.slab_part, accumulate ? 1 : 0); break;
-      case 9: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<9>), grid, dim3(256), 0, st, slab, dw, v.map, Ca, Cb, p.nblk_b, p.ksplit, g.slab_part, accumulate ? 1 : 0); break;
-      case 16: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<16>), grid, dim3(256), 0, st, slab, dw, v.map, Ca, Cb, p.nblk_b, p.ksplit, g.slab_part, accumulate ? 1 : 0); break;
-      default: hipLaunchKernelGGL((wg::wgrad_finalize_tiled<25>), grid, dim3(256), 0, st, slab, dw, v.map, Ca, Cb, p.nblk_b, p.ksplit, g.slab_part, accumulate ? 1 : 0); break;
-    }
-    return check_launch("conv_wgrad_finalize");
-  }
-  hipLaunchKernelGGL(wg::wgrad_finalize, dim3(blocks_for(quads, 256, 8192)), dim3(256), 0, st, slab, dw, v.map, Ca, Cb, p.nblk_b, quads, p.ksplit,
-                     g.slab_part, accumulate ? 1 : 0);
-  return check_launch("conv_wgrad_finalize");
+  return wgrad_finalize_parts(slab, dw, v.map, Ca, Cb, p.nblk_a, p.nblk_b, p.ksplit, g.slab_part, accumulate, stream);
 }

@@ -516,6 +516,27 @@ def conv_backward_arithmetic() -> str:
 if os.environ.get("FN2_DGRAD_ARITH"):
     set_conv_backward_arithmetic(os.environ["FN2_DGRAD_ARITH"])
 
+
+_WGRAD_ARITH = ["fp32"]
+
+
+def set_conv_weight_gradient_arithmetic(name: str):
+    """Arithmetic of the convolution WEIGHT GRADIENT, a switch of its own beside the other five: "fp32" (the default) or "bf16x3" --
+    split-bf16 arithmetic on the layers fn2_conv_backward_weights_arith hands to that kernel (csrc/conv_wgrad_bf16x3.hip: the 5x5 / 2 / 2
+    class, conv2 / conv3 of the encoders); the stem's fused weight + bias gradient, every Deconvolution, every other weight gradient,
+    every bias and data gradient and every forward stay as they are.  Initial value: $FN2_WGRAD_ARITH."""
+    if name not in _CONV_ARITHMETICS:
+        raise ValueError("conv weight gradient arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
+    _WGRAD_ARITH[0] = name
+
+
+def conv_weight_gradient_arithmetic() -> str:
+    return _WGRAD_ARITH[0]
+
+
+if os.environ.get("FN2_WGRAD_ARITH"):
+    set_conv_weight_gradient_arithmetic(os.environ["FN2_WGRAD_ARITH"])
+
 _CORR_ARITH = ["fp32"]
 
 
@@ -821,7 +842,8 @@ def _own_bwd_weight(d, x, w, stride, pad, transposed):
         d, x = d.contiguous(), x.contiguous()           # the stem kernel reads whole blobs
     xb, x0 = _channel_slice(x)
     db, d0 = _channel_slice(d)
-    return ops.conv_backward_weights(xb, db, desc, transposed, out=_grad_slot(w), bottom_c0=x0, top_c0=d0)
+    return ops.conv_backward_weights(xb, db, desc, transposed, out=_grad_slot(w), bottom_c0=x0, top_c0=d0,
+                                     bf16x3=not transposed and _WGRAD_ARITH[0] == "bf16x3")
 
 
 # (id(weight tensor), tag) -> (weak reference, _version, packed operand, weight generation), see _cached: the operand of a layer's

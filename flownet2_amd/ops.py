@@ -671,9 +671,16 @@ def conv_backward_weights_supported(desc, transposed=False) -> bool:
     return bool(_lib.lib().fn2_conv_backward_weights_supported(C.byref(desc), int(bool(transposed))))
 
 
-def conv_backward_weights(bottom, top_diff, desc, transposed=False, out=None, accumulate=False, bottom_c0=0, top_c0=0):
+def conv_backward_weights_arith(desc, transposed=False, bf16x3=False) -> int:
+    """Arithmetic of the layer's weight gradient (fn2_conv_backward_weights_arith): CONV_ARITH_BF16X3 where bf16x3 is asked for and the
+    split-bf16 kernel takes the layer (csrc/conv_wgrad_bf16x3.hip: Convolution{5, 2, 2}), else 0 = the exact kernel."""
+    return int(_lib.lib().fn2_conv_backward_weights_arith(C.byref(desc), int(bool(transposed)), ROUTE_BF16X3 if bf16x3 else 0))
+
+
+def conv_backward_weights(bottom, top_diff, desc, transposed=False, out=None, accumulate=False, bottom_c0=0, top_c0=0, bf16x3=False):
     """weight_diff of the layer ([Cout, Cin, k, k]; Deconvolution: [Cin, Cout, 4, 4]) (+)= ... (fn2_conv_backward_weights: the stem kernel or
-    csrc/conv_wgrad.hip, deterministic)."""
+    csrc/conv_wgrad.hip, deterministic).  bf16x3: in split-bf16 arithmetic where conv_backward_weights_arith gives the layer to that kernel
+    (fn2_conv_backward_weights_arith_run), exact everywhere else."""
     x, d = _chk(bottom, "bottom"), _chk(top_diff, "top_diff")
     L, tr = _lib.lib(), int(bool(transposed))
     k = desc.kernel
@@ -685,6 +692,13 @@ def conv_backward_weights(bottom, top_diff, desc, transposed=False, out=None, ac
         out = _chk(out, "weight diff")
         if tuple(out.shape) != shape:
             raise ValueError("conv_backward_weights: weight diff has the wrong shape")
+    arith = conv_backward_weights_arith(desc, transposed, True) if bf16x3 else 0
+    if arith:
+        need = int(L.fn2_conv_backward_weights_workspace_bytes_arith(C.byref(desc), tr, arith))
+        ws = _plane_workspace(x.device, need) if need else None
+        check(L.fn2_conv_backward_weights_arith_run(C.byref(desc), tr, arith, _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1], int(top_c0),
+                                                    _ptr(out), int(bool(accumulate)), _ptr(ws), need, _stream()))
+        return out
     need = int(L.fn2_conv_backward_weights_workspace_bytes(C.byref(desc), tr))
     ws = _plane_workspace(x.device, need) if need else None
     check(L.fn2_conv_backward_weights(C.byref(desc), tr, _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1], int(top_c0), _ptr(out),

@@ -661,6 +661,39 @@ int fn2_conv_backward_weights_bias(const fn2_conv_desc* desc, int transposed, co
                                    float* bias_diff, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 int fn2_conv_backward_bias(const float* top_diff, int diff_channels, int diff_c0, float* bias_diff, int N, int C, int H, int W,
                            int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* The split-bf16 arithmetic (FN2_CONV_ARITH_BF16X3, above) for the weight gradient of the stride-2 5x5 / 2 / 2 convolutions (conv2 / conv3 of
+ * the encoders; csrc/conv_wgrad_bf16x3.hip), a sixth switch of its own.  BOTH operands are activations, so nothing is split when weights are
+ * packed: the kernel stages the fp32 chunk of top_diff (4 rows x 8 pixels x 64 or 32 channels) and the window of bottom it needs (11 rows x 24
+ * columns x 32 channels) by LDS-DMA as the exact kernel does, and the workgroup cuts each staged value ONCE into its three bf16 pieces in LDS
+ * (top_diff [piece][row][channel][8 pixels]; bottom parity-deinterleaved by column, aligned 16 bytes plus the neighbour dwords, shifted by one
+ * element in registers for the taps kx = 0, 1, 4); no pre-split copy in global memory.  A k-step of v_mfma_f32_16x16x32_bf16 is 4 rows x 8
+ * pixels.  Summation order, a function of the layer geometry only: K parts of whole rows (fn2_conv_wgrad_bf16x3_ksplit: the exact kernel's
+ * split capped to at least 4 rows per part); within a part the k-steps ascend over (row groups, x blocks of 8); within a k-step the six piece
+ * products mm, lh, hl, mh, hm, hh (first letter: top_diff) on one fp32 accumulator; the parts are added in part order by the exact kernel's
+ * finalize pass.  Bit-reproducible, the same bits from every tile variant; not the exact kernel's bits, but within its fp64 bound
+ * (2e-6 x scale x sqrt(pixels), tests/test_wgrad_bf16x3.py).  Non-finite inputs reach exactly the weight elements the exact kernel gives them to
+ * (possibly NaN where that one gives Inf).  The bias gradient, the stem's fused weight + bias gradient, every Deconvolution and every other
+ * Convolution class stay exact.
+ *   fn2_conv_wgrad_bf16x3_supported       geometry alone: not transposed, kernel 5 / stride 2 / pad 2, Win % 4 == 0 and top_diff width % 4 == 0,
+ *                                         at least 16 channels on both sides (ragged channel blocks as in the exact kernel)
+ *   fn2_conv_wgrad_bf16x3_ksplit          the number of K parts of a layer the kernel takes (0: not this layer); _num_variants / the debug setter:
+ *                                         the tile variants (the same bits; -1 = the default, one past the last makes the next call fail on the host)
+ *   fn2_conv_backward_weights_arith       FN2_ROUTE_BF16X3 in `flags`: FN2_CONV_ARITH_BF16X3 for the layers the split kernel takes; 0 (= the
+ *                                         exact kernel) otherwise and for flags 0.  FN2_ROUTE_FORCE means nothing here.
+ *   ..._workspace_bytes_arith             arith 0: exactly fn2_conv_backward_weights_workspace_bytes; the bit: ksplit slabs of partial sums (the
+ *                                         larger of the tile variants'), 0 for a layer the kernel refuses
+ *   fn2_conv_backward_weights_arith_run   arith 0: exactly fn2_conv_backward_weights; the bit on a layer the kernel refuses, or any other
+ *                                         bit: FN2_ERR_UNSUPPORTED, decided on the host before any launch
+ * Measurements: profiles/wgrad_bf16x3_bench.md. */
+int fn2_conv_wgrad_bf16x3_supported(const fn2_conv_desc* desc, int transposed);
+int fn2_conv_wgrad_bf16x3_ksplit(const fn2_conv_desc* desc, int transposed);
+int fn2_conv_wgrad_bf16x3_num_variants(void);
+int fn2_debug_set_conv_wgrad_bf16x3_variant(int variant);
+int fn2_conv_backward_weights_arith(const fn2_conv_desc* desc, int transposed, int flags);
+size_t fn2_conv_backward_weights_workspace_bytes_arith(const fn2_conv_desc* desc, int transposed, int arith);
+int fn2_conv_backward_weights_arith_run(const fn2_conv_desc* desc, int transposed, int arith, const float* bottom, int bottom_channels, int bottom_c0,
+                                        const float* top_diff, int top_channels, int top_c0, float* weight_diff, int accumulate,
+                                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Transposed convolution, stride 2 (fp32 MFMA, NCHW, no column matrix / col2im):

@@ -69,11 +69,15 @@ def main():
     ap.add_argument("--prefetch-thread", action="store_true", help="draw on a background thread instead of a worker process")
     ap.add_argument("--dgrad-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the convolution data gradient (default: $FN2_DGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
+    ap.add_argument("--wgrad-arith", choices=["fp32", "bf16x3"], default=None,
+                    help="arithmetic of the convolution weight gradient (default: $FN2_WGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
     ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
                     help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0 (forward only: every gradient stays exact fp32)")
     a = ap.parse_args()
     if a.dgrad_arith:
         Fn.set_conv_backward_arithmetic(a.dgrad_arith)
+    if a.wgrad_arith:
+        Fn.set_conv_weight_gradient_arithmetic(a.wgrad_arith)
     if a.wino_arith:
         Fn.set_winograd_arithmetic(a.wino_arith)
     dev = torch.device("cuda")
@@ -150,6 +154,7 @@ def main():
     print("iteration (sum of the stages): %.3f ms" % sum(statistics.median(times[s_]) for s_ in stages))
     if not a.no_train:
         print("data-gradient arithmetic: %s" % Fn.conv_backward_arithmetic())
+        print("weight-gradient arithmetic: %s" % Fn.conv_weight_gradient_arithmetic())
         print("winograd forward arithmetic: %s" % Fn.get_winograd_arithmetic())
         print("loss %.4f, NaN ground truth kept: %s" % (float(loss), bool(torch.isnan(t_flow[0].data).any())))
 
