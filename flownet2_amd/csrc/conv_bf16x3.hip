@@ -23,8 +23,8 @@
 //     workgroup splits it ONCE into a bf16 image [piece][row][column][8 channels] (16 bytes per pixel and piece), so that a lane's
 //     operand of a tap is one ds_read_b128 per piece and every window element is converted once, not once per tap that reads it.
 //     One fp32 stage and one image: barrier -> split -> barrier -> (DMA of the next chunk into the stage) + MFMAs from the image.
-//   * weight operand: split once when packed (fn2::conv_bf16x3_pack_weights): [Cout / 16][k-step (+ 1 spare)][piece][lane][8 bf16], one
-//     global_load_dwordx4 per lane, piece and channel group, fetched a k-step ahead.
+//   * weight operand: split once when packed (fn2::conv_bf16x3_pack_weights): the packed layout of
+//     split_bf16.hpp with groups of 16 output channels, fetched a k-step ahead.
 //   * wave tile MW channel groups x NP patches, workgroup WM x WNX x WNY waves, epilogue as conv_mfma (store_row4).
 // Build figures (hipcc -O3, gfx950; __launch_bounds__(256, 2) allows 256 registers): variant 0 (32x4-pixel tile) 124 VGPRs, 70,848 bytes of
 // LDS; variant 1 (16x8) 126 VGPRs, 72,896 bytes; no spills, two workgroups per CU (LDS), four waves per SIMD by registers.
@@ -36,7 +36,7 @@ namespace fn2 {
 namespace cx {
 
 using namespace mfma;
-using namespace bf16x3;      // bf16x8, u32x4, piece2 / split8 (split_bf16.hpp)
+using namespace bf16x3;      // the toolkit of split_bf16.hpp
 
 struct Args {
   const float* in; const u32x4* wp; const float* bias; float* out;
@@ -88,12 +88,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
   window_plan<K>(voff, wave, lane, S * y0 - a.pad, S * x0 - K::PADL, a.Hin, a.Win, plane);
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
   const unsigned chunk_bytes = 4u * 8u * (unsigned)plane;
-  auto stage = [&](int chunk) {
-    unsigned vc[K::RPW];
-#pragma unroll
-    for (int i = 0; i < K::RPW; ++i) vc[i] = voff[i] == kOOB ? kOOB : voff[i] + (unsigned)chunk * chunk_bytes;      // (channels >= Cin: out of range = 0)
-    stage_chunk<K>(rs, vc, lds_base, wave, 0u);
-  };
+  const ChunkStage<K> stage{rs, voff, chunk_bytes, lds_base, wave};
 
   // ---- operands
   const int kq = lane >> 4, py = (lane & 15) >> 2, px = lane & 3;
@@ -106,7 +101,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
     tapoff[t] = abase + (T / KS) * K::WCP + T % KS;
   }
   const int cg0 = (g * K::WM + wm) * MW;                            // first 16-channel group of this wave
-  const u32x4* wl = a.wp + (size_t)cg0 * a.kalloc * 192 + lane;     // k-step ks, piece q of group cg0 + j: wl[(j kalloc + ks) 192 + 64 q]
+  const u32x4* wl = packed_lane(a.wp, cg0, a.kalloc, lane);         // group cg0 + j, k-step ks: load_pieces(wl, j kalloc + ks, ..)
 
   f32x4 acc[MW][NP];
 #pragma unroll
@@ -117,9 +112,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
   u32x4 w[MW][3], wn[MW][3];
   stage(0);
 #pragma unroll
-  for (int j = 0; j < MW; ++j)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) wn[j][q] = wl[(size_t)j * a.kalloc * 192 + 64 * q];
+  for (int j = 0; j < MW; ++j) load_pieces(wl, (size_t)j * a.kalloc, wn[j]);
 
   for (int c = 0; c < a.nchunks; ++c) {
     wait_vmcnt<0>();                     // this wave's part of the stage has landed
@@ -134,9 +127,7 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
         float v[8];
 #pragma unroll
         for (int ch = 0; ch < 8; ++ch) v[ch] = s[ch * K::CS];
-        u32x4 h, m, l;
-        split8(v, h, m, l);
-        img[idx] = h; img[K::PIX + idx] = m; img[2 * K::PIX + idx] = l;
+        store_pieces(img + idx, K::PIX, v);
       }
     }
     __syncthreads();                     // the image is whole, the stage is free
@@ -145,26 +136,24 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
     for (int t = 0; t < K::KST; ++t) {
       const int ks = c * K::KST + t;
 #pragma unroll
-      for (int j = 0; j < MW; ++j)
+      for (int j = 0; j < MW; ++j) {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          w[j][q] = wn[j][q];
-          wn[j][q] = wl[((size_t)j * a.kalloc + ks + 1) * 192 + 64 * q];        // (the packed array carries a spare k-step per group)
-        }
+        for (int q = 0; q < 3; ++q) w[j][q] = wn[j][q];
+        load_pieces(wl, (size_t)j * a.kalloc + ks + 1, wn[j]);                  // (the packed array carries a spare k-step per group)
+      }
       u32x4 x[NP][3];
 #pragma unroll
       for (int p = 0; p < NP; ++p)
 #pragma unroll
         for (int q = 0; q < 3; ++q) x[p][q] = img[q * K::PIX + tapoff[t] + 4 * S * p];
       // the six products, small terms first: (activation piece, weight piece) = mm, lh, hl, mh, hm, hh
-      constexpr int XP[6] = {1, 2, 0, 1, 0, 0}, WP[6] = {1, 0, 2, 0, 1, 0};
 #pragma unroll
       for (int i = 0; i < 6; ++i)
 #pragma unroll
         for (int j = 0; j < MW; ++j)
 #pragma unroll
           for (int p = 0; p < NP; ++p)
-            acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x[p][XP[i]]), __builtin_bit_cast(bf16x8, w[j][WP[i]]), acc[j][p], 0, 0, 0);
+            acc[j][p] = piece_mfma_16x16x32(i, x[p], w[j], acc[j][p]);
     }
   }
 
@@ -193,12 +182,10 @@ conv_bf16x3(Args a) {
   conv_body<K>(a, g, bx, (int)(t % a.ty), (int)(t / a.ty));
 }
 
-// weight [Cout][Cin][KS][KS] -> packed [Cout / 16][kalloc][piece][lane][8 bf16]; one thread per (group, k-step, lane)
+// weight [Cout][Cin][KS][KS] -> the packed layout of split_bf16.hpp, groups of 16 output channels
 __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ wsrc, u32x4* __restrict__ wp, int Cout, int Cin, int KS, int kalloc) {
-  const long long total = (long long)(Cout / 16) * kalloc * 64;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int lane = (int)(i & 63), ks = (int)((i >> 6) % kalloc), grp = (int)((i >> 6) / kalloc);
+  int lane, ks, grp;
+  if (!pack_thread(Cout / 16, kalloc, lane, ks, grp)) return;
   const int kst = cdiv(KS * KS, 4), chunk = ks / kst, tap = 4 * (ks % kst) + (lane >> 4), co = 16 * grp + (lane & 15);
   float v[8];
 #pragma unroll
@@ -206,10 +193,10 @@ __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ ws
     const int ci = 8 * chunk + j;
     v[j] = (ks < kalloc - 1 && tap < KS * KS && ci < Cin) ? wsrc[((size_t)co * Cin + ci) * KS * KS + tap] : 0.f;
   }
-  u32x4 h, m, l;
+  u32x4 h, m, l;                    // (store_pieces, written out: through the helper this kernel allocates other registers)
   split8(v, h, m, l);
-  u32x4* dst = wp + ((size_t)grp * kalloc + ks) * 192 + lane;
-  dst[0] = h; dst[64] = m; dst[128] = l;
+  u32x4* dst = wp + ((size_t)grp * kalloc + ks) * kStepVecs + lane;
+  dst[0] = h; dst[kPieceVecs] = m; dst[2 * kPieceVecs] = l;
 }
 
 template <class K>
@@ -218,12 +205,7 @@ static int launch(const Args& base, hipStream_t st) {
   a.tx = cdiv(a.Wout, K::TW); a.ty = cdiv(a.Hout, K::TH);
   a.ng = a.Cout / (16 * K::MW * K::WM);
   a.nchunks = cdiv(a.Cin, 8);
-  const long long tiles = (long long)a.N * a.tx * a.ty * a.ng;
-  if (tiles > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "conv_bf16x3: grid too large");
-  a.total = (unsigned)tiles;
-  set_dynamic_lds_once<&conv_bf16x3<K>>(K::LDS_BYTES);
-  hipLaunchKernelGGL((conv_bf16x3<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), K::LDS_BYTES, st, a);
-  return check_launch("conv_bf16x3_forward");
+  return launch_tiles<&conv_bf16x3<K>>(a, (long long)a.N * a.tx * a.ty * a.ng, K::THREADS, K::LDS_BYTES, "conv_bf16x3", "conv_bf16x3_forward", st);
 }
 
 struct Variant {
@@ -235,9 +217,7 @@ struct Variant {
 // 5x5 stride 2: 32x4- and 16x8-pixel tiles of 64 channels, two workgroups per CU.  (Measured and dropped: a 56x4-pixel tile with NP = 7 --
 // 110 KB of LDS, one workgroup per CU, which then idles through every split and barrier: 478 / 548 us where these take 308 / 334.)
 static const Variant kVariants[] = {FN2_CX_ROW(5, 2, 2, 4, 2, 2, 1) FN2_CX_ROW(5, 2, 2, 4, 2, 1, 2)};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-
-int g_forced_variant = -1;
+FN2_BF16X3_VARIANT_KNOBS(conv_bf16x3)
 
 static bool variant_applies(const Variant& v, const Args& a, int KS, int S) {
   return v.ks == KS && v.s == S && a.Win % 4 == 0 && a.Cout % (16 * v.mw * v.wm) == 0;
@@ -264,18 +244,14 @@ bool geometry_ok(int Cin, int Hin, int Win, int Cout, int kernel, int stride, in
 
 size_t conv_bf16x3_packed_floats(int Cout, int Cin, int kernel) {
   if (Cout <= 0 || Cout % 16 != 0 || Cin <= 0 || kernel <= 0) return 0;
-  return (size_t)(Cout / 16) * cx::kstep_alloc(Cin, kernel) * 192 * 4;
+  return bf16x3::packed_floats(Cout / 16, cx::kstep_alloc(Cin, kernel));
 }
 
 int conv_bf16x3_pack_weights(const float* weight, float* packed, int Cout, int Cin, int kernel, void* stream) {
-  if (!weight || !packed) return fail(FN2_ERR_INVALID_ARG, "conv_bf16x3_pack_weights: null blob");
-  if (conv_bf16x3_packed_floats(Cout, Cin, kernel) == 0) return fail(FN2_ERR_UNSUPPORTED, "conv_bf16x3_pack_weights: needs Cout %% 16 == 0 (got %d)", Cout);
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) return fail(FN2_ERR_UNSUPPORTED, "conv_bf16x3_pack_weights: the operand must be 16-byte aligned");
   const int kalloc = cx::kstep_alloc(Cin, kernel);
-  const long long total = (long long)(Cout / 16) * kalloc * 64;
-  hipLaunchKernelGGL(cx::pack_weights, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<cx::u32x4*>(packed), Cout, Cin, kernel, kalloc);
-  return check_launch("conv_bf16x3_pack_weights");
+  return bf16x3::pack_operand("conv_bf16x3_pack_weights", weight, packed, conv_bf16x3_packed_floats(Cout, Cin, kernel) != 0,
+                              [&] { return fail(FN2_ERR_UNSUPPORTED, "conv_bf16x3_pack_weights: needs Cout %% 16 == 0 (got %d)", Cout); },
+                              Cout / 16, kalloc, stream, cx::pack_weights, Cout, Cin, kernel, kalloc);
 }
 
 int conv_bf16x3_forward(const float* bottom, const float* packed_weight, const float* bias, float* top, int N, int Cin, int Hin, int Win,
@@ -298,13 +274,9 @@ int conv_bf16x3_forward(const float* bottom, const float* packed_weight, const f
   hipStream_t st = as_stream(stream);
   static TuneCache cache("conv_bf16x3", cx::kNumVariants);
   const TuneKey key{N, Cin, Hin, Win, Cout, kernel, stride, pad, bottom_channels == Cin, top_channels == Cout};
-  mfma::Pick p;
-  if (const int rc = mfma::pick_variant(p, "conv_bf16x3", cx::g_forced_variant, cx::kNumVariants, false, cache, key, st,
-                                        [&](int i) { return cx::variant_applies(cx::kVariants[i], a, kernel, stride); },
-                                        [&](int i, bool) { return cx::variant_cost(cx::kVariants[i], a); },
-                                        [&](int i, bool) { return cx::kVariants[i].fn(a, st); }, [](int) { return false; }))
-    return rc;
-  return cx::kVariants[p.variant].fn(a, st);
+  return bf16x3::pick_and_run("conv_bf16x3", cx::g_forced_variant, cx::kNumVariants, cache, key, st,
+                              [&](int i) { return cx::variant_applies(cx::kVariants[i], a, kernel, stride); },
+                              [&](int i) { return cx::variant_cost(cx::kVariants[i], a); }, [&](int i) { return cx::kVariants[i].fn(a, st); });
 }
 
 }  // namespace fn2
@@ -315,6 +287,3 @@ FN2_API int fn2_conv_bf16x3_supported(const fn2_conv_desc* d) {
   if (!d || d->N < 1 || d->Cin < 1 || d->Cout < 1 || d->Hin < 1 || d->Win < 1) return 0;
   return cx::geometry_ok(d->Cin, d->Hin, d->Win, d->Cout, d->kernel, d->stride, d->pad) ? 1 : 0;
 }
-
-FN2_API int fn2_conv_bf16x3_num_variants(void) { return cx::kNumVariants; }
-FN2_API int fn2_debug_set_conv_bf16x3_variant(int v) { cx::g_forced_variant = v; return FN2_OK; }

@@ -341,13 +341,8 @@ template <class K>
 static int launch(const Args& base, hipStream_t st) {
   Args a = base;
   set_geometry<K>(a);
-  if (tiles_of(a) > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "conv_mfma: grid too large");
-  a.total = (unsigned)tiles_of(a); a.nbig = a.total;
-  const unsigned grid = 8 * ((a.total + 7) / 8);
-  constexpr size_t lds = sizeof(float) * 2 * K::BUF;
-  set_dynamic_lds_once<&conv_mfma<K>>((int)lds);
-  hipLaunchKernelGGL((conv_mfma<K>), dim3(grid), dim3(K::THREADS), lds, st, a);
-  return check_launch("conv_mfma_forward");
+  a.nbig = (unsigned)tiles_of(a);          // (every tile is a whole one)
+  return launch_tiles<&conv_mfma<K>>(a, tiles_of(a), K::THREADS, (int)(sizeof(float) * 2 * K::BUF), "conv_mfma", "conv_mfma_forward", st);
 }
 
 // whole rounds of tiles, then the remainder as half-channel workgroups (conv_mfma_tail)

@@ -231,8 +231,7 @@ __device__ __forceinline__ void compute_chunk(const char* am, const char* bm, co
 #pragma unroll
         for (int ma = 0; ma < MA; ++ma) {
           const int ti = ma * K::T + ky * 5 + kx;
-          acc[ti] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av[ma][kXPiece[i]]), __builtin_bit_cast(bf16x8, bop[kx][kWPiece[i]]),
-                                                            acc[ti], 0, 0, 0);
+          acc[ti] = piece_mfma_16x16x32(i, av[ma], bop[kx], acc[ti]);
         }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -319,10 +318,9 @@ __global__ void __launch_bounds__(256, 1) conv_wgrad_bf16x3(Args a) {
 }
 
 template <class K>
-static int launch(const Args& a, hipStream_t st) {
-  set_dynamic_lds_once<&conv_wgrad_bf16x3<K>>(K::LDS_BYTES);
-  hipLaunchKernelGGL((conv_wgrad_bf16x3<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), K::LDS_BYTES, st, a);
-  return check_launch("conv_wgrad_bf16x3");
+static int launch(const Args& base, hipStream_t st) {
+  Args a = base;             // (total: set by the caller, within the limit by make_plan)
+  return launch_tiles<&conv_wgrad_bf16x3<K>>(a, a.total, K::THREADS, K::LDS_BYTES, "conv_wgrad_bf16x3", "conv_wgrad_bf16x3", st);
 }
 
 struct Variant {
@@ -333,9 +331,7 @@ struct Variant {
 
 #define FN2_WX_ROW(MA) {Cfg<MA>::CA, Cfg<MA>::CB, Cfg<MA>::TILES, SlabMap{MA, 1, 2, 2, 25, Cfg<MA>::CA, Cfg<MA>::CB, Cfg<MA>::TILES}, &launch<Cfg<MA>>},
 static const Variant kVariants[] = {FN2_WX_ROW(2) FN2_WX_ROW(1)};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-
-int g_forced_variant = -1;
+FN2_BF16X3_VARIANT_KNOBS(conv_wgrad_bf16x3)
 
 // The K split of a layer in this arithmetic: the exact kernel's (a function of the geometry only), with at least 4 rows -- one k-step -- per part
 inline int ksplit_for_split(int N, int Ca, int Ha, int Wa, int Cb) {
@@ -415,6 +411,3 @@ FN2_API int fn2_conv_wgrad_bf16x3_ksplit(const fn2_conv_desc* d, int transposed)
   wgx::Plan p;
   return wgx::plan_of(p, d, transposed) ? p.ksplit : 0;
 }
-
-FN2_API int fn2_conv_wgrad_bf16x3_num_variants(void) { return wgx::kNumVariants; }
-FN2_API int fn2_debug_set_conv_wgrad_bf16x3_variant(int v) { wgx::g_forced_variant = v; return FN2_OK; }

@@ -51,8 +51,7 @@ namespace fn2 {
 namespace wx {
 
 using namespace mfma;
-using namespace bf16x3;      // bf16x8, u32x4, piece2 / split8 (split_bf16.hpp)
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using namespace bf16x3;      // the toolkit of split_bf16.hpp
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 
 struct Args {
@@ -68,7 +67,7 @@ struct Args {
 };
 
 constexpr int kKC = 16;                  // input channels of a k-step
-constexpr int kStepVecs = 16 * 3 * 64;   // 16-byte vectors of the weight operand per k-step and 32-channel group
+constexpr int kStepVecs = 16 * bf16x3::kStepVecs;      // 16-byte vectors of the weight operand per k-step and 32-channel group: 16 positions
 constexpr int kAhead = 4;                // positions the weight fetch runs ahead
 
 template <int TGY_, int TGX_>
@@ -119,12 +118,7 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
   window_plan<K>(voff, wave, lane, y0 - 1, x0 - K::PADL, a.Hin, a.Win, plane);
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
   const unsigned step_bytes = 4u * kKC * (unsigned)plane;
-  auto stage = [&](int c) {
-    unsigned vc[K::RPW];
-#pragma unroll
-    for (int i = 0; i < K::RPW; ++i) vc[i] = voff[i] == kOOB ? kOOB : voff[i] + (unsigned)c * step_bytes;      // (channels >= Cin: out of range = 0)
-    stage_chunk<K>(rs, vc, lds_base, wave, 0u);
-  };
+  const ChunkStage<K> stage{rs, voff, step_bytes, lds_base, wave};
 
   // ---- transform item of this thread: tile it of the 64, channels 4 cq .. 4 cq + 3 of the k-step
   const int cq = tid & 3, it = tid >> 2;
@@ -146,7 +140,7 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
 #pragma unroll
   for (int p = 0; p < kAhead; ++p)
 #pragma unroll
-    for (int q = 0; q < 3; ++q) b[p][q] = bl[(3 * p + q) * 64];
+    for (int q = 0; q < 3; ++q) b[p][q] = bl[(3 * p + q) * kPieceVecs];
 
   for (int c = 0; c < a.nsteps; ++c) {
     wait_vmcnt<0>();                     // this wave's part of the stage has landed
@@ -180,12 +174,12 @@ __device__ __forceinline__ void wino_body(const Args& a, int g, int bx, int by, 
       for (int q = 0; q < 3; ++q) {
         if (p + 1 < 16) x[(p + 1) & 1][q] = *reinterpret_cast<const u32x4*>(ap + (q * 16 + p + 1) * K::PPLANE);
         w[q] = b[p % kAhead][q];
-        b[p % kAhead][q] = bk[(3 * (p + kAhead) + q) * 64];        // (runs into the next k-step; the operand carries a spare one)
+        b[p % kAhead][q] = bk[(3 * (p + kAhead) + q) * kPieceVecs];      // (runs into the next k-step; the operand carries a spare one)
       }
       // the six products, small terms first: (activation piece, weight piece) = mm, lh, hl, mh, hm, hh
 #pragma unroll
       for (int i = 0; i < 6; ++i)
-        acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x[p & 1][kXPiece[i]]), __builtin_bit_cast(bf16x8, w[kWPiece[i]]), acc[p], 0, 0, 0);
+        acc[p] = piece_mfma_32x32x16(i, x[p & 1], w, acc[p]);
       __builtin_amdgcn_sched_barrier(0);        // a position's reads stay with its MFMAs: hoisted together they do not fit the registers
     }
   }
@@ -258,10 +252,8 @@ __device__ inline void wino_u(const float g[3][3], float U[4][4]) {
 
 // weight [Cout][Cin][3][3] -> packed [Cout / 32][kalloc][position][piece][lane][8 bf16]; one thread per (group, k-step, lane)
 __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ wsrc, u32x4* __restrict__ up, int Cout, int Cin, int kalloc) {
-  const long long total = (long long)(Cout / 32) * kalloc * 64;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int lane = (int)(i & 63), ks = (int)((i >> 6) % kalloc), grp = (int)((i >> 6) / kalloc);
+  int lane, ks, grp;
+  if (!pack_thread(Cout / 32, kalloc, lane, ks, grp)) return;
   const int co = 32 * grp + (lane & 31), c0 = kKC * ks + 8 * (lane >> 5);
   float U[8][4][4];
 #pragma unroll
@@ -278,9 +270,7 @@ __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ ws
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = U[j][p >> 2][p & 3];
-    u32x4 h, m, l;
-    split8(v, h, m, l);
-    dst[(3 * p) * 64] = h; dst[(3 * p + 1) * 64] = m; dst[(3 * p + 2) * 64] = l;
+    store_pieces(dst + 3 * p * kPieceVecs, kPieceVecs, v);
   }
 }
 
@@ -292,12 +282,7 @@ static int launch(const Args& base, hipStream_t st) {
   a.tx = cdiv(a.Wout, K::TW); a.ty = cdiv(a.Hout, K::TH);
   a.ng = a.Cout / 64;
   a.nsteps = cdiv(a.Cin, kKC);
-  const long long tiles = (long long)a.N * a.tx * a.ty * a.ng;
-  if (tiles > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "conv_wino_bf16x3: grid too large");
-  a.total = (unsigned)tiles;
-  set_dynamic_lds_once<&conv_wino_bf16x3<K>>(K::LDS_BYTES);
-  hipLaunchKernelGGL((conv_wino_bf16x3<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), K::LDS_BYTES, st, a);
-  return check_launch("conv_wino_bf16x3_forward");
+  return launch_tiles<&conv_wino_bf16x3<K>>(a, (long long)a.N * a.tx * a.ty * a.ng, K::THREADS, K::LDS_BYTES, "conv_wino_bf16x3", "conv_wino_bf16x3_forward", st);
 }
 
 struct Variant {
@@ -308,9 +293,7 @@ struct Variant {
 #define FN2_WX_ROW(TGY, TGX) {TGY, TGX, &launch<Cfg<TGY, TGX>>},
 // 16x16- and 8x32-pixel tiles of 64 channels
 static const Variant kVariants[] = {FN2_WX_ROW(8, 8) FN2_WX_ROW(4, 16)};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-
-int g_forced_variant = -1;
+FN2_BF16X3_VARIANT_KNOBS(conv_wino_bf16x3)
 
 // Cost model: rounds of workgroups over the 256 CUs (one workgroup per CU; tiles hanging over the image edge included); the square
 // tile first among equals (it stages fewer window pixels per tile)
@@ -332,14 +315,10 @@ size_t conv_wino_bf16x3_packed_floats(int Cout, int Cin) {
 }
 
 int conv_wino_bf16x3_pack_weights(const float* weight, float* packed, int Cout, int Cin, void* stream) {
-  if (!weight || !packed) return fail(FN2_ERR_INVALID_ARG, "conv_wino_bf16x3_pack_weights: null blob");
-  if (conv_wino_bf16x3_packed_floats(Cout, Cin) == 0) return fail(FN2_ERR_UNSUPPORTED, "conv_wino_bf16x3_pack_weights: needs Cout %% 64 == 0 (got %d)", Cout);
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) return fail(FN2_ERR_UNSUPPORTED, "conv_wino_bf16x3_pack_weights: the operand must be 16-byte aligned");
   const int kalloc = wx::kstep_alloc(Cin);
-  const long long total = (long long)(Cout / 32) * kalloc * 64;
-  hipLaunchKernelGGL(wx::pack_weights, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<wx::u32x4*>(packed), Cout, Cin, kalloc);
-  return check_launch("conv_wino_bf16x3_pack_weights");
+  return bf16x3::pack_operand("conv_wino_bf16x3_pack_weights", weight, packed, conv_wino_bf16x3_packed_floats(Cout, Cin) != 0,
+                              [&] { return fail(FN2_ERR_UNSUPPORTED, "conv_wino_bf16x3_pack_weights: needs Cout %% 64 == 0 (got %d)", Cout); },
+                              Cout / 32, kalloc, stream, wx::pack_weights, Cout, Cin, kalloc);
 }
 
 int conv_wino_bf16x3_forward(const float* bottom, const float* packed_weight, const float* bias, float* top, int N, int Cin, int Hin, int Win,
@@ -361,13 +340,8 @@ int conv_wino_bf16x3_forward(const float* bottom, const float* packed_weight, co
   hipStream_t st = as_stream(stream);
   static TuneCache cache("conv_wino_bf16x3", wx::kNumVariants);
   const TuneKey key{N, Cin, Hin, Win, Cout, kernel, stride, pad, bottom_channels == Cin, top_channels == Cout};
-  mfma::Pick p;
-  if (const int rc = mfma::pick_variant(p, "conv_wino_bf16x3", wx::g_forced_variant, wx::kNumVariants, false, cache, key, st,
-                                        [](int) { return true; },
-                                        [&](int i, bool) { return wx::variant_cost(wx::kVariants[i], a); },
-                                        [&](int i, bool) { return wx::kVariants[i].fn(a, st); }, [](int) { return false; }))
-    return rc;
-  return wx::kVariants[p.variant].fn(a, st);
+  return bf16x3::pick_and_run("conv_wino_bf16x3", wx::g_forced_variant, wx::kNumVariants, cache, key, st, [](int) { return true; },
+                              [&](int i) { return wx::variant_cost(wx::kVariants[i], a); }, [&](int i) { return wx::kVariants[i].fn(a, st); });
 }
 
 }  // namespace fn2
@@ -378,6 +352,3 @@ FN2_API int fn2_conv_wino_bf16x3_supported(const fn2_conv_desc* d) {
   if (!d || d->N < 1 || d->Cin < 1 || d->Cout < 1 || d->Hin < 1 || d->Win < 1) return 0;
   return wx::geometry_ok(d->Cin, d->Hin, d->Win, d->Cout, d->kernel, d->stride, d->pad) ? 1 : 0;
 }
-
-FN2_API int fn2_conv_wino_bf16x3_num_variants(void) { return wx::kNumVariants; }
-FN2_API int fn2_debug_set_conv_wino_bf16x3_variant(int v) { wx::g_forced_variant = v; return FN2_OK; }

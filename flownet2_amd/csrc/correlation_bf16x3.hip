@@ -144,10 +144,7 @@ corr_fwd_bf16x3(Args g) {
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = xr[r][j][e];
-            u32x4 h, m, l;
-            split8(v, h, m, l);
-            const int w = widx[r] + (e & 1) * wps[r] + (e >> 1);
-            img[w] = h; img[K::PS + w] = m; img[2 * K::PS + w] = l;
+            store_pieces(img + widx[r] + (e & 1) * wps[r] + (e >> 1), K::PS, v);
           }
         }
       }
@@ -170,8 +167,7 @@ corr_fwd_bf16x3(Args g) {
           for (int i = 0; i < 6; ++i)
 #pragma unroll
             for (int px = 0; px < 2; ++px)
-              acc[u][px] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, xa[px][kXPiece[i]]),
-                                                                   __builtin_bit_cast(bf16x8, xb[px][kWPiece[i]]), acc[u][px], 0, 0, 0);
+              acc[u][px] = piece_mfma_16x16x32(i, xa[px], xb[px], acc[u][px]);
         }
       }
     }
@@ -239,9 +235,7 @@ struct Variant {
 };
 // 4 patches per task on 8 waves (one workgroup per CU), 2 patches on 4 waves (two per CU: narrow maps waste less of a group)
 static const Variant kVariants[] = {{4, 1, &launch<Cfg<4, 1>>}, {2, 2, &launch<Cfg<2, 2>>}};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-
-int g_forced_variant = -1;
+FN2_BF16X3_VARIANT_KNOBS(correlation_bf16x3)
 
 // Cost model: rounds of workgroups over the chip's slots (256 CUs x workgroups per CU) x the staged pixels of a task (the split of the
 // operands, not the matrix pipe, sets a k-step's time)
@@ -272,13 +266,8 @@ int corr_bf16x3_launch(const CorrGeom& cg, const float* b0, const float* b1, flo
   g.ctot = cg.top_ctot; g.c0 = cg.top_c0; g.relu = cg.relu; g.slope = cg.slope;
   static TuneCache cache("correlation_bf16x3", cbx::kNumVariants);
   const TuneKey key{cg.N, cg.C, cg.H, cg.W, cg.relu, 0, 0, 0, 0, 0};
-  mfma::Pick p;
-  if (const int rc = mfma::pick_variant(p, "correlation_bf16x3", cbx::g_forced_variant, cbx::kNumVariants, false, cache, key, st,
-                                        [](int) { return true; },
-                                        [&](int i, bool) { return cbx::variant_cost(cbx::kVariants[i], g); },
-                                        [&](int i, bool) { return cbx::kVariants[i].fn(g, st); }, [](int) { return false; }))
-    return rc;
-  return cbx::kVariants[p.variant].fn(g, st);
+  return bf16x3::pick_and_run("correlation_bf16x3", cbx::g_forced_variant, cbx::kNumVariants, cache, key, st, [](int) { return true; },
+                              [&](int i) { return cbx::variant_cost(cbx::kVariants[i], g); }, [&](int i) { return cbx::kVariants[i].fn(g, st); });
 }
 
 }  // namespace fn2
@@ -288,5 +277,3 @@ using namespace fn2;
 FN2_API int fn2_correlation_bf16x3_supported(const fn2_corr_params* p, int N, int C, int H, int W) {
   return corr_bf16x3_geometry_ok(p, N, C, H, W) ? 1 : 0;
 }
-FN2_API int fn2_correlation_bf16x3_num_variants(void) { return cbx::kNumVariants; }
-FN2_API int fn2_debug_set_correlation_bf16x3_variant(int v) { cbx::g_forced_variant = v; return FN2_OK; }

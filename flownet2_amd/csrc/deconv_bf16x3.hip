@@ -83,18 +83,14 @@ __device__ __forceinline__ void split_chunk(u32x4* img, int widx, const f32x4 (&
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = xr[j][i];
-    u32x4 h, m, l;
-    split8(v, h, m, l);
-    img[widx + i] = h; img[K::PS + widx + i] = m; img[2 * K::PS + widx + i] = l;
+    store_pieces(img + widx + i, K::PS, v);
   }
 }
 
 template <class K>
 __device__ __forceinline__ void load_weights(const u32x4* const (&wl)[K::MW], int ks, u32x4 (&w)[K::MW][3]) {
 #pragma unroll
-  for (int j = 0; j < K::MW; ++j)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) w[j][q] = wl[j][(size_t)ks * 192 + 64 * q];
+  for (int j = 0; j < K::MW; ++j) load_pieces(wl[j], (size_t)ks, w[j]);
 }
 
 template <class K>
@@ -117,10 +113,10 @@ __device__ __forceinline__ void gemm_body(const Args& a, int mtile, int ptile, i
 
   // ---- operands of this lane
   const int cg0 = (mtile * K::WM + wm) * MW;                         // first 16-row group of this wave
-  const u32x4* wl[MW];                                               // k-step ks, piece q of group cg0 + j: wl[j][ks 192 + 64 q]
+  const u32x4* wl[MW];                                               // group cg0 + j, k-step ks: load_pieces(wl[j], ks, ..)
 #pragma unroll
   for (int j = 0; j < MW; ++j)                                       // (a group outside the matrix re-reads the last one and stores nothing)
-    wl[j] = a.wp + (size_t)min(cg0 + j, a.M / 16 - 1) * a.kalloc * 192 + lane;
+    wl[j] = packed_lane(a.wp, min(cg0 + j, a.M / 16 - 1), a.kalloc, lane);
   const int kq = lane >> 4;
   const int ridx = (kq >> 1) * K::S2 + (kq & 1) * K::TP + 16 * NPW * wn + (lane & 15);
 
@@ -158,8 +154,7 @@ __device__ __forceinline__ void gemm_body(const Args& a, int mtile, int ptile, i
           for (int j = 0; j < MW; ++j)
 #pragma unroll
             for (int p = 0; p < NPW; ++p)
-              acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x[p][kXPiece[i]]), __builtin_bit_cast(bf16x8, w[s][j][kWPiece[i]]),
-                                                                  acc[j][p], 0, 0, 0);
+              acc[j][p] = piece_mfma_16x16x32(i, x[p], w[s][j], acc[j][p]);
       }
     }
   }
@@ -188,12 +183,10 @@ deconv_bf16x3_gemm(Args a) {
   gemm_body<K>(a, mtile, (int)(t % a.pt), (int)(t / a.pt));
 }
 
-// weight [Cin][Cout][4][4] = [Cin][M] -> packed [M / 16][kalloc][piece][lane][8 bf16]; one thread per (group, k-step, lane)
+// weight [Cin][Cout][4][4] = [Cin][M] -> the packed layout of split_bf16.hpp, groups of 16 rows of M
 __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ wsrc, u32x4* __restrict__ wp, int M, int Cin, int ksteps) {      // ksteps: kalloc
-  const long long total = (long long)(M / 16) * ksteps * 64;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int lane = (int)(i & 63), ks = (int)((i >> 6) % ksteps), grp = (int)((i >> 6) / ksteps);
+  int lane, ks, grp;
+  if (!pack_thread(M / 16, ksteps, lane, ks, grp)) return;
   const int m = 16 * grp + (lane & 15);
   float v[8];
 #pragma unroll
@@ -201,10 +194,10 @@ __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ ws
     const int ci = 32 * ks + 8 * (lane >> 4) + j;
     v[j] = ci < Cin ? wsrc[(size_t)ci * M + m] : 0.f;
   }
-  u32x4 h, mm, l;
+  u32x4 h, mm, l;                    // (store_pieces, written out: through the helper this kernel allocates other registers)
   split8(v, h, mm, l);
-  u32x4* dst = wp + ((size_t)grp * ksteps + ks) * 192 + lane;
-  dst[0] = h; dst[64] = mm; dst[128] = l;
+  u32x4* dst = wp + ((size_t)grp * ksteps + ks) * kStepVecs + lane;
+  dst[0] = h; dst[kPieceVecs] = mm; dst[2 * kPieceVecs] = l;
 }
 
 template <class K>
@@ -212,12 +205,7 @@ static int launch(const Args& base, hipStream_t st) {
   Args a = base;
   a.mt = cdiv(a.M, K::TM); a.pt = cdiv(a.P, K::TP);
   a.nchunks = cdiv(a.ksteps, K::KS);
-  const long long tiles = (long long)a.N * a.mt * a.pt;
-  if (tiles > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "deconv_bf16x3: grid too large");
-  a.total = (unsigned)tiles;
-  set_dynamic_lds_once<&deconv_bf16x3_gemm<K>>(K::LDS_BYTES);
-  hipLaunchKernelGGL((deconv_bf16x3_gemm<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), K::LDS_BYTES, st, a);
-  return check_launch("deconv_bf16x3_gemm");
+  return launch_tiles<&deconv_bf16x3_gemm<K>>(a, (long long)a.N * a.mt * a.pt, K::THREADS, K::LDS_BYTES, "deconv_bf16x3", "deconv_bf16x3_gemm", st);
 }
 
 struct Variant {
@@ -229,11 +217,9 @@ struct Variant {
 // rows x pixels of the workgroup tile: 128 x 128 and 64 x 128 (2 x 2 waves, chunks of 64 channels), 128 x 64 (4 x 1 waves, chunks of 128
 // channels: planes just over a multiple of 64 pixels -- deconv4's 140 -- waste less of it)
 static const Variant kVariants[] = {FN2_DX_ROW(4, 2, 2, 2, 2) FN2_DX_ROW(2, 2, 2, 2, 3) FN2_DX_ROW(2, 4, 1, 4, 3)};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+FN2_BF16X3_VARIANT_KNOBS(deconv_bf16x3)
 
 constexpr int kstep_alloc(int Cin) { return cdiv(Cin, 32) + 1; }
-
-int g_forced_variant = -1;
 
 // Cost model: rounds of workgroups over the chip's slots (256 CUs x workgroups per CU) x the tile's area (what hangs over the edges
 // included) x workgroups sharing a CU; the 128-channel chunks first among equals (half the barriers per product)
@@ -253,18 +239,14 @@ bool geometry_ok(int Cin, int Hin, int Win, int Cout) {
 
 size_t deconv_bf16x3_packed_floats(int Cin, int Cout) {
   if (Cin <= 0 || Cout <= 0 || (16 * (long long)Cout) % 32 != 0) return 0;
-  return (size_t)Cout * dx::kstep_alloc(Cin) * 192 * 4;
+  return bf16x3::packed_floats(Cout, dx::kstep_alloc(Cin));
 }
 
 int deconv_bf16x3_pack_weights(const float* weight, float* packed, int Cin, int Cout, void* stream) {
-  if (!weight || !packed) return fail(FN2_ERR_INVALID_ARG, "deconv_bf16x3_pack_weights: null blob");
-  if (deconv_bf16x3_packed_floats(Cin, Cout) == 0) return fail(FN2_ERR_UNSUPPORTED, "deconv_bf16x3_pack_weights: needs Cout %% 2 == 0 (got %d)", Cout);
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) return fail(FN2_ERR_UNSUPPORTED, "deconv_bf16x3_pack_weights: the operand must be 16-byte aligned");
   const int kalloc = dx::kstep_alloc(Cin);          // (channels >= Cin, the spare k-step among them: zeros)
-  const long long total = (long long)Cout * kalloc * 64;
-  hipLaunchKernelGGL(dx::pack_weights, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<dx::u32x4*>(packed), 16 * Cout, Cin, kalloc);
-  return check_launch("deconv_bf16x3_pack_weights");
+  return bf16x3::pack_operand("deconv_bf16x3_pack_weights", weight, packed, deconv_bf16x3_packed_floats(Cin, Cout) != 0,
+                              [&] { return fail(FN2_ERR_UNSUPPORTED, "deconv_bf16x3_pack_weights: needs Cout %% 2 == 0 (got %d)", Cout); },
+                              Cout, kalloc, stream, dx::pack_weights, 16 * Cout, Cin, kalloc);
 }
 
 int deconv_bf16x3_gemm(const float* bottom, const float* packed_weight, float* col, int N, int Cin, int Hin, int Win, int bottom_channels,
@@ -283,13 +265,8 @@ int deconv_bf16x3_gemm(const float* bottom, const float* packed_weight, float* c
   hipStream_t st = as_stream(stream);
   static TuneCache cache("deconv_bf16x3", dx::kNumVariants);
   const TuneKey key{N, Cin, Hin, Win, Cout, bottom_channels == Cin, 0, 0, 0, 0};
-  mfma::Pick p;
-  if (const int rc = mfma::pick_variant(p, "deconv_bf16x3", dx::g_forced_variant, dx::kNumVariants, false, cache, key, st,
-                                        [](int) { return true; },
-                                        [&](int i, bool) { return dx::variant_cost(dx::kVariants[i], a); },
-                                        [&](int i, bool) { return dx::kVariants[i].fn(a, st); }, [](int) { return false; }))
-    return rc;
-  return dx::kVariants[p.variant].fn(a, st);
+  return bf16x3::pick_and_run("deconv_bf16x3", dx::g_forced_variant, dx::kNumVariants, cache, key, st, [](int) { return true; },
+                              [&](int i) { return dx::variant_cost(dx::kVariants[i], a); }, [&](int i) { return dx::kVariants[i].fn(a, st); });
 }
 
 }  // namespace fn2
@@ -300,6 +277,3 @@ FN2_API int fn2_deconv_bf16x3_supported(const fn2_conv_desc* d) {
   if (!d || d->N < 1 || d->kernel != 4 || d->stride != 2 || d->pad != 1) return 0;
   return dx::geometry_ok(d->Cin, d->Hin, d->Win, d->Cout) ? 1 : 0;
 }
-
-FN2_API int fn2_deconv_bf16x3_num_variants(void) { return dx::kNumVariants; }
-FN2_API int fn2_debug_set_deconv_bf16x3_variant(int v) { dx::g_forced_variant = v; return FN2_OK; }

@@ -1,6 +1,6 @@
 // Building blocks shared by the MFMA tile kernels (conv_mfma, tconv_mfma, conv_plane, conv_wino, conv_wgrad; the correlation and
 // stem kernels take the primitives only): vector types, the LDS-DMA window of a workgroup tile, the packed-weight stream, the XCD
-// task remap, the row epilogue, and on the host the dynamic-LDS attribute, the argument checks and the variant picker.
+// task remap, the row epilogue, and on the host the dynamic-LDS attribute, the launch tail, the argument checks and the variant picker.
 // Everything on the device side is a __device__ __forceinline__ FUNCTION, never a lambda: the host pass of a __global__ template
 // cannot see amdgcn builtins inside a lambda body.
 #pragma once
@@ -90,6 +90,21 @@ __device__ __forceinline__ void stage_chunk(__amdgpu_buffer_rsrc_t rs, const uns
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(uintptr_t)(dst + 1024u * (unsigned)r), 16, voff[i], soff, 0, 0);
   }
 }
+
+// stage_chunk of the window `chunk` chunks further on (chunk_bytes: the planes of one chunk): the in-image lanes of the plan advance, the
+// kOOB lanes stay out of range (as do channels >= Cin: out of range = 0).  A function object over the kernel's own values with a plain
+// operator(), the one exception to the rule above: as a __forceinline__ function, expanded ahead of the optimiser, it changes the scalar
+// register allocation of the kernels that use it (profiles/bf16x3_toolkit.md).  It calls no amdgcn builtin itself.
+template <class K>
+struct ChunkStage {
+  const __amdgpu_buffer_rsrc_t& rs; const unsigned (&voff)[K::RPW]; const unsigned& chunk_bytes; const unsigned& dst; const int& wave;
+  __device__ void operator()(int chunk) const {
+    unsigned vc[K::RPW];
+#pragma unroll
+    for (int i = 0; i < K::RPW; ++i) vc[i] = voff[i] == kOOB ? kOOB : voff[i] + (unsigned)chunk * chunk_bytes;
+    stage_chunk<K>(rs, vc, dst, wave, 0u);
+  }
+};
 
 // ------------------------------------------------------------------------------------------------ weight stream
 // packed weights [Cout/64][ksteps][64 lanes][4] (fn2_conv_mfma_pack_weights): this lane's element of k-step 0 for the wave whose
@@ -201,6 +216,18 @@ inline void set_dynamic_lds_once(int bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     attr_set = true;
   }
+}
+
+// The launch tail of a tile kernel whose blocks find their task with xcd_task: `tiles` workgroups -> a.total, the dynamic-LDS
+// attribute, a grid of whole groups of 8 blocks (one per XCD), the launch check.  what: the family's name in the refusal; checked: the
+// name check_launch reports.
+template <auto Kernel, class Args>
+int launch_tiles(Args& a, long long tiles, int threads, int lds_bytes, const char* what, const char* checked, hipStream_t st) {
+  if (tiles > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "%s: grid too large", what);
+  a.total = (unsigned)tiles;
+  set_dynamic_lds_once<Kernel>(lds_bytes);
+  hipLaunchKernelGGL(Kernel, dim3(8 * ((a.total + 7) / 8)), dim3(threads), lds_bytes, st, a);
+  return check_launch(checked);
 }
 
 // The argument checks every forward entry point makes after its batch check: blobs present, the family's own geometry check

@@ -31,7 +31,7 @@
 //     ONCE into a bf16 image [piece][channel octet][row][column] (16 bytes per pixel, octet and piece): a lane's operand of a k-step is
 //     one ds_read_b128 per piece.  barrier -> split -> barrier -> (DMA of the next chunk into the stage) + MFMAs from the image.
 //   * weight operand: split once when packed (fn2::tconv_bf16x3_pack_weights) from the Convolution's own blob [Ct][Cb][k][k]:
-//     [Cb / 16][k-step (+ 1 spare)][piece][lane][8 bf16], one global_load_dwordx4 per lane, piece and channel group, a k-step ahead.
+//     the packed layout of split_bf16.hpp with groups of 16 bottom channels, fetched a k-step ahead.
 //   * wave tile MW channel groups x NP patches of 4x4 class positions x 4 classes; epilogue as tconv_body: 8 consecutive output pixels
 //     (x parities interleaved) per lane, patch and row parity, two 16-byte stores.
 // Build figures (hipcc -O3, gfx950; __launch_bounds__(256, 2) allows 256 registers): variant 0 (tile of 32x4 class positions = 64x8 output
@@ -120,12 +120,11 @@ __device__ __forceinline__ void kstep(f32x4 (&acc)[4][K::MW][K::NP], u32x4 (&x)[
                                       const u32x4* wl, size_t kalloc, int ks0, int abase, bool th) {
   constexpr int MW = K::MW, NP = K::NP, cls = K::P::cls_of(R);
 #pragma unroll
-  for (int j = 0; j < MW; ++j)
+  for (int j = 0; j < MW; ++j) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      w[j][q] = wn[j][q];
-      wn[j][q] = wl[((size_t)j * kalloc + ks0 + R + 1) * 192 + 64 * q];        // (the packed array carries a spare k-step per group)
-    }
+    for (int q = 0; q < 3; ++q) w[j][q] = wn[j][q];
+    load_pieces(wl, (size_t)j * kalloc + ks0 + R + 1, wn[j]);                  // (the packed array carries a spare k-step per group)
+  }
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     const int s = R * NP + p;
@@ -140,8 +139,7 @@ __device__ __forceinline__ void kstep(f32x4 (&acc)[4][K::MW][K::NP], u32x4 (&x)[
     for (int i = 0; i < 6; ++i)
 #pragma unroll
       for (int j = 0; j < MW; ++j)
-        acc[cls][j][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x[s & 1][kXPiece[i]]), __builtin_bit_cast(bf16x8, w[j][kWPiece[i]]),
-                                                                 acc[cls][j][p], 0, 0, 0);
+        acc[cls][j][p] = piece_mfma_16x16x32(i, x[s & 1], w[j], acc[cls][j][p]);
     // the patch's accumulators pass through an empty asm: without it the instruction selector defers the MFMAs of the second channel
     // group of every patch to the end of the chunk and spills the operands they wait for (652 registers in the gfx950 build)
 #pragma unroll
@@ -173,19 +171,14 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
   window_plan<K>(voff, wave, lane, i0 + K::DMIN, j0 - K::PADL, a.Hin, a.Win, plane);
   const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
   const unsigned chunk_bytes = 4u * 16u * (unsigned)plane;
-  auto stage = [&](int chunk) {
-    unsigned vc[K::RPW];
-#pragma unroll
-    for (int i = 0; i < K::RPW; ++i) vc[i] = voff[i] == kOOB ? kOOB : voff[i] + (unsigned)chunk * chunk_bytes;      // (channels >= Cin: out of range = 0)
-    stage_chunk<K>(rs, vc, lds_base, wave, 0u);
-  };
+  const ChunkStage<K> stage{rs, voff, chunk_bytes, lds_base, wave};
 
   // ---- operands: lane (pixel p16 -> (pi, pj) of the 4x4 patch, kq): channel octet kq & 1, tap 2 t + (kq >> 1) of the k-step's class
   const int kq = lane >> 4, p16 = lane & 15, pi = p16 >> 2, pj = p16 & 3;
   const int abase = (kq & 1) * K::PIXO + (4 * wny + pi - K::DMIN) * K::WCP + (4 * NP * wnx + pj) + K::PADL;      // + d_of(ky) * WCP + d_of(kx)
   const bool th = (kq >> 1) != 0;
   const int cg0 = (g * K::WM + wm) * MW;                            // first 16-channel group of this wave
-  const u32x4* wl = a.wp + (size_t)cg0 * a.kalloc * 192 + lane;     // k-step ks, piece q of group cg0 + j: wl[(j kalloc + ks) 192 + 64 q]
+  const u32x4* wl = packed_lane(a.wp, cg0, a.kalloc, lane);         // group cg0 + j, k-step ks: load_pieces(wl, j kalloc + ks, ..)
 
   f32x4 acc[4][MW][NP];
 #pragma unroll
@@ -198,9 +191,7 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
   u32x4 w[MW][3], wn[MW][3];
   stage(0);
 #pragma unroll
-  for (int j = 0; j < MW; ++j)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) wn[j][q] = wl[(size_t)j * a.kalloc * 192 + 64 * q];
+  for (int j = 0; j < MW; ++j) load_pieces(wl, (size_t)j * a.kalloc, wn[j]);
 
   for (int c = 0; c < a.nchunks; ++c) {
     wait_vmcnt<0>();                     // this wave's part of the stage has landed
@@ -216,9 +207,7 @@ __device__ __forceinline__ void tconv_body(const Args& a, int g, int bx, int by,
         float v[8];
 #pragma unroll
         for (int ch = 0; ch < 8; ++ch) v[ch] = s[ch * K::CS];
-        u32x4 h, m, l;
-        split8(v, h, m, l);
-        img[idx] = h; img[K::PIX + idx] = m; img[2 * K::PIX + idx] = l;
+        store_pieces(img + idx, K::PIX, v);
       }
     }
     __syncthreads();                     // the image is whole, the stage is free
@@ -279,10 +268,11 @@ tconv_bf16x3(Args a) {
   tconv_body<K>(a, g, bx, (int)(t % a.ty), (int)(t / a.ty));
 }
 
-// weight [Ct][Cb][KS][KS] (the Convolution's own blob) -> packed [Cb / 16][kalloc][piece][lane][8 bf16]; one thread per (group, k-step, lane)
+// weight [Ct][Cb][KS][KS] (the Convolution's own blob) -> the packed layout of split_bf16.hpp, groups of 16 bottom channels
 template <int KS, int PAD>
 __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ wsrc, u32x4* __restrict__ wp, int Cb, int Ct, int kalloc) {
   using P = Par<KS, PAD>;
+  // (pack_thread's decomposition, written out: through the helper this kernel's code comes out in another order)
   const long long total = (long long)(Cb / 16) * kalloc * 64;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -297,10 +287,10 @@ __global__ void __launch_bounds__(256) pack_weights(const float* __restrict__ ws
     const int ct = 16 * chunk + 8 * (kq & 1) + j;
     v[j] = (real && ct < Ct) ? wsrc[((size_t)ct * Cb + cb) * KS * KS + tap] : 0.f;
   }
-  u32x4 h, m, l;
+  u32x4 h, m, l;                    // (store_pieces, written out: through the helper this kernel allocates other registers)
   split8(v, h, m, l);
-  u32x4* dst = wp + ((size_t)grp * kalloc + ks) * 192 + lane;
-  dst[0] = h; dst[64] = m; dst[128] = l;
+  u32x4* dst = wp + ((size_t)grp * kalloc + ks) * kStepVecs + lane;
+  dst[0] = h; dst[kPieceVecs] = m; dst[2 * kPieceVecs] = l;
 }
 
 template <class K>
@@ -311,12 +301,7 @@ static int launch(const Args& base, hipStream_t st) {
   a.ng = a.Cout / (16 * K::MW * K::WM);
   a.nchunks = cdiv(a.Cin, 16);
   a.kalloc = kalloc_for(a.Cin, K::KST);
-  const long long tiles = (long long)a.N * a.tx * a.ty * a.ng;
-  if (tiles > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "tconv_bf16x3: grid too large");
-  a.total = (unsigned)tiles;
-  set_dynamic_lds_once<&tconv_bf16x3<K>>(K::LDS_BYTES);
-  hipLaunchKernelGGL((tconv_bf16x3<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), K::LDS_BYTES, st, a);
-  return check_launch("tconv_bf16x3");
+  return launch_tiles<&tconv_bf16x3<K>>(a, (long long)a.N * a.tx * a.ty * a.ng, K::THREADS, K::LDS_BYTES, "tconv_bf16x3", "tconv_bf16x3", st);
 }
 
 struct Variant {
@@ -329,9 +314,7 @@ struct Variant {
 // class from the same template, 5 k-steps per chunk -- 335.8 us against the exact kernel's 157.7 at conv4's shape, top_diff [8,512,20,28];
 // profiles/dgrad_bf16x3_bench.md.)
 static const Variant kVariants[] = {FN2_TX_ROW(5, 2, 2, 4, 2, 2, 1) FN2_TX_ROW(5, 2, 2, 4, 2, 1, 2)};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-
-int g_forced_variant = -1;
+FN2_BF16X3_VARIANT_KNOBS(tconv_bf16x3)
 
 static bool variant_applies(const Variant& v, const Args& a, int KS, int pad) {
   return v.ks == KS && v.pad == pad && a.Cout % (16 * v.mw * v.wm) == 0;
@@ -359,19 +342,14 @@ static bool geometry_ok(int Cin, int Hin, int Win, int Cout, int Hout, int Wout,
 
 size_t tconv_bf16x3_packed_floats(int Cb, int Ct, int kernel, int pad) {
   if (Cb <= 0 || Cb % 16 != 0 || Ct <= 0 || kernel != 5 || pad != 2) return 0;
-  return (size_t)(Cb / 16) * tx::kalloc_for(Ct, tx::Par<5, 2>::kst()) * 192 * 4;
+  return bf16x3::packed_floats(Cb / 16, tx::kalloc_for(Ct, tx::Par<5, 2>::kst()));
 }
 
 int tconv_bf16x3_pack_weights(const float* weight, float* packed, int Cb, int Ct, int kernel, int pad, void* stream) {
-  if (!weight || !packed) return fail(FN2_ERR_INVALID_ARG, "tconv_bf16x3_pack_weights: null blob");
-  if (tconv_bf16x3_packed_floats(Cb, Ct, kernel, pad) == 0)
-    return fail(FN2_ERR_UNSUPPORTED, "tconv_bf16x3_pack_weights: needs kernel 5, pad 2 and bottom channels %% 16 == 0 (got k %d p %d, %d)", kernel, pad, Cb);
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) return fail(FN2_ERR_UNSUPPORTED, "tconv_bf16x3_pack_weights: the operand must be 16-byte aligned");
   const int kalloc = tx::kalloc_for(Ct, tx::Par<5, 2>::kst());
-  const long long total = (long long)(Cb / 16) * kalloc * 64;
-  hipLaunchKernelGGL((tx::pack_weights<5, 2>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<tx::u32x4*>(packed), Cb, Ct, kalloc);
-  return check_launch("tconv_bf16x3_pack_weights");
+  return bf16x3::pack_operand("tconv_bf16x3_pack_weights", weight, packed, tconv_bf16x3_packed_floats(Cb, Ct, kernel, pad) != 0, [&] {
+    return fail(FN2_ERR_UNSUPPORTED, "tconv_bf16x3_pack_weights: needs kernel 5, pad 2 and bottom channels %% 16 == 0 (got k %d p %d, %d)", kernel, pad, Cb);
+  }, Cb / 16, kalloc, stream, tx::pack_weights<5, 2>, Cb, Ct, kalloc);
 }
 
 int tconv_bf16x3_masked(const float* top_diff, const float* packed_weight, float* bottom_diff, int N, int Cin, int Hin, int Win, int top_channels, int top_c0,
@@ -396,13 +374,9 @@ int tconv_bf16x3_masked(const float* top_diff, const float* packed_weight, float
   hipStream_t st = as_stream(stream);
   static TuneCache cache("tconv_bf16x3", tx::kNumVariants);
   const TuneKey key{N, Cin, Hin, Win, Cout, Hout, Wout, kernel * 16 + pad, top_channels == Cin, bottom_channels == Cout};
-  mfma::Pick p;
-  if (const int rc = mfma::pick_variant(p, "tconv_bf16x3", tx::g_forced_variant, tx::kNumVariants, false, cache, key, st,
-                                        [&](int i) { return tx::variant_applies(tx::kVariants[i], a, kernel, pad); },
-                                        [&](int i, bool) { return tx::variant_cost(tx::kVariants[i], a); },
-                                        [&](int i, bool) { return tx::kVariants[i].fn(a, st); }, [](int) { return false; }))
-    return rc;
-  return tx::kVariants[p.variant].fn(a, st);
+  return bf16x3::pick_and_run("tconv_bf16x3", tx::g_forced_variant, tx::kNumVariants, cache, key, st,
+                              [&](int i) { return tx::variant_applies(tx::kVariants[i], a, kernel, pad); },
+                              [&](int i) { return tx::variant_cost(tx::kVariants[i], a); }, [&](int i) { return tx::kVariants[i].fn(a, st); });
 }
 
 }  // namespace fn2
@@ -416,6 +390,3 @@ FN2_API int fn2_tconv_bf16x3_supported(const fn2_conv_desc* d, int transposed) {
   const int Ht = (d->Hin + 2 * d->pad - d->kernel) / d->stride + 1, Wt = (d->Win + 2 * d->pad - d->kernel) / d->stride + 1;
   return tx::geometry_ok(d->Cout, Ht, Wt, d->Cin, d->Hin, d->Win, d->kernel, d->pad) ? 1 : 0;
 }
-
-FN2_API int fn2_tconv_bf16x3_num_variants(void) { return tx::kNumVariants; }
-FN2_API int fn2_debug_set_tconv_bf16x3_variant(int v) { tx::g_forced_variant = v; return FN2_OK; }

@@ -202,13 +202,7 @@ static int launch(const Args& base, hipStream_t st) {
   a.tx = cdiv(Wc, K::TW); a.ty = cdiv(Hc, K::TH);
   a.ng = a.Cout / (16 * K::MW * K::WM);
   a.nchunks = cdiv(cdiv(a.Cin, 4), K::CQ);
-  const long long tiles = (long long)a.N * a.tx * a.ty * a.ng;
-  if (tiles > 0x3fffff00ll) return fail(FN2_ERR_UNSUPPORTED, "tconv: grid too large");
-  a.total = (unsigned)tiles;
-  constexpr size_t lds = sizeof(float) * 2 * K::BUF;
-  set_dynamic_lds_once<&tconv_mfma<K>>((int)lds);
-  hipLaunchKernelGGL((tconv_mfma<K>), dim3(8 * ((a.total + 7) / 8)), dim3(K::THREADS), lds, st, a);
-  return check_launch("tconv_forward");
+  return launch_tiles<&tconv_mfma<K>>(a, (long long)a.N * a.tx * a.ty * a.ng, K::THREADS, (int)(sizeof(float) * 2 * K::BUF), "tconv", "tconv_forward", st);
 }
 
 struct Variant {

@@ -6,6 +6,7 @@ reference, resample_layer.hpp:25, downsample_layer.hpp:30) return no gradient.
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import torch
@@ -70,7 +71,7 @@ class _Correlation(torch.autograd.Function):
     def forward(ctx, b0, b1, params):
         ctx.params = params
         ctx.save_for_backward(b0, b1)
-        return ops.correlation_forward(params, b0, b1, bf16x3=_CORR_ARITH[0] == "bf16x3")
+        return ops.correlation_forward(params, b0, b1, bf16x3=_bf16x3("corr"))
 
     @staticmethod
     def backward(ctx, g):
@@ -91,7 +92,7 @@ class _CorrelationReluInto(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, b0, b1, params, blob, c0, slope):
-        ops.correlation_forward(params, b0, b1, out=blob, out_c0=c0, relu=True, negative_slope=slope, bf16x3=_CORR_ARITH[0] == "bf16x3")
+        ops.correlation_forward(params, b0, b1, out=blob, out_c0=c0, relu=True, negative_slope=slope, bf16x3=_bf16x3("corr"))
         tc = ops.correlation_out_shape(params, b0.shape[1], b0.shape[2], b0.shape[3])[0]
         ctx.cfg = (params, c0, tc, slope)
         ctx.save_for_backward(b0, b1, blob)
@@ -118,7 +119,7 @@ def correlation_relu_into(b0, b1, out, out_c0, negative_slope, pad=0, kernel_siz
             return None
         return _CorrelationReluInto.apply(b0.contiguous(), b1.contiguous(), p, out, out_c0, negative_slope)
     return ops.correlation_forward(p, b0.contiguous(), b1.contiguous(), out=out, out_c0=out_c0, relu=True, negative_slope=negative_slope,
-                                   bf16x3=_CORR_ARITH[0] == "bf16x3")
+                                   bf16x3=_bf16x3("corr"))
 
 
 class _FlowWarp(torch.autograd.Function):
@@ -431,131 +432,146 @@ def set_route_force(on: bool = True):
     _ROUTE_FORCE[0] = bool(on)
 
 
+# The opt-in split-bf16 ("bf16x3") arithmetics: one switch per kernel family, each of its own.  "fp32" (exact fp32 products) is the default
+# of every one; "bf16x3" (six bf16 piece products per multiply, fp32 accumulation: include/flownet2_hip.h, FN2_CONV_ARITH_BF16X3) moves
+# only the layers the family's route function hands to that kernel, every other layer and every other pass stays exact fp32.
+#   key          the script flag is --<key>-arith
+#   env          the environment variable that sets the initial value (read once, below; a bad value raises there)
+#   setter, getter   the public functions of this module
+#   what         the switch's name in the setter's ValueError
+#   of           "arithmetic of the <of>" in a script's help;  report: "<report> arithmetic: ..." in a script's output
+#   covers       what bf16x3 moves
+ArithSwitch = collections.namedtuple("ArithSwitch", "key env setter getter what of report covers")
+ARITH_SWITCHES = (
+    ArithSwitch("conv", "FN2_CONV_ARITH", "set_conv_arithmetic", "conv_arithmetic", "conv", "convolution forward", "convolution forward",
+                "split-bf16 on the direct 5x5 / 2 layers"),
+    ArithSwitch("deconv", "FN2_DECONV_ARITH", "set_deconv_arithmetic", "deconv_arithmetic", "deconv", "deconvolution forward", "deconvolution forward",
+                "split-bf16 in the GEMM of the 4x4 / 2 layers"),
+    ArithSwitch("wino", "FN2_WINO_ARITH", "set_winograd_arithmetic", "winograd_arithmetic", "winograd", "Winograd 3x3 forward", "winograd forward",
+                "split-bf16 on the 3x3 / 1 layers with Cout % 64 == 0"),
+    ArithSwitch("corr", "FN2_CORR_ARITH", "set_correlation_arithmetic", "correlation_arithmetic", "correlation", "correlation forward", "correlation forward",
+                "split-bf16 in the FlowNetC correlation (same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)"),
+    ArithSwitch("dgrad", "FN2_DGRAD_ARITH", "set_conv_backward_arithmetic", "conv_backward_arithmetic", "conv backward", "convolution data gradient",
+                "data-gradient", "split-bf16 on the 5x5 / 2 layers"),
+    ArithSwitch("wgrad", "FN2_WGRAD_ARITH", "set_conv_weight_gradient_arithmetic", "conv_weight_gradient_arithmetic", "conv weight gradient",
+                "convolution weight gradient", "weight-gradient", "split-bf16 on the 5x5 / 2 layers"),
+)
 _CONV_ARITHMETICS = ("fp32", "bf16x3")
-_CONV_ARITH = ["fp32"]
+_ARITH_SWITCH = {s.key: s for s in ARITH_SWITCHES}
+_ARITH = {s.key: "fp32" for s in ARITH_SWITCHES}
+
+
+def _set_arithmetic(key: str, name: str):
+    if name not in _CONV_ARITHMETICS:
+        raise ValueError("%s arithmetic must be one of %s, got %r" % (_ARITH_SWITCH[key].what, ", ".join(_CONV_ARITHMETICS), name))
+    _ARITH[key] = name
+
+
+def arithmetic(key: str) -> str:
+    """The value of the switch `key` of ARITH_SWITCHES: "fp32" or "bf16x3"."""
+    return _ARITH[key]
+
+
+def _bf16x3(key: str) -> bool:
+    return _ARITH[key] == "bf16x3"
+
+
+for _s in ARITH_SWITCHES:
+    if os.environ.get(_s.env):
+        _set_arithmetic(_s.key, os.environ[_s.env])
 
 
 def set_conv_arithmetic(name: str = "fp32"):
-    """Arithmetic of the convolution FORWARD: "fp32" (exact fp32 products, the default) or "bf16x3" -- split-bf16 arithmetic (six bf16 piece
-    products per multiply, fp32 accumulation: include/flownet2_hip.h, FN2_CONV_ARITH_BF16X3) on the layers fn2_conv_route hands to that
-    kernel, the direct 5x5 / 2 layers; every other layer stays exact fp32, and so does every backward route (the data gradient has a
-    switch of its own: set_conv_backward_arithmetic).  Initial value: $FN2_CONV_ARITH."""
-    if name not in _CONV_ARITHMETICS:
-        raise ValueError("conv arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
-    _CONV_ARITH[0] = name
+    """Arithmetic of the convolution FORWARD on the layers fn2_conv_route hands to the split kernel: the direct 5x5 / 2 layers
+    (csrc/conv_bf16x3.hip).  Initial value: $FN2_CONV_ARITH."""
+    _set_arithmetic("conv", name)
 
 
 def conv_arithmetic() -> str:
-    return _CONV_ARITH[0]
-
-
-if os.environ.get("FN2_CONV_ARITH"):
-    set_conv_arithmetic(os.environ["FN2_CONV_ARITH"])
-
-
-_DECONV_ARITH = ["fp32"]
+    return arithmetic("conv")
 
 
 def set_deconv_arithmetic(name: str = "fp32"):
-    """Arithmetic of the Deconvolution{4, 2, 1} FORWARD, a switch of its own beside set_conv_arithmetic: "fp32" (the default) or "bf16x3" --
-    the weight^T x bottom GEMM of the layers fn2_deconv_route hands to the GEMM route in split-bf16 arithmetic (csrc/deconv_bf16x3.hip; the
-    col2im + bias + ReLU pass is unchanged); every other layer, and every backward route, stays exact fp32 (the stride-2 data gradient has
-    a switch of its own: set_conv_backward_arithmetic).  Initial value: $FN2_DECONV_ARITH."""
-    if name not in _CONV_ARITHMETICS:
-        raise ValueError("deconv arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
-    _DECONV_ARITH[0] = name
+    """Arithmetic of the Deconvolution{4, 2, 1} FORWARD: the weight^T x bottom GEMM of the layers fn2_deconv_route hands to the GEMM route
+    (csrc/deconv_bf16x3.hip; the col2im + bias + ReLU pass is unchanged).  Initial value: $FN2_DECONV_ARITH."""
+    _set_arithmetic("deconv", name)
 
 
 def deconv_arithmetic() -> str:
-    return _DECONV_ARITH[0]
-
-
-if os.environ.get("FN2_DECONV_ARITH"):
-    set_deconv_arithmetic(os.environ["FN2_DECONV_ARITH"])
-
-
-_WINO_ARITH = ["fp32"]
+    return arithmetic("deconv")
 
 
 def set_winograd_arithmetic(name: str = "fp32"):
-    """Arithmetic of the Winograd F(2x2, 3x3) FORWARD, a switch of its own beside the other four: "fp32" (the default) or "bf16x3" --
-    split-bf16 arithmetic on the Winograd layers fn2_conv_route hands to that kernel under FN2_ROUTE_WINO_BF16X3 (csrc/conv_wino_bf16x3.hip:
-    3x3 / 1 / 1, Win % 4 == 0, Cout % 64 == 0); every other layer, and every backward route, stays exact fp32.  Initial value:
-    $FN2_WINO_ARITH."""
-    if name not in _CONV_ARITHMETICS:
-        raise ValueError("winograd arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
-    _WINO_ARITH[0] = name
+    """Arithmetic of the Winograd F(2x2, 3x3) FORWARD on the Winograd layers fn2_conv_route hands to the split kernel under
+    FN2_ROUTE_WINO_BF16X3 (csrc/conv_wino_bf16x3.hip: 3x3 / 1 / 1, Win % 4 == 0, Cout % 64 == 0).  Initial value: $FN2_WINO_ARITH."""
+    _set_arithmetic("wino", name)
 
 
-def get_winograd_arithmetic() -> str:
-    return _WINO_ARITH[0]
+def winograd_arithmetic() -> str:
+    return arithmetic("wino")
 
 
-if os.environ.get("FN2_WINO_ARITH"):
-    set_winograd_arithmetic(os.environ["FN2_WINO_ARITH"])
-
-
-_DGRAD_ARITH = ["fp32"]
+get_winograd_arithmetic = winograd_arithmetic          # the name it was introduced under
 
 
 def set_conv_backward_arithmetic(name: str):
-    """Arithmetic of the convolution DATA GRADIENT, a switch of its own beside the three forward ones: "fp32" (the default) or "bf16x3" --
-    split-bf16 arithmetic on the layers fn2_conv_backward_data_route_flags hands to that kernel (csrc/tconv_bf16x3.hip: the stride-2
-    5x5 / 2 / 2 class of the transposed-convolution route, conv2 / conv3 of the encoders, plain and with the ReLU derivative of the layer
-    in front folded in); every other data gradient, every weight and bias gradient and every forward stay as they are.  Initial value:
+    """Arithmetic of the convolution DATA GRADIENT on the layers fn2_conv_backward_data_route_flags hands to the split kernel
+    (csrc/tconv_bf16x3.hip: the stride-2 5x5 / 2 / 2 class of the transposed-convolution route, conv2 / conv3 of the encoders, plain and
+    with the ReLU derivative of the layer in front folded in); every weight and bias gradient stays as it is.  Initial value:
     $FN2_DGRAD_ARITH."""
-    if name not in _CONV_ARITHMETICS:
-        raise ValueError("conv backward arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
-    _DGRAD_ARITH[0] = name
+    _set_arithmetic("dgrad", name)
 
 
 def conv_backward_arithmetic() -> str:
-    return _DGRAD_ARITH[0]
-
-
-if os.environ.get("FN2_DGRAD_ARITH"):
-    set_conv_backward_arithmetic(os.environ["FN2_DGRAD_ARITH"])
-
-
-_WGRAD_ARITH = ["fp32"]
+    return arithmetic("dgrad")
 
 
 def set_conv_weight_gradient_arithmetic(name: str):
-    """Arithmetic of the convolution WEIGHT GRADIENT, a switch of its own beside the other five: "fp32" (the default) or "bf16x3" --
-    split-bf16 arithmetic on the layers fn2_conv_backward_weights_arith hands to that kernel (csrc/conv_wgrad_bf16x3.hip: the 5x5 / 2 / 2
-    class, conv2 / conv3 of the encoders); the stem's fused weight + bias gradient, every Deconvolution, every other weight gradient,
-    every bias and data gradient and every forward stay as they are.  Initial value: $FN2_WGRAD_ARITH."""
-    if name not in _CONV_ARITHMETICS:
-        raise ValueError("conv weight gradient arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
-    _WGRAD_ARITH[0] = name
+    """Arithmetic of the convolution WEIGHT GRADIENT on the layers fn2_conv_backward_weights_arith hands to the split kernel
+    (csrc/conv_wgrad_bf16x3.hip: the 5x5 / 2 / 2 class, conv2 / conv3 of the encoders); the stem's fused weight + bias gradient, every
+    Deconvolution and every bias and data gradient stay as they are.  Initial value: $FN2_WGRAD_ARITH."""
+    _set_arithmetic("wgrad", name)
 
 
 def conv_weight_gradient_arithmetic() -> str:
-    return _WGRAD_ARITH[0]
-
-
-if os.environ.get("FN2_WGRAD_ARITH"):
-    set_conv_weight_gradient_arithmetic(os.environ["FN2_WGRAD_ARITH"])
-
-_CORR_ARITH = ["fp32"]
+    return arithmetic("wgrad")
 
 
 def set_correlation_arithmetic(name: str = "fp32"):
-    """Arithmetic of the Correlation FORWARD, a switch of its own beside set_conv_arithmetic / set_deconv_arithmetic: "fp32" (the default) or
-    "bf16x3" -- split-bf16 arithmetic on the layers fn2_correlation_route hands to that kernel (csrc/correlation_bf16x3.hip: the FlowNetC
-    instance, C % 32 == 0, W % 4 == 0); every other layer, and the backward, stays exact fp32.  Honoured by correlation /
-    correlation_relu_into here and by layers.CorrelationLayer.  Initial value: $FN2_CORR_ARITH."""
-    if name not in _CONV_ARITHMETICS:
-        raise ValueError("correlation arithmetic must be one of %s, got %r" % (", ".join(_CONV_ARITHMETICS), name))
-    _CORR_ARITH[0] = name
+    """Arithmetic of the Correlation FORWARD on the layers fn2_correlation_route hands to the split kernel (csrc/correlation_bf16x3.hip:
+    the FlowNetC instance, C % 32 == 0, W % 4 == 0); the backward stays exact fp32.  Honoured by correlation / correlation_relu_into here
+    and by layers.CorrelationLayer.  Initial value: $FN2_CORR_ARITH."""
+    _set_arithmetic("corr", name)
 
 
 def correlation_arithmetic() -> str:
-    return _CORR_ARITH[0]
+    return arithmetic("corr")
 
 
-if os.environ.get("FN2_CORR_ARITH"):
-    set_correlation_arithmetic(os.environ["FN2_CORR_ARITH"])
+def arithmetic_flags(keys=None):
+    """The script flags of the switches `keys` (default: all): ["--conv-arith", ...]."""
+    return ["--%s-arith" % s.key for s in ARITH_SWITCHES if keys is None or s.key in keys]
+
+
+def add_arithmetic_flags(ap, keys, notes=None):
+    """Adds --<key>-arith for every key of `keys` to the argparse parser `ap`, in that order; notes[key] is appended to that flag's help."""
+    for key in keys:
+        s = _ARITH_SWITCH[key]
+        text = "arithmetic of the %s (default: $%s, else fp32); bf16x3: %s%s" % (s.of, s.env, s.covers, (notes or {}).get(key, ""))
+        ap.add_argument("--%s-arith" % key, choices=list(_CONV_ARITHMETICS), default=None, help=text.replace("%", "%%"))
+
+
+def apply_arithmetic_flags(args, keys):
+    """Sets every switch of `keys` whose flag was given (add_arithmetic_flags) from the parsed arguments."""
+    for key in keys:
+        name = getattr(args, "%s_arith" % key)
+        if name:
+            _set_arithmetic(key, name)
+
+
+def print_arithmetics(keys):
+    for key in keys:
+        print("%s arithmetic: %s" % (_ARITH_SWITCH[key].report, _ARITH[key]))
 
 
 def _channel_slice(x):
@@ -723,7 +739,7 @@ def relu_chain_supported(x_shape, w, stride, pad) -> bool:
     desc = _layer_desc(w, stride, pad, False, x_shape=x_shape)
     if desc is None or not w.is_cuda:
         return False
-    route = ops.conv_backward_data_route(desc, False, bf16x3=_DGRAD_ARITH[0] == "bf16x3")
+    route = ops.conv_backward_data_route(desc, False, bf16x3=_bf16x3("dgrad"))
     return route != 0 and ops.conv_backward_data_masked_supported(desc, False, route)
 
 
@@ -843,7 +859,7 @@ def _own_bwd_weight(d, x, w, stride, pad, transposed):
     xb, x0 = _channel_slice(x)
     db, d0 = _channel_slice(d)
     return ops.conv_backward_weights(xb, db, desc, transposed, out=_grad_slot(w), bottom_c0=x0, top_c0=d0,
-                                     bf16x3=not transposed and _WGRAD_ARITH[0] == "bf16x3")
+                                     bf16x3=not transposed and _bf16x3("wgrad"))
 
 
 # (id(weight tensor), tag) -> (weak reference, _version, packed operand, weight generation), see _cached: the operand of a layer's
@@ -866,7 +882,7 @@ def _own_bwd_data(d, w, stride, pad, transposed, x_shape=None):
     desc = _layer_desc(w, stride, pad, transposed, x_shape=x_shape, d_shape=d.shape)
     if desc is None:
         return None
-    route = ops.conv_backward_data_route(desc, transposed, bf16x3=_DGRAD_ARITH[0] == "bf16x3")
+    route = ops.conv_backward_data_route(desc, transposed, bf16x3=_bf16x3("dgrad"))
     if route == 0:
         return None
     key = (desc.N, desc.Hin, desc.Win)       # the route (and with it the operand's layout) is a function of the layer geometry
@@ -881,7 +897,7 @@ def _own_bwd_data_masked(d, w, stride, pad, x, slope):
     desc = _layer_desc(w, stride, pad, False, x_shape=x.shape)
     if desc is None or not d.is_cuda:
         return None
-    route = ops.conv_backward_data_route(desc, False, bf16x3=_DGRAD_ARITH[0] == "bf16x3")
+    route = ops.conv_backward_data_route(desc, False, bf16x3=_bf16x3("dgrad"))
     if route == 0 or not ops.conv_backward_data_masked_supported(desc, False, route):
         return None
     key = (desc.N, desc.Hin, desc.Win)
@@ -899,7 +915,7 @@ def _needs_grad(*ts):
 def conv_forward_route(desc, act=True, whole_blobs=True) -> int:
     """The own kernel conv_mfma_relu runs this Convolution on (0 = none): the library's choice (fn2_conv_route, csrc/conv_route.cpp: thresholds,
     batch-invariant mode -- the one the Caffe adapter's Convolution gets) minus the layers this module does not serve."""
-    route = ops.conv_forward_route(desc, force=_ROUTE_FORCE[0], bf16x3=_CONV_ARITH[0] == "bf16x3", wino_bf16x3=_WINO_ARITH[0] == "bf16x3")
+    route = ops.conv_forward_route(desc, force=_ROUTE_FORCE[0], bf16x3=_bf16x3("conv"), wino_bf16x3=_bf16x3("wino"))
     stem = route == ops.CONV_ROUTE_STEM
     if route == ops.CONV_ROUTE_HEAD:                      # the predict_flow heads: predict_flow_conv, with an autograd function of its own
         return ops.CONV_ROUTE_NONE
@@ -914,7 +930,7 @@ def deconv_forward_route(desc, act=True) -> int:
     """The own kernel deconv_relu runs this Deconvolution{4, 2, 1} on (0 = none): fn2_deconv_route minus the layers this module does not serve."""
     if not act or desc.Cin < 64:                          # no fused ReLU asked for; fewer than 64 input channels
         return ops.DECONV_ROUTE_NONE
-    route = ops.deconv_forward_route(desc, bf16x3=_DECONV_ARITH[0] == "bf16x3")
+    route = ops.deconv_forward_route(desc, bf16x3=_bf16x3("deconv"))
     return ops.DECONV_ROUTE_NONE if route == ops.DECONV_ROUTE_HEAD else route      # (2 -> 2: upsample_flow_deconv, with an autograd function of its own)
 
 

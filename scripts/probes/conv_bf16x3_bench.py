@@ -6,41 +6,22 @@ ratio, every tile variant of the split kernel on its own, and the largest differ
 
     python scripts/probes/conv_bf16x3_bench.py [--out profiles/conv_bf16x3_bench.md]
 """
-import argparse
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+from bf16x3_probe import LAUNCHES, ROUNDS, alternate, arguments, fmt, variant_rows, write_report  # (puts the repository on sys.path)
 
 import torch  # noqa: E402
 
-from flownet2_amd import _lib, ops  # noqa: E402
+from flownet2_amd import ops  # noqa: E402
 
 LAYERS = {"conv2": (16, 64, 160, 224, 128), "conv3": (16, 128, 80, 112, 256)}          # [N, Cin, H, W] -> Cout, 5x5 / 2 / 2
-ROUNDS, LAUNCHES = 12, 20
 DIRECT, SPLIT = ops.CONV_ROUTE_DIRECT, ops.CONV_ROUTE_DIRECT | ops.CONV_ARITH_BF16X3
 # registers of the build (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950) and dynamic LDS per workgroup of the tile variants
 SPLIT_VARIANTS = [("32x4 px, MW 2 NP 4", 124, 70848), ("16x8 px, MW 2 NP 4", 126, 72896)]
 
 
-def window(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(LAUNCHES):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / LAUNCHES          # us per launch
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles", "conv_bf16x3_bench.md"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("conv_bf16x3_bench: needs the GPU (no fallback: a CPU time says nothing)")
-    L = _lib.lib()
+    a = arguments("conv_bf16x3_bench")
     lines = ["# Direct 5x5 / 2 convolution: exact fp32 against split-bf16 (bf16x3)", "",
              "`scripts/probes/conv_bf16x3_bench.py` on %s: both routes in one process, warmed up, timed alternately with device events, %d windows of "
              "%d launches each; us per launch, median (min .. max)." % (torch.cuda.get_device_name(0), ROUNDS, LAUNCHES), ""]
@@ -56,36 +37,17 @@ def main():
         out = {r: torch.empty((N, Cout, H // 2, W // 2), device="cuda") for r in (DIRECT, SPLIT)}
         packed = {r: ops.conv_pack_weights(w, d, r) for r in (DIRECT, SPLIT)}
         run = {r: (lambda r=r: ops.conv_forward(x, packed[r], b, d, r, False, True, 0.1, out=out[r])) for r in (DIRECT, SPLIT)}
-        for _ in range(3):                                    # warm-up: first launches, variant selection, clocks
-            for r in run:
-                window(run[r])
-        t = {r: [] for r in run}
-        for _ in range(ROUNDS):
-            for r in run:
-                t[r].append(window(run[r]))
+        t = alternate(run)
         med = {r: statistics.median(t[r]) for r in run}
         diff = float((out[DIRECT] - out[SPLIT]).abs().max())
         scale = float(out[DIRECT].abs().max())
-        fmt = lambda v: "%.1f (%.1f .. %.1f)" % (statistics.median(v), min(v), max(v))
         table.append("| %s `[%d,%d,%d,%d] -> %d` | %s | %s | %.3f | %.2e | %.2f |" % (name, N, Cin, H, W, Cout, fmt(t[DIRECT]), fmt(t[SPLIT]),
                                                                                  med[SPLIT] / med[DIRECT], diff, scale))
         verdict.append("%s: bf16x3 is %s than the exact kernel (%.1f against %.1f us, ratio %.3f; the arithmetic floor is 6/16 x 28/25 = 0.42 of the "
                        "exact kernel's matrix time)." % (name, "FASTER" if med[SPLIT] < med[DIRECT] else "NOT faster", med[SPLIT], med[DIRECT], med[SPLIT] / med[DIRECT]))
-        try:
-            for v in range(int(L.fn2_conv_bf16x3_num_variants())):
-                L.fn2_debug_set_conv_bf16x3_variant(v)
-                window(run[SPLIT])
-                tv = [window(run[SPLIT]) for _ in range(4)]
-                label, vgpr, lds = SPLIT_VARIANTS[v] if v < len(SPLIT_VARIANTS) else ("variant %d" % v, 0, 0)
-                per_variant.append("| %s | %d: %s | %d | %d | %s |" % (name, v, label, vgpr, lds, fmt(tv)))
-        finally:
-            L.fn2_debug_set_conv_bf16x3_variant(-1)
+        per_variant += variant_rows("conv_bf16x3", name, run[SPLIT], SPLIT_VARIANTS)
     lines += table + [""] + verdict + ["", "Tile variants of the split kernel, forced one by one (4 windows each):", ""] + per_variant + [""]
-    text = "\n".join(lines)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_report(a.out, lines)
 
 
 if __name__ == "__main__":

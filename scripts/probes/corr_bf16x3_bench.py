@@ -7,13 +7,10 @@ split kernel on its own, the largest difference of the two results.
 
     python scripts/probes/corr_bf16x3_bench.py [--out profiles/corr_bf16x3_bench.md]
 """
-import argparse
 import ctypes as C
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+from bf16x3_probe import LAUNCHES, ROUNDS, alternate, arguments, fmt, variant_rows, write_report  # (puts the repository on sys.path)
 
 import torch  # noqa: E402
 
@@ -21,29 +18,14 @@ from flownet2_amd import _lib, ops  # noqa: E402
 from flownet2_amd._lib import check  # noqa: E402
 
 SHAPES = {"A": (8, 256, 40, 56), "B": (4, 256, 48, 96), "C": (1, 256, 56, 128)}
-ROUNDS, LAUNCHES = 12, 20
 OWN, SPLIT = ops.CORR_ROUTE_OWN, ops.CORR_ROUTE_OWN | ops.CONV_ARITH_BF16X3
 TOPC, WIDE, C0 = 441, 473, 32          # the [conv_redir | corr] blob of FlowNetC: 32 + 441 channels
 # patches per task, waves, registers of the build (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950), dynamic LDS per workgroup, workgroups per CU
 SPLIT_VARIANTS = [("4 patches, 8 waves", 114, 86016, 1), ("2 patches, 4 waves", 150, 61440, 2)]
 
 
-def window(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(LAUNCHES):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / LAUNCHES          # us per launch
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles", "corr_bf16x3_bench.md"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("corr_bf16x3_bench: needs the GPU (no fallback: a CPU time says nothing)")
+    a = arguments("corr_bf16x3_bench")
     L = _lib.lib()
     p = ops.corr_params(20, 1, 20, 1, 2)
     lines = ["# Correlation forward (FlowNetC instance): exact fp32 against split-bf16 (bf16x3)", "",
@@ -69,35 +51,16 @@ def main():
                     check(L.fn2_correlation_forward_routed(C.byref(p), r, ops._ptr(b0), ops._ptr(b1), ops._ptr(top), N, Cc, H, W, ch, c0, relu, C.c_float(slope),
                                                            None, 0, st))
                 run[(form, what)] = call
-        for _ in range(3):                                    # warm-up: first launches, variant selection, clocks
-            for k in run:
-                window(run[k])
-        t = {k: [] for k in run}
-        for _ in range(ROUNDS):
-            for k in run:
-                t[k].append(window(run[k]))
+        t = alternate(run)
         torch.cuda.synchronize()
-        fmt = lambda v: "%.1f (%.1f .. %.1f)" % (statistics.median(v), min(v), max(v))
         for form in ("plain", "fused"):
             e, s = t[(form, "exact")], t[(form, "split")]
             diff = float((outs[(form, "exact")] - outs[(form, "split")]).abs().max())
             table.append("| %s `[%d,%d,%d,%d]` | %s | %s | %s | %.3f | %s | %.2e | %.2f |" % (name, N, Cc, H, W, form, fmt(e), fmt(s), statistics.median(s) / statistics.median(e),
                                                                                        "yes" if max(s) < min(e) else "NO", diff, float(outs[(form, "exact")].abs().max())))
-        try:
-            for v in range(int(L.fn2_correlation_bf16x3_num_variants())):
-                L.fn2_debug_set_correlation_bf16x3_variant(v)
-                window(run[("plain", "split")])
-                tv = [window(run[("plain", "split")]) for _ in range(4)]
-                label, vgpr, lds, wgs = SPLIT_VARIANTS[v] if v < len(SPLIT_VARIANTS) else ("variant %d" % v, 0, 0, 0)
-                per_variant.append("| %s | %d: %s | %d | %d | %d | %s |" % (name, v, label, vgpr, lds, wgs, fmt(tv)))
-        finally:
-            L.fn2_debug_set_correlation_bf16x3_variant(-1)
+        per_variant += variant_rows("correlation_bf16x3", name, run[("plain", "split")], SPLIT_VARIANTS)
     lines += table + ["", "Variants of the split kernel, forced one by one (4 windows each):", ""] + per_variant + [""]
-    text = "\n".join(lines)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_report(a.out, lines)
 
 
 if __name__ == "__main__":

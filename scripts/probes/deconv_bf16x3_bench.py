@@ -9,13 +9,10 @@ Reported: median and spread per launch, the ratios, every tile variant of the sp
 
     python scripts/probes/deconv_bf16x3_bench.py [--out profiles/deconv_bf16x3_bench.md]
 """
-import argparse
 import ctypes as C
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+from bf16x3_probe import LAUNCHES, ROUNDS, alternate, arguments, fmt, variant_rows, write_report  # (puts the repository on sys.path)
 
 import torch  # noqa: E402
 
@@ -23,29 +20,14 @@ from flownet2_amd import _lib, ops  # noqa: E402
 from flownet2_amd._lib import check  # noqa: E402
 
 LAYERS = {"deconv4": (8, 1026, 10, 14, 256), "deconv3": (8, 770, 20, 28, 128), "deconv2": (8, 386, 40, 56, 64)}      # [N, Cin, H, W] -> Cout
-ROUNDS, LAUNCHES = 12, 20
 GEMM, SPLIT = ops.DECONV_ROUTE_GEMM, ops.DECONV_ROUTE_GEMM | ops.CONV_ARITH_BF16X3
 # rows x pixels of the workgroup tile, channels per chunk, registers of the build (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950),
 # dynamic LDS per workgroup, workgroups per CU
 SPLIT_VARIANTS = [("128x128, 64 ch", 236, 49344, 2), ("64x128, 64 ch", 158, 49344, 3), ("128x64, 128 ch", 160, 49536, 3)]
 
 
-def window(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(LAUNCHES):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / LAUNCHES          # us per launch
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles", "deconv_bf16x3_bench.md"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("deconv_bf16x3_bench: needs the GPU (no fallback: a CPU time says nothing)")
+    a = arguments("deconv_bf16x3_bench")
     L = _lib.lib()
     lines = ["# Deconvolution 4x4 / 2 by GEMM + col2im: exact fp32 against split-bf16 (bf16x3) in the GEMM", "",
              "`scripts/probes/deconv_bf16x3_bench.py` on %s: both arithmetics in one process, warmed up, timed alternately with device events, %d windows "
@@ -82,19 +64,12 @@ def main():
                                           C.c_float(0.0), st))
 
         run = {"exact": lambda: whole(GEMM), "split": lambda: whole(SPLIT), "col2im": second_pass, "gemm": exact_gemm}
-        for _ in range(3):                                    # warm-up: first launches, variant selection, clocks
-            for k in run:
-                window(run[k])
-        t = {k: [] for k in run}
-        for _ in range(ROUNDS):
-            for k in run:
-                t[k].append(window(run[k]))
+        t = alternate(run)
         whole(GEMM), whole(SPLIT)
         torch.cuda.synchronize()
         med = {k: statistics.median(t[k]) for k in run}
         diff = float((out[GEMM] - out[SPLIT]).abs().max())
         scale = float(out[GEMM].abs().max())
-        fmt = lambda v: "%.1f (%.1f .. %.1f)" % (statistics.median(v), min(v), max(v))
         apart = max(t["split"]) < min(t["exact"])
         table.append("| %s `[%d,%d,%d,%d] -> %d` | %s | %s | %.3f | %s | %.2e | %.2f |" % (name, N, Cin, H, W, Cout, fmt(t["exact"]), fmt(t["split"]),
                                                                                       med["split"] / med["exact"], "yes" if apart else "NO", diff, scale))
@@ -103,21 +78,9 @@ def main():
         verdict.append("%s: the split route's windows (%.1f .. %.1f us) lie %s the exact route's (%.1f .. %.1f us); ratio of the medians %.3f whole call, %.3f "
                        "GEMM alone (the arithmetic floor is 6/16 = 0.375 of the exact kernel's matrix time)."
                        % (name, min(t["split"]), max(t["split"]), "BELOW" if apart else "NOT below", min(t["exact"]), max(t["exact"]), med["split"] / med["exact"], gs / ge))
-        try:
-            for v in range(int(L.fn2_deconv_bf16x3_num_variants())):
-                L.fn2_debug_set_deconv_bf16x3_variant(v)
-                window(run["split"])
-                tv = [window(run["split"]) for _ in range(4)]
-                label, vgpr, lds, wgs = SPLIT_VARIANTS[v] if v < len(SPLIT_VARIANTS) else ("variant %d" % v, 0, 0, 0)
-                per_variant.append("| %s | %d: %s | %d | %d | %d | %s |" % (name, v, label, vgpr, lds, wgs, fmt(tv)))
-        finally:
-            L.fn2_debug_set_deconv_bf16x3_variant(-1)
+        per_variant += variant_rows("deconv_bf16x3", name, run["split"], SPLIT_VARIANTS)
     lines += table + [""] + parts + [""] + verdict + ["", "Tile variants of the split kernel, forced one by one (4 windows each):", ""] + per_variant + [""]
-    text = "\n".join(lines)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_report(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -11,21 +11,17 @@ The 3x3 / 2 / 1 class of the route (conv4) was instantiated from the same templa
 [8,512,20,28] -> [8,256,40,56]): 335.8 us against the exact kernel's 157.7 us, ratio 2.13 (masked 2.08).  Not faster: the instantiation is
 deleted, the class stays exact under the flag, and NOTE_3X3 below carries the figures into the report.
 """
-import argparse
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+from bf16x3_probe import LAUNCHES, ROUNDS, alternate, arguments, fmt, variant_rows, write_report  # (puts the repository on sys.path)
 
 import torch  # noqa: E402
 
-from flownet2_amd import _lib, ops  # noqa: E402
+from flownet2_amd import ops  # noqa: E402
 
 # the layer's bottom [N, Cin, H, W] and Cout, 5x5 / 2 / 2: top_diff [N, Cout, H / 2, W / 2] -> bottom_diff [N, Cin, H, W]
 LAYERS = {"conv2": (8, 64, 160, 224, 128), "conv3": (8, 128, 80, 112, 256), "conv2, both towers": (16, 64, 160, 224, 128),
           "conv3, both towers": (16, 128, 80, 112, 256)}
-ROUNDS, LAUNCHES = 12, 20
 TCONV = 2                                   # FN2_BWD_ROUTE_TCONV
 SPLIT = TCONV | ops.CONV_ARITH_BF16X3
 # registers of the build (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950) and dynamic LDS per workgroup of the tile variants
@@ -35,30 +31,14 @@ SPLIT_VARIANTS = [("32x4 class positions, MW 2 NP 4", 242, 51456), ("16x8 class 
 NOTE_3X3 = ("The 3x3 / 2 / 1 class of the route (conv4; conv5 and conv6 are not on this route at this size) was instantiated from the same template (5 k-steps per chunk of 16 channels: the 1 / 2 / 2 / 4 taps of the classes in pairs) and measured at conv4's shape, top_diff `[8,512,20,28] -> [8,256,40,56]`: 335.8 us against the exact kernel's 157.7 us plain (ratio 2.13), 337.7 against 162.4 masked (2.08); by tile variant 504.9 / 507.9 us (32x4 / 16x8 class positions) and 339.6 / 337.2 us (16x4 / 8x8).  A map of 20x28 class positions gives 160 - 320 workgroups of 64 channels for 512 slots, and 5 k-steps between two splits of the window do not cover them.  It is NOT faster: the instantiation is deleted and the class stays exact under the flag.")
 
 
-def window(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(LAUNCHES):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / LAUNCHES          # us per launch
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles", "dgrad_bf16x3_bench.md"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("dgrad_bf16x3_bench: needs the GPU (no fallback: a CPU time says nothing)")
-    L = _lib.lib()
+    a = arguments("dgrad_bf16x3_bench")
     lines = ["# Data gradient of the 5x5 / 2 convolutions: exact fp32 against split-bf16 (bf16x3)", "",
              "`scripts/probes/dgrad_bf16x3_bench.py` on %s: both routes in one process, warmed up, timed alternately with device events, %d windows of "
              "%d launches each; us per launch, median (min .. max)." % (torch.cuda.get_device_name(0), ROUNDS, LAUNCHES), ""]
     table = ["| layer | form | exact fp32 (tconv_mfma) | bf16x3 (autotuned pick) | bf16x3 / exact | max abs difference | result scale |", "|---|---|---|---|---|---|---|"]
     per_variant = ["| layer | variant | VGPRs | LDS bytes / workgroup | us per launch |", "|---|---|---|---|---|"]
     verdict = []
-    fmt = lambda v: "%.1f (%.1f .. %.1f)" % (statistics.median(v), min(v), max(v))
     for name, (N, Cin, H, W, Cout) in LAYERS.items():
         d = ops.conv_desc(N, Cin, H, W, Cout, 5, 2, 2)
         assert ops.conv_backward_data_route(d, False, bf16x3=True) == SPLIT and ops.conv_backward_data_route(d, False) == TCONV
@@ -72,13 +52,7 @@ def main():
                  "masked": lambda r: out.__setitem__(r, ops.conv_backward_data_masked(top, packed[r], d, False, r, y, 0.1))}
         for form, call in forms.items():
             run = {r: (lambda r=r: call(r)) for r in (TCONV, SPLIT)}
-            for _ in range(3):                                    # warm-up: first launches, variant selection, clocks
-                for r in run:
-                    window(run[r])
-            t = {r: [] for r in run}
-            for _ in range(ROUNDS):
-                for r in run:
-                    t[r].append(window(run[r]))
+            t = alternate(run)
             med = {r: statistics.median(t[r]) for r in run}
             diff = float((out[TCONV] - out[SPLIT]).abs().max())
             scale = float(out[TCONV].abs().max())
@@ -87,26 +61,10 @@ def main():
             verdict.append("%s, %s: bf16x3 is %s than the exact kernel (%.1f against %.1f us, ratio %.3f; the arithmetic floor is 6/16 x 26/25 = 0.39 of "
                            "the exact kernel's matrix time)." % (name, form, "FASTER" if med[SPLIT] < med[TCONV] else "NOT faster", med[SPLIT], med[TCONV],
                                                                 med[SPLIT] / med[TCONV]))
-        run_split = lambda: forms["plain"](SPLIT)
-        try:
-            for v in range(int(L.fn2_tconv_bf16x3_num_variants())):
-                L.fn2_debug_set_tconv_bf16x3_variant(v)
-                try:
-                    window(run_split)
-                except _lib.Fn2Error:                         # a variant of another geometry class
-                    continue
-                tv = [window(run_split) for _ in range(4)]
-                label, vgpr, lds = SPLIT_VARIANTS[v] if v < len(SPLIT_VARIANTS) else ("variant %d" % v, 0, 0)
-                per_variant.append("| %s | %d: %s | %d | %d | %s |" % (name, v, label, vgpr, lds, fmt(tv)))
-        finally:
-            L.fn2_debug_set_tconv_bf16x3_variant(-1)
+        per_variant += variant_rows("tconv_bf16x3", name, lambda: forms["plain"](SPLIT), SPLIT_VARIANTS)
     lines += table + [""] + verdict + ["", "Tile variants of the split kernel, forced one by one (plain form, 4 windows each):", ""] + per_variant + [""]
     lines += [NOTE_3X3, ""]
-    text = "\n".join(lines)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_report(a.out, lines)
 
 
 if __name__ == "__main__":

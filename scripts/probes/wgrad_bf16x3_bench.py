@@ -10,13 +10,10 @@ ratio, every tile variant of the split kernel on its own, and error / bound of b
 The kernels' own times (K-part kernel and finalize apart) come from a kernel trace of this script in a run of its own
 (--rounds 2 under a profiler); profiles/wgrad_bf16x3_bench.md carries them beside the table this script writes.
 """
-import argparse
 import ctypes as C
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+from bf16x3_probe import LAUNCHES, alternate, arguments, fmt, variant_rows, write_report  # (puts the repository on sys.path)
 
 import torch  # noqa: E402
 
@@ -25,28 +22,12 @@ from flownet2_amd import _lib, ops  # noqa: E402
 # the layer's bottom [N, Cin, H, W] and Cout, 5x5 / 2 / 2: a = top_diff [N, Cout, H / 2, W / 2], b = bottom
 LAYERS = {"conv2, both towers": (16, 64, 160, 224, 128), "conv3, both towers": (16, 128, 80, 112, 256), "conv2": (8, 64, 160, 224, 128),
           "conv3": (8, 128, 80, 112, 256)}
-LAUNCHES = 20
 # registers of the build (hipcc -O3 --save-temps, gfx950: VGPRs + AGPRs) and dynamic LDS per workgroup of the tile variants
 SPLIT_VARIANTS = [("64 x 32 channels, MA 2", "168 + 200", 107008), ("32 x 32 channels, MA 1", "156 + 100", 96768)]
 
 
-def window(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(LAUNCHES):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / LAUNCHES          # us per call
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles", "wgrad_bf16x3_bench.md"))
-    ap.add_argument("--rounds", type=int, default=12)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("wgrad_bf16x3_bench: needs the GPU (no fallback: a CPU time says nothing)")
+    a = arguments("wgrad_bf16x3_bench", rounds=True)
     L = _lib.lib()
     lines = ["# Weight gradient of the 5x5 / 2 convolutions: exact fp32 against split-bf16 (bf16x3)", "",
              "`scripts/probes/wgrad_bf16x3_bench.py` on %s: both kernels in one process, warmed up, timed alternately with device events, %d windows of "
@@ -55,7 +36,6 @@ def main():
              "|---|---|---|---|---|---|---|"]
     per_variant = ["| layer | variant | VGPRs + AGPRs | LDS bytes / workgroup | us per call |", "|---|---|---|---|---|"]
     verdict = []
-    fmt = lambda v: "%.1f (%.1f .. %.1f)" % (statistics.median(v), min(v), max(v))
     for name, (N, Cin, H, W, Cout) in LAYERS.items():
         d = ops.conv_desc(N, Cin, H, W, Cout, 5, 2, 2)
         assert ops.conv_backward_weights_arith(d, False, bf16x3=True) == ops.CONV_ARITH_BF16X3 and ops.conv_backward_weights_arith(d, False) == 0
@@ -65,13 +45,7 @@ def main():
         top = torch.randn(N, Cout, Ht, Wt, device="cuda", generator=g)
         dw = {False: torch.empty(Cout, Cin, 5, 5, device="cuda"), True: torch.empty(Cout, Cin, 5, 5, device="cuda")}
         run = {s: (lambda s=s: ops.conv_backward_weights(x, top, d, False, out=dw[s], bf16x3=s)) for s in (False, True)}
-        for _ in range(3):                                    # warm-up: first launches, clocks
-            for s in run:
-                window(run[s])
-        t = {s: [] for s in run}
-        for _ in range(a.rounds):
-            for s in run:
-                t[s].append(window(run[s]))
+        t = alternate(run, a.rounds)
         med = {s: statistics.median(t[s]) for s in run}
         flops = 2.0 * N * Ht * Wt * Cout * Cin * 25
         # float64 reference of the gradients of 4 x 4 channel pairs, on the device
@@ -85,22 +59,10 @@ def main():
                       flops / med[True] / 1e6, err[False], err[True]))
         verdict.append("%s: bf16x3 is %s than the exact kernel (%.1f against %.1f us per call, ratio %.3f)." %
                        (name, "FASTER" if med[True] < med[False] else "NOT faster", med[True], med[False], med[True] / med[False]))
-        try:
-            for v in range(int(L.fn2_conv_wgrad_bf16x3_num_variants())):
-                L.fn2_debug_set_conv_wgrad_bf16x3_variant(v)
-                window(run[True])
-                tv = [window(run[True]) for _ in range(min(4, a.rounds))]
-                label, regs, lds = SPLIT_VARIANTS[v] if v < len(SPLIT_VARIANTS) else ("variant %d" % v, "?", 0)
-                per_variant.append("| %s | %d: %s | %s | %d | %s |" % (name, v, label, regs, lds, fmt(tv)))
-        finally:
-            L.fn2_debug_set_conv_wgrad_bf16x3_variant(-1)
+        per_variant += variant_rows("conv_wgrad_bf16x3", name, run[True], SPLIT_VARIANTS, min(4, a.rounds))
     lines += table + [""] + verdict + ["", "Tile variants of the split kernel, forced one by one (up to 4 windows each); one workgroup of 4 waves per CU (by LDS) for both:", ""]
     lines += per_variant + [""]
-    text = "\n".join(lines)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_report(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -11,16 +11,13 @@ and a layer with fewer input channels than one k-step (the fusion net's conv0).
 
     python scripts/probes/wino_bf16x3_bench.py [--out profiles/wino_bf16x3_bench.md]
 """
-import argparse
-import os
 import statistics
-import sys
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+from bf16x3_probe import LAUNCHES, ROUNDS, alternate, arguments, fmt, variant_rows, write_report  # (puts the repository on sys.path)
 
 import torch  # noqa: E402
 
-from flownet2_amd import _lib, ops  # noqa: E402
+from flownet2_amd import ops  # noqa: E402
 
 # [N, Cin, H, W] -> Cout, 3x3 / 1 / 1
 LAYERS = {
@@ -28,30 +25,14 @@ LAYERS = {
     "C conv3_1 @4x768x384": (4, 473, 48, 96, 256), "C/S conv4_1 @4x768x384": (4, 512, 24, 48, 512), "S conv3_1 @4x768x384": (4, 256, 48, 96, 256),
     "SD interconv2 @4x768x384": (4, 194, 96, 192, 64), "fusion conv0 @4x768x384": (4, 11, 384, 768, 64),
 }
-ROUNDS, LAUNCHES = 12, 20
 EXACT, SPLIT = ops.CONV_ROUTE_WINOGRAD, ops.CONV_ROUTE_WINOGRAD | ops.CONV_ARITH_BF16X3
 # registers of the build (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950: arch VGPRs + accumulator VGPRs, no spills) and dynamic
 # LDS per workgroup of the tile variants
 SPLIT_VARIANTS = [("16x16 px x 64 channels", "256 + 256", 145408), ("8x32 px x 64 channels", "256 + 256", 124928)]
 
 
-def window(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(LAUNCHES):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / LAUNCHES          # us per launch
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles", "wino_bf16x3_bench.md"))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("wino_bf16x3_bench: needs the GPU (no fallback: a CPU time says nothing)")
-    L = _lib.lib()
+    a = arguments("wino_bf16x3_bench")
     lines = ["# Winograd F(2x2, 3x3) convolution: exact fp32 against split-bf16 (bf16x3)", "",
              "`scripts/probes/wino_bf16x3_bench.py` on %s: both routes in one process, warmed up, timed alternately with device events, %d windows of "
              "%d launches each; us per launch, median (min .. max)." % (torch.cuda.get_device_name(0), ROUNDS, LAUNCHES), ""]
@@ -67,36 +48,17 @@ def main():
         out = {r: torch.empty((N, Cout, H, W), device="cuda") for r in (EXACT, SPLIT)}
         packed = {r: ops.conv_pack_weights(w, d, r) for r in (EXACT, SPLIT)}
         run = {r: (lambda r=r: ops.conv_forward(x, packed[r], b, d, r, False, True, 0.1, out=out[r])) for r in (EXACT, SPLIT)}
-        for _ in range(3):                                    # warm-up: first launches, variant selection, clocks
-            for r in run:
-                window(run[r])
-        t = {r: [] for r in run}
-        for _ in range(ROUNDS):
-            for r in run:
-                t[r].append(window(run[r]))
+        t = alternate(run)
         med = {r: statistics.median(t[r]) for r in run}
         diff = float((out[EXACT] - out[SPLIT]).abs().max())
         scale = float(out[EXACT].abs().max())
-        fmt = lambda v: "%.1f (%.1f .. %.1f)" % (statistics.median(v), min(v), max(v))
         table.append("| %s `[%d,%d,%d,%d] -> %d` | %s | %s | %.3f | %.2e | %.2f |" % (name, N, Cin, H, W, Cout, fmt(t[EXACT]), fmt(t[SPLIT]),
                                                                                  med[SPLIT] / med[EXACT], diff, scale))
         verdict.append("%s: bf16x3 is %s than the exact kernel (%.1f against %.1f us, ratio %.3f)."
                        % (name, "FASTER" if med[SPLIT] < med[EXACT] else "NOT faster", med[SPLIT], med[EXACT], med[SPLIT] / med[EXACT]))
-        try:
-            for v in range(int(L.fn2_conv_wino_bf16x3_num_variants())):
-                L.fn2_debug_set_conv_wino_bf16x3_variant(v)
-                window(run[SPLIT])
-                tv = [window(run[SPLIT]) for _ in range(4)]
-                label, vgpr, lds = SPLIT_VARIANTS[v] if v < len(SPLIT_VARIANTS) else ("variant %d" % v, "?", 0)
-                per_variant.append("| %s | %d: %s | %s | %d | %s |" % (name, v, label, vgpr, lds, fmt(tv)))
-        finally:
-            L.fn2_debug_set_conv_wino_bf16x3_variant(-1)
+        per_variant += variant_rows("conv_wino_bf16x3", name, run[SPLIT], SPLIT_VARIANTS)
     lines += table + [""] + verdict + ["", "Tile variants of the split kernel, forced one by one (4 windows each):", ""] + per_variant + [""]
-    text = "\n".join(lines)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text)
-    print(text)
+    write_report(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -91,9 +91,12 @@ def infer_prototxt(model, template_path, img0, img1, device):
     return n.blobs["predict_flow_final"].data
 
 
+ARITH = ("conv", "deconv", "wino", "corr")          # the switches of functional.ARITH_SWITCHES this script offers, as --<key>-arith
+
+
 def _positionals(argv):
     """Positional arguments of either form: the values of the value-taking options are not positionals."""
-    takes_value = {"--gpu", "--weights", "--net", "--conv-arith", "--deconv-arith", "--wino-arith"}
+    takes_value = {"--gpu", "--weights", "--net", *Fn.arithmetic_flags(ARITH)}
     out, skip = [], False
     for a in argv:
         if skip:
@@ -117,15 +120,7 @@ def main():
         ap.add_argument("--gpu", type=int, default=0)
         ap.add_argument("--verbose", action="store_true")
         ap.add_argument("--no-batch-invariant", action="store_true")
-        ap.add_argument("--conv-arith", choices=["fp32", "bf16x3"], default=None,
-                        help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
-        ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
-                        help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
-        ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
-                        help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0")
-        ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
-                        help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
-                             "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
+        Fn.add_arithmetic_flags(ap, ARITH)
         a = ap.parse_args()
         if not a.caffemodel.startswith("seed:") and not os.path.exists(a.caffemodel):
             raise SystemExit("caffemodel does not exist: " + a.caffemodel)                   # run-flownet.py:20
@@ -137,14 +132,7 @@ def main():
         dev = torch.device("cuda", a.gpu)
         torch.cuda.set_device(dev)
         Fn.set_batch_invariant(not a.no_batch_invariant)
-        if a.conv_arith:
-            Fn.set_conv_arithmetic(a.conv_arith)
-        if a.deconv_arith:
-            Fn.set_deconv_arithmetic(a.deconv_arith)
-        if a.corr_arith:
-            Fn.set_correlation_arithmetic(a.corr_arith)
-        if a.wino_arith:
-            Fn.set_winograd_arithmetic(a.wino_arith)
+        Fn.apply_arithmetic_flags(a, ARITH)
         i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
         flow = infer_prototxt(a.caffemodel, a.deployproto, i0, i1, dev)
         flo.write_flo(a.out, flow[0].cpu().numpy())
@@ -156,15 +144,7 @@ def main():
     ap.add_argument("--weights", default=None)
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection follow the work size (see run_flownet_many.py)")
-    ap.add_argument("--conv-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
-    ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
-    ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0")
-    ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
-                         "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
+    Fn.add_arithmetic_flags(ap, ARITH)
     a = ap.parse_args()
     for f in (a.img0, a.img1):
         if not os.path.exists(f):
@@ -172,14 +152,7 @@ def main():
     dev = torch.device("cuda", a.gpu)
     # same arithmetic as run_flownet_many.py on any batching / sharding of a list: a pair's .flo does not depend on how it was computed
     Fn.set_batch_invariant(not a.no_batch_invariant)
-    if a.conv_arith:
-        Fn.set_conv_arithmetic(a.conv_arith)
-    if a.deconv_arith:
-        Fn.set_deconv_arithmetic(a.deconv_arith)
-    if a.corr_arith:
-        Fn.set_correlation_arithmetic(a.corr_arith)
-    if a.wino_arith:
-        Fn.set_winograd_arithmetic(a.wino_arith)
+    Fn.apply_arithmetic_flags(a, ARITH)
     P, mean = load_params(a.net, a.weights, dev)
     i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
     flow = infer(a.net, P, i0, i1, mean)

@@ -34,6 +34,9 @@ from flownet2_amd import functional as Fn  # noqa: E402
 import run_flownet as RF  # noqa: E402
 
 
+ARITH = ("conv", "deconv", "wino", "corr")          # the switches of functional.ARITH_SWITCHES this script offers, as --<key>-arith
+
+
 def groups_of(entries, batch, read):
     """Yield (entries, img0 [n,3,H,W], img1) groups of at most `batch` consecutive pairs of equal size; every file is read once."""
     pending = None                         # (entry, img0, img1) that closed the previous group
@@ -66,15 +69,7 @@ def main():
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection depend on the batch size (faster library "
                     "calls; a pair's bits then depend on the batch it was computed in)")
     ap.add_argument("--gpu", type=int, default=None, help="device index (default: LOCAL_RANK)")
-    ap.add_argument("--conv-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the convolution forward (default: $FN2_CONV_ARITH, else fp32); bf16x3: split-bf16 on the direct 5x5 / 2 layers")
-    ap.add_argument("--deconv-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the deconvolution forward (default: $FN2_DECONV_ARITH, else fp32); bf16x3: split-bf16 in the GEMM of the 4x4 / 2 layers")
-    ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0")
-    ap.add_argument("--corr-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the correlation forward (default: $FN2_CORR_ARITH, else fp32); bf16x3: split-bf16 in the FlowNetC correlation "
-                         "(same fp64 bound as the exact kernel; measured times: profiles/corr_bf16x3_bench.md)")
+    Fn.add_arithmetic_flags(ap, ARITH)
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -83,14 +78,7 @@ def main():
     dev = torch.device("cuda", a.gpu if a.gpu is not None else int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
     torch.cuda.set_device(dev)
     Fn.set_batch_invariant(not a.no_batch_invariant)
-    if a.conv_arith:
-        Fn.set_conv_arithmetic(a.conv_arith)
-    if a.deconv_arith:
-        Fn.set_deconv_arithmetic(a.deconv_arith)
-    if a.corr_arith:
-        Fn.set_correlation_arithmetic(a.corr_arith)
-    if a.wino_arith:
-        Fn.set_winograd_arithmetic(a.wino_arith)
+    Fn.apply_arithmetic_flags(a, ARITH)
     entries = [l.split() for l in open(a.listfile) if l.strip()]
     mine = parallel.shard(entries)
     P, mean = RF.load_params(a.net, a.weights, dev)

@@ -37,6 +37,9 @@ AUG1 = dict(translate=dict(rand_type="gaussian_bernoulli", mean=0, spread=0.03, 
             zoom=dict(rand_type="gaussian_bernoulli", exp=True, mean=0, spread=0.03, prob=1.0), gamma=dict(rand_type="gaussian_bernoulli", exp=True, mean=0, spread=0.02, prob=1.0))
 
 
+ARITH = ("dgrad", "wgrad", "wino")          # the switches of functional.ARITH_SWITCHES this script offers, as --<key>-arith
+
+
 def synthetic_records(n, H, W, seed=0):
     rng = np.random.default_rng(seed)
     recs = []
@@ -67,19 +70,9 @@ def main():
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--no-prefetch", action="store_true")
     ap.add_argument("--prefetch-thread", action="store_true", help="draw on a background thread instead of a worker process")
-    ap.add_argument("--dgrad-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the convolution data gradient (default: $FN2_DGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
-    ap.add_argument("--wgrad-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the convolution weight gradient (default: $FN2_WGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
-    ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
-                    help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0 (forward only: every gradient stays exact fp32)")
+    Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
     a = ap.parse_args()
-    if a.dgrad_arith:
-        Fn.set_conv_backward_arithmetic(a.dgrad_arith)
-    if a.wgrad_arith:
-        Fn.set_conv_weight_gradient_arithmetic(a.wgrad_arith)
-    if a.wino_arith:
-        Fn.set_winograd_arithmetic(a.wino_arith)
+    Fn.apply_arithmetic_flags(a, ARITH)
     dev = torch.device("cuda")
     B, H, W, ch, cw = a.batch, a.height, a.width, a.crop_height, a.crop_width
     recs = synthetic_records(2 * B, H, W)
@@ -153,9 +146,7 @@ def main():
     print("coefficient draws: %s" % how)
     print("iteration (sum of the stages): %.3f ms" % sum(statistics.median(times[s_]) for s_ in stages))
     if not a.no_train:
-        print("data-gradient arithmetic: %s" % Fn.conv_backward_arithmetic())
-        print("weight-gradient arithmetic: %s" % Fn.conv_weight_gradient_arithmetic())
-        print("winograd forward arithmetic: %s" % Fn.get_winograd_arithmetic())
+        Fn.print_arithmetics(ARITH)
         print("loss %.4f, NaN ground truth kept: %s" % (float(loss), bool(torch.isnan(t_flow[0].data).any())))
 
 

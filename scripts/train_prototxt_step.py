@@ -7,19 +7,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flownet2_amd import functional as Fn, net as fnet, nets, templates
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--dgrad-arith", choices=["fp32", "bf16x3"], default=None,
-                help="arithmetic of the convolution data gradient (default: $FN2_DGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
-ap.add_argument("--wgrad-arith", choices=["fp32", "bf16x3"], default=None,
-                help="arithmetic of the convolution weight gradient (default: $FN2_WGRAD_ARITH, else fp32); bf16x3: split-bf16 on the 5x5 / 2 layers")
-ap.add_argument("--wino-arith", choices=["fp32", "bf16x3"], default=None,
-                help="arithmetic of the Winograd 3x3 forward (default: $FN2_WINO_ARITH, else fp32); bf16x3: split-bf16 on the 3x3 / 1 layers with Cout %% 64 == 0 (forward only: every gradient stays exact fp32)")
+ARITH = ("dgrad", "wgrad", "wino")
+Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
 args = ap.parse_args()
-if args.dgrad_arith:
-    Fn.set_conv_backward_arithmetic(args.dgrad_arith)
-if args.wgrad_arith:
-    Fn.set_conv_weight_gradient_arithmetic(args.wgrad_arith)
-if args.wino_arith:
-    Fn.set_winograd_arithmetic(args.wino_arith)
+Fn.apply_arithmetic_flags(args, ARITH)
 
 N, H, W = 8, 320, 448
 P = {k: v.cuda() for k, v in nets.init_params("C", seed=0).items()}
@@ -56,8 +47,6 @@ def timeit(fn, n=20, warm=8):
 
 
 a, b = timeit(autograd_step), timeit(proto_step)
-print("data-gradient arithmetic: %s" % Fn.conv_backward_arithmetic())
-print("weight-gradient arithmetic: %s" % Fn.conv_weight_gradient_arithmetic())
-print("winograd forward arithmetic: %s" % Fn.get_winograd_arithmetic())
+Fn.print_arithmetics(ARITH)
 print("FlowNetC forward + backward, batch 8 @448x320: nets.py + autograd %.2f ms, prototxt Net.ForwardBackward %.2f ms (losses %.6f / %.6f)"
       % (a, b, float(autograd_step().detach()), float(proto_step())))

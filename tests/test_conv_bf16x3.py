@@ -18,12 +18,11 @@ import torch
 
 from flownet2_amd import Fn2Error, _lib, nets, ops
 from flownet2_amd._lib import check
+from bf16x3_helpers import BIT, F_BF16X3, F_FORCE, forced_variants, host
 from test_conv_backward_routes import dev, flownetc_training_layers, rand, same_bits, scale_of
 from test_conv_forward_routes import DIRECT, FWD, PLANE, SENTINEL, TOL, WINOGRAD, flag_sets, production_layers
 
-BIT = 0x100                         # FN2_CONV_ARITH_BF16X3
 SPLIT = DIRECT | BIT
-F_FORCE, F_BF16X3 = 1, 2            # FN2_ROUTE_*
 # (N, Cin, H, W, Cout), all 5x5 / 2 / 2
 SHAPES = {
     "A": (2, 12, 17, 28, 64),       # the direct-5x5 case: odd H, Cin = 1.5 chunks of 8 channels
@@ -57,10 +56,6 @@ def ref64(x, w, b, relu, slope):
     y = torch.nn.functional.conv2d(torch.from_numpy(x).double(), torch.from_numpy(w).double(), None if b is None else torch.from_numpy(b).double(),
                                    stride=2, padding=2)
     return (torch.nn.functional.leaky_relu(y, slope) if relu else y).numpy()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -258,18 +253,15 @@ def test_reproducible_across_runs_batch_and_variants(name):
         assert same_bits(run(name, packed, x[:1], b, True, 0.1, N=1), batch[:1])
     finally:
         ops.set_batch_invariant(was)
-    nv = int(L.fn2_conv_bf16x3_num_variants())
     ran = 0
-    try:
+    with forced_variants("conv_bf16x3") as (nv, force):
         for v in range(nv):
-            check(L.fn2_debug_set_conv_bf16x3_variant(v))
+            force(v)
             assert same_bits(run(name, packed, x, b, True, 0.1, N=3), batch), v          # (every variant applies: they all block 64 channels)
             ran += 1
-        check(L.fn2_debug_set_conv_bf16x3_variant(nv))
+        force(nv)
         with pytest.raises(Fn2Error):
             run(name, packed, x, b, True, 0.1, N=3)
-    finally:
-        check(L.fn2_debug_set_conv_bf16x3_variant(-1))
     assert ran == nv >= 2
 
 

@@ -17,12 +17,11 @@ import torch
 import ref_torch64
 from flownet2_amd import Fn2Error, _lib, nets, ops
 from flownet2_amd._lib import check
+from bf16x3_helpers import BIT, F_BF16X3, forced_variants, host
 from test_conv_backward_routes import dev, rand, same_bits, scale_of
 
-BIT = 0x100                         # FN2_CONV_ARITH_BF16X3
 NONE, OWN = 0, 1                    # FN2_CORR_ROUTE_*
 SPLIT = OWN | BIT
-F_BF16X3 = 2                        # FN2_ROUTE_BF16X3
 SENTINEL = -12345.0
 FNC = (20, 1, 20, 1, 2)             # pad, kernel_size, max_displacement, stride_1, stride_2 of FlowNetC's layer
 TOPC = 441
@@ -51,10 +50,6 @@ def route(p, shape, flags=0):
 
 def supported(p, shape):
     return int(_lib.lib().fn2_correlation_bf16x3_supported(C.byref(p), *[int(v) for v in shape]))
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def routed(p, r, b0, b1, top, shape, top_ch=0, top_c0=0, relu=0, slope=0.0):
@@ -291,19 +286,16 @@ def test_reproducible_across_runs_batch_and_variants(name):
     batch = run(b0, b1, relu=True, slope=0.1)
     assert same_bits(run(b0, b1, relu=True, slope=0.1), batch)
     assert same_bits(run(b0[:1], b1[:1], relu=True, slope=0.1), batch[:1])
-    nv = int(L.fn2_correlation_bf16x3_num_variants())
     ran = 0
-    try:
+    with forced_variants("correlation_bf16x3") as (nv, force):
         for v in range(nv):
-            check(L.fn2_debug_set_correlation_bf16x3_variant(v))
+            force(v)
             assert same_bits(run(b0, b1, relu=True, slope=0.1), batch), v
             assert same_bits(run(b0[:1], b1[:1], relu=True, slope=0.1), batch[:1]), v
             ran += 1
-        check(L.fn2_debug_set_correlation_bf16x3_variant(nv))
+        force(nv)
         with pytest.raises(Fn2Error):
             run(b0, b1, relu=True, slope=0.1)
-    finally:
-        check(L.fn2_debug_set_correlation_bf16x3_variant(-1))
     assert ran == nv >= 1
     assert same_bits(run(b0, b1, relu=True, slope=0.1), batch)
 

@@ -13,12 +13,11 @@ import torch
 
 from flownet2_amd import Fn2Error, _lib, nets, ops
 from flownet2_amd._lib import check
+from bf16x3_helpers import BIT, F_BF16X3, F_FORCE, forced_variants, host
 from test_conv_backward_routes import dev, flownetc_training_layers, rand, same_bits, scale_of
 from test_conv_forward_routes import D_GEMM, D_HEAD, D_NONE, D_PLANE, DIRECT, FWD, HEAD, SENTINEL, TOL, flag_sets, production_layers
 
-BIT = 0x100                         # FN2_CONV_ARITH_BF16X3
 SPLIT = D_GEMM | BIT
-F_FORCE, F_BF16X3 = 1, 2            # FN2_ROUTE_*
 # (N, Cin, H, W, Cout), all Deconvolution{4, 2, 1}.  The workgroup tiles are 128 and 64 rows x 128 pixels, a k-step is 32 channels
 SHAPES = {
     "A": (3, 70, 5, 8, 36),         # two k-steps + 6 ragged channels; a 40-pixel plane, smaller than the pixel tile; M = 576 hangs over a 128-row tile
@@ -53,10 +52,6 @@ def ref64(x, w, b, relu, slope):
     y = torch.nn.functional.conv_transpose2d(torch.from_numpy(x).double(), torch.from_numpy(w).double(), None if b is None else torch.from_numpy(b).double(),
                                              stride=2, padding=1)
     return (torch.nn.functional.leaky_relu(y, slope) if relu else y).numpy()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -274,18 +269,15 @@ def test_reproducible_across_runs_batch_and_variants(name):
         assert same_bits(run(name, packed, x[:1], b, True, 0.1, N=1), batch[:1])
     finally:
         ops.set_batch_invariant(was)
-    nv = int(L.fn2_deconv_bf16x3_num_variants())
     ran = 0
-    try:
+    with forced_variants("deconv_bf16x3") as (nv, force):
         for v in range(nv):
-            check(L.fn2_debug_set_deconv_bf16x3_variant(v))
+            force(v)
             assert same_bits(run(name, packed, x, b, True, 0.1, N=3), batch), v
             ran += 1
-        check(L.fn2_debug_set_deconv_bf16x3_variant(nv))
+        force(nv)
         with pytest.raises(Fn2Error):
             run(name, packed, x, b, True, 0.1, N=3)
-    finally:
-        check(L.fn2_debug_set_deconv_bf16x3_variant(-1))
     assert ran == nv >= 2
 
 

@@ -19,12 +19,11 @@ import torch
 
 from flownet2_amd import Fn2Error, _lib, nets, ops
 from flownet2_amd._lib import check
+from bf16x3_helpers import BIT, F_BF16X3, forced_variants, host
 from test_conv_backward_routes import DGRAD, TOL, dev, flownetc_training_layers, rand, same_bits, scale_of
 
 NONE, WINOGRAD, TCONV, PLANE, DIRECT, DECONV_PLANE = 0, 1, 2, 3, 4, 5        # FN2_BWD_ROUTE_*
-BIT = 0x100                         # FN2_CONV_ARITH_BF16X3
 SPLIT = TCONV | BIT
-F_BF16X3 = 2                        # FN2_ROUTE_BF16X3
 SENTINEL = np.float32(-7.25)
 KST = 13                            # k-steps per chunk of 16 top_diff channels: the 9 / 6 / 6 / 4 taps of the four parity classes in pairs
 # convolution descriptors (N, Cin, H, W, Cout), all 5x5 / 2 / 2; top_diff is [N, Cout, Ht, Wt]
@@ -72,10 +71,6 @@ def ref64(top, w, H, W):
     op = (H - (2 * (Ht - 1) + 1), W - (2 * (Wt - 1) + 1))
     return torch.nn.functional.conv_transpose2d(torch.from_numpy(top).double(), torch.from_numpy(w).double(), None, stride=2, padding=2,
                                                 output_padding=op).numpy()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -184,6 +179,7 @@ def test_switch_is_its_own_and_reads_the_environment(monkeypatch):
     try:
         Fn.set_conv_backward_arithmetic("bf16x3")
         assert Fn.conv_backward_arithmetic() == "bf16x3" and Fn.conv_arithmetic() == "fp32" and Fn.deconv_arithmetic() == "fp32"
+        assert Fn.arithmetic("dgrad") == Fn.conv_backward_arithmetic() and Fn.winograd_arithmetic() == Fn.get_winograd_arithmetic() == "fp32"
         with pytest.raises(ValueError):
             Fn.set_conv_backward_arithmetic("bf16")
         assert Fn.conv_backward_arithmetic() == "bf16x3"
@@ -413,19 +409,16 @@ def test_reproducible_across_runs_batch_and_variants(name):
         assert same_bits(run(name, packed, top[:1], N=1), batch[:1])
     finally:
         ops.set_batch_invariant(was)
-    nv = int(L.fn2_tconv_bf16x3_num_variants())
     ran = 0
-    try:
+    with forced_variants("tconv_bf16x3") as (nv, force):
         for v in range(nv):
-            check(L.fn2_debug_set_tconv_bf16x3_variant(v))
+            force(v)
             assert same_bits(run(name, packed, top, N=3), batch), v          # (every variant applies: they all block 64 channels)
             assert same_bits(run_masked(name, packed, top, y, 4, 0.1, N=3), masked), v
             ran += 1
-        check(L.fn2_debug_set_tconv_bf16x3_variant(nv))                       # one past the last
+        force(nv)                       # one past the last
         with pytest.raises(Fn2Error):
             run(name, packed, top, N=3)
-    finally:
-        check(L.fn2_debug_set_tconv_bf16x3_variant(-1))
     assert ran == nv >= 2
 
 

@@ -16,10 +16,9 @@ import torch
 
 from flownet2_amd import Fn2Error, _lib, nets, ops
 from flownet2_amd._lib import check
+from bf16x3_helpers import BIT, F_BF16X3, F_FORCE, forced_variants, host
 from test_conv_backward_routes import dev, flownetc_training_layers, rand, same_bits, scale_of
 
-BIT = 0x100                         # FN2_CONV_ARITH_BF16X3
-F_FORCE, F_BF16X3 = 1, 2            # FN2_ROUTE_FORCE, FN2_ROUTE_BF16X3
 SENTINEL = np.float32(-7.25)
 CHUNK = 8                           # pixels of a row per chunk (= per k-step), every tile variant
 # convolution descriptors (N, Cin, H, W, Cout), all 5x5 / 2 / 2; a = top_diff [N, Cout, Ht, Wt], b = bottom [N, Cin, H, W]
@@ -56,10 +55,6 @@ def supported(d, tr=0):
 
 def ksplit(d):
     return int(_lib.lib().fn2_conv_wgrad_bf16x3_ksplit(C.byref(d), 0))
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -133,6 +128,7 @@ def test_switch_is_its_own_and_reads_the_environment():
         Fn.set_conv_weight_gradient_arithmetic("bf16x3")
         assert Fn.conv_weight_gradient_arithmetic() == "bf16x3" and Fn.conv_backward_arithmetic() == "fp32" and Fn.conv_arithmetic() == "fp32"
         assert Fn.deconv_arithmetic() == "fp32"
+        assert Fn.arithmetic("wgrad") == Fn.conv_weight_gradient_arithmetic() and Fn.winograd_arithmetic() == Fn.get_winograd_arithmetic() == "fp32"
         with pytest.raises(ValueError):
             Fn.set_conv_weight_gradient_arithmetic("bf16")
         assert Fn.conv_weight_gradient_arithmetic() == "bf16x3"
@@ -292,21 +288,18 @@ def test_reproducible_across_runs_and_variants(name):
     base = run(name, xb, gb)
     assert same_bits(run(name, xb, gb), base)
     assert same_bits(run_whole(name, xb[:, B_C0:B_C0 + Cin], gb[:, A_C0:A_C0 + Cout]), base)          # whole blobs: the same bits
-    nv = int(L.fn2_conv_wgrad_bf16x3_num_variants())
     ran = 0
-    try:
+    with forced_variants("conv_wgrad_bf16x3") as (nv, force):
         for v in range(nv):
-            check(L.fn2_debug_set_conv_wgrad_bf16x3_variant(v))
+            force(v)
             assert same_bits(run(name, xb, gb), base), v
             ran += 1
-        check(L.fn2_debug_set_conv_wgrad_bf16x3_variant(nv))                  # one past the last
+        force(nv)                  # one past the last
         dw = torch.full((Cout, Cin, 5, 5), float(SENTINEL), device="cuda")
         with pytest.raises(Fn2Error):
             ops.conv_backward_weights(dev(xb), dev(gb), desc(name), False, out=dw, bottom_c0=B_C0, top_c0=A_C0, bf16x3=True)
         torch.cuda.synchronize()
         assert bool((dw == float(SENTINEL)).all())
-    finally:
-        check(L.fn2_debug_set_conv_wgrad_bf16x3_variant(-1))
     assert ran == nv >= 2
     assert same_bits(run(name, xb, gb), base)
 

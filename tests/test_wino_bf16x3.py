@@ -30,12 +30,12 @@ import torch
 
 from flownet2_amd import Fn2Error, _lib, nets, ops
 from flownet2_amd._lib import check
+from bf16x3_helpers import BIT, F_BF16X3, F_FORCE, forced_variants, host
 from test_conv_backward_routes import dev, rand, same_bits, scale_of
 from test_conv_forward_routes import DIRECT, FWD, PLANE, SENTINEL, TOL, WINOGRAD, flag_sets, production_layers
 
-BIT = 0x100                                  # FN2_CONV_ARITH_BF16X3
 SPLIT = WINOGRAD | BIT
-F_FORCE, F_BF16X3, F_WINO = 1, 2, 4          # FN2_ROUTE_*
+F_WINO = 4                                   # FN2_ROUTE_WINO_BF16X3
 BOUND = TOL[(False, WINOGRAD)]               # the exact Winograd kernel's own fp64 bound
 # (N, Cin, H, W, Cout), all 3x3 / 1 / 1.  The tile variants are 16x16 and 8x32 output pixels.
 SHAPES = {
@@ -80,10 +80,6 @@ def ref64(x, w, b, relu, slope):
     y = torch.nn.functional.conv2d(torch.from_numpy(x).double(), torch.from_numpy(w).double(), None if b is None else torch.from_numpy(b).double(),
                                    stride=1, padding=1)
     return (torch.nn.functional.leaky_relu(y, slope) if relu else y).numpy()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def inputs(name, N=None):
@@ -309,6 +305,9 @@ def test_switch():
     try:
         Fn.set_winograd_arithmetic("bf16x3")
         assert Fn.get_winograd_arithmetic() == "bf16x3" and others() == before
+        assert Fn.winograd_arithmetic() == Fn.get_winograd_arithmetic() == Fn.arithmetic("wino")          # the regular-named getter, the table's
+        for s in Fn.ARITH_SWITCHES:                         # the names the table gives are the module's functions
+            assert getattr(Fn, s.getter)() == Fn.arithmetic(s.key) and callable(getattr(Fn, s.setter)), s.key
         assert Fn.conv_forward_route(thr) == SPLIT and Fn.conv_forward_route(fwd_desc("direct-5x5")) == DIRECT
         for bad in ("bf16", "fp16", "", "BF16X3"):
             with pytest.raises(ValueError):
@@ -322,6 +321,7 @@ def test_switch():
     finally:
         Fn.set_winograd_arithmetic("fp32")
     assert Fn.get_winograd_arithmetic() == "fp32" and others() == before and Fn.conv_forward_route(thr) == WINOGRAD
+    assert Fn.winograd_arithmetic() == Fn.get_winograd_arithmetic() == Fn.arithmetic("wino")
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
@@ -436,19 +436,16 @@ def test_reproducible_across_runs_batch_and_variants(name):
     assert same_bits(run(name, packed, x, b, True, 0.1, N=3), batch)
     for i in range(3):
         assert same_bits(run(name, pack(name, w, N=1), x[i:i + 1], b, True, 0.1, N=1), batch[i:i + 1]), i
-    nv = int(L.fn2_conv_wino_bf16x3_num_variants())
     ran = 0
-    try:
+    with forced_variants("conv_wino_bf16x3") as (nv, force):
         for v in range(nv):
-            check(L.fn2_debug_set_conv_wino_bf16x3_variant(v))
+            force(v)
             assert same_bits(run(name, packed, x, b, True, 0.1, N=3), batch), v
             assert same_bits(run(name, packed, x[:1], b, True, 0.1, N=1), batch[:1]), v
             ran += 1
-        check(L.fn2_debug_set_conv_wino_bf16x3_variant(nv))
+        force(nv)
         with pytest.raises(Fn2Error):
             run(name, packed, x, b, True, 0.1, N=3)
-    finally:
-        check(L.fn2_debug_set_conv_wino_bf16x3_variant(-1))
     assert ran == nv >= 2
 
 
