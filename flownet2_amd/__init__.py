@@ -4,8 +4,18 @@ csrc/      hand-written HIP kernels + the C ABI (include/flownet2_hip.h) -> libf
 _lib/ops   ctypes binding (no fallback: a missing library raises)
 layers     host-side mirror of the reference's Caffe Layer<Dtype> / LayerRegistry interface
 functional torch.autograd glue,  nets: FlowNetC/S graphs,  flo: .flo I/O
+solver     SolverParameter, Solver (SGDSolver / AdamSolver, get_solver) and CaffeOptimizer on the one-launch HIP update
 """
 from . import _lib  # noqa: F401
 from ._lib import Fn2Error, version  # noqa: F401
 
-__all__ = ["Fn2Error", "version"]
+_SOLVER_EXPORTS = ("SolverParameter", "Solver", "SGDSolver", "AdamSolver", "get_solver", "CaffeOptimizer")
+__all__ = ["Fn2Error", "version", *_SOLVER_EXPORTS]
+
+
+def __getattr__(name):
+    # the solver's names, resolved on first use: importing the package alone still loads neither torch nor the operator modules
+    if name in _SOLVER_EXPORTS:
+        from . import solver
+        return getattr(solver, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

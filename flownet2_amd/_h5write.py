@@ -4,7 +4,8 @@ What libhdf5 1.8 / 1.10 produce with default libver bounds for Net::ToHDF5 (src/
 version-1 object headers, groups as Symbol Table message -> version-1 B-tree (one level-0 node) -> symbol-table nodes + local heap,
 datasets as dataspace v1 + IEEE float32 datatype + contiguous layout v3.  Written from the HDF5 File Format Specification; checked by
 tests/test_hdf5.py against libhdf5 itself where one is installed (the build container's /opt/conda/lib) and against this package's
-reader everywhere.  Limits: <= 256 links per group (32 symbol-table nodes x 8 entries under one B-tree node), float32 only."""
+reader everywhere.  Limits: <= 256 links per group (32 symbol-table nodes x 8 entries under one B-tree node), float32 arrays, and
+-- for SGDSolver::SnapshotSolverStateToHDF5 (sgd_solver.cpp:279-302) -- one-element int32 datasets (IntScalar / numpy.int32 leaves)."""
 from __future__ import annotations
 
 import struct
@@ -15,6 +16,10 @@ import numpy as np
 UNDEF = 0xFFFFFFFFFFFFFFFF
 LEAF_K, INTERNAL_K = 4, 16                   # libhdf5 defaults: 2 * LEAF_K entries per symbol-table node, 2 * INTERNAL_K children per B-tree node
 Tree = Dict[str, Union["Tree", np.ndarray]]
+
+
+class IntScalar(int):
+    """A leaf that is written as a one-element int32 dataset (a solver state's `iter` / `current_step`); so is a numpy.int32 scalar."""
 
 
 def _pad8(b: bytes) -> bytes:
@@ -41,7 +46,18 @@ class _File:
         self.buf += data
         return at
 
+    def int_scalar(self, value: int) -> int:
+        """hdf5_save_int (util/hdf5.cpp:158-164: H5LTmake_dataset_int with rank 1, dims {1}): one little-endian signed 32-bit integer."""
+        addr = self.alloc(struct.pack("<i", int(value)))
+        space = struct.pack("<BBB5x", 1, 1, 0) + struct.pack("<Q", 1)
+        # class 0 (fixed point) version 1; bit field: little-endian, signed (bit 3); bit offset 0, precision 32
+        dtype = struct.pack("<BBBBI", 0x10, 0x08, 0x00, 0x00, 4) + struct.pack("<HH", 0, 32)
+        layout = struct.pack("<BBQQ", 3, 1, addr, 4)
+        return self.alloc(_object_header([_msg(0x01, space), _msg(0x03, dtype), _msg(0x08, layout)]))
+
     def dataset(self, a: np.ndarray) -> int:
+        if isinstance(a, (np.int32, IntScalar)):
+            return self.int_scalar(int(a))
         a = np.ascontiguousarray(a, dtype="<f4")
         raw = a.tobytes()
         addr = self.alloc(raw) if raw else UNDEF

@@ -113,7 +113,27 @@ class L1LossScale(C.Structure):
                 ("N", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("loss_weight", C.c_float)]
 
 
+class SolverBlob(C.Structure):
+    """fn2_solver_blob (include/flownet2_hip_solver.h)."""
+    _fields_ = [("data", C.c_void_p), ("diff", C.c_void_p), ("hist0", C.c_void_p), ("hist1", C.c_void_p), ("count", C.c_longlong),
+                ("lr_mult", C.c_float), ("decay_mult", C.c_float)]
+
+
+class SolverParams(C.Structure):
+    """fn2_solver_params (include/flownet2_hip_solver.h)."""
+    _fields_ = [("type", C.c_int), ("regularization", C.c_int), ("momentum", C.c_float), ("momentum2", C.c_float), ("delta", C.c_float),
+                ("weight_decay", C.c_float), ("clip_gradients", C.c_float), ("accum_normalization", C.c_float)]
+
+
+class SolverTableInfo(C.Structure):
+    """fn2_solver_table_info (include/flownet2_hip_solver.h): what the host keeps about a built table."""
+    _fields_ = [("nblobs", C.c_int), ("has_hist1", C.c_int), ("nchunks", C.c_longlong), ("bytes", C.c_size_t)]
+
+
 _lib = None
+
+# include/flownet2_hip_solver.h: the solver update (no CPU twin in the oracle: tests/test_solver_update.py pins it to NumPy float64)
+SOLVER_EXPORTS = ["fn2_solver_table_bytes", "fn2_solver_table_build", "fn2_solver_apply_update"]
 
 # include/flownet2_hip_corr_route.h: the correlation's route query and routed forward (dispatchers: no CPU twin in the oracle)
 CORR_ROUTE_EXPORTS = ["fn2_correlation_route", "fn2_correlation_forward_routed"]
@@ -313,6 +333,10 @@ def lib():
     L.fn2_conv_backward_weights_bias_fused.argtypes = [dp, i]
     L.fn2_conv_backward_weights_bias.argtypes = [dp, i, fp, fp, fp, fp, i, vp, sz, vp]
     L.fn2_conv_backward_bias.argtypes = [fp, i, i, fp, i, i, i, i, i, vp, sz, vp]
+    L.fn2_solver_table_bytes.argtypes = [i, C.POINTER(SolverBlob)]
+    L.fn2_solver_table_bytes.restype = sz
+    L.fn2_solver_table_build.argtypes = [i, C.POINTER(SolverBlob), vp, sz, C.POINTER(SolverTableInfo), vp]
+    L.fn2_solver_apply_update.argtypes = [C.POINTER(SolverParams), vp, C.POINTER(SolverTableInfo), C.c_float, C.c_float, i, vp]
     if hasattr(L, "fn2_debug_set_correlation_impl"):
         L.fn2_debug_set_correlation_impl.argtypes = [i]
     if hasattr(L, "fn2_debug_correlation_units_plan"):

@@ -19,8 +19,9 @@ runner (scripts/run-flownet.py:64-98), on the layer mirrors of this repository.
     Net::BackwardFromTo  net.cpp:592-602            layers in reverse order, Layer::Backward with the bottom flags
     ClearParamDiffs / Update  net.cpp:949-967, 929-934   parameter diffs are ACCUMULATED by the layers and cleared per iteration
 
-Not reproduced: the Solver (learning-rate policies, momentum / Adam history, snapshots): `Update()` applies the diffs as they are, a caller
-scales them.  One executor-level optimisation: a ReLU that runs in place on the top of the Convolution / Deconvolution directly in front
+The Solver (learning-rate policies, momentum / Adam history, clipping, weight decay, snapshots) is flownet2_amd/solver.py: its ApplyUpdate
+replaces `Update()` with one HIP launch over every learnable blob.  `Update()` itself applies the diffs as they are (a caller has scaled
+them), as Net::Update does.  One executor-level optimisation: a ReLU that runs in place on the top of the Convolution / Deconvolution directly in front
 of it is folded into that layer (one fused kernel, as in nets.py); results are unchanged.
 """
 from __future__ import annotations
@@ -458,7 +459,7 @@ class Net:
 
     def Update(self):
         """Net::Update -> Blob::Update, net.cpp:929-934, blob.cpp:166-188: data -= diff for every learnable parameter (the solver has
-        scaled the diffs by its learning rate before; there is no solver here)."""
+        scaled the diffs by its learning rate before; flownet2_amd.solver.Solver.ApplyUpdate does both in one launch instead)."""
         with torch.no_grad():
             for b in self.learnable_:
                 b.data.sub_(b.mutable_gpu_diff())

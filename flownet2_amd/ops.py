@@ -1176,3 +1176,80 @@ def data_augmentation_forward(p, bottom, coeffs=None, mean=None):
     check(_lib.lib().fn2_data_augmentation_forward(C.byref(p), _ptr(x), C.c_void_p(host.ctypes.data) if host is not None else None, _ptr(m),
                                                    _ptr(top), N, Cc, H, W, _ptr(ws), nws, _stream()))
     return top
+
+
+# ---- solver update (include/flownet2_hip_solver.h, csrc/solver_update.hip) ------------------------------------------------------------
+SOLVER_SGD, SOLVER_ADAM = 0, 1            # FN2_SOLVER_*
+SOLVER_REG_L2, SOLVER_REG_L1 = 0, 1       # FN2_SOLVER_REG_*
+SOLVER_CHUNK = 4096                       # FN2_SOLVER_CHUNK: elements per chunk-list entry (one workgroup each)
+
+
+def solver_params(type=SOLVER_SGD, regularization=SOLVER_REG_L2, momentum=0.0, momentum2=0.999, delta=1e-8, weight_decay=0.0,
+                  clip_gradients=-1.0, accum_normalization=1.0) -> "_lib.SolverParams":
+    return _lib.SolverParams(int(type), int(regularization), float(momentum), float(momentum2), float(delta), float(weight_decay),
+                             float(clip_gradients), float(accum_normalization))
+
+
+def _solver_tensor(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA (HIP) tensor; flownet2_amd has no CPU path")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous float32 tensor, got {t.dtype}, strides {t.stride()}")
+    return t
+
+
+class SolverTable:
+    """The device-resident descriptor table of one set of blobs (fn2_solver_table_build): {data, diff, hist0, hist1, count, lr_mult,
+    decay_mult} per blob, the chunk list and the clip partials, plus the host-side fn2_solver_table_info.  Holds the tensors it points
+    to; `ptrs` are their addresses at build time (`matches()` compares them with the tensors a caller holds now)."""
+
+    def __init__(self, data, diff, hist0, hist1=None, lr_mults=None, decay_mults=None):
+        n = len(data)
+        hist1 = list(hist1) if hist1 is not None else [None] * n
+        if not (len(diff) == len(hist0) == len(hist1) == n):
+            raise ValueError("solver table: data, diff, hist0 and hist1 must list the same number of blobs")
+        lr_mults = [1.0] * n if lr_mults is None else [float(v) for v in lr_mults]
+        decay_mults = [1.0] * n if decay_mults is None else [float(v) for v in decay_mults]
+        if len(lr_mults) != n or len(decay_mults) != n:
+            raise ValueError("solver table: one lr_mult and one decay_mult per blob")
+        blobs = (_lib.SolverBlob * max(1, n))()
+        for k in range(n):
+            w, g, h0 = _solver_tensor(data[k], f"data[{k}]"), _solver_tensor(diff[k], f"diff[{k}]"), _solver_tensor(hist0[k], f"hist0[{k}]")
+            h1 = _solver_tensor(hist1[k], f"hist1[{k}]") if hist1[k] is not None else None
+            for t, name in ((g, "diff"), (h0, "hist0"), (h1, "hist1")):
+                if t is not None and (t.numel() != w.numel() or t.device != w.device):
+                    raise ValueError(f"{name}[{k}]: {t.numel()} values on {t.device}, data[{k}] has {w.numel()} on {w.device}")
+            blobs[k] = _lib.SolverBlob(w.data_ptr(), g.data_ptr(), h0.data_ptr(), h1.data_ptr() if h1 is not None else None, w.numel(),
+                                       lr_mults[k], decay_mults[k])
+        L = _lib.lib()
+        nbytes = L.fn2_solver_table_bytes(n, blobs)
+        if nbytes == 0:
+            check(-1)                                                                   # the library has recorded why
+        self.tensors = (list(data), list(diff), list(hist0), hist1)
+        self.ptrs = self.addresses(*self.tensors)
+        self.nblobs = n
+        self.device = data[0].device
+        self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.info = _lib.SolverTableInfo()
+        with torch.cuda.device(self.device):
+            check(L.fn2_solver_table_build(n, blobs, _ptr(self.buffer), nbytes, C.byref(self.info), _stream()))
+
+    @staticmethod
+    def addresses(data, diff, hist0, hist1=None):
+        hist1 = hist1 if hist1 is not None else [None] * len(data)
+        return tuple(t.data_ptr() if t is not None else 0 for group in (data, diff, hist0, hist1) for t in group)
+
+    def matches(self, data, diff, hist0, hist1=None) -> bool:
+        """Whether the table still describes these tensors (none has moved since the build: no Reshape, no re-assigned .data / .grad)."""
+        return self.addresses(data, diff, hist0, hist1) == self.ptrs
+
+    @property
+    def nchunks(self) -> int:
+        return int(self.info.nchunks)
+
+
+def solver_apply_update(table: SolverTable, params: "_lib.SolverParams", rate: float, correction: float = 1.0, write_update: bool = False):
+    """One fn2_solver_apply_update on the current stream: every blob of `table` in one launch (three with clipping); no host readback."""
+    with torch.cuda.device(table.device):
+        check(_lib.lib().fn2_solver_apply_update(C.byref(params), _ptr(table.buffer), C.byref(table.info), float(rate), float(correction),
+                                                 int(bool(write_update)), _stream()))

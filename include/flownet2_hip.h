@@ -925,6 +925,13 @@ size_t fn2_data_augmentation_workspace_bytes(int N);
 int fn2_data_augmentation_forward(const fn2_data_aug_params* p, const float* bottom, const float* coeffs_host, const float* mean,
                                   float* top, int N, int C, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Solver update  (SGDSolver / AdamSolver ::ApplyUpdate, src/caffe/solvers/sgd_solver.cpp:101-116, adam_solver.cpp:25-89): clip,
+ * normalize, regularize, history update and Net::Update of every learnable blob in one launch over a device-resident table.  The
+ * declarations, the arithmetic and the table scheme are in the included file.
+ * ---------------------------------------------------------------------------------------------- */
+#include "flownet2_hip_solver.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,9 @@ def main():
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--no-prefetch", action="store_true")
     ap.add_argument("--prefetch-thread", action="store_true", help="draw on a background thread instead of a worker process")
+    ap.add_argument("--solver", metavar="PATH", default=None,
+                    help="solver prototxt: step with flownet2_amd.CaffeOptimizer (Caffe's SGD / Adam, lr_policy, weight decay with decay_mult 0 on the "
+                         "biases, clip_gradients) instead of torch.optim.Adam")
     Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
     a = ap.parse_args()
     Fn.apply_arithmetic_flags(a, ARITH)
@@ -88,7 +91,13 @@ def main():
     draw = functools.partial(draw_pair, B=B, W=W, H=H, cw=cw, ch=ch)
     pre = None if a.no_prefetch else augment.CoefficientPrefetcher(draw, depth=4, process=not a.prefetch_thread)
     P = {k: v.to(dev).requires_grad_(True) for k, v in nets.init_params("C", seed=0).items()}
-    opt = torch.optim.Adam(list(P.values()), lr=1e-5, fused=True)
+    if a.solver:
+        from flownet2_amd.solver import CaffeOptimizer, SolverParameter
+        sp = SolverParameter(a.solver)
+        assert sp.iter_size == 1, "this script runs one backward pass per step"
+        opt = CaffeOptimizer(list(P.values()), sp, decay_mults=[0.0 if k.endswith(".b") else 1.0 for k in P])
+    else:
+        opt = torch.optim.Adam(list(P.values()), lr=1e-5, fused=True)
     stages = ["decode", "scale", "draw0 (host)", "augment0", "draw1 (host)", "augment1", "flow_aug", "train step"]
     times = {s: [] for s in stages}
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -128,7 +137,9 @@ def main():
         faug.Forward(bf, t_flow)
         marks[7].record()
         if not a.no_train:
-            opt.zero_grad(set_to_none=True)          # gradients handed over, not zero-filled + accumulated (as bench.py --mode train)
+            # gradients handed over, not zero-filled + accumulated (as bench.py --mode train); with --solver they are zero-filled in place so
+            # that the .grad tensors, and with them the optimizer's device table, stay where they are
+            opt.zero_grad(set_to_none=not a.solver)
             loss = nets.multiscale_loss(nets.flownet_c_core(P, t_img0[0].data, t_img1[0].data, Fn), t_flow[0].data, Fn)
             loss.backward()
             opt.step()
