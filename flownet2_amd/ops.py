@@ -13,9 +13,15 @@ import torch
 from . import _lib
 from ._lib import CorrParams, L1LossParams, check
 
-MULTIPLY, SUBTRACT = 0, 1
-FILL_ZERO, FILL_NAN = 1, 2
-NEAREST, LINEAR, CUBIC, AREA = 1, 2, 3, 4
+
+def _consts(*names):
+    """The values of the headers' FN2_<name> enumerators / #defines (_lib.CONSTANTS), in the order asked for."""
+    return tuple(_lib.CONSTANTS["FN2_" + n] for n in names)
+
+
+MULTIPLY, SUBTRACT = _consts("CORR_MULTIPLY", "CORR_SUBTRACT")
+FILL_ZERO, FILL_NAN = _consts("FILL_ZERO", "FILL_NAN")
+NEAREST, LINEAR, CUBIC, AREA = _consts("RESAMPLE_NEAREST", "RESAMPLE_LINEAR", "RESAMPLE_CUBIC", "RESAMPLE_AREA")
 
 
 def _stream():
@@ -32,8 +38,30 @@ def _chk(t: torch.Tensor, name: str, ndim: int = 4):
     return t.contiguous()
 
 
+def _chk_opt(t, name: str, ndim: int = 4):
+    """_chk of a blob that may be absent (a bias, a second bottom)."""
+    return _chk(t, name, ndim) if t is not None else None
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _top(what: str, out, N, Cc, Ho, Wo, device):
+    """The top blob of a layer: a new [N, Cc, Ho, Wo] one, or `out` (the layer writes a channel slice of it) checked against [N, *, Ho, Wo]."""
+    if out is None:
+        return torch.empty((N, Cc, Ho, Wo), device=device, dtype=torch.float32)
+    _chk(out, "top[0]")
+    if out.shape[0] != N or tuple(out.shape[2:]) != (Ho, Wo):
+        raise ValueError(f"{what}: top blob {tuple(out.shape)} does not match [{N},*,{Ho},{Wo}]")
+    return out
+
+
+def _packed(w, n, pack, *dims):
+    """n floats on w's device, filled by pack(weight, packed, *dims, stream): the operand a kernel reads."""
+    packed = torch.empty(n, device=w.device, dtype=torch.float32)
+    check(pack(_ptr(w), _ptr(packed), *dims, _stream()))
+    return packed
 
 
 def corr_params(pad=0, kernel_size=1, max_displacement=0, stride_1=1, stride_2=1, correlation_type=MULTIPLY, do_abs=False,
@@ -48,7 +76,7 @@ def correlation_out_shape(p: CorrParams, Cc: int, H: int, W: int):
     return tc.value, th.value, tw.value
 
 
-CORR_ROUTE_NONE, CORR_ROUTE_OWN = 0, 1    # FN2_CORR_ROUTE_*: the layer's own dispatch; CONV_ARITH_BF16X3 (below) is the arithmetic bit beside it
+CORR_ROUTE_NONE, CORR_ROUTE_OWN = _consts("CORR_ROUTE_NONE", "CORR_ROUTE_OWN")    # the layer's own dispatch; CONV_ARITH_BF16X3 (below) is the arithmetic bit beside it
 
 
 def correlation_forward_route(p: CorrParams, N: int, Cc: int, H: int, W: int, bf16x3: bool = False) -> int:
@@ -254,7 +282,7 @@ def l1loss_workspace(x: torch.Tensor) -> torch.Tensor:
 def l1loss_forward(p: L1LossParams, bottom0, bottom1=None, workspace=None):
     """Returns (loss [0-axis device tensor], workspace).  workspace[:8] viewed as float32 = {loss, normalize_coeff}."""
     b0 = _chk(bottom0, "bottom[0]")
-    b1 = _chk(bottom1, "bottom[1]") if bottom1 is not None else None
+    b1 = _chk_opt(bottom1, "bottom[1]")
     if b1 is not None and b1.shape != b0.shape:
         raise ValueError("L1Loss: bottom blobs must have the same shape")
     N, Cc, H, W = b0.shape
@@ -266,7 +294,7 @@ def l1loss_forward(p: L1LossParams, bottom0, bottom1=None, workspace=None):
 
 def l1loss_backward(p: L1LossParams, bottom0, bottom1, top_diff: float, workspace):
     b0 = _chk(bottom0, "bottom[0]")
-    b1 = _chk(bottom1, "bottom[1]") if bottom1 is not None else None
+    b1 = _chk_opt(bottom1, "bottom[1]")
     N, Cc, H, W = b0.shape
     d0 = torch.empty_like(b0)
     d1 = torch.empty_like(b0) if b1 is not None else None
@@ -424,7 +452,7 @@ def bias_leaky_relu_(x, bias=None, negative_slope=0.1):
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
         raise ValueError("bias_leaky_relu_: expected a contiguous float32 CUDA (HIP) NCHW tensor")
     N, Cc, H, W = x.shape
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
+    b = _chk_opt(bias, "bias", 1)
     if b is not None and b.numel() != Cc:
         raise ValueError(f"bias must have {Cc} entries, got {b.numel()}")
     check(_lib.lib().fn2_bias_leaky_relu_forward(_ptr(x), _ptr(b), N, Cc, H, W, C.c_float(float(negative_slope)), _stream()))
@@ -442,7 +470,7 @@ def scale_shift_forward(x, scale, shift=None, out=None, out_c0=0):
         _chk(out, "top[0]")
         if out.shape[0] != N or tuple(out.shape[2:]) != (H, W):
             raise ValueError("scale_shift: top blob does not match the bottom")
-    s = _chk(shift, "shift", ndim=1) if shift is not None else None
+    s = _chk_opt(shift, "shift", 1)
     check(_lib.lib().fn2_scale_shift_forward(_ptr(x), _ptr(out), _ptr(s), N, Cc, H, W, out.shape[1], out_c0, C.c_float(float(scale)), _stream()))
     return out
 
@@ -504,8 +532,7 @@ def conv_k7s2_wgrad(top_diff, bottom):
     if tuple(d.shape) != (N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
         raise ValueError(f"conv_k7s2_wgrad: top_diff {tuple(d.shape)} does not belong to a bottom of {tuple(x.shape)}")
     dw = torch.empty((Cout, Cin, 7, 7), device=x.device, dtype=torch.float32)
-    need = int(_lib.lib().fn2_conv_k7s2_wgrad_workspace_bytes(N, Cin, H, W, Cout))
-    ws = _plane_workspace(x.device, need) if need else None
+    ws, need = _scratch(x.device, _lib.lib().fn2_conv_k7s2_wgrad_workspace_bytes(N, Cin, H, W, Cout))
     check(_lib.lib().fn2_conv_k7s2_wgrad(_ptr(d), _ptr(x), _ptr(dw), N, Cin, H, W, Cout, 0, _ptr(ws), need, _stream()))
     return dw
 
@@ -517,17 +544,19 @@ def conv_k7s2_relu_forward(x, weight, bias=None, negative_slope=0.1):
     Cout = w.shape[0]
     if tuple(w.shape) != (Cout, Cin, 7, 7):
         raise ValueError(f"stem weight must be [Cout,{Cin},7,7], got {tuple(w.shape)}")
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
+    b = _chk_opt(bias, "bias", 1)
     out = torch.empty((N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1), device=x.device, dtype=torch.float32)
     check(_lib.lib().fn2_conv_k7s2_relu_forward(_ptr(x), _ptr(w), _ptr(b), _ptr(out), N, Cin, H, W, Cout,
                                                 C.c_float(float(negative_slope)), _stream()))
     return out
 
 
-CONV_ROUTE_NONE, CONV_ROUTE_DIRECT, CONV_ROUTE_WINOGRAD, CONV_ROUTE_PLANE, CONV_ROUTE_STEM, CONV_ROUTE_HEAD = range(6)        # FN2_CONV_ROUTE_*
-DECONV_ROUTE_NONE, DECONV_ROUTE_GEMM, DECONV_ROUTE_PLANE, DECONV_ROUTE_HEAD = range(4)        # FN2_DECONV_ROUTE_*
-ROUTE_FORCE, ROUTE_BF16X3, ROUTE_WINO_BF16X3 = 1, 2, 4          # FN2_ROUTE_*: flags of fn2_conv_route
-CONV_ARITH_BF16X3 = 0x100                 # FN2_CONV_ARITH_BF16X3: split-bf16 arithmetic, a bit beside CONV_ROUTE_DIRECT / CONV_ROUTE_WINOGRAD in the route value (not a route)
+CONV_ROUTE_NONE, CONV_ROUTE_DIRECT, CONV_ROUTE_WINOGRAD, CONV_ROUTE_PLANE, CONV_ROUTE_STEM, CONV_ROUTE_HEAD = _consts(
+    "CONV_ROUTE_NONE", "CONV_ROUTE_DIRECT", "CONV_ROUTE_WINOGRAD", "CONV_ROUTE_PLANE", "CONV_ROUTE_STEM", "CONV_ROUTE_HEAD")
+DECONV_ROUTE_NONE, DECONV_ROUTE_GEMM, DECONV_ROUTE_PLANE, DECONV_ROUTE_HEAD = _consts("DECONV_ROUTE_NONE", "DECONV_ROUTE_GEMM", "DECONV_ROUTE_PLANE",
+                                                                                      "DECONV_ROUTE_HEAD")
+ROUTE_FORCE, ROUTE_BF16X3, ROUTE_WINO_BF16X3 = _consts("ROUTE_FORCE", "ROUTE_BF16X3", "ROUTE_WINO_BF16X3")          # flags of fn2_conv_route
+CONV_ARITH_BF16X3, = _consts("CONV_ARITH_BF16X3")         # split-bf16 arithmetic, a bit beside CONV_ROUTE_DIRECT / CONV_ROUTE_WINOGRAD in the route value (not a route)
 CONV_FWD_ROUTES = {0: None, 1: "direct", 2: "wino", 3: "plane", 4: "stem", 5: "head"}
 DECONV_FWD_ROUTES = {0: None, 1: "gemm", 2: "plane", 3: "head"}
 CONV_ROUTES = {0: None, 1: "direct", 2: "wino", 3: "plane", 4: None, 5: None}     # conv_route(): the three general families only (4 / 5: stem / flow head)
@@ -764,9 +793,7 @@ def conv_mfma_pack_weights(weight):
     n = _lib.lib().fn2_conv_mfma_packed_floats(Cout, Cin, k)
     if k != k2 or n == 0:
         raise ValueError(f"conv_mfma: unsupported weight shape {tuple(w.shape)}")
-    packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_mfma_pack_weights(_ptr(w), _ptr(packed), Cout, Cin, k, _stream()))
-    return packed
+    return _packed(w, n, _lib.lib().fn2_conv_mfma_pack_weights, Cout, Cin, k)
 
 
 def conv_mfma_pack_weights_view(blob, Cout, Cin, kernel, src_cout, src_cin, stride_cout, stride_cin, flip=False):
@@ -782,10 +809,8 @@ def conv_mfma_pack_weights_view(blob, Cout, Cin, kernel, src_cout, src_cin, stri
     last = (src_cout - 1) * stride_cout + (src_cin - 1) * stride_cin + kernel * kernel - 1
     if last >= w.numel():
         raise ValueError("conv_mfma_pack_weights_view: the view reaches beyond the blob")
-    packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_mfma_pack_weights_view(_ptr(w), _ptr(packed), int(Cout), int(Cin), int(kernel), int(src_cout), int(src_cin),
-                                                     int(stride_cout), int(stride_cin), int(bool(flip)), _stream()))
-    return packed
+    return _packed(w, n, _lib.lib().fn2_conv_mfma_pack_weights_view, int(Cout), int(Cin), int(kernel), int(src_cout), int(src_cin),
+                   int(stride_cout), int(stride_cin), int(bool(flip)))
 
 
 def conv_mfma_forward(x, packed_weight, bias, Cout, kernel, stride, pad, relu=True, negative_slope=0.1, out=None, out_c0=0,
@@ -794,15 +819,8 @@ def conv_mfma_forward(x, packed_weight, bias, Cout, kernel, stride, pad, relu=Tr
     x = _chk(x, "bottom[0]")
     N, Ctot, H, W = x.shape
     Cin = Ctot - in_c0 if Cin is None else Cin
-    Ho, Wo = (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1
-    if out is None:
-        out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "top[0]")
-        if out.shape[0] != N or tuple(out.shape[2:]) != (Ho, Wo):
-            raise ValueError(f"conv_mfma: top blob {tuple(out.shape)} does not match [{N},*,{Ho},{Wo}]")
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
-    pw = _chk(packed_weight, "packed weight", ndim=1)
+    out = _top("conv_mfma", out, N, Cout, (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1, x.device)
+    b, pw = _chk_opt(bias, "bias", 1), _chk(packed_weight, "packed weight", ndim=1)
     check(_lib.lib().fn2_conv_mfma_forward(_ptr(x), _ptr(pw), _ptr(b), _ptr(out), N, Cin, H, W, Ctot, in_c0, Cout, out.shape[1], out_c0,
                                            kernel, stride, pad, int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
     return out
@@ -827,9 +845,7 @@ def conv_wino_pack_weights(weight):
     n = _lib.lib().fn2_conv_wino_packed_floats(Cout, Cin)
     if k != 3 or k2 != 3 or n == 0:
         raise ValueError(f"conv_wino: unsupported weight shape {tuple(w.shape)}")
-    packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_wino_pack_weights(_ptr(w), _ptr(packed), Cout, Cin, _stream()))
-    return packed
+    return _packed(w, n, _lib.lib().fn2_conv_wino_pack_weights, Cout, Cin)
 
 
 def conv_wino_forward(x, packed_weight, bias, Cout, pad=1, relu=True, negative_slope=0.1, out=None, out_c0=0, in_c0=0, Cin=None):
@@ -837,15 +853,8 @@ def conv_wino_forward(x, packed_weight, bias, Cout, pad=1, relu=True, negative_s
     x = _chk(x, "bottom[0]")
     N, Ctot, H, W = x.shape
     Cin = Ctot - in_c0 if Cin is None else Cin
-    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-    if out is None:
-        out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "top[0]")
-        if out.shape[0] != N or tuple(out.shape[2:]) != (Ho, Wo):
-            raise ValueError(f"conv_wino: top blob {tuple(out.shape)} does not match [{N},*,{Ho},{Wo}]")
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
-    pw = _chk(packed_weight, "packed weight", ndim=1)
+    out = _top("conv_wino", out, N, Cout, H + 2 * pad - 2, W + 2 * pad - 2, x.device)
+    b, pw = _chk_opt(bias, "bias", 1), _chk(packed_weight, "packed weight", ndim=1)
     check(_lib.lib().fn2_conv_wino_forward(_ptr(x), _ptr(pw), _ptr(b), _ptr(out), N, Cin, H, W, Ctot, in_c0, Cout, out.shape[1], out_c0,
                                            pad, int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
     return out
@@ -876,6 +885,12 @@ def _plane_workspace(device, need):
     return ws
 
 
+def _scratch(device, need):
+    """What a *_workspace_bytes() query answered -> (that much of the per-stream scratch, or None for 0; the bytes as an int)."""
+    need = int(need)
+    return (_plane_workspace(device, need) if need else None), need
+
+
 def conv_plane_k_supported(N, Cin, Hin, Win, Cout, kernel, stride, pad) -> bool:
     return bool(_lib.lib().fn2_conv_plane_k_supported(int(N), int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad)))
 
@@ -890,20 +905,11 @@ def conv_plane_forward(x, packed_weight, bias, Cout, stride, pad, relu=True, neg
     x = _chk(x, "bottom[0]")
     N, Ctot, H, W = x.shape
     Cin = Ctot - in_c0 if Cin is None else Cin
-    Ho, Wo = (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1
-    if out is None:
-        out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "top[0]")
-        if out.shape[0] != N or tuple(out.shape[2:]) != (Ho, Wo):
-            raise ValueError(f"conv_plane: top blob {tuple(out.shape)} does not match [{N},*,{Ho},{Wo}]")
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
-    pw = _chk(packed_weight, "packed weight", ndim=1)
-    need = int(_lib.lib().fn2_conv_plane_k_workspace_bytes(N, Cin, H, W, Cout, kernel, stride, pad))
-    ws = _plane_workspace(x.device, need) if need else None
+    out = _top("conv_plane", out, N, Cout, (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1, x.device)
+    b, pw = _chk_opt(bias, "bias", 1), _chk(packed_weight, "packed weight", ndim=1)
+    ws, need = _scratch(x.device, _lib.lib().fn2_conv_plane_k_workspace_bytes(N, Cin, H, W, Cout, kernel, stride, pad))
     check(_lib.lib().fn2_conv_plane_k_forward(_ptr(x), _ptr(pw), _ptr(b), _ptr(out), N, Cin, H, W, Ctot, in_c0, Cout, out.shape[1], out_c0,
-                                              kernel, stride, pad, int(bool(relu)), C.c_float(float(negative_slope)),
-                                              _ptr(ws if need else None), need, _stream()))
+                                              kernel, stride, pad, int(bool(relu)), C.c_float(float(negative_slope)), _ptr(ws), need, _stream()))
     return out
 
 
@@ -926,14 +932,8 @@ def tconv_forward(x, packed_weight, bias, Cout, kernel, pad, out_hw=None, relu=F
     N, Ctot, H, W = x.shape
     Cin = Ctot - in_c0 if Cin is None else Cin
     Ho, Wo = out_hw if out_hw is not None else (2 * (H - 1) + kernel - 2 * pad, 2 * (W - 1) + kernel - 2 * pad)
-    if out is None:
-        out = torch.empty((N, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "top[0]")
-        if out.shape[0] != N or tuple(out.shape[2:]) != (Ho, Wo):
-            raise ValueError(f"tconv: top blob {tuple(out.shape)} does not match [{N},*,{Ho},{Wo}]")
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
-    pw = _chk(packed_weight, "packed weight", ndim=1)
+    out = _top("tconv", out, N, Cout, Ho, Wo, x.device)
+    b, pw = _chk_opt(bias, "bias", 1), _chk(packed_weight, "packed weight", ndim=1)
     check(_lib.lib().fn2_tconv_forward(_ptr(x), _ptr(pw), _ptr(b), _ptr(out), N, Cin, H, W, Ctot, in_c0, Cout, Ho, Wo, out.shape[1], out_c0,
                                        int(kernel), int(pad), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
     return out
@@ -972,8 +972,7 @@ def conv_wgrad(a, b, kernel, stride, pad, out=None, accumulate=False, a_c0=0, Ca
         out = _chk(out, "weight diff")
         if tuple(out.shape) != (Ca, Cb, kernel, kernel):
             raise ValueError("conv_wgrad: weight diff has the wrong shape")
-    need = int(_lib.lib().fn2_conv_wgrad_workspace_bytes(N, Ca, Ha, Wa, Cb, Hb, Wb, kernel, stride, pad))
-    ws = _plane_workspace(a.device, need) if need else None
+    ws, need = _scratch(a.device, _lib.lib().fn2_conv_wgrad_workspace_bytes(N, Ca, Ha, Wa, Cb, Hb, Wb, kernel, stride, pad))
     check(_lib.lib().fn2_conv_wgrad(_ptr(a), _ptr(b), _ptr(out), N, Ca, Ha, Wa, Atot, a_c0, Cb, Hb, Wb, Btot, b_c0, int(kernel), int(stride), int(pad),
                                     int(bool(accumulate)), _ptr(ws), need, _stream()))
     return out
@@ -996,9 +995,7 @@ def deconv_plane_pack_weights(weight):
     n = _lib.lib().fn2_deconv_plane_packed_floats(Cin, Cout)
     if k not in (3, 4) or k2 != k or n == 0:
         raise ValueError(f"deconv_plane: unsupported weight shape {tuple(w.shape)}")
-    packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    check(_lib.lib().fn2_deconv_plane_pack_weights_k(_ptr(w), _ptr(packed), Cin, Cout, k, _stream()))
-    return packed
+    return _packed(w, n, _lib.lib().fn2_deconv_plane_pack_weights_k, Cin, Cout, k)
 
 
 def deconv_plane_forward(x, packed_weight, bias, Cout, relu=True, negative_slope=0.1, out=None, out_c0=0, in_c0=0, Cin=None):
@@ -1006,18 +1003,11 @@ def deconv_plane_forward(x, packed_weight, bias, Cout, relu=True, negative_slope
     x = _chk(x, "bottom[0]")
     N, Ctot, H, W = x.shape
     Cin = Ctot - in_c0 if Cin is None else Cin
-    if out is None:
-        out = torch.empty((N, Cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "top[0]")
-        if out.shape[0] != N or tuple(out.shape[2:]) != (2 * H, 2 * W):
-            raise ValueError(f"deconv_plane: top blob {tuple(out.shape)} does not match [{N},*,{2 * H},{2 * W}]")
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
-    pw = _chk(packed_weight, "packed weight", ndim=1)
-    need = int(_lib.lib().fn2_deconv_plane_workspace_bytes(N, Cin, H, W, Cout))
-    ws = _plane_workspace(x.device, need) if need else None
+    out = _top("deconv_plane", out, N, Cout, 2 * H, 2 * W, x.device)
+    b, pw = _chk_opt(bias, "bias", 1), _chk(packed_weight, "packed weight", ndim=1)
+    ws, need = _scratch(x.device, _lib.lib().fn2_deconv_plane_workspace_bytes(N, Cin, H, W, Cout))
     check(_lib.lib().fn2_deconv_plane_forward(_ptr(x), _ptr(pw), _ptr(b), _ptr(out), N, Cin, H, W, Ctot, in_c0, Cout, out.shape[1], out_c0,
-                                              int(bool(relu)), C.c_float(float(negative_slope)), _ptr(ws if need else None), need, _stream()))
+                                              int(bool(relu)), C.c_float(float(negative_slope)), _ptr(ws), need, _stream()))
     return out
 
 
@@ -1068,11 +1058,9 @@ def col2im_bias_relu_forward(col, bias, N, Cc, H, W, kernel, pad, stride, relu=T
     Hc, Wc = (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1
     if col.numel() != N * Cc * kernel * kernel * Hc * Wc:
         raise ValueError(f"col2im: column blob has {col.numel()} entries, expected {N * Cc * kernel * kernel * Hc * Wc}")
-    b = _chk(bias, "bias", ndim=1) if bias is not None else None
+    b = _chk_opt(bias, "bias", 1)
     if out is not None:
-        _chk(out, "top[0]")
-        if out.shape[0] != N or tuple(out.shape[2:]) != (H, W):
-            raise ValueError(f"col2im: top blob {tuple(out.shape)} does not match [{N},*,{H},{W}]")
+        _top("col2im", out, N, Cc, H, W, col.device)
         check(_lib.lib().fn2_col2im_bias_relu_forward_into(_ptr(col), _ptr(b), _ptr(out), N, Cc, H, W, int(kernel), int(pad), int(stride),
                                                            int(bool(relu)), C.c_float(float(negative_slope)), out.shape[1], int(out_c0), _stream()))
         return out[:, out_c0:out_c0 + Cc]
@@ -1100,7 +1088,7 @@ def bias_leaky_relu_backward(top_data, top_diff, negative_slope=0.1, need_bias_d
     return d, db
 
 
-AUG_NUM_PARAMS = 42      # AugmentationCoeff fields, caffe.proto:436-486
+AUG_NUM_PARAMS, = _consts("AUG_NUM_PARAMS")      # AugmentationCoeff fields, caffe.proto:436-486
 
 
 def augmentation_matrix(coeffs, crop_width, crop_height, bottom_width, bottom_height, invert=False):
@@ -1136,7 +1124,7 @@ def flow_augmentation_forward(flow, coeffs1, coeffs2, crop_height, crop_width):
     return top
 
 
-MEAN_NONE, MEAN_PER_CHANNEL, MEAN_PER_PIXEL = 0, 1, 2
+MEAN_NONE, MEAN_PER_CHANNEL, MEAN_PER_PIXEL = _consts("MEAN_NONE", "MEAN_PER_CHANNEL", "MEAN_PER_PIXEL")
 
 
 def data_aug_params(crop_width=0, crop_height=0, max_multiplier=255.0, chromatic_eigvec=None, mean_mode=MEAN_NONE, noise_seed=0, noise_stream=0):
@@ -1179,9 +1167,9 @@ def data_augmentation_forward(p, bottom, coeffs=None, mean=None):
 
 
 # ---- solver update (include/flownet2_hip_solver.h, csrc/solver_update.hip) ------------------------------------------------------------
-SOLVER_SGD, SOLVER_ADAM = 0, 1            # FN2_SOLVER_*
-SOLVER_REG_L2, SOLVER_REG_L1 = 0, 1       # FN2_SOLVER_REG_*
-SOLVER_CHUNK = 4096                       # FN2_SOLVER_CHUNK: elements per chunk-list entry (one workgroup each)
+SOLVER_SGD, SOLVER_ADAM = _consts("SOLVER_SGD", "SOLVER_ADAM")
+SOLVER_REG_L2, SOLVER_REG_L1 = _consts("SOLVER_REG_L2", "SOLVER_REG_L1")
+SOLVER_CHUNK, = _consts("SOLVER_CHUNK")   # elements per chunk-list entry (one workgroup each)
 
 
 def solver_params(type=SOLVER_SGD, regularization=SOLVER_REG_L2, momentum=0.0, momentum2=0.999, delta=1e-8, weight_decay=0.0,

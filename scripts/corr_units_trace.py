@@ -7,7 +7,6 @@ import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flownet2_amd import ops, _lib
 L = _lib.lib()
-L.fn2_debug_set_correlation_trace.argtypes = [C.c_void_p]
 shape = tuple(int(v) for v in sys.argv[2].split(",")) if len(sys.argv) > 2 else (8, 256, 40, 56)
 N, Cc, H, W = shape
 g = torch.Generator(device="cuda").manual_seed(0)

@@ -11,7 +11,7 @@ x = torch.randn(N, Cc, H, W, device="cuda", generator=g); y = torch.randn(N, Cc,
 p = ops.corr_params(20, 1, 20, 1, 2)
 out = torch.empty(N, 441, H, W, device="cuda")
 dbg = torch.zeros(4 * 1024 + 4 * 8 * 1024 + 2 * 1024, dtype=torch.int64, device="cuda")
-L = _lib.lib(); L.fn2_debug_set_correlation_trace.argtypes = [C.c_void_p]
+L = _lib.lib()
 for _ in range(50): ops.correlation_forward(p, x, y, out=out)
 L.fn2_debug_set_correlation_trace(C.c_void_p(dbg.data_ptr()))
 ops.correlation_forward(p, x, y, out=out); torch.cuda.synchronize()

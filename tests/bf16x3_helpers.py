@@ -1,11 +1,11 @@
 """What the tests of the split-bf16 ("bf16x3") kernels share: the flag values of include/flownet2_hip.h and the forced-variant loop."""
 import contextlib
 
-from flownet2_amd import _lib
+from flownet2_amd import _lib, ops
 from flownet2_amd._lib import check
 
-BIT = 0x100                         # FN2_CONV_ARITH_BF16X3
-F_FORCE, F_BF16X3 = 1, 2            # FN2_ROUTE_FORCE, FN2_ROUTE_BF16X3
+BIT = ops.CONV_ARITH_BF16X3
+F_FORCE, F_BF16X3 = ops.ROUTE_FORCE, ops.ROUTE_BF16X3
 
 
 def host(t):
