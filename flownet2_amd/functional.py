@@ -592,8 +592,8 @@ def _channel_slice(x):
 class _OwnForwardConv(torch.autograd.Function):
     """Training form of the fused forward kernels: `runner(x, weight, bias)` is one of the own kernels (convolution or
     deconvolution + bias [+ leaky ReLU] in one launch or one GEMM route); the backward undoes the activation and reduces the bias
-    gradient in one fused pass (csrc/bias_act.hip, from the saved OUTPUT) and hands the two convolution gradients to the library
-    (aten::convolution_backward = MIOpen's bwd-data / bwd-weights kernels)."""
+    gradient in one fused pass (csrc/bias_act.hip, from the saved OUTPUT) and computes the two convolution gradients on the own backward
+    routes (conv_backward: fn2_conv_backward_data / _weights; what they decline is the counted library's convolution_backward)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, runner, stride, pad, negative_slope, act, transposed, into=None, relu_chain=None):

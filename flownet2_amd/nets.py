@@ -4,24 +4,25 @@ TOPOLOGY CAVEAT: the prototxt templates are NOT in the reference tree (models/do
 fetches them); the graphs below restate them from the FlowNet / FlowNet2 papers and the layer names
 third-party converters use.  Every topology assumption lives in this file.
 
-The custom layers (Correlation, Resample, FlowWarp, ChannelNorm, L1Loss, Downsample) go through
-`backend` = flownet2_amd.functional (HIP kernels).  Convolution / Deconvolution / ReLU / Eltwise /
-Concat are the stock Caffe layers of the reference (conv_layer.cpp:8-40, deconv_layer.cpp:8-45,
-relu_layer.cu:8-14): dense fp32 contractions executed by MIOpen through torch (conv2d /
-conv_transpose2d); Caffe's weight layouts ([Cout,Cin,kh,kw], deconv [Cin,Cout,kh,kw],
-base_conv_layer.cpp:125-139) are torch's, so .caffemodel blobs load without transposition.
+Every layer goes through `backend`: flownet2_amd.functional (HIP kernels) in the product, oracle.backend or a minimal namespace on the
+host.  Each public entry turns it into a graph_backend.GraphBackend once (backend_of) and the graphs below are written against that adapter
+(`be`): the custom layers (Correlation, Resample, FlowWarp, ChannelNorm, L1Loss, Downsample) by name; Convolution / Deconvolution / ReLU
+(conv_layer.cpp:8-40, deconv_layer.cpp:8-45, relu_layer.cu:8-14) through be.conv / be.deconv / be.predict_flow / be.upsample_flow: the own
+MFMA kernels (functional.conv_mfma_relu / deconv_relu, optionally writing into a channel slice of the consumer's Concat blob), and what
+they decline -- or a backend without them -- on the counted library convolution or plain torch (conv2d / conv_transpose2d).  What a
+backend can do is asked in the adapter alone; listening(fn) sees every layer that ran.  Caffe's weight layouts ([Cout,Cin,kh,kw], deconv
+[Cin,Cout,kh,kw], base_conv_layer.cpp:125-139) are torch's, so .caffemodel blobs load without transposition.
 """
 from __future__ import annotations
 
 import math
-import weakref
+import os
 from typing import Dict, Optional
 
-
 import torch
-import torch.nn.functional as F
 
-NEG_SLOPE = 0.1          # ReLU negative_slope of every FlowNet conv/deconv
+from .graph_backend import NEG_SLOPE, GraphBackend, backend_of, listening  # noqa: F401
+
 FLOW_SCALE = 20.0        # deploy multiplies predict_flow2 by 20 (training divides GT by 20)
 SD_FLOW_SCALE = 0.05     # FlowNet-SD predicts in units of 0.05 px: its deploy branch multiplies by 0.05 (released FlowNet2 graph; flownetsd_flow2 / div_flow in the third-party ports)
 LOSS_WEIGHTS = {6: 0.32, 5: 0.08, 4: 0.02, 3: 0.01, 2: 0.005}   # Appendix B (memory)
@@ -73,46 +74,39 @@ def num_params(params) -> int:
     return sum(int(v.numel()) for v in params.values())
 
 
-def _conv(x, P, name, stride, pad, act=True, backend=None, relu_chain=None):
-    """Convolution (+ ReLU{negative_slope 0.1}).  With a backend that has conv_bias_leaky_relu the library runs the
-    bias-free convolution and bias + activation are one in-place pass (csrc/bias_act.hip) instead of two."""
-    w = P[name + ".w"]
-    if relu_chain is not None:
-        y = conv_forward(x, w, P[name + ".b"], stride, pad, act, backend, relu_chain=relu_chain)
-    else:
-        y = _conv_routed(x, P, name, stride, pad, act, backend)
-    if _TRACE_CONV:
-        print("conv route %-16s in %-22s k%d s%d act=%d -> %s" % (name, tuple(x.shape), w.shape[2], stride, act, _LAST_ROUTE[0]))
-    return y
+def conv_forward(x, w, b, stride, pad, act, backend, slope=None, relu_chain=None):
+    """Convolution{w, stride, pad} + bias (+ ReLU{NEG_SLOPE} when act) on explicit tensors: the call every graph of this file (be.conv) and the
+    Convolution layer of the prototxt executor (flownet2_amd.layers.ConvolutionLayer) share -- same kernels, same bits.  The backend routes
+    (functional.conv_mfma_relu: the library's fn2_conv_route); what it declines is the counted library convolution's."""
+    return backend_of(backend).conv_wb(x, w, b, stride, pad, act, NEG_SLOPE if slope is None else slope, relu_chain=relu_chain)
 
 
-_TRACE_CONV = __import__("os").environ.get("FN2_TRACE_CONV") == "1"
 _LAST_ROUTE = [""]
 
 
-def _conv_routed(x, P, name, stride, pad, act, backend):
-    return conv_forward(x, P[name + ".w"], P[name + ".b"], stride, pad, act, backend)
+def _note_route(name, y, info):
+    """Listener: which kernel a convolution ran on, into _LAST_ROUTE[0]."""
+    if info["kind"] != "conv":
+        return
+    be, x, w = info["backend"], info["x"], info["w"]
+    if not info["own"]:
+        _LAST_ROUTE[0] = "library conv2d"
+    elif be.conv_route_name is None:
+        _LAST_ROUTE[0] = "own kernel"
+    else:
+        _LAST_ROUTE[0] = "fn2 %s" % be.conv_route_name(x.shape, w, info["stride"], info["pad"], info["act"], not info["into"])
 
 
-def conv_forward(x, w, b, stride, pad, act, backend, slope=None, relu_chain=None):
-    """Convolution{w, stride, pad} + bias (+ ReLU{NEG_SLOPE} when act) on explicit tensors: the call every graph of this file and the
-    Convolution layer of the prototxt executor (flownet2_amd.layers.ConvolutionLayer) share -- same kernels, same bits.  The backend routes
-    (functional.conv_mfma_relu: the library's fn2_conv_route); what it declines is the counted library convolution's."""
-    slope = NEG_SLOPE if slope is None else slope
-    y = None
-    if backend is not None and hasattr(backend, "conv_mfma_relu"):
-        y = backend.conv_mfma_relu(x, w, b, stride, pad, slope, act, relu_chain=relu_chain)
-    if y is not None:
-        _LAST_ROUTE[0] = "fn2 %s" % backend.conv_route_name(x.shape, w, stride, pad, act) if _TRACE_CONV and hasattr(backend, "conv_route_name") else "own kernel"
-        return y
-    if relu_chain is not None:
-        raise RuntimeError("relu_chain: no own kernel takes this layer (its consumer was told the stem kernel would)")
-    _LAST_ROUTE[0] = "library conv2d"
-    conv2d = getattr(backend, "lib_conv2d", None) or (lambda xx, ww, bb, s, p: F.conv2d(xx, ww, bb, stride=s, padding=p))
-    if act and backend is not None and hasattr(backend, "conv_bias_leaky_relu"):
-        return backend.conv_bias_leaky_relu(conv2d(x, w, None, stride, pad), b, slope)
-    y = conv2d(x, w, b, stride, pad)
-    return F.leaky_relu(y, slope) if act else y
+def _trace_route(name, y, info):
+    """Listener of FN2_TRACE_CONV=1: one line per convolution."""
+    if info["kind"] == "conv":
+        _note_route(name, y, info)
+        print("conv route %-16s in %-22s k%d s%d act=%d -> %s%s" % (name, tuple(info["x"].shape), info["w"].shape[2], info["stride"], info["act"],
+                                                                  _LAST_ROUTE[0], " (into its Concat blob)" if info["into"] else ""))
+
+
+if os.environ.get("FN2_TRACE_CONV") == "1":
+    listening(_trace_route).__enter__()
 
 
 _CONSTS: Dict[tuple, torch.Tensor] = {}
@@ -127,53 +121,33 @@ def _const(device, values):
     return _CONSTS[key]
 
 
-def _deconv(x, P, name, act=True, backend=None):
-    return deconv_forward(x, P[name + ".w"], P[name + ".b"], act, backend)
-
-
 def deconv_forward(x, w, b, act=True, backend=None, slope=None):
     """Deconvolution{4, 2, 1} + bias (+ ReLU): the call shared with flownet2_amd.layers.DeconvolutionLayer.  The backend routes
     (functional.deconv_relu: the library's fn2_deconv_route); what it declines is the counted library deconvolution's."""
-    slope = NEG_SLOPE if slope is None else slope
-    if backend is not None and hasattr(backend, "deconv_relu"):
-        y = backend.deconv_relu(x, w, b, slope, act)
-        if y is not None:
-            return y
-    deconv2d = getattr(backend, "lib_conv_transpose2d", None) or (lambda xx, ww, bb, s, p: F.conv_transpose2d(xx, ww, bb, stride=s, padding=p))
-    if act and backend is not None and hasattr(backend, "conv_bias_leaky_relu"):
-        return backend.conv_bias_leaky_relu(deconv2d(x, w, None, 2, 1), b, slope)
-    y = deconv2d(x, w, b, 2, 1)
-    return F.leaky_relu(y, slope) if act else y
+    return backend_of(backend).deconv_wb(x, w, b, act, NEG_SLOPE if slope is None else slope)
 
 
-def _conv_into_concat(x, P, name, stride, pad, extra_channels, backend, relu_chain=None):
-    """A convolution whose output is the FIRST input of a Concat (a decoder skip tensor): where the own MFMA kernels apply and no
-    gradient is needed, the Concat blob [N, Cout + extra_channels, H, W] is allocated here and the convolution writes its channels
-    straight into it (ConcatLayer, concat_layer.cu:8-52, becomes a no-op for this input).  Returns (blob or None, the layer's output --
-    a channel-slice view of the blob, or an ordinary tensor)."""
+def _conv_into_concat(x, P, name, stride, pad, extra_channels, be, relu_chain=None):
+    """A convolution whose output is the FIRST input of a Concat (a decoder skip tensor): where an own kernel writes into a channel slice
+    and -- in a training graph -- the backend trains in place, the Concat blob [N, Cout + extra_channels, H, W] is allocated here and the
+    convolution writes its channels straight into it (ConcatLayer, concat_layer.cu:8-52, becomes a no-op for this input).  Returns (blob or
+    None, the layer's output -- a channel-slice view of the blob, or an ordinary tensor)."""
     w = P[name + ".w"]
     # The blob route writes the later Concat inputs in place (deconvolution, upsampled flow).  Without autograd what those calls return is
-    # discarded.  With autograd (round 5, CONCAT_IN_PLACE_TRAINING) every producer is an autograd function whose output is its slice view
-    # of the blob -- a plain buffer outside the graph -- and _ConcatInPlace ties the slices together for the consumer: no Concat copy in a
-    # training step either.
+    # discarded.  With autograd every producer is an autograd function whose output is its slice view of the blob -- a plain buffer outside
+    # the graph -- and _ConcatInPlace ties the slices together for the consumer: no Concat copy in a training step either.
     training = torch.is_grad_enabled() and (x.requires_grad or _any_requires_grad(P))
-    if (backend is not None and hasattr(backend, "conv_mfma_relu") and x.is_cuda and w.shape[2] in (3, 5)
-            and (not training or (CONCAT_IN_PLACE_TRAINING[0] and hasattr(backend, "conv_backward")))):
+    if be.writes_slices and w.shape[2] in (3, 5) and (be.trains_in_place or not training):
         k = w.shape[2]
         ho, wo = (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1
         blob = torch.empty((x.shape[0], w.shape[0] + extra_channels, ho, wo), device=x.device, dtype=x.dtype)
-        y = backend.conv_mfma_relu(x, w, P[name + ".b"], stride, pad, NEG_SLOPE, True, out=blob, out_c0=0, relu_chain=relu_chain)
+        y = be.own_conv(x, w, P[name + ".b"], stride, pad, NEG_SLOPE, True, out=blob, out_c0=0, relu_chain=relu_chain)
         if y is not None:
+            be.wrote("conv", name, y, blob, 0, w.shape[0], x, w, stride, pad)
             return blob, (y if (training and y.requires_grad) else blob[:, :w.shape[0]])
     if relu_chain is not None:
         raise RuntimeError("relu_chain: conv '%s' left the own-kernel route after its producer was told it would fold the ReLU derivative" % name)
-    return None, _conv(x, P, name, stride, pad, backend=backend)
-
-
-def _conv_into(x, P, name, stride, pad, blob, c0, backend):
-    """Convolution + bias + ReLU written into channels [c0, c0 + Cout) of `blob` by the own kernels, as an autograd function when a gradient
-    is needed (the returned slice view carries the graph); None when no own kernel takes the layer."""
-    return backend.conv_mfma_relu(x, P[name + ".w"], P[name + ".b"], stride, pad, NEG_SLOPE, True, out=blob, out_c0=c0)
+    return None, be.conv(x, P, name, stride, pad)
 
 
 def _any_requires_grad(P) -> bool:
@@ -181,109 +155,81 @@ def _any_requires_grad(P) -> bool:
     return any(v.requires_grad for v in vals)
 
 
-def _stage_deconv(P, x, dname, blob, cs, cd, backend, allow_copy=True):
-    """ReLU(deconv(x)) written into channels [cs, cs + cd) of a refinement stage's Concat blob.  Returns what the kernel wrapper
-    returned (with autograd: the slice view that carries the graph), or None after the copy fallback."""
-    d = backend.deconv_relu(x, P[dname + ".w"], P[dname + ".b"], NEG_SLOPE, True, out=blob, out_c0=cs) if hasattr(backend, "deconv_relu") else None
-    if d is None and allow_copy:
-        blob[:, cs:cs + cd].copy_(_deconv(x, P, dname, backend=backend))
-    return d
-
-
-def _refine_stage(P, skip, x, dname, flow, uname, backend):
+def _refine_stage(P, skip, x, dname, flow, uname, be):
     """One refinement Concat [skip | ReLU(deconv(x)) | upsampled flow].  `skip` is a tensor or a pair (concat blob, tensor) from
     _conv_into_concat: with a blob the Concat layer (concat_layer.cu:8-52) has nothing to copy -- the skip convolution already wrote its
     channels there, and the deconvolution and the upsampled flow are written behind them by their own kernels."""
-    def up(t, name, out=None, out_c0=0):
-        if backend is not None and hasattr(backend, "upsample_flow_deconv"):
-            if out is not None:
-                return backend.upsample_flow_deconv(t, P[name + ".w"], P[name + ".b"], out=out, out_c0=out_c0)
-            return backend.upsample_flow_deconv(t, P[name + ".w"], P[name + ".b"])
-        return _deconv(t, P, name, act=False)
-
     blob, s = skip if isinstance(skip, tuple) else (None, skip)
     if blob is None:
-        return torch.cat([s, _deconv(x, P, dname, backend=backend), up(flow, uname)], 1)
-    cs, cd = s.shape[1], P[dname + ".w"].shape[1]
+        return torch.cat([s, be.deconv(x, P, dname), be.upsample_flow(flow, P, uname)], 1)
+    wd, bd = P[dname + ".w"], P[dname + ".b"]
+    cs, cd = s.shape[1], wd.shape[1]
     assert blob.shape[1] == cs + cd + 2
-    stage_params = [P[n] for n in (dname + ".w", dname + ".b", uname + ".w", uname + ".b")]
+    # ReLU(deconv(x)) written into channels [cs, cs + cd) of the blob (with autograd: d is the slice view that carries the graph)
+    d = be.own_deconv(x, wd, bd, NEG_SLOPE, True, out=blob, out_c0=cs)
+    if d is not None:
+        be.wrote("deconv", dname, d, blob, cs, cd, x, wd, 2, 1)
+    stage_params = [wd, bd, P[uname + ".w"], P[uname + ".b"]]
     if torch.is_grad_enabled() and (s.requires_grad or x.requires_grad or flow.requires_grad or any(p.requires_grad for p in stage_params)):
         # training (also a partial freeze whose first trainable tensors are this stage's own deconvolution / up-sampling weights): the
         # three producers are autograd functions that wrote / write their slices; _ConcatInPlace hands the consumer the blob
-        d = _stage_deconv(P, x, dname, blob, cs, cd, backend, allow_copy=False)
-        u = up(flow, uname, out=blob, out_c0=cs + cd) if (d is not None and hasattr(backend, "upsample_flow_deconv")) else None
+        u = be.upsample_flow(flow, P, uname, out=blob, out_c0=cs + cd) if d is not None else None
         if d is None or u is None:          # a producer without an own kernel for this shape: the stock Concat (a copy) for this stage
-            return torch.cat([s, _deconv(x, P, dname, backend=backend), up(flow, uname)], 1)
+            return torch.cat([s, be.deconv(x, P, dname), be.upsample_flow(flow, P, uname)], 1)
         part = lambda t, c0, c: t if t.requires_grad else blob[:, c0:c0 + c]      # (a frozen producer returned the blob it wrote into)
         return _ConcatInPlace.apply(blob, s, part(d, cs, cd), part(u, cs + cd, 2))
-    _stage_deconv(P, x, dname, blob, cs, cd, backend)
-    if hasattr(backend, "upsample_flow_deconv"):
-        up(flow, uname, out=blob, out_c0=cs + cd)
-    else:
-        blob[:, cs + cd:].copy_(up(flow, uname))
+    if d is None:
+        blob[:, cs:cs + cd].copy_(be.deconv(x, P, dname))
+    if be.upsample_flow(flow, P, uname, out=blob, out_c0=cs + cd) is None:
+        blob[:, cs + cd:].copy_(be.upsample_flow(flow, P, uname))
     return blob
 
 
-def _decoder(P, conv6_1, conv5_1, conv4_1, conv3_1, conv2, backend=None):
+def _decoder(P, conv6_1, conv5_1, conv4_1, conv3_1, conv2, be):
     """The refinement stages.  Every skip argument is a tensor or a pair (concat blob, tensor) from _conv_into_concat: with a blob the
     Concat layer (concat_layer.cu:8-52) has nothing to copy -- the skip convolution already wrote its channels there, and the
     deconvolution and the upsampled flow are written behind them by their own kernels."""
-    # predict_flow (3x3 conv -> 2 ch) and upsample_flow (4x4/2 deconv 2 -> 2) go through the backend's flow-head
-    # kernels when it has them (HIP: flow_head.hip); otherwise the stock conv path
-    def pf(x, name):
-        if backend is not None and hasattr(backend, "predict_flow_conv"):
-            return backend.predict_flow_conv(x, P[name + ".w"], P[name + ".b"])
-        return _conv(x, P, name, 1, 1, act=False, backend=backend)
-
-    def stage(skip, x, dname, flow, uname):
-        return _refine_stage(P, skip, x, dname, flow, uname, backend)
-
     # (Round 4 measured the flow head of every level on a second HIP stream beside that level's deconvolution: 2.366 ms per FlowNetC step against
     # 2.343 without -- the fork / join event pairs cost more than ~90 us of head kernels can hide behind GEMMs that fill every CU.  The branch was
     # removed in round 5; what a second stream pays for is LONG independent chains: FlowNet-SD beside the CSS stack, weight gradients beside data
     # gradients.)
-
-    flow6 = pf(conv6_1, "Convolution1")
-    c5 = stage(conv5_1, conv6_1, "deconv5", flow6, "upsample_flow6to5")
-    flow5 = pf(c5, "Convolution2")
-    c4 = stage(conv4_1, c5, "deconv4", flow5, "upsample_flow5to4")
-    flow4 = pf(c4, "Convolution3")
-    c3 = stage(conv3_1, c4, "deconv3", flow4, "upsample_flow4to3")
-    flow3 = pf(c3, "Convolution4")
-    c2 = stage(conv2, c3, "deconv2", flow3, "upsample_flow3to2")
-    flow2 = pf(c2, "Convolution5")
+    flow6 = be.predict_flow(conv6_1, P, "Convolution1")
+    c5 = _refine_stage(P, conv5_1, conv6_1, "deconv5", flow6, "upsample_flow6to5", be)
+    flow5 = be.predict_flow(c5, P, "Convolution2")
+    c4 = _refine_stage(P, conv4_1, c5, "deconv4", flow5, "upsample_flow5to4", be)
+    flow4 = be.predict_flow(c4, P, "Convolution3")
+    c3 = _refine_stage(P, conv3_1, c4, "deconv3", flow4, "upsample_flow4to3", be)
+    flow3 = be.predict_flow(c3, P, "Convolution4")
+    c2 = _refine_stage(P, conv2, c3, "deconv2", flow3, "upsample_flow3to2", be)
+    flow2 = be.predict_flow(c2, P, "Convolution5")
     return {2: flow2, 3: flow3, 4: flow4, 5: flow5, 6: flow6}
 
 
-def _skip_conv(x, P, name, stride, pad, dname, backend, relu_chain=None):
+def _skip_conv(x, P, name, stride, pad, dname, be, relu_chain=None):
     """An encoder convolution whose output is also the first input of a refinement Concat: (concat blob or None, output tensor)."""
-    return _conv_into_concat(x, P, name, stride, pad, P[dname + ".w"].shape[1] + 2, backend, relu_chain=relu_chain)
+    return _conv_into_concat(x, P, name, stride, pad, P[dname + ".w"].shape[1] + 2, be, relu_chain=relu_chain)
 
 
 RELU_CHAIN = [True]      # A/B hook: False = every layer undoes its own ReLU in a pass of its own (rounds 1-5)
 
 
-def _stem_chain(P, x, backend):
+def _stem_chain(P, x, be):
     """conv1 -> conv2 in a TRAINING graph: conv2 is conv1's only consumer, so ReLUBackward of conv1 is folded into the epilogue of conv2's data
     gradient (the transposed 5x5 / 2 convolution) and conv1's bias gradient comes out of its weight-gradient kernel: no pass over the largest
     activation of the net (147 MB at batch 8 @448x320: read twice, written once) between the two.  Returns the (producer, consumer) handles
     for the two layers, or (None, None)."""
-    if not (RELU_CHAIN[0] and CONCAT_IN_PLACE_TRAINING[0] and torch.is_grad_enabled() and x.is_cuda and hasattr(backend, "relu_chain_supported")
-            and hasattr(backend, "conv_route_name")):
+    if not (RELU_CHAIN[0] and be.has_stem_chain and torch.is_grad_enabled() and x.is_cuda):
         return None, None
     w1, w2 = P["conv1.w"], P["conv2.w"]
     if not (w1.requires_grad and w2.requires_grad and P["conv1.b"].requires_grad) or x.requires_grad:
         return None, None
-    if backend.conv_route_name(x.shape, w1, 2, 3) != "stem":                  # (conv1 must take the stem kernel: whole blobs)
+    if be.conv_route_name(x.shape, w1, 2, 3) != "stem":                       # (conv1 must take the stem kernel: whole blobs)
         return None, None
     c1_shape = (x.shape[0], w1.shape[0], (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1)
-    if not backend.relu_chain_supported(c1_shape, w2, 2, 2):
+    if not be.relu_chain_supported(c1_shape, w2, 2, 2):
         return None, None
     cell = {"masked": False, "slope": NEG_SLOPE}
     return (1, cell), (2, cell)
-
-
-CONCAT_IN_PLACE_TRAINING = [True]      # A/B hook: False = torch.cat for the refinement Concats of a training graph (rounds 1-4)
 
 
 class _ConcatInPlace(torch.autograd.Function):
@@ -303,9 +249,6 @@ class _ConcatInPlace(torch.autograd.Function):
             out.append(g[:, c0:c0 + c])
             c0 += c
         return tuple(out)
-
-
-TOWER_SPLIT_OPS = [True]      # A/B hook: False = plain slices of the stacked tower batch in the training graph
 
 
 class _SplitTowers(torch.autograd.Function):
@@ -343,76 +286,86 @@ class _StackedAndFirstTower(torch.autograd.Function):
         return g_all
 
 
+_CORR = dict(pad=20, kernel_size=1, max_displacement=20, stride_1=1, stride_2=2)      # FlowNetC's Correlation layer: 21 x 21 = 441 planes
+
+
 def flownet_c_core(P, img0, img1, backend, towers=None):
     """Pre-processed images [N,3,H,W] (H, W multiples of 64) -> {scale: flow prediction /20}.  `towers`: the two images already
     stacked along the batch axis [2N,3,H,W] (the deploy head writes them there directly)."""
+    be = backend_of(backend)
     # siamese towers share weights (param { name: } sharing, net.cpp:451-540): one batch of 2N through conv1-3
     x = towers if towers is not None else torch.cat([img0, img1], 0)
     n = x.shape[0] // 2
-    chain1, chain2 = _stem_chain(P, x, backend)
-    c1 = _conv(x, P, "conv1", 2, 3, backend=backend, relu_chain=chain1)
+    chain1, chain2 = _stem_chain(P, x, be)
+    c1 = be.conv(x, P, "conv1", 2, 3, relu_chain=chain1)
     # conv2 of BOTH towers goes into a [2N, 128 + 64 + 2, h, w] blob: its first N samples are the concat2 blob of the refinement
-    blob2, c2 = _skip_conv(c1, P, "conv2", 2, 2, "deconv2", backend, relu_chain=chain2)
-    training = TOWER_SPLIT_OPS[0] and torch.is_grad_enabled() and c2.requires_grad
+    blob2, c2 = _skip_conv(c1, P, "conv2", 2, 2, "deconv2", be, relu_chain=chain2)
+    training = torch.is_grad_enabled() and c2.requires_grad
     c2_first = None
     if training:
         c2, c2_first = _StackedAndFirstTower.apply(c2)
-    c3 = _conv(c2, P, "conv3", 2, 2, backend=backend)
+    c3 = be.conv(c2, P, "conv3", 2, 2)
     c3a, c3b = _SplitTowers.apply(c3) if (training and c3.requires_grad) else (c3[:n], c3[n:])
-    cat = redir = None
-    cr = P["conv_redir.w"].shape[0]
-    if hasattr(backend, "correlation_relu_into") and c3a.is_cuda:
-        # the correlation writes its 441 activated planes straight into the [conv_redir | corr] blob (no ReLU pass, no Concat pass), and
-        # conv_redir (1x1: the own MFMA GEMM kernel) its 32 channels in front of them
+    # the correlation writes its 441 activated planes straight into the [conv_redir | corr] blob (no ReLU pass, no Concat pass), and
+    # conv_redir (1x1: the own MFMA GEMM kernel) its 32 channels in front of them -- where the backend has these forms
+    wr, br = P["conv_redir.w"], P["conv_redir.b"]
+    cr = wr.shape[0]
+    cat = None
+    if be.fuses_correlation:
         cat = torch.empty((n, cr + 441, c3a.shape[2], c3a.shape[3]), device=c3a.device, dtype=c3a.dtype)
-        in_graph = (CONCAT_IN_PLACE_TRAINING[0] and torch.is_grad_enabled() and (c3a.requires_grad or c3b.requires_grad)
-                    and hasattr(backend, "conv_backward"))
-        if in_graph:
-            # training: both producers are autograd functions that write their slice of the blob (the fused correlation + ReLU; conv_redir)
-            redir = _conv_into(c3a, P, "conv_redir", 1, 0, cat, 0, backend)
-            corr = backend.correlation_relu_into(c3a, c3b, cat, cr, NEG_SLOPE, pad=20, kernel_size=1, max_displacement=20, stride_1=1, stride_2=2,
-                                                 training=True)
+        if be.trains_in_place and torch.is_grad_enabled() and (c3a.requires_grad or c3b.requires_grad):
+            # training: both producers are autograd functions that write their slice of the blob (conv_redir; the fused correlation + ReLU)
+            redir = be.own_conv(c3a, wr, br, 1, 0, NEG_SLOPE, True, out=cat, out_c0=0)
+            if redir is not None:
+                be.wrote("conv", "conv_redir", redir, cat, 0, cr, c3a, wr, 1, 0)
+            corr = be.own_correlation_relu_into(c3a, c3b, cat, cr, NEG_SLOPE, training=True, **_CORR)
+            be.wrote("relu", "relu", corr, cat, cr, 441, c3a)
             if redir is not None and redir.requires_grad:
                 cat = _ConcatInPlace.apply(cat, redir, corr)
             else:                                       # conv_redir without an own kernel for this shape (or frozen): the stock Concat
-                cat = torch.cat([_conv(c3a, P, "conv_redir", 1, 0, backend=backend), corr], 1)
-        elif backend.correlation_relu_into(c3a, c3b, cat, cr, NEG_SLOPE, pad=20, kernel_size=1, max_displacement=20,
-                                           stride_1=1, stride_2=2) is None:
-            cat = None
+                cat = torch.cat([be.conv(c3a, P, "conv_redir", 1, 0), corr], 1)
         else:
-            into = None
-            if hasattr(backend, "conv_mfma_relu") and not (torch.is_grad_enabled() and _any_requires_grad(P)):
-                into = backend.conv_mfma_relu(c3a, P["conv_redir.w"], P["conv_redir.b"], 1, 0, NEG_SLOPE, True, out=cat, out_c0=0)
-            if into is None:
-                cat[:, :cr].copy_(_conv(c3a, P, "conv_redir", 1, 0, backend=backend))
+            corr = be.own_correlation_relu_into(c3a, c3b, cat, cr, NEG_SLOPE, **_CORR)
+            if corr is None:
+                cat = None
+            else:
+                be.wrote("relu", "relu", corr, cat, cr, 441, c3a)
+                redir = None
+                if not (torch.is_grad_enabled() and _any_requires_grad(P)):
+                    redir = be.own_conv(c3a, wr, br, 1, 0, NEG_SLOPE, True, out=cat, out_c0=0)
+                if redir is None:
+                    cat[:, :cr].copy_(be.conv(c3a, P, "conv_redir", 1, 0))
+                else:
+                    be.wrote("conv", "conv_redir", redir, cat, 0, cr, c3a, wr, 1, 0)
     if cat is None:
-        redir = _conv(c3a, P, "conv_redir", 1, 0, backend=backend)
-        corr = backend.correlation(c3a, c3b, pad=20, kernel_size=1, max_displacement=20, stride_1=1, stride_2=2)
-        cat = torch.cat([redir, F.leaky_relu(corr, NEG_SLOPE)], 1)
-    blob3, c31 = _skip_conv(cat, P, "conv3_1", 1, 1, "deconv3", backend)
-    c4 = _conv(c31, P, "conv4", 2, 1, backend=backend)
-    blob4, c41 = _skip_conv(c4, P, "conv4_1", 1, 1, "deconv4", backend)
-    c5 = _conv(c41, P, "conv5", 2, 1, backend=backend)
-    blob5, c51 = _skip_conv(c5, P, "conv5_1", 1, 1, "deconv5", backend)
-    c6 = _conv(c51, P, "conv6", 2, 1, backend=backend)
-    c61 = _conv(c6, P, "conv6_1", 1, 1, backend=backend)
+        redir = be.conv(c3a, P, "conv_redir", 1, 0)
+        corr = be.correlation(c3a, c3b, **_CORR)
+        cat = torch.cat([redir, be.leaky_relu(corr, "relu")], 1)
+    blob3, c31 = _skip_conv(cat, P, "conv3_1", 1, 1, "deconv3", be)
+    c4 = be.conv(c31, P, "conv4", 2, 1)
+    blob4, c41 = _skip_conv(c4, P, "conv4_1", 1, 1, "deconv4", be)
+    c5 = be.conv(c41, P, "conv5", 2, 1)
+    blob5, c51 = _skip_conv(c5, P, "conv5_1", 1, 1, "deconv5", be)
+    c6 = be.conv(c51, P, "conv6", 2, 1)
+    c61 = be.conv(c6, P, "conv6_1", 1, 1)
     c2s = c2_first if c2_first is not None else c2[:n]
     skip2 = (blob2[:n], c2s) if blob2 is not None else c2s
-    return _decoder(P, c61, (blob5, c51), (blob4, c41), (blob3, c31), skip2, backend)
+    return _decoder(P, c61, (blob5, c51), (blob4, c41), (blob3, c31), skip2, be)
 
 
 def flownet_s_core(P, x, backend=None):
-    c1 = _conv(x, P, "conv1", 2, 3, backend=backend)
-    blob2, c2 = _skip_conv(c1, P, "conv2", 2, 2, "deconv2", backend)
-    c3 = _conv(c2, P, "conv3", 2, 2, backend=backend)
-    blob3, c31 = _skip_conv(c3, P, "conv3_1", 1, 1, "deconv3", backend)
-    c4 = _conv(c31, P, "conv4", 2, 1, backend=backend)
-    blob4, c41 = _skip_conv(c4, P, "conv4_1", 1, 1, "deconv4", backend)
-    c5 = _conv(c41, P, "conv5", 2, 1, backend=backend)
-    blob5, c51 = _skip_conv(c5, P, "conv5_1", 1, 1, "deconv5", backend)
-    c6 = _conv(c51, P, "conv6", 2, 1, backend=backend)
-    c61 = _conv(c6, P, "conv6_1", 1, 1, backend=backend)
-    return _decoder(P, c61, (blob5, c51), (blob4, c41), (blob3, c31), (blob2, c2), backend)
+    be = backend_of(backend)
+    c1 = be.conv(x, P, "conv1", 2, 3)
+    blob2, c2 = _skip_conv(c1, P, "conv2", 2, 2, "deconv2", be)
+    c3 = be.conv(c2, P, "conv3", 2, 2)
+    blob3, c31 = _skip_conv(c3, P, "conv3_1", 1, 1, "deconv3", be)
+    c4 = be.conv(c31, P, "conv4", 2, 1)
+    blob4, c41 = _skip_conv(c4, P, "conv4_1", 1, 1, "deconv4", be)
+    c5 = be.conv(c41, P, "conv5", 2, 1)
+    blob5, c51 = _skip_conv(c5, P, "conv5_1", 1, 1, "deconv5", be)
+    c6 = be.conv(c51, P, "conv6", 2, 1)
+    c61 = be.conv(c6, P, "conv6_1", 1, 1)
+    return _decoder(P, c61, (blob5, c51), (blob4, c41), (blob3, c31), (blob2, c2), be)
 
 
 def adapted_size(h: int, w: int, divisor: int = 64):
@@ -426,12 +379,13 @@ def deploy_forward(kind: str, P, img0, img1, backend, mean: Optional[torch.Tenso
     Head/tail as in SURVEY.md Appendix B: Eltwise(1/255) -> Resample(ADAPTED, LINEAR) -> mean
     subtraction -> net -> x20 -> Resample(TARGET, LINEAR) -> diag(SCALE_WIDTH, SCALE_HEIGHT) 1x1 conv.
     """
+    backend = backend_of(backend)
     N, _, H, W = img0.shape
     ah, aw = adapted_size(H, W)
     neg_default = mean is None
     if mean is None:
         mean = _const(img0.device, (0.411, 0.433, 0.45))   # BGR order of a typical RGB mean
-    if (ah, aw) == (H, W) and img0.is_cuda and not torch.is_grad_enabled() and hasattr(backend, "scale_shift"):
+    if (ah, aw) == (H, W) and img0.is_cuda and not torch.is_grad_enabled() and backend.has_scale_shift:
         # At the ADAPTED size the LINEAR Resample is the identity (one tap of weight 1), so the head is x * (1 / 255) - mean per image:
         # one pass per image (product and difference rounded separately: the bits of the Eltwise and mean-subtraction layers), written
         # straight into the blob the towers (C: batch axis) or conv1 (S: channel axis) read -- instead of scale, subtract and concat.
@@ -457,7 +411,7 @@ def deploy_forward(kind: str, P, img0, img1, backend, mean: Optional[torch.Tenso
             flows = flownet_c_core(P, pre[0], pre[1], backend)
         else:
             flows = flownet_s_core(P, torch.cat(pre, 1), backend)
-    if img0.is_cuda and not torch.is_grad_enabled() and hasattr(backend, "resample_slices"):
+    if img0.is_cuda and not torch.is_grad_enabled() and backend.has_slices:
         flow = backend.resample_slices(flows[2], H, W, in_scale=FLOW_SCALE)         # Eltwise{20} folded into the Resample (same roundings)
         if (ah, aw) == (H, W):
             return flow                                                              # diag(1, 1): x * 1.0f is x
@@ -472,7 +426,8 @@ def loss_targets_ahead(gt_flow, backend, divisors=None):
     """The Downsample(GT * 0.05) pyramid of multiscale_loss issued ahead of the forward pass on a second stream (backend.downsample_ahead:
     it depends on the ground truth alone).  Returns an opaque handle for multiscale_loss(..., targets=handle), or None when the backend
     has no such form."""
-    if not (hasattr(backend, "downsample_ahead") and gt_flow.is_cuda):
+    backend = backend_of(backend)
+    if not (backend.targets_ahead and gt_flow.is_cuda):
         return None
     H, W = gt_flow.shape[2], gt_flow.shape[3]
     divisors = divisors or {s: 2 ** s for s in LOSS_WEIGHTS}
@@ -488,6 +443,7 @@ FINAL_FLOW_GT_SCALE = {"SD": 1.0 / SD_FLOW_SCALE, "fusion": 1.0}     # pixels ->
 def final_flow_loss(flow, gt_flow, backend, scale):
     """Training loss of a core that returns only its final flow (flownet_sd_core, fusion_core): Downsample(GT * scale) to that flow's size
     -> L1Loss{l2_per_location, normalize_by_num_entries}, the loss layer multiscale_loss uses per scale."""
+    backend = backend_of(backend)
     tgt = backend.downsample(gt_flow * scale, flow.shape[2], flow.shape[3])
     return backend.l1_loss(flow, tgt, l2_per_location=True, normalize_by_num_entries=True)
 
@@ -495,7 +451,8 @@ def final_flow_loss(flow, gt_flow, backend, scale):
 def multiscale_loss(flows, gt_flow, backend, targets=None):
     """Training loss: per scale Downsample(GT * 0.05) -> L1Loss{l2_per_location, normalize_by_num_entries}.  `targets`: the handle of
     loss_targets_ahead (the same Downsample launches, issued at the start of the step on a second stream)."""
-    if hasattr(backend, "l1_loss_multi") and gt_flow.is_cuda:
+    backend = backend_of(backend)
+    if backend.has_multi_loss and gt_flow.is_cuda:
         # the five loss layers in one launch per direction, the weighted sum (Net::ForwardFromTo's loss += ...) included
         scales = list(LOSS_WEIGHTS.items())
         preds = [flows[s] for s, _ in scales]
@@ -614,56 +571,53 @@ class _Prefixed(dict):
         return self.P[self.prefix + k]
 
 
-def _pf(P, x, name, backend):
-    if backend is not None and hasattr(backend, "predict_flow_conv"):
-        return backend.predict_flow_conv(x, P[name + ".w"], P[name + ".b"])
-    return _conv(x, P, name, 1, 1, act=False, backend=backend)
-
-
 def flownet_sd_core(P, x, backend):
-    c0 = _conv(x, P, "conv0", 1, 1, backend=backend)
-    c1 = _conv(_conv(c0, P, "conv1", 2, 1, backend=backend), P, "conv1_1", 1, 1, backend=backend)
+    be = backend_of(backend)
+    c0 = be.conv(x, P, "conv0", 1, 1)
+    c1 = be.conv(be.conv(c0, P, "conv1", 2, 1), P, "conv1_1", 1, 1)
     # the skip tensors of the two finest decoder levels are written straight into their Concat blobs (66 / 66 % of those copies)
-    blob2, c2 = _conv_into_concat(_conv(c1, P, "conv2", 2, 1, backend=backend), P, "conv2_1", 1, 1, 64 + 2, backend)
-    blob3, c3 = _conv_into_concat(_conv(c2, P, "conv3", 2, 1, backend=backend), P, "conv3_1", 1, 1, 128 + 2, backend)
-    blob4, c4 = _skip_conv(_conv(c3, P, "conv4", 2, 1, backend=backend), P, "conv4_1", 1, 1, "deconv4", backend)
-    blob5, c5 = _skip_conv(_conv(c4, P, "conv5", 2, 1, backend=backend), P, "conv5_1", 1, 1, "deconv5", backend)
-    c6 = _conv(_conv(c5, P, "conv6", 2, 1, backend=backend), P, "conv6_1", 1, 1, backend=backend)
-    flow6 = _pf(P, c6, "Convolution1", backend)
-    cat5 = _refine_stage(P, (blob5, c5), c6, "deconv5", flow6, "upsample_flow6to5", backend)
-    flow5 = _pf(P, _conv(cat5, P, "interconv5", 1, 1, act=False, backend=backend), "Convolution2", backend)
-    cat4 = _refine_stage(P, (blob4, c4), cat5, "deconv4", flow5, "upsample_flow5to4", backend)
-    flow4 = _pf(P, _conv(cat4, P, "interconv4", 1, 1, act=False, backend=backend), "Convolution3", backend)
-    cat3 = _refine_stage(P, (blob3, c3), cat4, "deconv3", flow4, "upsample_flow4to3", backend)
-    flow3 = _pf(P, _conv(cat3, P, "interconv3", 1, 1, act=False, backend=backend), "Convolution4", backend)
-    cat2 = _refine_stage(P, (blob2, c2), cat3, "deconv2", flow3, "upsample_flow3to2", backend)
-    return _pf(P, _conv(cat2, P, "interconv2", 1, 1, act=False, backend=backend), "Convolution5", backend)      # 1/4 resolution, units of 1/SD_FLOW_SCALE px
+    blob2, c2 = _conv_into_concat(be.conv(c1, P, "conv2", 2, 1), P, "conv2_1", 1, 1, 64 + 2, be)
+    blob3, c3 = _conv_into_concat(be.conv(c2, P, "conv3", 2, 1), P, "conv3_1", 1, 1, 128 + 2, be)
+    blob4, c4 = _skip_conv(be.conv(c3, P, "conv4", 2, 1), P, "conv4_1", 1, 1, "deconv4", be)
+    blob5, c5 = _skip_conv(be.conv(c4, P, "conv5", 2, 1), P, "conv5_1", 1, 1, "deconv5", be)
+    c6 = be.conv(be.conv(c5, P, "conv6", 2, 1), P, "conv6_1", 1, 1)
+    flow6 = be.predict_flow(c6, P, "Convolution1")
+    cat5 = _refine_stage(P, (blob5, c5), c6, "deconv5", flow6, "upsample_flow6to5", be)
+    flow5 = be.predict_flow(be.conv(cat5, P, "interconv5", 1, 1, act=False), P, "Convolution2")
+    cat4 = _refine_stage(P, (blob4, c4), cat5, "deconv4", flow5, "upsample_flow5to4", be)
+    flow4 = be.predict_flow(be.conv(cat4, P, "interconv4", 1, 1, act=False), P, "Convolution3")
+    cat3 = _refine_stage(P, (blob3, c3), cat4, "deconv3", flow4, "upsample_flow4to3", be)
+    flow3 = be.predict_flow(be.conv(cat3, P, "interconv3", 1, 1, act=False), P, "Convolution4")
+    cat2 = _refine_stage(P, (blob2, c2), cat3, "deconv2", flow3, "upsample_flow3to2", be)
+    return be.predict_flow(be.conv(cat2, P, "interconv2", 1, 1, act=False), P, "Convolution5")      # 1/4 resolution, units of 1/SD_FLOW_SCALE px
 
 
 def fusion_core(P, x, backend):
+    be = backend_of(backend)
     # conv0 / conv1_1 write their 64 / 128 channels straight into the 82- / 162-channel Concat blobs of the decoder (387 MB and 191 MB
     # at 768x384 batch 4: the two largest copies of a FlowNet2 forward)
-    blob0, c0 = _conv_into_concat(x, P, "conv0", 1, 1, 16 + 2, backend)
-    blob1, c1 = _conv_into_concat(_conv(c0, P, "conv1", 2, 1, backend=backend), P, "conv1_1", 1, 1, 32 + 2, backend)
-    c2 = _conv(_conv(c1, P, "conv2", 2, 1, backend=backend), P, "conv2_1", 1, 1, backend=backend)
-    flow2 = _pf(P, c2, "Convolution5", backend)
-    cat1 = _refine_stage(P, (blob1, c1), c2, "deconv1", flow2, "upsample_flow2to1", backend)
-    flow1 = _pf(P, _conv(cat1, P, "interconv1", 1, 1, act=False, backend=backend), "Convolution6", backend)
-    cat0 = _refine_stage(P, (blob0, c0), cat1, "deconv0", flow1, "upsample_flow1to0", backend)
-    return _pf(P, _conv(cat0, P, "interconv0", 1, 1, act=False, backend=backend), "Convolution7", backend)        # full resolution, pixels
+    blob0, c0 = _conv_into_concat(x, P, "conv0", 1, 1, 16 + 2, be)
+    blob1, c1 = _conv_into_concat(be.conv(c0, P, "conv1", 2, 1), P, "conv1_1", 1, 1, 32 + 2, be)
+    c2 = be.conv(be.conv(c1, P, "conv2", 2, 1), P, "conv2_1", 1, 1)
+    flow2 = be.predict_flow(c2, P, "Convolution5")
+    cat1 = _refine_stage(P, (blob1, c1), c2, "deconv1", flow2, "upsample_flow2to1", be)
+    flow1 = be.predict_flow(be.conv(cat1, P, "interconv1", 1, 1, act=False), P, "Convolution6")
+    cat0 = _refine_stage(P, (blob0, c0), cat1, "deconv0", flow1, "upsample_flow1to0", be)
+    return be.predict_flow(be.conv(cat0, P, "interconv0", 1, 1, act=False), P, "Convolution7")        # full resolution, pixels
 
 
 def flownet2_deploy_forward(P, img0, img1, backend, mean: Optional[torch.Tensor] = None):
     """Full FlowNet2: raw 0..255 BGR pairs [N,3,H,W] -> flow [N,2,H,W] in pixels.  Four FlowWarp + four ChannelNorm
     + six Resample calls per forward."""
+    backend = backend_of(backend)
     N, _, H, W = img0.shape
     ah, aw = adapted_size(H, W)
     neg_mean = _const(img0.device, (-0.411, -0.433, -0.45)) if mean is None else (-mean).contiguous()
     if mean is None:
         mean = _const(img0.device, (0.411, 0.433, 0.45))
-    if img0.is_cuda and not torch.is_grad_enabled() and hasattr(backend, "resample_slices"):
+    if img0.is_cuda and not torch.is_grad_enabled() and backend.has_slices:
         return _flownet2_pick_streams(P, img0, img1, backend, neg_mean)
-    if (ah, aw) == (H, W) and img0.is_cuda and not torch.is_grad_enabled() and hasattr(backend, "scale_shift"):
+    if (ah, aw) == (H, W) and img0.is_cuda and not torch.is_grad_enabled() and backend.has_scale_shift:
         # LINEAR Resample at equal size is the identity: scale and mean in one pass per image (two roundings, like the two layers)
         a = backend.scale_shift(img0, 1.0 / 255.0, neg_mean)
         b = backend.scale_shift(img1, 1.0 / 255.0, neg_mean)

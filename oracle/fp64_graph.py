@@ -77,8 +77,9 @@ def _l1_loss(b0, b1, l2_per_location=False, normalize_by_num_entries=False, epsi
     return d.abs().sum() / norm
 
 
-def backend64():
-    """The minimal backend nets.flownet_c_core / multiscale_loss need (everything else falls to torch's own ops in the tensors' dtype)."""
+def backend64(leaky_relu=None):
+    """The minimal backend nets.flownet_c_core / multiscale_loss need (everything else falls to torch's own ops in the tensors' dtype).
+    leaky_relu(x, negative_slope, layer name): the activation of every layer instead of torch's (train_reference's pinned branches)."""
     import oracle
 
     def correlation(b0, b1, pad=0, kernel_size=1, max_displacement=0, stride_1=1, stride_2=1):
@@ -94,14 +95,16 @@ def backend64():
     be.correlation = correlation
     be.downsample = downsample
     be.l1_loss = lambda b0, b1, l2_per_location=False, normalize_by_num_entries=False: _l1_loss(b0, b1, l2_per_location, normalize_by_num_entries)
+    if leaky_relu is not None:
+        be.leaky_relu = leaky_relu
     return be
 
 
 class record_relu_branches:
     """Context manager around a forward pass of a FlowNet core (nets.flownet_c_core / flownet_s_core / flownet_sd_core / fusion_core) in ANY
-    backend: records, in execution order, which side of the kink every leaky-ReLU output of the graph is on (the activated outputs of
-    nets._conv / nets._deconv with act = True, of the producers that write into a Concat blob, and the plain F.leaky_relu calls of the graph
-    itself: the correlation's ReLU).  `branches` is the list train_reference(masks=...) takes.
+    backend: records, in execution order, which side of the kink every leaky-ReLU output of the graph is on -- a listener (nets.listening) on
+    every activated convolution / deconvolution, whether it returned a tensor or wrote into a Concat blob, and on the ReLU of the graph
+    itself (the correlation's, "relu").  `branches` is the list train_reference(masks=...) takes.
 
     Why: a leaky ReLU is piecewise linear.  An fp32 and an fp64 evaluation of the same net disagree about the SIGN of the few
     pre-activations that are within rounding of zero (about one in 10^6: a handful among the 5 M outputs of conv3_1 at batch 8), and each
@@ -110,83 +113,14 @@ class record_relu_branches:
     Evaluating the fp64 comparator on the branch the fp32 run took removes that term: what is left is rounding."""
 
     def __enter__(self):
-        import torch.nn.functional as F
         from flownet2_amd import nets
         self.branches = []
-        self._oc, self._od, self._lr = nets._conv, nets._deconv, F.leaky_relu
-        depth = [0]
-
-        def conv(x, P, name, stride, pad, act=True, backend=None, **kw):
-            depth[0] += 1
-            try:
-                y = self._oc(x, P, name, stride, pad, act, backend, **kw)
-            finally:
-                depth[0] -= 1
-            if act:
-                self.branches.append((name, (y.detach() > 0).cpu()))
-            return y
-
-        def deconv(x, P, name, act=True, backend=None):
-            depth[0] += 1
-            try:
-                y = self._od(x, P, name, act, backend)
-            finally:
-                depth[0] -= 1
-            if act:
-                self.branches.append((name, (y.detach() > 0).cpu()))
-            return y
-
-        def leaky_relu(x, negative_slope=0.01, inplace=False):
-            if depth[0] == 0:                                   # a ReLU of the graph itself (not one inside a convolution's fallback path)
-                self.branches.append(("relu", (x.detach() > 0).cpu()))
-            return self._lr(x, negative_slope, inplace)
-        from flownet2_amd import functional as Fn
-        self._cri = Fn.correlation_relu_into
-
-        def correlation_relu_into(b0, b1, out, out_c0, negative_slope, **kw):
-            r = self._cri(b0, b1, out, out_c0, negative_slope, **kw)
-            if r is not None:                                   # inference-style fused route (frozen towers): the activated planes sit in the blob
-                nch = (2 * (kw.get("max_displacement", 0) // kw.get("stride_2", 1)) + 1) ** 2
-                self.branches.append(("relu", (out[:, out_c0:out_c0 + nch].detach() > 0).cpu()))
-            return r
-        Fn.correlation_relu_into = correlation_relu_into
-        # the layers that write straight into a refinement stage's Concat blob (nets._conv_into_concat, nets._stage_deconv: inference, and
-        # since round 5 the training graph too) do not pass through nets._conv / nets._deconv: record them where they run
-        self._cic, self._sd = nets._conv_into_concat, nets._stage_deconv
-
-        def conv_into_concat(x, P, name, stride, pad, extra_channels, backend, **kw):
-            blob, y = self._cic(x, P, name, stride, pad, extra_channels, backend, **kw)
-            if blob is not None:                                # (else the fallback went through nets._conv above)
-                self.branches.append((name, (y.detach() > 0).cpu()))
-            return blob, y
-
-        def stage_deconv(P, x, dname, blob, cs, cd, backend, **kw):
-            d = self._sd(P, x, dname, blob, cs, cd, backend, **kw)
-            if d is not None:                                   # (else the copy fallback went through nets._deconv above)
-                self.branches.append((dname, (blob[:, cs:cs + cd].detach() > 0).cpu()))
-            return d
-        self._ci = nets._conv_into
-
-        def conv_into(x, P, name, stride, pad, blob, c0, backend):
-            y = self._ci(x, P, name, stride, pad, blob, c0, backend)
-            if y is not None:
-                co = P[name + ".w"].shape[0]
-                self.branches.append((name, (blob[:, c0:c0 + co].detach() > 0).cpu()))
-            return y
-        nets._conv_into = conv_into
-        nets._conv_into_concat, nets._stage_deconv = conv_into_concat, stage_deconv
-        nets._conv, nets._deconv, F.leaky_relu = conv, deconv, leaky_relu
+        self._listening = nets.listening(lambda name, y, info: info["act"] and self.branches.append((name, (y.detach() > 0).cpu())))
+        self._listening.__enter__()
         return self
 
     def __exit__(self, *exc):
-        import torch.nn.functional as F
-        from flownet2_amd import nets
-        from flownet2_amd import functional as Fn
-        nets._conv, nets._deconv, F.leaky_relu = self._oc, self._od, self._lr
-        nets._conv_into_concat, nets._stage_deconv = self._cic, self._sd
-        nets._conv_into = self._ci
-        Fn.correlation_relu_into = self._cri
-        return False
+        return self._listening.__exit__(*exc)
 
 
 PREFIX = {"C": "", "S": "", "SD": "netsd_", "fusion": "fuse_"}      # parameter-name prefix of each core (nets.init_params_flownet2 tables)
@@ -209,7 +143,6 @@ def train_reference(kind, P, inputs, gt, device=None, mean=0.43, masks=None, dty
     its own input (y = x or x * slope by the recorded mask): the fp64 value and gradient of the piecewise-linear function that run evaluated.
     dtype = torch.float32 turns the same torch graph into the LIBRARY-fp32 yardstick (torch's fp32 conv2d / conv_transpose2d = MIOpen on the
     GPU box, none of the product's kernels): how far a stock fp32 implementation sits from the fp64 graph on the same inputs."""
-    import torch.nn.functional as F
     from flownet2_amd import nets
     assert kind in PREFIX, kind
     prefix = PREFIX[kind]
@@ -217,45 +150,28 @@ def train_reference(kind, P, inputs, gt, device=None, mean=0.43, masks=None, dty
     P64 = {k: v.detach().to(device=dev, dtype=dtype).requires_grad_(True) for k, v in P.items() if k.startswith(prefix)}
     ins = [t.detach().to(device=dev, dtype=dtype) for t in inputs]
     g = gt.detach().to(device=dev, dtype=dtype)
-    be = backend64()
     Pc = nets._Prefixed(P64, prefix) if prefix else P64
-    lr, oc, od = F.leaky_relu, nets._conv, nets._deconv
     todo = dict(masks) if masks is not None else None          # by layer name ("relu": the correlation's): the two runs may order them differently
     if masks is not None:
         assert len(todo) == len(masks), "a layer name occurs twice among the recorded branches"
-    current = [None]
 
-    def named(fn):
-        def wrapped(x, P_, name, *a, **k):
-            prev, current[0] = current[0], name
-            try:
-                return fn(x, P_, name, *a, **k)
-            finally:
-                current[0] = prev
-        return wrapped
-
-    def pinned(x, negative_slope=0.01, inplace=False):
-        name = current[0] or "relu"
+    def pinned(x, negative_slope, name):
         m = todo.pop(name)
         assert tuple(m.shape) == tuple(x.shape), (name, tuple(m.shape), tuple(x.shape))
         # leaky_relu's own formula on the recorded branch (a factor tensor from torch.where(m, 1.0, slope) would be float32: slope 0.1f)
         return torch.where(m.to(x.device), x, x * float(negative_slope))
-    if todo is not None:
-        F.leaky_relu, nets._conv, nets._deconv = pinned, named(oc), named(od)
-    try:
-        if kind == "C":
-            assert len(ins) == 2, "C: inputs = (img0, img1)"
-            pre = [(im * (1.0 / 255.0)) - mean for im in ins]
-            loss = nets.multiscale_loss(nets.flownet_c_core(Pc, pre[0], pre[1], be), g, be)
+    be = backend64(leaky_relu=pinned if masks is not None else None)
+    if kind == "C":
+        assert len(ins) == 2, "C: inputs = (img0, img1)"
+        pre = [(im * (1.0 / 255.0)) - mean for im in ins]
+        loss = nets.multiscale_loss(nets.flownet_c_core(Pc, pre[0], pre[1], be), g, be)
+    else:
+        assert len(ins) == 1, "%s: inputs = (x,)" % kind
+        if kind == "S":
+            loss = nets.multiscale_loss(nets.flownet_s_core(Pc, ins[0], be), g, be)
         else:
-            assert len(ins) == 1, "%s: inputs = (x,)" % kind
-            if kind == "S":
-                loss = nets.multiscale_loss(nets.flownet_s_core(Pc, ins[0], be), g, be)
-            else:
-                core = nets.flownet_sd_core if kind == "SD" else nets.fusion_core
-                loss = nets.final_flow_loss(core(Pc, ins[0], be), g, be, nets.FINAL_FLOW_GT_SCALE[kind])
-    finally:
-        F.leaky_relu, nets._conv, nets._deconv = lr, oc, od
+            core = nets.flownet_sd_core if kind == "SD" else nets.fusion_core
+            loss = nets.final_flow_loss(core(Pc, ins[0], be), g, be, nets.FINAL_FLOW_GT_SCALE[kind])
     assert not todo, "recorded ReLU branches left over: the two graphs differ (%s)" % sorted(todo)
     loss.backward()
     return float(loss.detach()), {k: v.grad.detach().cpu() for k, v in P64.items() if v.grad is not None}

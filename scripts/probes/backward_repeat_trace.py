@@ -2,6 +2,7 @@
 process on the same inputs?  Every operator output of flownet2_amd.functional is recorded (value + gradient hook)."""
 import os
 import sys
+import types
 
 import torch
 
@@ -33,9 +34,9 @@ def wrap(name, fn):
     return f
 
 
-orig = {n: getattr(Fn, n) for n in NAMES if hasattr(Fn, n)}
-for n, fn in orig.items():
-    setattr(Fn, n, wrap(n, fn))
+be = types.SimpleNamespace(**vars(Fn))          # functional's ops, the recorded ones wrapped
+for n in NAMES:
+    setattr(be, n, wrap(n, getattr(Fn, n)))
 
 
 def run():
@@ -43,7 +44,7 @@ def run():
     rec = {"fwd": [], "bwd": []}
     for v in P.values():
         v.grad = None
-    loss = nets.multiscale_loss(nets.flownet_c_core(P, a - 0.43, b - 0.43, Fn), gt, Fn)
+    loss = nets.multiscale_loss(nets.flownet_c_core(P, a - 0.43, b - 0.43, be), gt, be)
     loss.backward()
     torch.cuda.synchronize()
     return rec, {k: v.grad.clone() for k, v in P.items()}

@@ -2,6 +2,7 @@
 one of its samples alone, records the output of every layer call (in call order) and prints the first ones that differ in bits."""
 import os
 import sys
+import types
 
 import numpy as np
 import torch
@@ -11,34 +12,26 @@ sys.path.insert(0, ROOT)
 from flownet2_amd import functional as Fn, nets  # noqa: E402
 
 
-def record(log):
-    """Wrap the layer-level entry points of nets / functional so that every call appends (label, output)."""
-    saved = {}
-
-    def wrap(mod, name, label_of):
-        f = getattr(mod, name)
-        saved[(mod, name)] = f
+def recorder(log):
+    """(backend, listener): functional with its custom layers and flow heads wrapped, and a nets.listening callback for the convolutions /
+    deconvolutions, so that every layer call appends (label, output) to `log`."""
+    def wrap(name):
+        f = getattr(Fn, name)
 
         def g(*a, **k):
             r = f(*a, **k)
-            t = r[1] if isinstance(r, tuple) else r
-            if torch.is_tensor(t):
-                if name == "conv_mfma_relu" and k.get("out") is not None:       # written into a Concat blob: only its own channel slice is defined yet
-                    c0 = k.get("out_c0", 0)
-                    t = t[:, c0:c0 + a[1].shape[0]]
-                if name in ("deconv_relu", "upsample_flow_deconv") and k.get("out") is not None and t.shape[1] == k["out"].shape[1]:
-                    c0 = k.get("out_c0", 0)
-                    t = t[:, c0:c0 + a[1].shape[1]]
-                log.append((label_of(a, k), t.detach().clone()))
+            if torch.is_tensor(r):
+                t = r
+                if name == "upsample_flow_deconv" and k.get("out") is not None:       # written into a Concat blob: only its own slice is defined yet
+                    t = t[:, k.get("out_c0", 0):k.get("out_c0", 0) + a[1].shape[1]]
+                log.append((name + " " + "x".join(str(v) for v in a[0].shape), t.detach().clone()))
             return r
-        setattr(mod, name, g)
+        return g
 
-    wrap(nets, "_conv_routed", lambda a, k: "conv " + a[2])
-    wrap(nets, "_deconv", lambda a, k: "deconv " + a[2])
-    wrap(nets, "_conv_into_concat", lambda a, k: "conv_into " + a[2])
-    for nm in ("correlation", "flow_warp", "resample", "channel_norm", "predict_flow_conv", "upsample_flow_deconv", "deconv_relu", "conv_mfma_relu"):
-        wrap(Fn, nm, lambda a, k, nm=nm: nm + " " + "x".join(str(v) for v in a[0].shape))
-    return saved
+    be = types.SimpleNamespace(**vars(Fn))
+    for nm in ("correlation", "flow_warp", "resample", "channel_norm", "predict_flow_conv", "upsample_flow_deconv"):
+        setattr(be, nm, wrap(nm))
+    return be, lambda name, y, info: log.append(("%s %s%s" % (info["kind"], name, " (into)" if info["into"] else ""), y.detach().clone()))
 
 
 def main():
@@ -49,19 +42,15 @@ def main():
     rng = np.random.default_rng(54)
     i0 = torch.from_numpy(rng.integers(0, 256, (B, 3, H, W)).astype(np.float32)).cuda()
     i1 = torch.from_numpy(np.roll(i0.cpu().numpy(), (3, -5), (2, 3)).copy()).cuda()
-    run = (lambda a, b: nets.flownet2_deploy_forward(Pd, a, b, Fn)) if net == "2" else (lambda a, b: nets.deploy_forward(net, Pd, a, b, Fn))
+    def run(log, a, b):
+        be, listener = recorder(log)
+        with torch.no_grad(), nets.listening(listener):
+            return nets.flownet2_deploy_forward(Pd, a, b, be) if net == "2" else nets.deploy_forward(net, Pd, a, b, be)
+
     Fn.set_batch_invariant(True)
     logs = ([], [])
-    saved = record(logs[0])
-    with torch.no_grad():
-        whole = run(i0, i1)
-    for (mod, name), f in saved.items():
-        setattr(mod, name, f)
-    saved = record(logs[1])
-    with torch.no_grad():
-        one = run(i0[1:2], i1[1:2])
-    for (mod, name), f in saved.items():
-        setattr(mod, name, f)
+    whole = run(logs[0], i0, i1)
+    one = run(logs[1], i0[1:2], i1[1:2])
     print("calls:", len(logs[0]), len(logs[1]), "final equal:", torch.equal(whole[1:2], one))
     bad = 0
     for (la, ta), (lb, tb) in zip(*logs):

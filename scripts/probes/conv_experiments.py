@@ -15,10 +15,6 @@ def run(tag, channels_last=False, steps=20):
     a = torch.from_numpy(rng.integers(0, 256, (8, 3, 320, 448)).astype(np.float32)).to(dev)
     b = torch.from_numpy(rng.integers(0, 256, (8, 3, 320, 448)).astype(np.float32)).to(dev)
     def fwd():
-        if not channels_last:
-            return nets.deploy_forward("C", P, a, b, Fn)
-        # same graph, activations kept channels_last between convs
-        orig_conv = nets._conv
         return nets.deploy_forward("C", P, a, b, Fn)
     with torch.no_grad():
         for _ in range(4):

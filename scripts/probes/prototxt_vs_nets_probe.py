@@ -2,6 +2,7 @@
 kernels / conv_mfma_relu in the same order; their outputs are recorded and compared in call order."""
 import os
 import sys
+import types
 
 import numpy as np
 import torch
@@ -11,28 +12,28 @@ sys.path.insert(0, ROOT)
 from flownet2_amd import functional as Fn, net as fnet, nets, templates  # noqa: E402
 
 
-def record(log):
-    saved = []
-
-    def wrap(mod, name):
-        f = getattr(mod, name)
-        saved.append((mod, name, f))
+def recorder(log):
+    """A backend: functional's ops, with the layer-level ones wrapped so that every call appends (label, output) to `log`."""
+    def wrap(name):
+        f = getattr(Fn, name)
 
         def g(*a, **k):
             r = f(*a, **k)
             if torch.is_tensor(r):
                 t = r
-                if k.get("out") is not None and r.shape[1] == k["out"].shape[1]:
+                if name in ("conv_mfma_relu", "deconv_relu", "upsample_flow_deconv") and k.get("out") is not None and r.shape[1] == k["out"].shape[1]:
                     c0 = k.get("out_c0", 0)
                     n = a[1].shape[0] if name == "conv_mfma_relu" else a[1].shape[1]      # (a Deconvolution blob is [Cin, Cout, 4, 4])
                     t = r[:, c0:c0 + n]
                 log.append((name + " " + "x".join(str(v) for v in a[0].shape), t.detach().clone()))
             return r
-        setattr(mod, name, g)
+        return g
+
+    be = types.SimpleNamespace(**vars(Fn))
     for nm in ("conv_mfma_relu", "deconv_relu", "predict_flow_conv", "upsample_flow_deconv", "lib_conv2d",
                "lib_conv_transpose2d", "correlation", "correlation_relu_into", "resample", "flow_warp", "channel_norm", "scale_shift"):
-        wrap(Fn, nm)
-    return saved
+        setattr(be, nm, wrap(nm))
+    return be
 
 
 def main():
@@ -45,17 +46,12 @@ def main():
     i1 = torch.from_numpy(np.roll(i0.cpu().numpy(), (2, -3), (2, 3)).copy()).cuda()
     Fn.set_batch_invariant(True)
     logs = ([], [])
-    saved = record(logs[0])
+    be = recorder(logs[0])
     with torch.no_grad():
-        want = nets.flownet2_deploy_forward(Pd, i0, i1, Fn) if kind == "2" else nets.deploy_forward(kind, Pd, i0, i1, Fn)
-    for mod, name, f in saved:
-        setattr(mod, name, f)
-    saved = record(logs[1])
-    n = fnet.from_template(open(templates.template_path(kind)).read(), W, H, batch=B, device="cuda")
+        want = nets.flownet2_deploy_forward(Pd, i0, i1, be) if kind == "2" else nets.deploy_forward(kind, Pd, i0, i1, be)
+    n = fnet.from_template(open(templates.template_path(kind)).read(), W, H, batch=B, device="cuda", backend=recorder(logs[1]))
     n.load_param_dict(Pd)
     got = n.forward(img0=i0, img1=i1)["predict_flow_final"]
-    for mod, name, f in saved:
-        setattr(mod, name, f)
     print("final equal:", torch.equal(got, want), "max |d|", float((got - want).abs().max()), "calls", len(logs[0]), len(logs[1]))
     skip = ("scale_shift", "resample", "flow_warp", "channel_norm", "correlation")       # the executor's custom layers call ops directly
     logs = tuple([e for e in lg if not e[0].startswith(skip)] for lg in logs)

@@ -19,38 +19,25 @@ acts = {}
 order = []
 
 
-def patch(tag):
-    oc, od = nets._conv, nets._deconv
-
-    def conv(x, P, name, stride, pad, act=True, backend=None):
-        y = oc(x, P, name, stride, pad, act, backend)
-        if y.requires_grad:
+def tracer(tag):
+    """Listener: the output of every Convolution / Deconvolution that carries a graph, and a hook for its gradient."""
+    def layer(name, y, info):
+        if info["kind"] != "relu" and y.requires_grad:
             acts[(tag, name)] = y.detach().double().cpu()
             y.register_hook(lambda g, n=name: (store.__setitem__((tag, n), g.detach().double().cpu()), order.append(n) if tag == "own" else None) and None)
-        return y
-
-    def deconv(x, P, name, act=True, backend=None):
-        y = od(x, P, name, act, backend)
-        if y.requires_grad:
-            acts[(tag, name)] = y.detach().double().cpu()
-            y.register_hook(lambda g, n=name: (store.__setitem__((tag, n), g.detach().double().cpu()), order.append(n) if tag == "own" else None) and None)
-        return y
-    nets._conv, nets._deconv = conv, deconv
-    return oc, od
+    return layer
 
 
 dev = torch.device("cuda:0")
 P = nets.init_params("C", seed=0)
 a, b, gt = _batch(8, 320, 448, 4)
 Pd = {k: v.to(dev).requires_grad_(True) for k, v in P.items()}
-oc, od = patch("own")
 pre = [(im.to(dev) * (1.0 / 255.0)) - 0.43 for im in (a, b)]
-loss = nets.multiscale_loss(nets.flownet_c_core(Pd, pre[0], pre[1], Fn), gt.to(dev), Fn)
+with nets.listening(tracer("own")):
+    loss = nets.multiscale_loss(nets.flownet_c_core(Pd, pre[0], pre[1], Fn), gt.to(dev), Fn)
 loss.backward()
-nets._conv, nets._deconv = oc, od
-patch("f64")
-fp64_graph.flownetc_train_reference(P, a, b, gt, device=dev)
-nets._conv, nets._deconv = oc, od
+with nets.listening(tracer("f64")):
+    fp64_graph.flownetc_train_reference(P, a, b, gt, device=dev)
 rel = lambda x, y: float((x - y).norm() / y.norm())
 print("%-22s %-12s %-12s" % ("layer (backward order)", "grad of out", "activation"))
 for n in order:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Per-layer GPU time of one deploy forward as the graph routes it (own kernels, GEMM route, library): wraps nets._conv_routed / nets._deconv
-and the backend's flow heads / correlation with HIP events.  Each layer is timed in isolation (synchronised), so the sum exceeds the
+"""Per-layer GPU time of one deploy forward as the graph routes it (own kernels, GEMM route, library): a nets.GraphBackend whose layer ops
+and custom layers run between two HIP events.  Each layer is timed in isolation (synchronised), so the sum exceeds the
 pipelined step a little; the point is the ranking.
     python scripts/step_breakdown.py [--net C|2] [--batch 8 --height 320 --width 448] [--iters 10]"""
 import argparse
@@ -45,12 +45,15 @@ def main():
     i0 = torch.rand(a.batch, 3, a.height, a.width, device=dev, generator=g) * 255
     i1 = torch.rand(a.batch, 3, a.height, a.width, device=dev, generator=g) * 255
 
+    # a wrapping adapter: the layer ops of the graphs and the backend's custom layers, each between two HIP events; a listener notes the route
+    be = nets.GraphBackend(Fn)
+    layer_of = {id(v): k[:-2] for k, v in P.items() if k.endswith(".w")}
+
     def conv_label(args, k, y):
         x, PP, name = args[0], args[1], args[2]
         w = PP[name + ".w"]
         gf = 2.0 * y.shape[0] * y.shape[1] * y.shape[2] * y.shape[3] * w.shape[1] * w.shape[2] * w.shape[3] / 1e9
-        pre = getattr(PP, "prefix", "") if hasattr(PP, "prefix") else ""
-        return "%s%-12s %-20s k%ds%d %7.2f GF  %s" % (pre, name, tuple(x.shape), w.shape[2], args[3], gf, nets._LAST_ROUTE[0])
+        return "%s%-12s %-20s k%ds%d %7.2f GF  %s" % (getattr(PP, "prefix", ""), name, tuple(x.shape), w.shape[2], args[3], gf, nets._LAST_ROUTE[0])
 
     def deconv_label(args, k, y):
         x, PP, name = args[0], args[1], args[2]
@@ -58,26 +61,23 @@ def main():
         gf = 2.0 * x.shape[0] * x.shape[2] * x.shape[3] * w.shape[0] * w.shape[1] * 16 / 1e9
         return "%-12s %-20s deconv %7.2f GF" % (name, tuple(x.shape), gf)
 
-    nets._conv_routed = timed(conv_label, nets._conv_routed)
-    nets._deconv = timed(deconv_label, nets._deconv)
+    def into_label(args, k, y):                     # own_conv(x, w, b, stride, pad, slope, act, out=blob, ...): a skip convolution or conv_redir
+        x, w, o = args[0], args[1], k["out"]
+        gf = 2.0 * o.shape[0] * w.shape[0] * o.shape[2] * o.shape[3] * w.shape[1] * w.shape[2] * w.shape[3] / 1e9
+        return "%-12s %-20s k%ds%d %7.2f GF  %s" % (layer_of[id(w)], tuple(x.shape), w.shape[2], args[3], gf, "into concat blob" if y is not None else "(declined)")
 
-    def into_label(args, k, y):
-        x, PP, name = args[0], args[1], args[2]
-        w = PP[name + ".w"]
-        o = y[1]
-        gf = 2.0 * o.shape[0] * o.shape[1] * o.shape[2] * o.shape[3] * w.shape[1] * w.shape[2] * w.shape[3] / 1e9
-        return "%-12s %-20s k%ds%d %7.2f GF  %s" % (name, tuple(x.shape), w.shape[2], args[3], gf, "into concat blob" if y[0] is not None else "-> " + nets._LAST_ROUTE[0])
-
-    nets._conv_into_concat = timed(into_label, nets._conv_into_concat)
-    Fn.deconv_relu = timed(lambda args, k, y: "%-12s %-20s -> %d  %s" % ("deconv_relu", tuple(args[0].shape), args[1].shape[1], "own kernel" if y is not None else "(declined)"),
-                           Fn.deconv_relu)
-    for nm in ("predict_flow_conv", "upsample_flow_deconv", "correlation_relu_into", "resample", "flow_warp", "channel_norm"):
-        if hasattr(Fn, nm):
-            setattr(Fn, nm, timed(lambda args, k, y, nm=nm: "%-12s %s" % (nm, tuple(args[0].shape)), getattr(Fn, nm)))
+    be.conv, be.deconv = timed(conv_label, be.conv), timed(deconv_label, be.deconv)
+    own_conv, timed_into = be.own_conv, timed(into_label, be.own_conv)
+    be.own_conv = lambda *args, **k: (timed_into if k.get("out") is not None else own_conv)(*args, **k)      # (a plain call is inside its conv row)
+    be.own_deconv = timed(lambda args, k, y: "%-12s %-20s -> %d  %s" % ("deconv_relu", tuple(args[0].shape), args[1].shape[1], "own kernel" if y is not None else "(declined)"),
+                          be.own_deconv)
+    for nm, shown in (("predict_flow", "predict_flow_conv"), ("upsample_flow", "upsample_flow_deconv"), ("own_correlation_relu_into", "correlation_relu_into"),
+                      ("resample",) * 2, ("flow_warp",) * 2, ("channel_norm",) * 2):
+        setattr(be, nm, timed(lambda args, k, y, shown=shown: "%-12s %s" % (shown, tuple(args[0].shape)), getattr(be, nm)))
     cat = torch.cat
     torch.cat = timed(lambda args, k, y: "torch.cat -> %s" % (tuple(y.shape),), cat)
-    fwd = (lambda: nets.flownet2_deploy_forward(P, i0, i1, Fn)) if a.net == "2" else (lambda: nets.deploy_forward(a.net, P, i0, i1, Fn))
-    with torch.no_grad():
+    fwd = (lambda: nets.flownet2_deploy_forward(P, i0, i1, be)) if a.net == "2" else (lambda: nets.deploy_forward(a.net, P, i0, i1, be))
+    with torch.no_grad(), nets.listening(nets._note_route):
         for _ in range(3):
             fwd()
         T.clear()

@@ -147,16 +147,16 @@ def test_train_reference_on_its_own_branches_is_the_unpinned_graph(kind, cin):
         fp64_graph.train_reference(kind, P, inputs, gt, device="cpu", masks=swapped)
 
 
-def test_trace_conv_keeps_the_relu_chain(monkeypatch):
-    """FN2_TRACE_CONV=1 (nets._TRACE_CONV) must not drop relu_chain: a chain producer handed to a backend without the stem kernel is refused
+def test_trace_conv_keeps_the_relu_chain():
+    """FN2_TRACE_CONV=1 (the nets._trace_route listener) must not drop relu_chain: a chain producer handed to a backend without the stem kernel is refused
     as without tracing (it used to be dropped silently -- the consumer then folded the ReLU derivative the producer applied again)."""
     from flownet2_amd import nets
     x, P = torch.randn(1, 3, 16, 16), {"conv1.w": torch.randn(8, 3, 7, 7) * 0.1, "conv1.b": torch.zeros(8)}
     for trace in (False, True):
-        monkeypatch.setattr(nets, "_TRACE_CONV", trace)
-        with pytest.raises(RuntimeError, match="relu_chain"):
-            nets._conv(x, P, "conv1", 2, 3, backend=None, relu_chain=(1, {"masked": False, "slope": nets.NEG_SLOPE}))
-        y = nets._conv(x, P, "conv1", 2, 3, backend=None)
+        with nets.listening(nets._trace_route) if trace else contextlib.nullcontext():
+            with pytest.raises(RuntimeError, match="relu_chain"):
+                nets.conv_forward(x, P["conv1.w"], P["conv1.b"], 2, 3, True, None, relu_chain=(1, {"masked": False, "slope": nets.NEG_SLOPE}))
+            y = nets.conv_forward(x, P["conv1.w"], P["conv1.b"], 2, 3, True, None)
         ref = torch.nn.functional.leaky_relu(torch.nn.functional.conv2d(x, P["conv1.w"], P["conv1.b"], stride=2, padding=3), nets.NEG_SLOPE)
         assert torch.equal(y, ref)
 
@@ -330,7 +330,7 @@ def test_fusion_training_step_matches_fp64():
 
 
 @pytest.mark.gpu
-def test_trace_conv_training_step_has_the_bits_of_the_untraced_one(monkeypatch):
+def test_trace_conv_training_step_has_the_bits_of_the_untraced_one():
     """FN2_TRACE_CONV=1 used to drop conv1's relu_chain: conv2 still folded conv1's ReLU derivative into its data gradient and conv1's backward
     applied it a second time (slope 0.01 instead of 0.1 on negative activations).  A FlowNetC step with the stem chain active, traced and
     untraced: the same gradient bits."""
@@ -340,13 +340,13 @@ def test_trace_conv_training_step_has_the_bits_of_the_untraced_one(monkeypatch):
     b = torch.rand(2, 3, 128, 192, device="cuda", generator=g) - 0.43
     gt = torch.randn(2, 2, 128, 192, device="cuda", generator=g) * 3
     P = {k: v.cuda().requires_grad_(True) for k, v in nets.init_params("C", seed=5).items()}
-    assert nets._stem_chain(P, torch.cat([a, b], 0), Fn)[0] is not None       # the chain is what this test is about
+    assert nets._stem_chain(P, torch.cat([a, b], 0), nets.backend_of(Fn))[0] is not None       # the chain is what this test is about
 
     def grads(trace):
-        monkeypatch.setattr(nets, "_TRACE_CONV", trace)
         for v in P.values():
             v.grad = None
-        loss = nets.multiscale_loss(nets.flownet_c_core(P, a, b, Fn), gt, Fn)
+        with nets.listening(nets._trace_route) if trace else contextlib.nullcontext():
+            loss = nets.multiscale_loss(nets.flownet_c_core(P, a, b, Fn), gt, Fn)
         loss.backward()
         torch.cuda.synchronize()
         return float(loss.detach()), {k: v.grad.clone() for k, v in P.items()}
@@ -356,3 +356,30 @@ def test_trace_conv_training_step_has_the_bits_of_the_untraced_one(monkeypatch):
     assert l0 == l1
     bad = [k for k in g0 if not torch.equal(g0[k], g1[k])]
     assert not bad, bad
+
+
+@pytest.mark.gpu
+def test_the_layer_seam_sees_the_16_activated_layers_of_flownetc_on_the_product_path():
+    """nets.listening around flownet_c_core on flownet2_amd.functional at [2, 3, 128, 192] (the stem chain active in training): one no_grad
+    forward (every Concat written in place, the fused correlation + ReLU) and one training forward (the in-place producers as autograd
+    functions) each show the 16 activated layers of tests/test_train_parity.py exactly once, and no layer leaves the own kernels.  In the
+    training graph the order is the stock graph's; without autograd the fused correlation is issued in front of conv_redir."""
+    from flownet2_amd import functional as Fn, nets
+    expected = ["conv1", "conv2", "conv3", "conv_redir", "relu", "conv3_1", "conv4", "conv4_1", "conv5", "conv5_1", "conv6", "conv6_1",
+                "deconv5", "deconv4", "deconv3", "deconv2"]
+    g = torch.Generator(device="cuda").manual_seed(13)
+    a = torch.rand(2, 3, 128, 192, device="cuda", generator=g) - 0.43
+    b = torch.rand(2, 3, 128, 192, device="cuda", generator=g) - 0.43
+    P = {k: v.cuda().requires_grad_(True) for k, v in nets.init_params("C", seed=5).items()}
+    assert nets._stem_chain(P, torch.cat([a, b], 0), nets.backend_of(Fn))[0] is not None
+    before = Fn.LIBRARY_FALLBACKS[0]
+    seen = {}
+    for mode, grad in (("no_grad", False), ("training", True)):
+        names = seen[mode] = []
+        with torch.set_grad_enabled(grad), nets.listening(lambda name, y, info: info["act"] and names.append(name)):
+            flows = nets.flownet_c_core(P, a, b, Fn)
+        assert flows[2].requires_grad == grad
+    torch.cuda.synchronize()
+    assert seen["training"] == expected, seen["training"]
+    assert seen["no_grad"] == expected[:3] + ["relu", "conv_redir"] + expected[5:], seen["no_grad"]
+    assert Fn.LIBRARY_FALLBACKS[0] == before
