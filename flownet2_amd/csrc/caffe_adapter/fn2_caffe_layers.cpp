@@ -27,6 +27,7 @@
 #include "caffe/proto/caffe.pb.h"
 
 #include "flownet2_hip.h"
+#include "flownet2_hip_conv_general.h"
 
 namespace caffe {
 
@@ -402,9 +403,10 @@ class DownsampleLayer : public Layer<Dtype> {
 //   <- ConvolutionLayer / DeconvolutionLayer (conv_layer.cpp:8-40, deconv_layer.cpp:8-45) over BaseConvolutionLayer::LayerSetUp / Reshape
 //      (base_conv_layer.cpp:14-253): same convolution_param fields (num_output, kernel_size, stride, pad, bias_term, weight / bias fillers),
 //      same blob shapes -- weight [num_output, C, k, k] (Deconvolution: [C, num_output, k, k]), bias [num_output] --, same top shape.
-// Scope: square kernels, group 1, dilation 1, one bottom / top pair, the geometries the library has a kernel for (every Convolution and
-// Deconvolution of the FlowNet graphs); anything else aborts in Reshape with a message naming the layer -- keep the stock class for those
-// (INTEGRATION.md shows the two-line factory that falls back to it).
+// Scope: square kernels, group 1, dilation 1, one bottom / top pair.  Every Convolution and Deconvolution of the FlowNet graphs runs on its
+// specialised family; a geometry no family takes -- and a gradient pass of a layer whose forward has a family but that pass none -- runs on
+// the general kernels (include/flownet2_hip_conv_general.h: any kernel, stride and pad).  Only what fn2_conv_general_supported refuses (an
+// empty output, a blob beyond the 32-bit index limits) aborts in Reshape with a message naming the layer.
 // The packed weight operand (round 6): packed ONCE and kept while the weights provably have not changed -- Caffe has no "weights changed"
 // signal below Solver::ApplyUpdate, so the layer reads what SyncedMemory already records: the operand is reused iff the layer runs in the
 // TEST phase, the weight blob's memory is SYNCED on entry (no mutable_cpu_data / mutable_gpu_data since the last const access: a
@@ -460,22 +462,29 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       oh = (desc_.Hin + 2 * pad_ - kernel_) / stride_ + 1; ow = (desc_.Win + 2 * pad_ - kernel_) / stride_ + 1;
       route_ = fn2_conv_route(&desc_, 0);
     }
-    if (route_ == 0)
+    const int tr = transposed_ ? 1 : 0;
+    // the general kernels: the forward of a geometry no family takes, and below the gradient passes that have no route of their own
+    size_t gen_fwd = 0, gen_dgrad = 0, gen_ws = 0;
+    general_ = fn2_conv_general_supported(&desc_, tr) != 0;
+    if (general_) FN2_CALL(fn2_conv_general_sizes(&desc_, tr, &gen_fwd, &gen_dgrad, nullptr, &gen_ws));
+    if (route_ == 0 && !general_)
       LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no kernel for " << type() << "{kernel " << kernel_ << ", stride " << stride_
-                 << ", pad " << pad_ << "} " << channels_ << " -> " << num_output_ << " on " << desc_.Hin << " x " << desc_.Win << "; keep the stock layer for it";
+                 << ", pad " << pad_ << "} " << channels_ << " -> " << num_output_ << " on " << desc_.Hin << " x " << desc_.Win
+                 << " (empty output, or a blob beyond the 32-bit index limits)";
     top[0]->Reshape(desc_.N, num_output_, oh, ow);
-    const size_t pf = transposed_ ? fn2_deconv_packed_weight_floats(&desc_, route_) : fn2_conv_packed_weight_floats(&desc_, route_);
-    size_t wb = transposed_ ? fn2_deconv_workspace_bytes(&desc_, route_) : fn2_conv_workspace_bytes(&desc_, route_);
+    const size_t pf = route_ == 0 ? gen_fwd : transposed_ ? fn2_deconv_packed_weight_floats(&desc_, route_) : fn2_conv_packed_weight_floats(&desc_, route_);
+    size_t wb = route_ == 0 ? 0 : transposed_ ? fn2_deconv_workspace_bytes(&desc_, route_) : fn2_conv_workspace_bytes(&desc_, route_);
     packed_.Reshape(vector<int>{(int)pf});
     // backward: the library's own routes (csrc/conv_route.cpp); one scratch blob serves every call of the layer (they run in stream order)
     bwd_route_ = fn2_conv_backward_data_route(&desc_, transposed_);
     bwd_weights_ = fn2_conv_backward_weights_supported(&desc_, transposed_) != 0;
-    const int tr = transposed_ ? 1 : 0;
     wb = std::max(wb, fn2_bias_leaky_relu_backward_workspace_bytes(desc_.N, num_output_, oh, ow));
     head_ = transposed_ ? route_ == FN2_DECONV_ROUTE_HEAD : route_ == FN2_CONV_ROUTE_HEAD;      // the 2-channel flow heads: kernels of their own, forward and backward
     if (head_) wb = std::max(wb, transposed_ ? fn2_upsample_flow_deconv_backward_workspace_bytes(desc_.N, desc_.Hin, desc_.Win)
                                              : fn2_predict_flow_conv_backward_workspace_bytes(desc_.N, channels_, desc_.Hin, desc_.Win));
     wb = std::max(wb, fn2_conv_backward_weights_workspace_bytes(&desc_, tr));
+    if (!bwd_weights_ && general_ && !head_) wb = std::max(wb, gen_ws);
+    if (bwd_route_ == FN2_BWD_ROUTE_NONE && general_ && !head_) packed_bwd_.Reshape(vector<int>{(int)gen_dgrad});
     if (bwd_route_ != FN2_BWD_ROUTE_NONE) {
       wb = std::max(wb, fn2_conv_backward_data_workspace_bytes(&desc_, tr, bwd_route_));
       wb = std::max(wb, fn2_conv_backward_data_pack_workspace_bytes(&desc_, tr, bwd_route_));
@@ -502,12 +511,16 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     if (reuse) {
       fn2_adapter_stats().weight_pack_reuses++;
     } else {
-      if (transposed_) FN2_CALL(fn2_deconv_pack_weights(&desc_, route_, w, pk, kStream));
+      if (route_ == 0) FN2_CALL(fn2_conv_general_pack_weights(&desc_, transposed_ ? 1 : 0, 0, w, pk, kStream));
+      else if (transposed_) FN2_CALL(fn2_deconv_pack_weights(&desc_, route_, w, pk, kStream));
       else FN2_CALL(fn2_conv_pack_weights(&desc_, route_, w, pk, kStream));
       packed_for_ = w; packed_route_ = route_; packed_count_ = packed_.count();
       fn2_adapter_stats().weight_packs++;
     }
-    if (transposed_) {
+    if (route_ == 0) {
+      FN2_CALL(fn2_conv_general_forward(&desc_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
+                                        num_output_, 0, 0, 0.f, kStream));
+    } else if (transposed_) {
       FN2_CALL(fn2_deconv_forward(&desc_, route_, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()), num_output_, 0,
                                   0, 0.f, ws, wsb, kStream));
     } else {
@@ -541,21 +554,31 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       FN2_CALL(fn2_conv_backward_bias(td, num_output_, 0, f32(this->blobs_[1]->mutable_gpu_diff()), desc_.N, num_output_, top[0]->height(), top[0]->width(),
                                       1, ws, wsb, kStream));
     if (this->param_propagate_down_[0]) {
-      if (!bwd_weights_)
-        LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no weight-gradient kernel for this " << type() << "; keep the stock layer for it";
-      FN2_CALL(fn2_conv_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0, f32(this->blobs_[0]->mutable_gpu_diff()),
-                                         1, ws, wsb, kStream));
+      if (!bwd_weights_ && !general_)
+        LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no weight-gradient kernel for this " << type();
+      if (bwd_weights_) {
+        FN2_CALL(fn2_conv_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0, f32(this->blobs_[0]->mutable_gpu_diff()),
+                                           1, ws, wsb, kStream));
+      } else {      // the general kernel (the bias gradient was taken above)
+        FN2_CALL(fn2_conv_general_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
+                                                   f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
+      }
     }
     if (propagate_down[0]) {
-      if (bwd_route_ == FN2_BWD_ROUTE_NONE)
-        LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no data-gradient kernel for this " << type() << "; keep the stock layer for it";
+      if (bwd_route_ == FN2_BWD_ROUTE_NONE && !general_)
+        LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no data-gradient kernel for this " << type();
       float* pk = f32(packed_bwd_.mutable_gpu_data());
+      if (bwd_route_ == FN2_BWD_ROUTE_NONE) {
+        FN2_CALL(fn2_conv_general_pack_weights(&desc_, tr, 1, f32(this->blobs_[0]->gpu_data()), pk, kStream));
+        FN2_CALL(fn2_conv_general_backward_data(&desc_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
+        return;
+      }
       FN2_CALL(fn2_conv_backward_data_pack_weights(&desc_, tr, bwd_route_, f32(this->blobs_[0]->gpu_data()), pk, ws, wsb, kStream));
       // bottom_room = channels_: a Caffe blob has no room for the channel groups the kernels round up to (the result goes through the scratch)
       FN2_CALL(fn2_conv_backward_data(&desc_, tr, bwd_route_, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, channels_, ws, wsb, kStream));
     }
   }
-  bool transposed_, bias_term_ = true, bwd_weights_ = false, head_ = false;
+  bool transposed_, bias_term_ = true, bwd_weights_ = false, head_ = false, general_ = false;
   int kernel_ = 0, stride_ = 1, pad_ = 0, num_output_ = 0, channels_ = 0, route_ = 0, bwd_route_ = 0;
   fn2_conv_desc desc_;
   Blob<Dtype> packed_, packed_bwd_, workspace_;

@@ -45,6 +45,9 @@ def _note_fallback(what, x, w):
 def lib_conv2d(x, w, b, stride, pad):
     """Last resort for a Convolution no own kernel serves (a layer shape outside FlowNet's families, or CPU tensors): the library's
     convolution through torch, counted in LIBRARY_FALLBACKS for CUDA tensors; sample by sample in batch-invariant mode."""
+    desc = _general_desc(x, w, b, stride, pad, False)
+    if desc is not None:
+        return _GeneralConv.apply(x, w, b, desc, False)
     if x.is_cuda:
         _note_fallback("Convolution{stride %d, pad %d}" % (stride, pad), x, w)
     if not _BATCH_INVARIANT[0] or not x.is_cuda:
@@ -53,11 +56,89 @@ def lib_conv2d(x, w, b, stride, pad):
 
 
 def lib_conv_transpose2d(x, w, b, stride, pad):
+    desc = _general_desc(x, w, b, stride, pad, True)
+    if desc is not None:
+        return _GeneralConv.apply(x, w, b, desc, True)
     if x.is_cuda:
         _note_fallback("Deconvolution{stride %d, pad %d}" % (stride, pad), x, w)
     if not _BATCH_INVARIANT[0] or not x.is_cuda:
         return torch.nn.functional.conv_transpose2d(x, w, b, stride=stride, padding=pad)
     return torch.cat([torch.nn.functional.conv_transpose2d(x[n:n + 1], w, b, stride=stride, padding=pad) for n in range(x.shape[0])], 0)
+
+
+# What lib_conv2d / lib_conv_transpose2d run CUDA float32 tensors on: "library" (the default: the library convolution through torch, counted
+# and refused under FN2_STRICT=1 as above) or "own" (the general-geometry kernels, csrc/conv_general.hip: any square-tap geometry, exact
+# fp32, forward and backward; nothing leaves the own kernels, so nothing is counted).  A switch of its own, not one of ARITH_SWITCHES.
+_GENERAL_CONVOLUTIONS = ("library", "own")
+_GENERAL_CONV = ["library"]
+
+
+def set_general_convolution(name: str = "library"):
+    """Where the last-resort convolutions run: "library" or "own".  Initial value: $FN2_CONV_GENERAL."""
+    if name not in _GENERAL_CONVOLUTIONS:
+        raise ValueError("general convolution must be one of %s, got %r" % (", ".join(_GENERAL_CONVOLUTIONS), name))
+    _GENERAL_CONV[0] = name
+
+
+def general_convolution() -> str:
+    return _GENERAL_CONV[0]
+
+
+if os.environ.get("FN2_CONV_GENERAL"):
+    set_general_convolution(os.environ["FN2_CONV_GENERAL"])
+
+
+def add_general_convolution_flag(ap):
+    ap.add_argument("--general-conv", choices=list(_GENERAL_CONVOLUTIONS), default=None,
+                    help="where convolutions outside FlowNet's kernel families run (default: $FN2_CONV_GENERAL, else library); own: the general-geometry kernels")
+
+
+def apply_general_convolution_flag(args):
+    if args.general_conv:
+        set_general_convolution(args.general_conv)
+
+
+def _general_desc(x, w, b, stride, pad, transposed):
+    """The descriptor of the layer where the switch is "own" and the general kernels take the call, else None."""
+    if _GENERAL_CONV[0] != "own" or not (x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float32 and x.dim() == w.dim() == 4):
+        return None
+    if w.shape[2] != w.shape[3] or x.shape[1] != w.shape[0 if transposed else 1] or (b is not None and (not b.is_cuda or b.dtype != torch.float32)):
+        return None
+    if isinstance(stride, (tuple, list)) or isinstance(pad, (tuple, list)):
+        return None
+    desc = ops.conv_desc(x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[1 if transposed else 0], w.shape[2], stride, pad)
+    return desc if ops.conv_general_supported(desc, transposed) else None
+
+
+class _GeneralConv(torch.autograd.Function):
+    """Convolution / Deconvolution of any square-tap geometry on the general kernels; the operands are packed once per weight version."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, desc, transposed):
+        ctx.desc, ctx.transposed, ctx.has_bias = desc, transposed, b is not None
+        ctx.save_for_backward(x, w)
+        key = (desc.kernel, desc.stride, desc.pad)
+        packed = _cached_pack(_PACKED_T, w, ("general-fwd", transposed) + key,
+                              lambda: ops.conv_general_pack_weights(w.detach().contiguous(), desc, transposed))
+        xb, x0 = _channel_slice(x)
+        return ops.conv_general_forward(xb, packed, b.detach() if b is not None else None, desc, transposed, in_c0=x0)
+
+    @staticmethod
+    def backward(ctx, d):
+        x, w = ctx.saved_tensors
+        desc, transposed = ctx.desc, ctx.transposed
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        d = d.contiguous()
+        gx = gw = gb = None
+        if need_x:
+            key = (desc.kernel, desc.stride, desc.pad)
+            packed = _cached_pack(_PACKED_T, w, ("general-dgrad", transposed) + key,
+                                  lambda: ops.conv_general_pack_weights(w.detach().contiguous(), desc, transposed, backward=True))
+            gx = ops.conv_general_backward_data(d, packed, desc, transposed)
+        if need_w or need_b:
+            xb, x0 = _channel_slice(x)
+            gw, gb = ops.conv_general_backward_weights(xb, d, desc, transposed, bias=bool(need_b), bottom_c0=x0)
+        return gx, (gw if need_w else None), gb, None, None
 
 
 def scale_shift(x, scale, shift=None, out=None, out_c0=0):

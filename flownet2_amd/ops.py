@@ -782,6 +782,117 @@ def conv_backward_bias(top_diff, C_, top_c0=0, out=None, accumulate=False):
     return out
 
 
+def conv_general_supported(desc, transposed=False) -> bool:
+    """Whether the general-geometry kernels (csrc/conv_general.hip) take this layer (fn2_conv_general_supported; host-only)."""
+    return bool(_lib.lib().fn2_conv_general_supported(C.byref(desc), int(bool(transposed))))
+
+
+def set_conv_general_groups(groups: int = 0):
+    """Test hook (fn2_debug_set_conv_general_groups): 16-channel groups per workgroup of the general gather kernels; 0 = by geometry."""
+    check(_lib.lib().fn2_debug_set_conv_general_groups(int(groups)))
+
+
+def conv_general_sizes(desc, transposed=False):
+    """(floats of the forward operand, of the data-gradient operand, of the weight-gradient operand (0), bytes of the weight-gradient
+    workspace) of the general kernels (fn2_conv_general_sizes; host-only)."""
+    n = [C.c_size_t() for _ in range(4)]
+    check(_lib.lib().fn2_conv_general_sizes(C.byref(desc), int(bool(transposed)), *(C.byref(v) for v in n)))
+    return tuple(int(v.value) for v in n)
+
+
+def conv_general_out_shape(desc, transposed=False):
+    """(Hout, Wout) of the layer as the reference computes it (conv_layer.cpp:8-23, deconv_layer.cpp:8-24)."""
+    k, s, p = desc.kernel, desc.stride, desc.pad
+    if transposed:
+        return s * (desc.Hin - 1) + k - 2 * p, s * (desc.Win - 1) + k - 2 * p
+    return (desc.Hin + 2 * p - k) // s + 1, (desc.Win + 2 * p - k) // s + 1
+
+
+def _general_weight_shape(desc, transposed):
+    k = desc.kernel
+    return (desc.Cin, desc.Cout, k, k) if transposed else (desc.Cout, desc.Cin, k, k)
+
+
+def conv_general_pack_weights(weight, desc, transposed=False, backward=False):
+    """The layer's weight blob -> the operand of the general forward (backward: data-gradient) kernel (fn2_conv_general_pack_weights)."""
+    w = _chk(weight, "weight")
+    if tuple(w.shape) != _general_weight_shape(desc, transposed):
+        raise ValueError("conv_general_pack_weights: weight of shape %s is not this layer's" % (tuple(w.shape),))
+    packed = torch.empty(conv_general_sizes(desc, transposed)[1 if backward else 0], device=w.device, dtype=torch.float32)
+    check(_lib.lib().fn2_conv_general_pack_weights(C.byref(desc), int(bool(transposed)), 1 if backward else 0, _ptr(w), _ptr(packed), _stream()))
+    return packed
+
+
+def _general_blobs(what, desc, transposed, bottom, bottom_c0, top, top_c0):
+    Ho, Wo = conv_general_out_shape(desc, transposed)
+    for t, c0, Cc, H, W, name in ((bottom, bottom_c0, desc.Cin, desc.Hin, desc.Win, "bottom"), (top, top_c0, desc.Cout, Ho, Wo, "top")):
+        if t is not None and (not t.is_contiguous() or (t.shape[0], t.shape[2], t.shape[3]) != (desc.N, H, W) or c0 < 0 or c0 + Cc > t.shape[1]):
+            raise ValueError(f"{what}: {name} blob {tuple(t.shape)} does not hold the layer's [{desc.N},{Cc},{H},{W}] at channel {c0}")
+    return Ho, Wo
+
+
+def conv_general_forward(x, packed, bias, desc, transposed=False, relu=False, negative_slope=0.0, out=None, out_c0=0, in_c0=0):
+    """act(layer(x[:, in_c0:in_c0+Cin]) + bias) -> out[:, out_c0:out_c0+Cout] (a new blob if out is None) on the general kernel
+    (fn2_conv_general_forward).  packed = conv_general_pack_weights(weight, desc, transposed)."""
+    x = _chk(x, "bottom[0]")
+    if out is not None:
+        _chk(out, "top[0]")
+    Ho, Wo = _general_blobs("conv_general_forward", desc, transposed, x, in_c0, out, out_c0)
+    if out is None:
+        out = torch.empty((desc.N, desc.Cout, Ho, Wo), device=x.device, dtype=torch.float32)
+    b = _chk_opt(bias, "bias", ndim=1)
+    pw = _chk(packed, "packed weight", ndim=None)
+    if pw.numel() != conv_general_sizes(desc, transposed)[0]:
+        raise ValueError("conv_general_forward: the operand has %d floats, not what the forward reads for this layer" % pw.numel())
+    check(_lib.lib().fn2_conv_general_forward(C.byref(desc), int(bool(transposed)), _ptr(x), x.shape[1], int(in_c0), _ptr(pw), _ptr(b), _ptr(out),
+                                              out.shape[1], int(out_c0), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
+    return out
+
+
+def conv_general_backward_data(top_diff, packed, desc, transposed=False, top_c0=0, out=None, out_c0=0):
+    """bottom_diff [N, Cin, Hin, Win] (or the slice of `out` at out_c0) of the layer on the general kernel (fn2_conv_general_backward_data).
+    packed = conv_general_pack_weights(weight, desc, transposed, backward=True)."""
+    d = _chk(top_diff, "top_diff")
+    if out is not None:
+        _chk(out, "bottom diff")
+    _general_blobs("conv_general_backward_data", desc, transposed, out, out_c0, d, top_c0)
+    if out is None:
+        out = torch.empty((desc.N, desc.Cin, desc.Hin, desc.Win), device=d.device, dtype=torch.float32)
+    pw = _chk(packed, "packed weight", ndim=None)
+    if pw.numel() != conv_general_sizes(desc, transposed)[1]:
+        raise ValueError("conv_general_backward_data: the operand has %d floats, not what the data gradient reads for this layer" % pw.numel())
+    check(_lib.lib().fn2_conv_general_backward_data(C.byref(desc), int(bool(transposed)), _ptr(d), d.shape[1], int(top_c0), _ptr(pw), _ptr(out),
+                                                    out.shape[1], int(out_c0), _stream()))
+    return out
+
+
+def conv_general_backward_weights(bottom, top_diff, desc, transposed=False, weight_diff=None, bias_diff=None, bias=True, accumulate=False,
+                                  bottom_c0=0, top_c0=0):
+    """(weight_diff, bias_diff) of the layer on the general kernels (fn2_conv_general_backward_weights; deterministic).  accumulate adds
+    into the diffs given; bias=False: no bias gradient (None comes back)."""
+    x, d = _chk(bottom, "bottom"), _chk(top_diff, "top_diff")
+    _general_blobs("conv_general_backward_weights", desc, transposed, x, bottom_c0, d, top_c0)
+    shape = _general_weight_shape(desc, transposed)
+    if weight_diff is None:
+        if accumulate:
+            raise ValueError("conv_general_backward_weights: accumulate needs the diffs to add into")
+        weight_diff = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif tuple(_chk(weight_diff, "weight diff").shape) != shape or not weight_diff.is_contiguous():
+        raise ValueError("conv_general_backward_weights: weight diff has the wrong shape")
+    if bias and bias_diff is None:
+        if accumulate:
+            raise ValueError("conv_general_backward_weights: accumulate needs the diffs to add into")
+        bias_diff = torch.empty(desc.Cout, device=x.device, dtype=torch.float32)
+    elif bias and (tuple(_chk(bias_diff, "bias diff", ndim=1).shape) != (desc.Cout,) or not bias_diff.is_contiguous()):
+        raise ValueError("conv_general_backward_weights: bias diff has the wrong shape")
+    need = conv_general_sizes(desc, transposed)[3]
+    ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
+    check(_lib.lib().fn2_conv_general_backward_weights(C.byref(desc), int(bool(transposed)), _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1],
+                                                       int(top_c0), _ptr(weight_diff), _ptr(bias_diff if bias else None), int(bool(accumulate)),
+                                                       _ptr(ws), need, _stream()))
+    return weight_diff, (bias_diff if bias else None)
+
+
 def conv_mfma_supported(Cin, Hin, Win, Cout, kernel, stride, pad) -> bool:
     return bool(_lib.lib().fn2_conv_mfma_supported(int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad)))
 

@@ -1,0 +1,106 @@
+#!/usr/bin/env python
+"""Timing of the general-geometry convolution (csrc/conv_general.hip) next to what it stands in for, on the same tensors in one run:
+the library convolution through torch at three shapes outside FlowNet's kernel families, and the specialised own route at one FlowNet
+shape (the conv3_1 class), which states what generality costs.  Forward, data gradient and weight (+ bias) gradient.  Run on the GPU box:
+    python scripts/conv_general_bench.py [--iters 20] [--repeats 5] [--batch 8]
+Per (shape, pass) one line: the median over the repeats of the mean time per call of each side, the spread (min .. max over the repeats),
+the ratio of the medians, and the largest difference between the two results over the result's scale.  The two sides alternate inside
+every repeat; every shape is warmed up first (operands are packed outside the timed window, as a layer packs once per weight version)."""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from flownet2_amd import ops  # noqa: E402
+
+# name, transposed, Cin, H, W, Cout, kernel, stride, pad, the other side
+SHAPES = [
+    ("stem 11x11/4 3->96 @224x224", False, 3, 224, 224, 96, 11, 4, 0, "library"),
+    ("3x3/1 48->24 @80x112", False, 48, 80, 112, 24, 3, 1, 1, "library"),
+    ("deconv 4x4/2 32->16 @40x56", True, 32, 40, 56, 16, 4, 2, 1, "library"),
+    ("conv3_1 class 3x3/1 256->256 @40x56", False, 256, 40, 56, 256, 3, 1, 1, "specialised"),
+]
+
+
+def timeit(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters           # us per call
+
+
+def library_passes(x, w, b, g, tr, s, p):
+    conv = F.conv_transpose2d if tr else F.conv2d
+
+    def backward(mask):
+        return torch.ops.aten.convolution_backward(g, x, w, [w.shape[1 if tr else 0]], [s, s], [p, p], [1, 1], tr, [0, 0], 1, mask)
+    return {"forward": lambda: conv(x, w, b, stride=s, padding=p), "data gradient": lambda: backward([True, False, False])[0],
+            "weight + bias gradient": lambda: backward([False, True, True])[1]}
+
+
+def general_passes(x, w, b, g, desc, tr):
+    pf, pd = ops.conv_general_pack_weights(w, desc, tr), ops.conv_general_pack_weights(w, desc, tr, backward=True)
+    return {"forward": lambda: ops.conv_general_forward(x, pf, b, desc, tr), "data gradient": lambda: ops.conv_general_backward_data(g, pd, desc, tr),
+            "weight + bias gradient": lambda: ops.conv_general_backward_weights(x, g, desc, tr)[0]}
+
+
+def specialised_passes(x, w, b, g, desc, tr):
+    route, broute = (ops.deconv_forward_route if tr else ops.conv_forward_route)(desc), ops.conv_backward_data_route(desc, tr)
+    if not route or not broute or not ops.conv_backward_weights_supported(desc, tr):
+        raise SystemExit("no specialised route for this shape")
+    pf, pd = ops.conv_pack_weights(w, desc, route, tr), ops.conv_backward_data_pack_weights(w, desc, tr, broute)
+
+    def wgrad():
+        ops.conv_backward_bias(g, desc.Cout)
+        return ops.conv_backward_weights(x, g, desc, tr)
+    return {"forward": lambda: ops.conv_forward(x, pf, b, desc, route, tr, relu=False), "data gradient": lambda: ops.conv_backward_data(g, pd, desc, tr, broute),
+            "weight + bias gradient": wgrad}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=8)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("conv_general_bench: needs the GPU (a CPU run measures nothing)")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    N = a.batch
+    for name, tr, Cin, H, W, Cout, k, s, p, other in SHAPES:
+        desc = ops.conv_desc(N, Cin, H, W, Cout, k, s, p)
+        Ho, Wo = ops.conv_general_out_shape(desc, tr)
+        x = torch.randn(N, Cin, H, W, device="cuda", generator=gen)
+        w = torch.randn((Cin, Cout, k, k) if tr else (Cout, Cin, k, k), device="cuda", generator=gen) * 0.1
+        b = torch.randn(Cout, device="cuda", generator=gen)
+        g = torch.randn(N, Cout, Ho, Wo, device="cuda", generator=gen)
+        gflop = 2.0 * N * Cin * Cout * k * k * (H * W if tr else Ho * Wo) / 1e9
+        print("%s, batch %d: %.2f GFLOP per pass" % (name, N, gflop), flush=True)
+        mine = general_passes(x, w, b, g, desc, tr)
+        theirs = library_passes(x, w, b, g, tr, s, p) if other == "library" else specialised_passes(x, w, b, g, desc, tr)
+        for what in mine:
+            f, r = mine[what], theirs[what]
+            got, want = f(), r()                       # (also the warm-up of both sides at this shape)
+            for _ in range(2):
+                f(), r()
+            torch.cuda.synchronize()
+            diff = float((got - want[:, :got.shape[1]] if what == "data gradient" else got - want).abs().max()) / max(1.0, float(want.abs().max()))
+            tm, tt = [], []
+            for _ in range(a.repeats):
+                tm.append(timeit(f, a.iters))
+                tt.append(timeit(r, a.iters))
+            m, t = statistics.median(tm), statistics.median(tt)
+            print("   %-22s general %8.1f us (%.1f .. %.1f)  %6.2f TFLOP/s | %s %8.1f us (%.1f .. %.1f) | general / %s = %.2f | max diff / scale %.1e"
+                  % (what, m, min(tm), max(tm), gflop / m * 1e3, other, t, min(tt), max(tt), other, m / t, diff), flush=True)
+
+
+if __name__ == "__main__":
+    main()

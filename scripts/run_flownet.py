@@ -96,7 +96,7 @@ ARITH = ("conv", "deconv", "wino", "corr")          # the switches of functional
 
 def _positionals(argv):
     """Positional arguments of either form: the values of the value-taking options are not positionals."""
-    takes_value = {"--gpu", "--weights", "--net", *Fn.arithmetic_flags(ARITH)}
+    takes_value = {"--gpu", "--weights", "--net", "--general-conv", *Fn.arithmetic_flags(ARITH)}
     out, skip = [], False
     for a in argv:
         if skip:
@@ -121,6 +121,7 @@ def main():
         ap.add_argument("--verbose", action="store_true")
         ap.add_argument("--no-batch-invariant", action="store_true")
         Fn.add_arithmetic_flags(ap, ARITH)
+        Fn.add_general_convolution_flag(ap)
         a = ap.parse_args()
         if not a.caffemodel.startswith("seed:") and not os.path.exists(a.caffemodel):
             raise SystemExit("caffemodel does not exist: " + a.caffemodel)                   # run-flownet.py:20
@@ -133,6 +134,7 @@ def main():
         torch.cuda.set_device(dev)
         Fn.set_batch_invariant(not a.no_batch_invariant)
         Fn.apply_arithmetic_flags(a, ARITH)
+        Fn.apply_general_convolution_flag(a)
         i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
         flow = infer_prototxt(a.caffemodel, a.deployproto, i0, i1, dev)
         flo.write_flo(a.out, flow[0].cpu().numpy())
@@ -145,6 +147,7 @@ def main():
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection follow the work size (see run_flownet_many.py)")
     Fn.add_arithmetic_flags(ap, ARITH)
+    Fn.add_general_convolution_flag(ap)
     a = ap.parse_args()
     for f in (a.img0, a.img1):
         if not os.path.exists(f):
@@ -153,6 +156,7 @@ def main():
     # same arithmetic as run_flownet_many.py on any batching / sharding of a list: a pair's .flo does not depend on how it was computed
     Fn.set_batch_invariant(not a.no_batch_invariant)
     Fn.apply_arithmetic_flags(a, ARITH)
+    Fn.apply_general_convolution_flag(a)
     P, mean = load_params(a.net, a.weights, dev)
     i0, i1 = torch.from_numpy(read_image(a.img0)).to(dev), torch.from_numpy(read_image(a.img1)).to(dev)
     flow = infer(a.net, P, i0, i1, mean)

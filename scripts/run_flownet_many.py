@@ -70,6 +70,7 @@ def main():
                     "calls; a pair's bits then depend on the batch it was computed in)")
     ap.add_argument("--gpu", type=int, default=None, help="device index (default: LOCAL_RANK)")
     Fn.add_arithmetic_flags(ap, ARITH)
+    Fn.add_general_convolution_flag(ap)
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
@@ -79,6 +80,7 @@ def main():
     torch.cuda.set_device(dev)
     Fn.set_batch_invariant(not a.no_batch_invariant)
     Fn.apply_arithmetic_flags(a, ARITH)
+    Fn.apply_general_convolution_flag(a)
     entries = [l.split() for l in open(a.listfile) if l.strip()]
     mine = parallel.shard(entries)
     P, mean = RF.load_params(a.net, a.weights, dev)

@@ -74,8 +74,10 @@ def main():
                     help="solver prototxt: step with flownet2_amd.CaffeOptimizer (Caffe's SGD / Adam, lr_policy, weight decay with decay_mult 0 on the "
                          "biases, clip_gradients) instead of torch.optim.Adam")
     Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
+    Fn.add_general_convolution_flag(ap)
     a = ap.parse_args()
     Fn.apply_arithmetic_flags(a, ARITH)
+    Fn.apply_general_convolution_flag(a)
     dev = torch.device("cuda")
     B, H, W, ch, cw = a.batch, a.height, a.width, a.crop_height, a.crop_width
     recs = synthetic_records(2 * B, H, W)

@@ -9,8 +9,10 @@ from flownet2_amd import functional as Fn, net as fnet, nets, templates
 ap = argparse.ArgumentParser()
 ARITH = ("dgrad", "wgrad", "wino")
 Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
+Fn.add_general_convolution_flag(ap)
 args = ap.parse_args()
 Fn.apply_arithmetic_flags(args, ARITH)
+Fn.apply_general_convolution_flag(args)
 
 N, H, W = 8, 320, 448
 P = {k: v.cuda() for k, v in nets.init_params("C", seed=0).items()}
