@@ -175,6 +175,7 @@ class ConvolutionParameter {
   FN2_OPTIONAL(pad_h) FN2_OPTIONAL(pad_w) FN2_OPTIONAL(kernel_h) FN2_OPTIONAL(kernel_w) FN2_OPTIONAL(stride_h) FN2_OPTIONAL(stride_w)
 #undef FN2_OPTIONAL
   unsigned group() const { return group_; }
+  void set_group(unsigned v) { group_ = v; }
   const FillerParameter& weight_filler() const { return weight_filler_; }
   FillerParameter* mutable_weight_filler() { return &weight_filler_; }
   const FillerParameter& bias_filler() const { return bias_filler_; }

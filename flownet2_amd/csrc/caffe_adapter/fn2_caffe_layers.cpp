@@ -28,6 +28,7 @@
 
 #include "flownet2_hip.h"
 #include "flownet2_hip_conv_general.h"
+#include "flownet2_hip_conv_geometry.h"
 
 namespace caffe {
 
@@ -403,9 +404,13 @@ class DownsampleLayer : public Layer<Dtype> {
 //   <- ConvolutionLayer / DeconvolutionLayer (conv_layer.cpp:8-40, deconv_layer.cpp:8-45) over BaseConvolutionLayer::LayerSetUp / Reshape
 //      (base_conv_layer.cpp:14-253): same convolution_param fields (num_output, kernel_size, stride, pad, bias_term, weight / bias fillers),
 //      same blob shapes -- weight [num_output, C, k, k] (Deconvolution: [C, num_output, k, k]), bias [num_output] --, same top shape.
-// Scope: square kernels, group 1, dilation 1, one bottom / top pair.  Every Convolution and Deconvolution of the FlowNet graphs runs on its
-// specialised family; a geometry no family takes -- and a gradient pass of a layer whose forward has a family but that pass none -- runs on
-// the general kernels (include/flownet2_hip_conv_general.h: any kernel, stride and pad).  Only what fn2_conv_general_supported refuses (an
+// Scope: every ConvolutionParameter of a 2D layer the stock layers accept -- kernel_size / kernel_h, kernel_w, stride, pad, dilation with one
+// or two entries, group -- read with the checks and messages of base_conv_layer.cpp:24-124; one bottom / top pair.  Refused, with a message
+// naming the layer: axis != 1, force_nd_im2col, more than two spatial axes.  A PLAIN layer (square taps, one stride, one pad, dilation 1,
+// group 1) takes the path it always took: every Convolution and Deconvolution of the FlowNet graphs runs on its specialised family; a
+// geometry no family takes -- and a gradient pass of a layer whose forward has a family but that pass none -- runs on the general kernels
+// (include/flownet2_hip_conv_general.h: any kernel, stride and pad).  Every other layer runs forward and all three gradient passes on the
+// same kernels through include/flownet2_hip_conv_geometry.h.  Only what fn2_conv_general_supported / fn2_conv_geometry_supported refuse (an
 // empty output, a blob beyond the 32-bit index limits) aborts in Reshape with a message naming the layer.
 // The packed weight operand (round 6): packed ONCE and kept while the weights provably have not changed -- Caffe has no "weights changed"
 // signal below Solver::ApplyUpdate, so the layer reads what SyncedMemory already records: the operand is reused iff the layer runs in the
@@ -424,22 +429,65 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
   explicit Fn2ConvolutionLayer(const LayerParameter& param, bool transposed) : Layer<Dtype>(param), transposed_(transposed) {}
   virtual void LayerSetUp(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
     const ConvolutionParameter& cp = this->layer_param_.convolution_param();
-    CHECK(cp.kernel_size_size() == 1 && !cp.has_kernel_h() && !cp.has_kernel_w()) << "square kernel_size required";
-    CHECK_LE(cp.stride_size(), 1); CHECK_LE(cp.pad_size(), 1); CHECK_LE(cp.dilation_size(), 1);
-    CHECK(cp.dilation_size() == 0 || cp.dilation(0) == 1) << "dilation 1 only";
-    CHECK_EQ(cp.group(), 1u) << "group 1 only";
-    kernel_ = (int)cp.kernel_size(0);
-    stride_ = cp.stride_size() ? (int)cp.stride(0) : 1;
-    pad_ = cp.pad_size() ? (int)cp.pad(0) : 0;
+    // base_conv_layer.cpp:14-124 for two spatial axes, with its messages
+    CHECK(cp.axis() == 1 && !cp.force_nd_im2col() && bottom[0]->num_axes() == 4)
+        << this->layer_param_.name() << ": libflownet2_hip runs 2D convolutions only (axis 1, no force_nd_im2col, two spatial axes)";
+    const int num_spatial_axes = 2;
+    if (cp.has_kernel_h() || cp.has_kernel_w()) {
+      CHECK_EQ(0, cp.kernel_size_size()) << "Either kernel_size or kernel_h/w should be specified; not both.";
+      kernel_h_ = (int)cp.kernel_h(); kernel_w_ = (int)cp.kernel_w();
+    } else {
+      const int n = cp.kernel_size_size();
+      CHECK(n == 1 || n == num_spatial_axes) << "kernel_size must be specified once, or once per spatial dimension "
+                                             << "(kernel_size specified " << n << " times; " << num_spatial_axes << " spatial dims).";
+      kernel_h_ = (int)cp.kernel_size(0); kernel_w_ = (int)cp.kernel_size(n - 1);
+    }
+    CHECK_GT(kernel_h_, 0) << "Filter dimensions must be nonzero.";
+    CHECK_GT(kernel_w_, 0) << "Filter dimensions must be nonzero.";
+    if (cp.has_stride_h() || cp.has_stride_w()) {
+      CHECK_EQ(0, cp.stride_size()) << "Either stride or stride_h/w should be specified; not both.";
+      stride_h_ = (int)cp.stride_h(); stride_w_ = (int)cp.stride_w();
+    } else {
+      const int n = cp.stride_size();
+      CHECK(n == 0 || n == 1 || n == num_spatial_axes) << "stride must be specified once, or once per spatial dimension "
+                                                       << "(stride specified " << n << " times; " << num_spatial_axes << " spatial dims).";
+      stride_h_ = n ? (int)cp.stride(0) : 1; stride_w_ = n ? (int)cp.stride(n - 1) : 1;
+    }
+    CHECK_GT(stride_h_, 0) << "Stride dimensions must be nonzero.";
+    CHECK_GT(stride_w_, 0) << "Stride dimensions must be nonzero.";
+    if (cp.has_pad_h() || cp.has_pad_w()) {
+      CHECK_EQ(0, cp.pad_size()) << "Either pad or pad_h/w should be specified; not both.";
+      pad_h_ = (int)cp.pad_h(); pad_w_ = (int)cp.pad_w();
+    } else {
+      const int n = cp.pad_size();
+      CHECK(n == 0 || n == 1 || n == num_spatial_axes) << "pad must be specified once, or once per spatial dimension "
+                                                       << "(pad specified " << n << " times; " << num_spatial_axes << " spatial dims).";
+      pad_h_ = n ? (int)cp.pad(0) : 0; pad_w_ = n ? (int)cp.pad(n - 1) : 0;
+    }
+    {
+      const int n = cp.dilation_size();
+      CHECK(n == 0 || n == 1 || n == num_spatial_axes) << "dilation must be specified once, or once per spatial dimension "
+                                                       << "(dilation specified " << n << " times; " << num_spatial_axes << " spatial dims).";
+      dilation_h_ = n ? (int)cp.dilation(0) : 1; dilation_w_ = n ? (int)cp.dilation(n - 1) : 1;
+    }
+    CHECK_GT(dilation_h_, 0) << "Dilation dimensions must be nonzero.";
+    CHECK_GT(dilation_w_, 0) << "Dilation dimensions must be nonzero.";
     num_output_ = (int)cp.num_output();
     CHECK_GT(num_output_, 0);
     bias_term_ = cp.bias_term();
     channels_ = bottom[0]->channels();
+    group_ = (int)cp.group();
+    CHECK_GT(group_, 0);
+    CHECK_EQ(channels_ % group_, 0);
+    CHECK_EQ(num_output_ % group_, 0) << "Number of output should be multiples of group.";
+    // a PLAIN layer (all a FlowNet has) keeps the specialised route and the square-tap general kernels behind it
+    plain_ = kernel_h_ == kernel_w_ && stride_h_ == stride_w_ && pad_h_ == pad_w_ && dilation_h_ == 1 && dilation_w_ == 1 && group_ == 1;
+    kernel_ = kernel_h_; stride_ = stride_h_; pad_ = pad_h_;      // read by the plain paths only
     if (this->blobs_.size() == 0) {
       this->blobs_.resize(bias_term_ ? 2 : 1);
-      // base_conv_layer.cpp:125-139: [conv_out_channels, conv_in_channels / group, k, k]; for a Deconvolution the roles are swapped
-      const int d0 = transposed_ ? channels_ : num_output_, d1 = transposed_ ? num_output_ : channels_;
-      this->blobs_[0].reset(new Blob<Dtype>(d0, d1, kernel_, kernel_));
+      // base_conv_layer.cpp:125-139: [conv_out_channels, conv_in_channels / group, kh, kw]; for a Deconvolution the roles are swapped
+      const int d0 = transposed_ ? channels_ : num_output_, d1 = (transposed_ ? num_output_ : channels_) / group_;
+      this->blobs_[0].reset(new Blob<Dtype>(d0, d1, kernel_h_, kernel_w_));
       shared_ptr<Filler<Dtype> > wf(GetFiller<Dtype>(cp.weight_filler()));
       wf->Fill(this->blobs_[0].get());
       if (bias_term_) {
@@ -454,6 +502,8 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     CHECK_EQ(bottom[0]->channels(), channels_) << "Input size incompatible with convolution kernel.";
     desc_.N = bottom[0]->num(); desc_.Cin = channels_; desc_.Hin = bottom[0]->height(); desc_.Win = bottom[0]->width();
     desc_.Cout = num_output_; desc_.kernel = kernel_; desc_.stride = stride_; desc_.pad = pad_;
+    const int tr = transposed_ ? 1 : 0;
+    if (!plain_) { ReshapeGeometry(top); return; }
     int oh, ow;
     if (transposed_) {      // deconv_layer.cpp:8-24
       oh = stride_ * (desc_.Hin - 1) + kernel_ - 2 * pad_; ow = stride_ * (desc_.Win - 1) + kernel_ - 2 * pad_;
@@ -462,7 +512,6 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       oh = (desc_.Hin + 2 * pad_ - kernel_) / stride_ + 1; ow = (desc_.Win + 2 * pad_ - kernel_) / stride_ + 1;
       route_ = fn2_conv_route(&desc_, 0);
     }
-    const int tr = transposed_ ? 1 : 0;
     // the general kernels: the forward of a geometry no family takes, and below the gradient passes that have no route of their own
     size_t gen_fwd = 0, gen_dgrad = 0, gen_ws = 0;
     general_ = fn2_conv_general_supported(&desc_, tr) != 0;
@@ -492,6 +541,34 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     }
     workspace_.Reshape(vector<int>{(int)((wb + 3) / 4) + 4});
   }
+  // a layer that is not plain: no specialised route, all four passes on fn2_conv_geometry_* (include/flownet2_hip_conv_geometry.h)
+  void ReshapeGeometry(const vector<Blob<Dtype>*>& top) {
+    const int tr = transposed_ ? 1 : 0;
+    const int g[14] = {desc_.N, channels_, desc_.Hin, desc_.Win, num_output_, kernel_h_, kernel_w_, stride_h_, stride_w_, pad_h_, pad_w_,
+                       dilation_h_, dilation_w_, group_};
+    std::copy(g, g + 14, geom_);
+    route_ = 0; bwd_route_ = FN2_BWD_ROUTE_NONE; bwd_weights_ = false; head_ = false;
+    general_ = fn2_conv_geometry_supported(geom_, tr) != 0;
+    if (!general_)
+      LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no kernel for " << type() << "{kernel " << kernel_h_ << " x " << kernel_w_
+                 << ", stride " << stride_h_ << " x " << stride_w_ << ", pad " << pad_h_ << " x " << pad_w_ << ", dilation " << dilation_h_ << " x "
+                 << dilation_w_ << ", group " << group_ << "} " << channels_ << " -> " << num_output_ << " on " << desc_.Hin << " x " << desc_.Win
+                 << " (empty output, or a blob beyond the 32-bit index limits)";
+    int oh = 0, ow = 0;
+    size_t gen_fwd = 0, gen_dgrad = 0, gen_ws = 0;
+    FN2_CALL(fn2_conv_geometry_out_shape(geom_, tr, &oh, &ow));      // conv_layer.cpp:8-23 / deconv_layer.cpp:8-24 with the dilated extent
+    FN2_CALL(fn2_conv_geometry_sizes(geom_, tr, &gen_fwd, &gen_dgrad, nullptr, &gen_ws));
+    top[0]->Reshape(desc_.N, num_output_, oh, ow);
+    packed_.Reshape(vector<int>{(int)gen_fwd});
+    packed_bwd_.Reshape(vector<int>{(int)gen_dgrad});
+    const size_t wb = std::max(gen_ws, fn2_bias_leaky_relu_backward_workspace_bytes(desc_.N, num_output_, oh, ow));
+    workspace_.Reshape(vector<int>{(int)((wb + 3) / 4) + 4});
+  }
+  // the general kernels of either header: the square-tap entry points for a plain layer (the bits of before), else the 14-int ones
+  int GeneralPack(int pass, const float* w, float* pk) const {
+    const int tr = transposed_ ? 1 : 0;
+    return plain_ ? fn2_conv_general_pack_weights(&desc_, tr, pass, w, pk, kStream) : fn2_conv_geometry_pack_weights(geom_, tr, pass, w, pk, kStream);
+  }
   virtual inline const char* type() const { return transposed_ ? "Deconvolution" : "Convolution"; }
   virtual inline int ExactNumBottomBlobs() const { return 1; }
   virtual inline int ExactNumTopBlobs() const { return 1; }
@@ -511,13 +588,16 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     if (reuse) {
       fn2_adapter_stats().weight_pack_reuses++;
     } else {
-      if (route_ == 0) FN2_CALL(fn2_conv_general_pack_weights(&desc_, transposed_ ? 1 : 0, 0, w, pk, kStream));
+      if (route_ == 0) FN2_CALL(GeneralPack(0, w, pk));
       else if (transposed_) FN2_CALL(fn2_deconv_pack_weights(&desc_, route_, w, pk, kStream));
       else FN2_CALL(fn2_conv_pack_weights(&desc_, route_, w, pk, kStream));
       packed_for_ = w; packed_route_ = route_; packed_count_ = packed_.count();
       fn2_adapter_stats().weight_packs++;
     }
-    if (route_ == 0) {
+    if (route_ == 0 && !plain_) {
+      FN2_CALL(fn2_conv_geometry_forward(geom_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
+                                         num_output_, 0, 0, 0.f, kStream));
+    } else if (route_ == 0) {
       FN2_CALL(fn2_conv_general_forward(&desc_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
                                         num_output_, 0, 0, 0.f, kStream));
     } else if (transposed_) {
@@ -559,6 +639,9 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       if (bwd_weights_) {
         FN2_CALL(fn2_conv_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0, f32(this->blobs_[0]->mutable_gpu_diff()),
                                            1, ws, wsb, kStream));
+      } else if (!plain_) {
+        FN2_CALL(fn2_conv_geometry_backward_weights(geom_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
+                                                    f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
       } else {      // the general kernel (the bias gradient was taken above)
         FN2_CALL(fn2_conv_general_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
                                                    f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
@@ -569,8 +652,9 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
         LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no data-gradient kernel for this " << type();
       float* pk = f32(packed_bwd_.mutable_gpu_data());
       if (bwd_route_ == FN2_BWD_ROUTE_NONE) {
-        FN2_CALL(fn2_conv_general_pack_weights(&desc_, tr, 1, f32(this->blobs_[0]->gpu_data()), pk, kStream));
-        FN2_CALL(fn2_conv_general_backward_data(&desc_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
+        FN2_CALL(GeneralPack(1, f32(this->blobs_[0]->gpu_data()), pk));
+        if (plain_) FN2_CALL(fn2_conv_general_backward_data(&desc_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
+        else FN2_CALL(fn2_conv_geometry_backward_data(geom_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
         return;
       }
       FN2_CALL(fn2_conv_backward_data_pack_weights(&desc_, tr, bwd_route_, f32(this->blobs_[0]->gpu_data()), pk, ws, wsb, kStream));
@@ -578,9 +662,11 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       FN2_CALL(fn2_conv_backward_data(&desc_, tr, bwd_route_, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, channels_, ws, wsb, kStream));
     }
   }
-  bool transposed_, bias_term_ = true, bwd_weights_ = false, head_ = false, general_ = false;
+  bool transposed_, bias_term_ = true, bwd_weights_ = false, head_ = false, general_ = false, plain_ = true;
   int kernel_ = 0, stride_ = 1, pad_ = 0, num_output_ = 0, channels_ = 0, route_ = 0, bwd_route_ = 0;
+  int kernel_h_ = 0, kernel_w_ = 0, stride_h_ = 1, stride_w_ = 1, pad_h_ = 0, pad_w_ = 0, dilation_h_ = 1, dilation_w_ = 1, group_ = 1;
   fn2_conv_desc desc_;
+  int geom_[14] = {0};
   Blob<Dtype> packed_, packed_bwd_, workspace_;
   const float* packed_for_ = nullptr;      // device pointer of the weights packed_ was built from
   int packed_route_ = -1, packed_count_ = -1;

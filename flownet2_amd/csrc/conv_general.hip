@@ -1,12 +1,17 @@
 // General-geometry Convolution / Deconvolution on v_mfma_f32_16x16x4_f32 (exact fp32): the last resort behind the specialised families.
-// Contract, operand layout and summation order: include/flownet2_hip_conv_general.h.
+// Contract, operand layout and summation order: include/flownet2_hip_conv_general.h (square taps, fn2_conv_desc) and
+// include/flownet2_hip_conv_geometry.h (rectangular taps, per-axis stride / pad / dilation, groups: the same code, widened).
 //
 // Everything is stated on the two SIDES of the layer, the larger map L and the smaller map S (Convolution: L = bottom, S = top;
-// Deconvolution: L = top, S = bottom).  The weight blob is [Cs][Cl][k][k] for both kinds.  Then
-//   forward gather    L -> S   Convolution forward, Deconvolution data gradient      M = Cs, K = Cl k k, Wp[cs][(cl, tap)] = W[cs][cl][tap]
-//   transposed gather S -> L   Convolution data gradient, Deconvolution forward      M = Cl, K = Cs k k, Wp[cl][(cs, tap)] = W[cs][cl][tap]
+// Deconvolution: L = top, S = bottom).  The weight blob is [Cs][Cl / group][kh][kw] for both kinds.  Per group (channels Clg = Cl / group,
+// Csg = Cs / group, the slices [g Clg, ...) and [g Csg, ...) of the two blobs, the rows [g Csg, ...) of the weight blob)
+//   forward gather    L -> S   Convolution forward, Deconvolution data gradient      M = Csg, K = Clg kh kw, Wp[cs][(cl, tap)] = W[cs][cl][tap]
+//   transposed gather S -> L   Convolution data gradient, Deconvolution forward      M = Clg, K = Csg kh kw, Wp[cl][(cs, tap)] = W[cs][cl][tap]
 //   weight gradient            dW[cs][(cl, tap)] = sum over (n, S pixels) of S[cs][p] x (forward gather of L)[(cl, tap)][p]
-// so there are two gather kernels (one template), two pack layouts and one weight-gradient kernel for the four layer uses.
+// so there are two gather kernels (one template), two pack layouts and one weight-gradient kernel for the four layer uses.  The group is a
+// grid factor.  Every kernel that gathers exists twice: GEN = false is the plain geometry (square taps, one stride, one pad, dilation 1,
+// group 1), where the per-axis values, the dilation products and the group offsets compile away; GEN = true is everything else.  Both run
+// the same accumulation chain per output value.
 //
 // Tiles.  A workgroup is 4 waves.  Gather kernel: 64 consecutive pixels (flattened y Wout + x, so a tile may wrap rows) of one sample x
 // NG = 1, 2 or 4 groups of 16 output channels (by the channel count alone); per chunk of 16 k-rows every thread gathers 4 values (its
@@ -17,6 +22,7 @@
 #include "mfma_tile.hpp"
 
 #include "../../include/flownet2_hip_conv_general.h"
+#include "../../include/flownet2_hip_conv_geometry.h"
 
 namespace fn2 {
 namespace {
@@ -33,52 +39,81 @@ constexpr long long kMaxTiles = 0x3fffff00ll;
 
 // ------------------------------------------------------------------------------------------------ host geometry
 struct Sides {
-  int N, Cl, Hl, Wl, Cs, Hs, Ws, k, s, pad;
+  int N, Cl, Hl, Wl, Cs, Hs, Ws, kh, kw, sh, sw, ph, pw, dh, dw, group;
+  int Cin, Cout;            // the layer's own names of the two channel counts (the slices of bottom and top)
+  bool plain;               // square taps, one stride, one pad, dilation 1, group 1: the GEN = false kernels
 };
+
+// the 14 ints of include/flownet2_hip_conv_geometry.h
+enum { kGN, kGCin, kGHin, kGWin, kGCout, kGkh, kGkw, kGsh, kGsw, kGph, kGpw, kGdh, kGdw, kGgroup, kGeomInts };
 
 inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 
-// the descriptor on its two sides; false: invalid, output extent below 1, or a blob beyond the 32-bit index limits
-bool make_sides(const fn2_conv_desc* d, int transposed, Sides& g) {
-  if (!d) return false;
-  if (d->N < 1 || d->Cin < 1 || d->Hin < 1 || d->Win < 1 || d->Cout < 1 || d->kernel < 1 || d->stride < 1 || d->pad < 0) return false;
+// the geometry on its two sides; false: invalid, output extent below 1, or a blob beyond the 32-bit index limits
+bool make_sides(const int* v, int transposed, Sides& g) {
+  if (!v) return false;
+  if (v[kGN] < 1 || v[kGCin] < 1 || v[kGHin] < 1 || v[kGWin] < 1 || v[kGCout] < 1 || v[kGkh] < 1 || v[kGkw] < 1 || v[kGsh] < 1 || v[kGsw] < 1 ||
+      v[kGph] < 0 || v[kGpw] < 0 || v[kGdh] < 1 || v[kGdw] < 1 || v[kGgroup] < 1)
+    return false;
+  if (v[kGCin] % v[kGgroup] != 0 || v[kGCout] % v[kGgroup] != 0) return false;
+  // the dilated extent of the taps, per axis
+  const long long eh = (long long)v[kGdh] * (v[kGkh] - 1) + 1, ew = (long long)v[kGdw] * (v[kGkw] - 1) + 1;
+  const long long Hp = (long long)v[kGHin] + 2ll * v[kGph], Wp = (long long)v[kGWin] + 2ll * v[kGpw];
+  if (eh > kMaxElems || ew > kMaxElems) return false;
   long long Ho, Wo;
   if (!transposed) {
-    if ((long long)d->Hin + 2ll * d->pad < d->kernel || (long long)d->Win + 2ll * d->pad < d->kernel) return false;
-    Ho = ((long long)d->Hin + 2ll * d->pad - d->kernel) / d->stride + 1;
-    Wo = ((long long)d->Win + 2ll * d->pad - d->kernel) / d->stride + 1;
+    if (Hp < eh || Wp < ew) return false;
+    Ho = (Hp - eh) / v[kGsh] + 1;
+    Wo = (Wp - ew) / v[kGsw] + 1;
   } else {
-    Ho = (long long)d->stride * (d->Hin - 1) + d->kernel - 2ll * d->pad;
-    Wo = (long long)d->stride * (d->Win - 1) + d->kernel - 2ll * d->pad;
+    Ho = (long long)v[kGsh] * (v[kGHin] - 1) + eh - 2ll * v[kGph];
+    Wo = (long long)v[kGsw] * (v[kGWin] - 1) + ew - 2ll * v[kGpw];
   }
   if (Ho < 1 || Wo < 1 || Ho > kMaxElems || Wo > kMaxElems) return false;
-  const long long kk = (long long)d->kernel * d->kernel;
+  const long long kk = (long long)v[kGkh] * v[kGkw];
   if (kk > kMaxElems) return false;
-  const long long bottom = (long long)d->N * d->Cin, top = (long long)d->N * d->Cout;
+  const long long bottom = (long long)v[kGN] * v[kGCin], top = (long long)v[kGN] * v[kGCout];
   if (bottom > kMaxElems || top > kMaxElems) return false;
-  const long long pb = (long long)d->Hin * d->Win, pt = Ho * Wo;
+  const long long pb = (long long)v[kGHin] * v[kGWin], pt = Ho * Wo;
   if (pb > kMaxElems || pt > kMaxElems || bottom * pb > kMaxElems || top * pt > kMaxElems) return false;
-  const long long cc = (long long)d->Cin * d->Cout;
+  const long long cc = (long long)v[kGCin] * (v[kGCout] / v[kGgroup]);
   if (cc > kMaxElems || cc * kk > kMaxElems) return false;
-  // the padded operands: (channels rounded to 16) x (K rounded to 16)
-  const long long cmax = d->Cin > d->Cout ? d->Cin : d->Cout;
-  if ((cdivll(cmax, 16) * 16) * (cdivll(cmax * kk, kKC) * kKC + kKC) > kMaxElems) return false;
-  g.N = d->N; g.k = d->kernel; g.s = d->stride; g.pad = d->pad;
-  if (!transposed) { g.Cl = d->Cin; g.Hl = d->Hin; g.Wl = d->Win; g.Cs = d->Cout; g.Hs = (int)Ho; g.Ws = (int)Wo; }
-  else { g.Cs = d->Cin; g.Hs = d->Hin; g.Ws = d->Win; g.Cl = d->Cout; g.Hl = (int)Ho; g.Wl = (int)Wo; }
+  // the padded operands: group x (channels of a group rounded to 16) x (K of a group rounded to 16)
+  const long long cmax = (v[kGCin] > v[kGCout] ? v[kGCin] : v[kGCout]) / v[kGgroup];
+  if (v[kGgroup] * (cdivll(cmax, 16) * 16) * (cdivll(cmax * kk, kKC) * kKC + kKC) > kMaxElems) return false;
+  g.N = v[kGN]; g.kh = v[kGkh]; g.kw = v[kGkw]; g.sh = v[kGsh]; g.sw = v[kGsw]; g.ph = v[kGph]; g.pw = v[kGpw]; g.dh = v[kGdh]; g.dw = v[kGdw];
+  g.group = v[kGgroup]; g.Cin = v[kGCin]; g.Cout = v[kGCout];
+  g.plain = g.kh == g.kw && g.sh == g.sw && g.ph == g.pw && g.dh == 1 && g.dw == 1 && g.group == 1;
+  if (!transposed) { g.Cl = v[kGCin]; g.Hl = v[kGHin]; g.Wl = v[kGWin]; g.Cs = v[kGCout]; g.Hs = (int)Ho; g.Ws = (int)Wo; }
+  else { g.Cs = v[kGCin]; g.Hs = v[kGHin]; g.Ws = v[kGWin]; g.Cl = v[kGCout]; g.Hl = (int)Ho; g.Wl = (int)Wo; }
+  // the gathers' coordinates (y stride - pad + ky dilation and y + pad - ky dilation over the larger map) stay inside int
+  if ((long long)g.Hl + 2ll * g.ph + eh > kMaxElems || (long long)g.Wl + 2ll * g.pw + ew > kMaxElems) return false;
   return true;
 }
 
-// one GEMM view: M output channels, R reduction channels (K = R k k)
+// fn2_conv_desc as the 14 ints: (k, k, s, s, p, p, 1, 1, 1)
+struct DescGeom {
+  int v[kGeomInts];
+  bool null;
+  explicit DescGeom(const fn2_conv_desc* d) : null(!d) {
+    if (d) {
+      const int w[kGeomInts] = {d->N, d->Cin, d->Hin, d->Win, d->Cout, d->kernel, d->kernel, d->stride, d->stride, d->pad, d->pad, 1, 1, 1};
+      for (int i = 0; i < kGeomInts; ++i) v[i] = w[i];
+    }
+  }
+  const int* geom() const { return null ? nullptr : v; }
+};
+
+// one GEMM view of ONE group: M output channels, R reduction channels (K = R kh kw)
 struct Gemm {
-  int M, R, G, ksteps;      // G: 16-channel groups; ksteps: k-steps of the padded K (a multiple of 4)
+  int M, R, G, ksteps;      // G: 16-channel row groups; ksteps: k-steps of the padded K (a multiple of 4)
   long long K, Kpad;
 };
 
-Gemm make_gemm(int M, int R, int k) {
+Gemm make_gemm(int M, int R, int kh, int kw) {
   Gemm m;
   m.M = M; m.R = R; m.G = (M + 15) / 16;
-  m.K = (long long)R * k * k;
+  m.K = (long long)R * kh * kw;
   m.Kpad = cdivll(m.K, kKC) * kKC;
   m.ksteps = (int)(m.Kpad / 4);
   return m;
@@ -86,11 +121,14 @@ Gemm make_gemm(int M, int R, int k) {
 
 // which gather serves pass 0 (forward) / 1 (data gradient) of the layer kind: true = the transposed gather
 inline bool pass_is_tr(int transposed, int pass) { return (pass == 1) != (transposed != 0); }
-inline Gemm pass_gemm(const Sides& g, bool tr) { return tr ? make_gemm(g.Cl, g.Cs, g.k) : make_gemm(g.Cs, g.Cl, g.k); }
-inline size_t packed_floats(const Gemm& m) { return (size_t)m.G * (size_t)m.ksteps * 64; }
+inline Gemm pass_gemm(const Sides& g, bool tr) {
+  const int cl = g.Cl / g.group, cs = g.Cs / g.group;
+  return tr ? make_gemm(cl, cs, g.kh, g.kw) : make_gemm(cs, cl, g.kh, g.kw);
+}
+inline size_t packed_floats(const Sides& g, const Gemm& m) { return (size_t)g.group * (size_t)m.G * (size_t)m.ksteps * 64; }
 
 struct WgradPlan {
-  Gemm m;                   // M = Cs, R = Cl
+  Gemm m;                   // M = Csg, R = Clg
   int ptiles, nsplit;       // 64-pixel chunks per sample; parts of the reduction
   long long chunks, per_part, tiles;
   size_t workspace_bytes;
@@ -98,10 +136,10 @@ struct WgradPlan {
 
 WgradPlan make_wgrad(const Sides& g) {
   WgradPlan p;
-  p.m = make_gemm(g.Cs, g.Cl, g.k);
+  p.m = pass_gemm(g, false);
   p.ptiles = (int)cdivll((long long)g.Hs * g.Ws, kPix);
   p.chunks = (long long)g.N * p.ptiles;
-  const long long out_tiles = (p.m.Kpad / kKC) * ((p.m.G + 3) / 4);
+  const long long out_tiles = (p.m.Kpad / kKC) * ((p.m.G + 3) / 4) * g.group;       // a 64-channel tile stays inside one group
   long long want = 2048 / out_tiles;                   // enough workgroups for the chip when the output has few tiles
   if (want > 64) want = 64;
   if (want > p.chunks) want = p.chunks;
@@ -109,11 +147,11 @@ WgradPlan make_wgrad(const Sides& g) {
   p.per_part = cdivll(p.chunks, want);
   p.nsplit = (int)cdivll(p.chunks, p.per_part);      // no empty part
   p.tiles = out_tiles * p.nsplit;
-  p.workspace_bytes = sizeof(float) * (size_t)p.nsplit * (size_t)(16 * p.m.G) * (size_t)p.m.Kpad;
+  p.workspace_bytes = sizeof(float) * (size_t)p.nsplit * (size_t)g.group * (size_t)(16 * p.m.G) * (size_t)p.m.Kpad;
   return p;
 }
 
-// 16-channel groups per workgroup of the gather kernels: the three instantiations run the same accumulation chain per output value (the
+// 16-channel row groups per workgroup of the gather kernels: the three instantiations run the same accumulation chain per output value (the
 // same bits); which one runs is a function of the channel count alone -- no autotuning -- unless the debug hook forces one
 int& forced_groups() { static int f = 0; return f; }
 inline int natural_groups(int G) { return G <= 1 ? 1 : G <= 2 ? 2 : 4; }
@@ -121,11 +159,11 @@ inline int groups_per_block(int G) { return forced_groups() ? forced_groups() : 
 
 long long gather_tiles(const Sides& g, bool tr, const Gemm& m, int ng) {
   const long long P = tr ? (long long)g.Hl * g.Wl : (long long)g.Hs * g.Ws;
-  return (long long)g.N * cdivll(P, kPix) * cdivll(m.G, ng);
+  return (long long)g.N * cdivll(P, kPix) * cdivll(m.G, ng) * g.group;
 }
 
-bool supported(const fn2_conv_desc* d, int transposed, Sides& g) {
-  if (!make_sides(d, transposed, g)) return false;
+bool supported(const int* geom, int transposed, Sides& g) {
+  if (!make_sides(geom, transposed, g)) return false;
   const Gemm mf = pass_gemm(g, false), mt = pass_gemm(g, true);
   if (gather_tiles(g, false, mf, natural_groups(mf.G)) > kMaxTiles || gather_tiles(g, true, mt, natural_groups(mt.G)) > kMaxTiles) return false;
   const WgradPlan w = make_wgrad(g);
@@ -138,8 +176,11 @@ struct GatherSrc {
   int ctot, C, IH, IW;      // channels of the blob / of the slice, input map
   int OW;                   // width of the pixel space the tile runs over
   long long OP;             // its pixels
-  int k, s, pad;
-  unsigned ow_magic, s_magic;   // div_magic(OW), div_magic(s)
+  int kh, sh, ph;               // GEN = false reads these alone, for both axes ...
+  unsigned ow_magic, sh_magic;  // div_magic(OW), div_magic(sh)
+  int kw, sw, pw, dh, dw;       // ... GEN = true these too
+  int group;                    // the input channels of group g are [g C, (g + 1) C) from `in`
+  unsigned sw_magic;            // div_magic(sw)
 };
 
 // n / d for 0 <= n < 2^32 without an integer division: with m = div_magic(d) = floor((2^32 - 1) / d), umulhi(n, m) is the quotient or one
@@ -152,63 +193,65 @@ __device__ __forceinline__ void divmod(unsigned n, unsigned d, unsigned magic, u
   if (r >= d) { ++q; r -= d; }
 }
 
-// the pixel of a thread in its tile, as the gather needs it: forward (y s - pad, x s - pad), transposed (y + pad, x + pad)
+// the pixel of a thread in its tile, as the gather needs it: forward (y sh - ph, x sw - pw), transposed (y + ph, x + pw)
 struct PixelBase { int by, bx; bool valid; };
 
-template <bool TR>
+template <bool TR, bool GEN>
 __device__ __forceinline__ PixelBase pixel_base(const GatherSrc& a, long long p) {
   PixelBase b;
   b.valid = p < a.OP;
   unsigned uy, ux;
   divmod(b.valid ? (unsigned)p : 0u, (unsigned)a.OW, a.ow_magic, uy, ux);
   const int y = (int)uy, x = (int)ux;
-  b.by = TR ? y + a.pad : y * a.s - a.pad;
-  b.bx = TR ? x + a.pad : x * a.s - a.pad;
+  const int sw = GEN ? a.sw : a.sh, pw = GEN ? a.pw : a.ph;
+  b.by = TR ? y + a.ph : y * a.sh - a.ph;
+  b.bx = TR ? x + pw : x * sw - pw;
   return b;
 }
 
 // A k-row as (channel, ky, kx), wave-uniform: decomposed once, then advanced by a constant number of rows per chunk with two carries
-// instead of two divisions
+// (kx against kw, ky against kh) instead of two divisions
 struct KRow { int c, ky, kx; };
 struct KStep { int dc, dky, dkx; };
 
-__device__ __forceinline__ KRow k_row(int kg, int k) {
-  const int kk = k * k;
+__device__ __forceinline__ KRow k_row(int kg, int kh, int kw) {
+  const int kk = kh * kw;
   KRow r;
   r.c = kg / kk;
   const int tap = kg - r.c * kk;
-  r.ky = tap / k;
-  r.kx = tap - r.ky * k;
+  r.ky = tap / kw;
+  r.kx = tap - r.ky * kw;
   return r;
 }
 
-__device__ __forceinline__ KStep k_step(int rows, int k) {
-  const KRow r = k_row(rows, k);
+__device__ __forceinline__ KStep k_step(int rows, int kh, int kw) {
+  const KRow r = k_row(rows, kh, kw);
   return KStep{r.c, r.ky, r.kx};
 }
 
-__device__ __forceinline__ void k_advance(KRow& r, const KStep& d, int k) {
+__device__ __forceinline__ void k_advance(KRow& r, const KStep& d, int kh, int kw) {
   r.kx += d.dkx;
-  if (r.kx >= k) { r.kx -= k; ++r.ky; }
+  if (r.kx >= kw) { r.kx -= kw; ++r.ky; }
   r.ky += d.dky;
-  if (r.ky >= k) { r.ky -= k; ++r.c; }
+  if (r.ky >= kh) { r.ky -= kh; ++r.c; }
   r.c += d.dc;
 }
 
 // col[k-row][pixel] of sample slice `src`; 0 outside the image, beyond K and for a pixel beyond the tile's map
-template <bool TR>
+template <bool TR, bool GEN>
 __device__ __forceinline__ float gather_one(const GatherSrc& a, const float* src, const KRow& kr, const PixelBase& b) {
   int yi, xi;
   bool ok = b.valid && kr.c < a.C;
+  const int oy = GEN ? kr.ky * a.dh : kr.ky, ox = GEN ? kr.kx * a.dw : kr.kx;      // the tap's offset, dilated
   if constexpr (TR) {
-    const int ty = b.by - kr.ky, tx = b.bx - kr.kx;
+    const int ty = b.by - oy, tx = b.bx - ox;
     unsigned qy, ry, qx, rx;
-    divmod((unsigned)max(ty, 0), (unsigned)a.s, a.s_magic, qy, ry);
-    divmod((unsigned)max(tx, 0), (unsigned)a.s, a.s_magic, qx, rx);
+    divmod((unsigned)max(ty, 0), (unsigned)a.sh, a.sh_magic, qy, ry);
+    divmod((unsigned)max(tx, 0), (unsigned)(GEN ? a.sw : a.sh), GEN ? a.sw_magic : a.sh_magic, qx, rx);
     yi = (int)qy; xi = (int)qx;
     ok = ok && ty >= 0 && tx >= 0 && ry == 0 && rx == 0 && yi < a.IH && xi < a.IW;
   } else {
-    yi = b.by + kr.ky; xi = b.bx + kr.kx;
+    yi = b.by + oy; xi = b.bx + ox;
     ok = ok && yi >= 0 && yi < a.IH && xi >= 0 && xi < a.IW;
   }
   float v = 0.f;
@@ -227,38 +270,41 @@ struct GatherArgs {
   float slope;
 };
 
-template <bool TR, int NG>
+template <bool TR, int NG, bool GEN>
 __global__ __launch_bounds__(kThreads) void conv_general_gather(GatherArgs a) {
   __shared__ float col[kKC * kColStrideG];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   unsigned task = blockIdx.x;
   const int mb = task % a.mblocks; task /= a.mblocks;
+  int grp = 0;                // the layer's group: a grid factor; M, G, ksteps and C are those of one group
+  if constexpr (GEN) { grp = task % a.g.group; task /= a.g.group; }
   const int pt = task % a.ptiles;
   const int n = task / a.ptiles;
   const long long p0 = (long long)pt * kPix;
   const size_t iplane = (size_t)a.g.IH * a.g.IW;
-  const float* src = a.g.in + (size_t)n * a.g.ctot * iplane;
-  const PixelBase pb = pixel_base<TR>(a.g, p0 + lane);
+  const float* src = a.g.in + ((size_t)n * a.g.ctot + (size_t)grp * a.g.C) * iplane;
+  const PixelBase pb = pixel_base<TR, GEN>(a.g, p0 + lane);
+  const int kh = a.g.kh, kw = GEN ? a.g.kw : a.g.kh;
 
-  // this wave's NG weight groups; beyond the last real group the last one again (computed, not stored)
+  // this wave's NG row groups of the weights; beyond the last real one of the group the last one again (computed, not stored)
   const float* wl[NG];
 #pragma unroll
   for (int j = 0; j < NG; ++j) {
     const int g = min(NG * mb + j, a.G - 1);
-    wl[j] = a.wp + (size_t)g * a.ksteps * 64 + lane;
+    wl[j] = a.wp + ((size_t)grp * a.G + g) * a.ksteps * 64 + lane;
   }
   f32x4 acc[NG];
 #pragma unroll
   for (int j = 0; j < NG; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nchunks = a.ksteps / 4;
-  const KStep kstep = k_step(kKC, a.g.k);
+  const KStep kstep = k_step(kKC, kh, kw);
   KRow kr[4];
   float v[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    kr[i] = k_row(wave + 4 * i, a.g.k);
-    v[i] = gather_one<TR>(a.g, src, kr[i], pb);
+    kr[i] = k_row(wave + 4 * i, kh, kw);
+    v[i] = gather_one<TR, GEN>(a.g, src, kr[i], pb);
   }
   // the weight operand of a chunk (4 k-steps x NG groups) is fetched a chunk ahead, like the col values
   float w[4][NG];
@@ -280,8 +326,8 @@ __global__ __launch_bounds__(kThreads) void conv_general_gather(GatherArgs a) {
       for (int j = 0; j < NG; ++j) wn[ks][j] = wl[j][(size_t)(4 * nx + ks) * 64];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      k_advance(kr[i], kstep, a.g.k);
-      v[i] = gather_one<TR>(a.g, src, kr[i], pb);
+      k_advance(kr[i], kstep, kh, kw);
+      v[i] = gather_one<TR, GEN>(a.g, src, kr[i], pb);
     }
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -302,9 +348,10 @@ __global__ __launch_bounds__(kThreads) void conv_general_gather(GatherArgs a) {
   for (int j = 0; j < NG; ++j) {
     const int co = 16 * (NG * mb + j) + (lane & 15);
     if (co >= a.M || p >= a.g.OP) continue;
-    const float bv = a.bias ? a.bias[co] : 0.f;
+    const int cg = grp * a.M + co;      // the channel in the layer's slice
+    const float bv = a.bias ? a.bias[cg] : 0.f;
     const f32x4 r = mfma::bias_relu4(acc[j], bv, a.relu, a.slope);
-    float* o = a.out + ((size_t)n * a.out_ctot + co) * (size_t)a.g.OP + p;
+    float* o = a.out + ((size_t)n * a.out_ctot + cg) * (size_t)a.g.OP + p;
     if (p + 3 < a.g.OP && (reinterpret_cast<uintptr_t>(o) & 15) == 0) *reinterpret_cast<f32x4*>(o) = r;
     else {
 #pragma unroll
@@ -319,32 +366,37 @@ struct WgradArgs {
   const float* x;           // channel c0 of sample 0 of the S blob
   int x_ctot, A, G, ablocks, ktiles, ptiles;
   long long chunks, per_part, Kpad;
-  float* ws;                // [nsplit][16 G][Kpad]
+  float* ws;                // [nsplit][group][16 G][Kpad]; A, G, Kpad and g.C are those of one group
 };
 
-// the values of a thread for pixel chunk q: 4 of the col tile (k-rows kr) and 16 of the S blob (channels ch0, ch0 + 4, ...)
-__device__ __forceinline__ void wgrad_fetch(const WgradArgs& a, const KRow (&kr)[4], long long q, int ch0, int lane, float (&cv)[4], float (&xv)[16]) {
+// the values of a thread for pixel chunk q: 4 of the col tile (k-rows kr) and 16 of the S blob (channels ch0, ch0 + 4, ... of group grp)
+template <bool GEN>
+__device__ __forceinline__ void wgrad_fetch(const WgradArgs& a, const KRow (&kr)[4], long long q, int grp, int ch0, int lane, float (&cv)[4],
+                                            float (&xv)[16]) {
   const int n = (int)(q / a.ptiles);
   const long long p = (q - (long long)n * a.ptiles) * kPix + lane;
-  const float* src = a.g.in + (size_t)n * a.g.ctot * a.g.IH * a.g.IW;
-  const PixelBase pb = pixel_base<false>(a.g, p);
+  const float* src = a.g.in + ((size_t)n * a.g.ctot + (size_t)grp * a.g.C) * a.g.IH * a.g.IW;
+  const PixelBase pb = pixel_base<false, GEN>(a.g, p);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) cv[i] = gather_one<false>(a.g, src, kr[i], pb);
+  for (int i = 0; i < 4; ++i) cv[i] = gather_one<false, GEN>(a.g, src, kr[i], pb);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int ch = ch0 + 4 * i;
-    xv[i] = (ch < a.A && pb.valid) ? a.x[((size_t)n * a.x_ctot + ch) * (size_t)a.g.OP + p] : 0.f;
+    xv[i] = (ch < a.A && pb.valid) ? a.x[((size_t)n * a.x_ctot + (size_t)grp * a.A + ch) * (size_t)a.g.OP + p] : 0.f;
   }
 }
 
+template <bool GEN>
 __global__ __launch_bounds__(kThreads) void conv_general_wgrad(WgradArgs a) {
   __shared__ float col[kKC * kColStrideW];
   __shared__ float xs[64 * kColStrideW];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   unsigned task = blockIdx.x;
   const int kt = task % a.ktiles; task /= a.ktiles;
-  const int ab = task % a.ablocks;
-  const int part = task / a.ablocks;
+  const int ab = task % a.ablocks; task /= a.ablocks;
+  int grp = 0, ngrp = 1;      // the layer's group: a grid factor, a 64-channel tile stays inside one group
+  if constexpr (GEN) { ngrp = a.g.group; grp = task % ngrp; task /= ngrp; }
+  const int part = task;
   const long long q0 = (long long)part * a.per_part, q1 = min(q0 + a.per_part, a.chunks);
   const bool active = 4 * ab + wave < a.G;          // a wave beyond the last channel group only helps staging
 
@@ -352,9 +404,9 @@ __global__ __launch_bounds__(kThreads) void conv_general_wgrad(WgradArgs a) {
   float cv[4], xv[16];
   KRow kr[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) kr[i] = k_row(kt * kKC + wave + 4 * i, a.g.k);
+  for (int i = 0; i < 4; ++i) kr[i] = k_row(kt * kKC + wave + 4 * i, a.g.kh, GEN ? a.g.kw : a.g.kh);
   // chunk q's values are fetched while chunk q - 1 is multiplied (the last chunk of the part is fetched twice: no branch)
-  wgrad_fetch(a, kr, q0, 64 * ab + wave, lane, cv, xv);
+  wgrad_fetch<GEN>(a, kr, q0, grp, 64 * ab + wave, lane, cv, xv);
   for (long long q = q0; q < q1; ++q) {
     __syncthreads();      // the previous chunk's reads are done
 #pragma unroll
@@ -362,7 +414,7 @@ __global__ __launch_bounds__(kThreads) void conv_general_wgrad(WgradArgs a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) xs[(wave + 4 * i) * kColStrideW + lane] = xv[i];
     __syncthreads();
-    wgrad_fetch(a, kr, min(q + 1, q1 - 1), 64 * ab + wave, lane, cv, xv);
+    wgrad_fetch<GEN>(a, kr, min(q + 1, q1 - 1), grp, 64 * ab + wave, lane, cv, xv);
     if (active) {
       const float* xr = xs + (16 * wave + (lane & 15)) * kColStrideW + (lane >> 4);
       const float* cr = col + (lane & 15) * kColStrideW + (lane >> 4);
@@ -372,19 +424,24 @@ __global__ __launch_bounds__(kThreads) void conv_general_wgrad(WgradArgs a) {
   }
   if (active) {
     // lane holds channels 16 g + 4 (lane >> 4) + r of k-column 16 kt + (lane & 15)
-    float* o = a.ws + ((size_t)part * (16 * a.G) + 16 * (4 * ab + wave) + 4 * (lane >> 4)) * (size_t)a.Kpad + (size_t)kt * kKC + (lane & 15);
+    float* o = a.ws + (((size_t)part * ngrp + grp) * (16 * a.G) + 16 * (4 * ab + wave) + 4 * (lane >> 4)) * (size_t)a.Kpad + (size_t)kt * kKC + (lane & 15);
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[(size_t)r * a.Kpad] = acc[r];
   }
 }
 
-// weight_diff[a][k] (+)= the parts in part order
-__global__ void conv_general_wgrad_finalize(const float* ws, float* dw, int A, long long K, long long Kpad, int rows, int nsplit, int accumulate) {
-  const long long total = (long long)A * K;
+// weight_diff[a][k] (+)= the parts in part order; blob row a = (group, row of the group), A rows per group, `rows` = 16 G of them in the workspace
+__global__ void conv_general_wgrad_finalize(const float* ws, float* dw, int A, int group, long long K, long long Kpad, int rows, int nsplit, int accumulate) {
+  const long long total = (long long)A * group * K, part_rows = (long long)group * rows;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long ch = i / K, k = i - ch * K;
-    float s = ws[ch * Kpad + k];
-    for (int part = 1; part < nsplit; ++part) s += ws[((long long)part * rows + ch) * Kpad + k];
+    long long row = ch;
+    if (group > 1) {          // (uniform; without groups the workspace rows are the blob's)
+      const int grp = (int)ch / A;
+      row = (long long)grp * rows + ((int)ch - grp * A);
+    }
+    float s = ws[row * Kpad + k];
+    for (int part = 1; part < nsplit; ++part) s += ws[(part * part_rows + row) * Kpad + k];
     dw[i] = accumulate ? dw[i] + s : s;
   }
 }
@@ -409,18 +466,21 @@ __global__ __launch_bounds__(kThreads) void conv_general_bias_grad(const float* 
 }
 
 // ------------------------------------------------------------------------------------------------ packing
-// W [Cs][Cl][kk] -> Wp[g][ks][lane]; swapped: rows are Cl (the transposed gather), else Cs
-__global__ void conv_general_pack(const float* w, float* wp, int M, int R, int kk, long long K, int ksteps, long long total, int swapped) {
+// W [Cs][Cl / group][kk] -> Wp[group][g][ks][lane]; swapped: rows are Clg (the transposed gather), else Csg.  The blob rows of group grp are
+// [grp Csg, ...): not swapped M = Csg, K = Clg kk; swapped R = Csg, M = Clg
+__global__ void conv_general_pack(const float* w, float* wp, int M, int R, int G, int kk, long long K, int ksteps, long long total, int swapped) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int lane = (int)(i & 63);
     const long long r = i >> 6;
-    const int ks = (int)(r % ksteps), g = (int)(r / ksteps);
+    const int ks = (int)(r % ksteps);
+    const long long gg = r / ksteps;
+    const int grp = (int)(gg / G), g = (int)(gg - (long long)grp * G);
     const int m = 16 * g + (lane & 15);
     const long long kg = 4ll * ks + (lane >> 4);
     float v = 0.f;
     if (m < M && kg < K) {
       const long long c = kg / kk, tap = kg - c * kk;
-      v = swapped ? w[(c * M + m) * kk + tap] : w[(long long)m * K + kg];
+      v = swapped ? w[(((long long)grp * R + c) * M + m) * kk + tap] : w[((long long)grp * M + m) * K + kg];
     }
     wp[i] = v;
   }
@@ -429,6 +489,11 @@ __global__ void conv_general_pack(const float* w, float* wp, int M, int R, int k
 // ------------------------------------------------------------------------------------------------ host entry helpers
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 
+inline void set_taps(GatherSrc& a, const Sides& g) {
+  a.kh = g.kh; a.kw = g.kw; a.sh = g.sh; a.sw = g.sw; a.ph = g.ph; a.pw = g.pw; a.dh = g.dh; a.dw = g.dw; a.group = g.group;
+  a.sh_magic = div_magic(g.sh); a.sw_magic = div_magic(g.sw);
+}
+
 int run_gather(const Sides& g, bool tr, const float* in, int in_ctot, int in_c0, const float* packed, const float* bias, float* out, int out_ctot,
                int out_c0, int relu, float slope, hipStream_t st) {
   const Gemm m = pass_gemm(g, tr);
@@ -436,8 +501,8 @@ int run_gather(const Sides& g, bool tr, const float* in, int in_ctot, int in_c0,
   const int IH = tr ? g.Hs : g.Hl, IW = tr ? g.Ws : g.Wl, OH = tr ? g.Hl : g.Hs, OW = tr ? g.Wl : g.Ws;
   a.g.in = in + (size_t)in_c0 * IH * IW;
   a.g.ctot = in_ctot; a.g.C = m.R; a.g.IH = IH; a.g.IW = IW; a.g.OW = OW; a.g.OP = (long long)OH * OW;
-  a.g.k = g.k; a.g.s = g.s; a.g.pad = g.pad;
-  a.g.ow_magic = div_magic(OW); a.g.s_magic = div_magic(g.s);
+  set_taps(a.g, g);
+  a.g.ow_magic = div_magic(OW);
   a.wp = packed; a.bias = bias;
   a.out = out + (size_t)out_c0 * a.g.OP;
   a.out_ctot = out_ctot; a.M = m.M; a.G = m.G; a.ksteps = m.ksteps;
@@ -447,106 +512,91 @@ int run_gather(const Sides& g, bool tr, const float* in, int in_ctot, int in_c0,
   const long long tiles = gather_tiles(g, tr, m, ng);
   if (tiles > kMaxTiles) return fail(FN2_ERR_UNSUPPORTED, "fn2_conv_general: grid too large");
   const dim3 grid((unsigned)tiles), block(kThreads);
-#define FN2_GATHER(TR_, NG_) hipLaunchKernelGGL((conv_general_gather<TR_, NG_>), grid, block, 0, st, a)
+#define FN2_GATHER(TR_, NG_) \
+  do { if (g.plain) hipLaunchKernelGGL((conv_general_gather<TR_, NG_, false>), grid, block, 0, st, a); \
+       else hipLaunchKernelGGL((conv_general_gather<TR_, NG_, true>), grid, block, 0, st, a); } while (0)
   if (tr) { if (ng == 1) FN2_GATHER(true, 1); else if (ng == 2) FN2_GATHER(true, 2); else FN2_GATHER(true, 4); }
   else { if (ng == 1) FN2_GATHER(false, 1); else if (ng == 2) FN2_GATHER(false, 2); else FN2_GATHER(false, 4); }
 #undef FN2_GATHER
   return check_launch("fn2_conv_general");
 }
 
-int check_slices(const char* what, const fn2_conv_desc* d, int bottom_channels, int bottom_c0, int top_channels, int top_c0) {
-  if (bottom_c0 < 0 || bottom_channels < 1 || (long long)bottom_c0 + d->Cin > bottom_channels || top_c0 < 0 || top_channels < 1 ||
-      (long long)top_c0 + d->Cout > top_channels)
+int check_slices(const char* what, const Sides& g, int bottom_channels, int bottom_c0, int top_channels, int top_c0) {
+  if (bottom_c0 < 0 || bottom_channels < 1 || (long long)bottom_c0 + g.Cin > bottom_channels || top_c0 < 0 || top_channels < 1 ||
+      (long long)top_c0 + g.Cout > top_channels)
     return fail(FN2_ERR_INVALID_ARG, "%s: channel slice outside the blob", what);
   return FN2_OK;
 }
 
-int refuse(const char* what, const fn2_conv_desc* d, int transposed) {
-  if (!d) return fail(FN2_ERR_UNSUPPORTED, "%s: null descriptor", what);
-  return fail(FN2_ERR_UNSUPPORTED, "%s: no kernel for %s N=%d Cin=%d %dx%d Cout=%d kernel=%d stride=%d pad=%d (invalid, empty output, or beyond the 32-bit index limits)",
-              what, transposed ? "Deconvolution" : "Convolution", d->N, d->Cin, d->Hin, d->Win, d->Cout, d->kernel, d->stride, d->pad);
+int refuse(const char* what, const int* v, int transposed) {
+  if (!v) return fail(FN2_ERR_UNSUPPORTED, "%s: null descriptor", what);
+  return fail(FN2_ERR_UNSUPPORTED,
+              "%s: no kernel for %s N=%d Cin=%d %dx%d Cout=%d kernel=%dx%d stride=%dx%d pad=%dx%d dilation=%dx%d group=%d (invalid, empty output, or beyond "
+              "the 32-bit index limits)",
+              what, transposed ? "Deconvolution" : "Convolution", v[kGN], v[kGCin], v[kGHin], v[kGWin], v[kGCout], v[kGkh], v[kGkw], v[kGsh], v[kGsw],
+              v[kGph], v[kGpw], v[kGdh], v[kGdw], v[kGgroup]);
 }
 
-}  // namespace
-}  // namespace fn2
-
-using namespace fn2;
-
-FN2_API int fn2_conv_general_supported(const fn2_conv_desc* desc, int transposed) {
-  Sides g;
-  return supported(desc, transposed, g) ? 1 : 0;
-}
-
-FN2_API int fn2_debug_set_conv_general_groups(int groups) {
-  if (groups != 0 && groups != 1 && groups != 2 && groups != 4)
-    return fail(FN2_ERR_INVALID_ARG, "fn2_debug_set_conv_general_groups: %d (0 = by geometry, 1, 2 or 4)", groups);
-  forced_groups() = groups;
-  return FN2_OK;
-}
-
-FN2_API int fn2_conv_general_sizes(const fn2_conv_desc* desc, int transposed, size_t* forward_packed, size_t* backward_data_packed,
-                                   size_t* backward_weights_packed, size_t* backward_weights_workspace) {
+// ------------------------------------------------------------------------------------------------ the entry points, on the 14 ints
+int geom_sizes(const char* what, const int* geom, int transposed, size_t* forward_packed, size_t* backward_data_packed, size_t* backward_weights_packed,
+               size_t* backward_weights_workspace) {
   if (forward_packed) *forward_packed = 0;
   if (backward_data_packed) *backward_data_packed = 0;
   if (backward_weights_packed) *backward_weights_packed = 0;
   if (backward_weights_workspace) *backward_weights_workspace = 0;
   Sides g;
-  if (!supported(desc, transposed, g)) return refuse("fn2_conv_general_sizes", desc, transposed);
-  if (forward_packed) *forward_packed = packed_floats(pass_gemm(g, pass_is_tr(transposed, 0)));
-  if (backward_data_packed) *backward_data_packed = packed_floats(pass_gemm(g, pass_is_tr(transposed, 1)));
+  if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
+  if (forward_packed) *forward_packed = packed_floats(g, pass_gemm(g, pass_is_tr(transposed, 0)));
+  if (backward_data_packed) *backward_data_packed = packed_floats(g, pass_gemm(g, pass_is_tr(transposed, 1)));
   if (backward_weights_workspace) *backward_weights_workspace = make_wgrad(g).workspace_bytes;
   return FN2_OK;
 }
 
-FN2_API int fn2_conv_general_pack_weights(const fn2_conv_desc* desc, int transposed, int pass, const float* weight, float* packed, void* stream) {
+int geom_pack_weights(const char* what, const int* geom, int transposed, int pass, const float* weight, float* packed, void* stream) {
   Sides g;
-  if (!supported(desc, transposed, g)) return refuse("fn2_conv_general_pack_weights", desc, transposed);
-  if (pass < 0 || pass > 2) return fail(FN2_ERR_INVALID_ARG, "fn2_conv_general_pack_weights: pass %d (0 forward, 1 data gradient, 2 weight gradient)", pass);
+  if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
+  if (pass < 0 || pass > 2) return fail(FN2_ERR_INVALID_ARG, "%s: pass %d (0 forward, 1 data gradient, 2 weight gradient)", what, pass);
   if (pass == 2) return FN2_OK;      // the weight gradient has no weight operand
-  if (!weight || !packed) return fail(FN2_ERR_INVALID_ARG, "fn2_conv_general_pack_weights: null blob");
-  if (misaligned(weight) || misaligned(packed)) return fail(FN2_ERR_INVALID_ARG, "fn2_conv_general_pack_weights: blobs must be 4-byte aligned");
+  if (!weight || !packed) return fail(FN2_ERR_INVALID_ARG, "%s: null blob", what);
+  if (misaligned(weight) || misaligned(packed)) return fail(FN2_ERR_INVALID_ARG, "%s: blobs must be 4-byte aligned", what);
   const bool tr = pass_is_tr(transposed, pass);
   const Gemm m = pass_gemm(g, tr);
-  const long long total = (long long)packed_floats(m);
-  hipLaunchKernelGGL(conv_general_pack, dim3(blocks_for(total, 256)), dim3(256), 0, as_stream(stream), weight, packed, m.M, m.R, g.k * g.k, m.K,
+  const long long total = (long long)packed_floats(g, m);
+  hipLaunchKernelGGL(conv_general_pack, dim3(blocks_for(total, 256)), dim3(256), 0, as_stream(stream), weight, packed, m.M, m.R, m.G, g.kh * g.kw, m.K,
                      m.ksteps, total, tr ? 1 : 0);
-  return check_launch("fn2_conv_general_pack_weights");
+  return check_launch(what);
 }
 
-FN2_API int fn2_conv_general_forward(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
-                                     const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
-                                     int relu, float negative_slope, void* stream) {
-  const char* what = "fn2_conv_general_forward";
+int geom_forward(const char* what, const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0, const float* packed_weight,
+                 const float* bias, float* top, int top_channels, int top_c0, int relu, float negative_slope, void* stream) {
   Sides g;
-  if (!supported(desc, transposed, g)) return refuse(what, desc, transposed);
+  if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
   if (!bottom || !packed_weight || !top) return fail(FN2_ERR_INVALID_ARG, "%s: null blob", what);
-  if (const int rc = check_slices(what, desc, bottom_channels, bottom_c0, top_channels, top_c0)) return rc;
+  if (const int rc = check_slices(what, g, bottom_channels, bottom_c0, top_channels, top_c0)) return rc;
   if (misaligned(bottom) || misaligned(packed_weight) || misaligned(top) || misaligned(bias))
     return fail(FN2_ERR_INVALID_ARG, "%s: blobs must be 4-byte aligned", what);
   return run_gather(g, pass_is_tr(transposed, 0), bottom, bottom_channels, bottom_c0, packed_weight, bias, top, top_channels, top_c0, relu,
                     negative_slope, as_stream(stream));
 }
 
-FN2_API int fn2_conv_general_backward_data(const fn2_conv_desc* desc, int transposed, const float* top_diff, int top_channels, int top_c0,
-                                           const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
-  const char* what = "fn2_conv_general_backward_data";
+int geom_backward_data(const char* what, const int* geom, int transposed, const float* top_diff, int top_channels, int top_c0,
+                       const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
   Sides g;
-  if (!supported(desc, transposed, g)) return refuse(what, desc, transposed);
+  if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
   if (!top_diff || !packed_weight || !bottom_diff) return fail(FN2_ERR_INVALID_ARG, "%s: null blob", what);
-  if (const int rc = check_slices(what, desc, bottom_channels, bottom_c0, top_channels, top_c0)) return rc;
+  if (const int rc = check_slices(what, g, bottom_channels, bottom_c0, top_channels, top_c0)) return rc;
   if (misaligned(top_diff) || misaligned(packed_weight) || misaligned(bottom_diff)) return fail(FN2_ERR_INVALID_ARG, "%s: blobs must be 4-byte aligned", what);
   return run_gather(g, pass_is_tr(transposed, 1), top_diff, top_channels, top_c0, packed_weight, nullptr, bottom_diff, bottom_channels, bottom_c0, 0,
                     0.f, as_stream(stream));
 }
 
-FN2_API int fn2_conv_general_backward_weights(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
-                                              const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff,
-                                              int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* what = "fn2_conv_general_backward_weights";
+int geom_backward_weights(const char* what, const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+                          const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff, int accumulate, void* workspace,
+                          size_t workspace_bytes, void* stream) {
   Sides g;
-  if (!supported(desc, transposed, g)) return refuse(what, desc, transposed);
+  if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
   if (!bottom || !top_diff || !weight_diff) return fail(FN2_ERR_INVALID_ARG, "%s: null blob", what);
-  if (const int rc = check_slices(what, desc, bottom_channels, bottom_c0, top_channels, top_c0)) return rc;
+  if (const int rc = check_slices(what, g, bottom_channels, bottom_c0, top_channels, top_c0)) return rc;
   if (misaligned(bottom) || misaligned(top_diff) || misaligned(weight_diff) || misaligned(bias_diff) || misaligned(workspace))
     return fail(FN2_ERR_INVALID_ARG, "%s: blobs must be 4-byte aligned", what);
   const WgradPlan p = make_wgrad(g);
@@ -560,23 +610,123 @@ FN2_API int fn2_conv_general_backward_weights(const fn2_conv_desc* desc, int tra
   const int l_ctot = transposed ? top_channels : bottom_channels, l_c0 = transposed ? top_c0 : bottom_c0;
   WgradArgs a;
   a.g.in = lblob + (size_t)l_c0 * g.Hl * g.Wl;
-  a.g.ctot = l_ctot; a.g.C = g.Cl; a.g.IH = g.Hl; a.g.IW = g.Wl; a.g.OW = g.Ws; a.g.OP = (long long)g.Hs * g.Ws;
-  a.g.k = g.k; a.g.s = g.s; a.g.pad = g.pad;
-  a.g.ow_magic = div_magic(g.Ws); a.g.s_magic = div_magic(g.s);
+  a.g.ctot = l_ctot; a.g.C = p.m.R; a.g.IH = g.Hl; a.g.IW = g.Wl; a.g.OW = g.Ws; a.g.OP = (long long)g.Hs * g.Ws;
+  set_taps(a.g, g);
+  a.g.ow_magic = div_magic(g.Ws);
   a.x = sblob + (size_t)s_c0 * a.g.OP;
-  a.x_ctot = s_ctot; a.A = g.Cs; a.G = p.m.G; a.ablocks = (p.m.G + 3) / 4; a.ktiles = (int)(p.m.Kpad / kKC); a.ptiles = p.ptiles;
+  a.x_ctot = s_ctot; a.A = p.m.M; a.G = p.m.G; a.ablocks = (p.m.G + 3) / 4; a.ktiles = (int)(p.m.Kpad / kKC); a.ptiles = p.ptiles;
   a.chunks = p.chunks; a.per_part = p.per_part; a.Kpad = p.m.Kpad;
   a.ws = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(conv_general_wgrad, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
+  if (g.plain) hipLaunchKernelGGL(conv_general_wgrad<false>, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
+  else hipLaunchKernelGGL(conv_general_wgrad<true>, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
   if (const int rc = check_launch(what)) return rc;
-  hipLaunchKernelGGL(conv_general_wgrad_finalize, dim3(blocks_for((long long)g.Cs * p.m.K, 256)), dim3(256), 0, st, a.ws, weight_diff, g.Cs, p.m.K,
-                     p.m.Kpad, 16 * p.m.G, p.nsplit, accumulate);
+  hipLaunchKernelGGL(conv_general_wgrad_finalize, dim3(blocks_for((long long)g.Cs * p.m.K, 256)), dim3(256), 0, st, a.ws, weight_diff, p.m.M, g.group,
+                     p.m.K, p.m.Kpad, 16 * p.m.G, p.nsplit, accumulate);
   if (const int rc = check_launch(what)) return rc;
   if (bias_diff) {
     const long long Pt = transposed ? (long long)g.Hl * g.Wl : (long long)g.Hs * g.Ws;
-    hipLaunchKernelGGL(conv_general_bias_grad, dim3((unsigned)desc->Cout), dim3(kThreads), 0, st, top_diff + (size_t)top_c0 * Pt, top_channels, g.N, Pt,
+    hipLaunchKernelGGL(conv_general_bias_grad, dim3((unsigned)g.Cout), dim3(kThreads), 0, st, top_diff + (size_t)top_c0 * Pt, top_channels, g.N, Pt,
                        bias_diff, accumulate);
     if (const int rc = check_launch(what)) return rc;
   }
   return FN2_OK;
+}
+
+}  // namespace
+}  // namespace fn2
+
+using namespace fn2;
+
+FN2_API int fn2_conv_general_supported(const fn2_conv_desc* desc, int transposed) {
+  Sides g;
+  return supported(DescGeom(desc).geom(), transposed, g) ? 1 : 0;
+}
+
+FN2_API int fn2_debug_set_conv_general_groups(int groups) {
+  if (groups != 0 && groups != 1 && groups != 2 && groups != 4)
+    return fail(FN2_ERR_INVALID_ARG, "fn2_debug_set_conv_general_groups: %d (0 = by geometry, 1, 2 or 4)", groups);
+  forced_groups() = groups;
+  return FN2_OK;
+}
+
+// the square-tap entry points (include/flownet2_hip_conv_general.h): the same code with (k, k, s, s, p, p, 1, 1, 1)
+FN2_API int fn2_conv_general_sizes(const fn2_conv_desc* desc, int transposed, size_t* forward_packed, size_t* backward_data_packed,
+                                   size_t* backward_weights_packed, size_t* backward_weights_workspace) {
+  const DescGeom d(desc);
+  return geom_sizes("fn2_conv_general_sizes", d.geom(), transposed, forward_packed, backward_data_packed, backward_weights_packed,
+                    backward_weights_workspace);
+}
+
+FN2_API int fn2_conv_general_pack_weights(const fn2_conv_desc* desc, int transposed, int pass, const float* weight, float* packed, void* stream) {
+  const DescGeom d(desc);
+  return geom_pack_weights("fn2_conv_general_pack_weights", d.geom(), transposed, pass, weight, packed, stream);
+}
+
+FN2_API int fn2_conv_general_forward(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+                                     const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
+                                     int relu, float negative_slope, void* stream) {
+  const DescGeom d(desc);
+  return geom_forward("fn2_conv_general_forward", d.geom(), transposed, bottom, bottom_channels, bottom_c0, packed_weight, bias, top, top_channels,
+                      top_c0, relu, negative_slope, stream);
+}
+
+FN2_API int fn2_conv_general_backward_data(const fn2_conv_desc* desc, int transposed, const float* top_diff, int top_channels, int top_c0,
+                                           const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
+  const DescGeom d(desc);
+  return geom_backward_data("fn2_conv_general_backward_data", d.geom(), transposed, top_diff, top_channels, top_c0, packed_weight, bottom_diff,
+                            bottom_channels, bottom_c0, stream);
+}
+
+FN2_API int fn2_conv_general_backward_weights(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+                                              const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff,
+                                              int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  const DescGeom d(desc);
+  return geom_backward_weights("fn2_conv_general_backward_weights", d.geom(), transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels,
+                               top_c0, weight_diff, bias_diff, accumulate, workspace, workspace_bytes, stream);
+}
+
+// the 14-int entry points (include/flownet2_hip_conv_geometry.h)
+FN2_API int fn2_conv_geometry_supported(const int* geom, int transposed) {
+  Sides g;
+  return supported(geom, transposed, g) ? 1 : 0;
+}
+
+FN2_API int fn2_conv_geometry_out_shape(const int* geom, int transposed, int* out_h, int* out_w) {
+  if (out_h) *out_h = 0;
+  if (out_w) *out_w = 0;
+  Sides g;
+  if (!supported(geom, transposed, g)) return refuse("fn2_conv_geometry_out_shape", geom, transposed);
+  if (out_h) *out_h = transposed ? g.Hl : g.Hs;
+  if (out_w) *out_w = transposed ? g.Wl : g.Ws;
+  return FN2_OK;
+}
+
+FN2_API int fn2_conv_geometry_sizes(const int* geom, int transposed, size_t* forward_packed, size_t* backward_data_packed,
+                                    size_t* backward_weights_packed, size_t* backward_weights_workspace) {
+  return geom_sizes("fn2_conv_geometry_sizes", geom, transposed, forward_packed, backward_data_packed, backward_weights_packed,
+                    backward_weights_workspace);
+}
+
+FN2_API int fn2_conv_geometry_pack_weights(const int* geom, int transposed, int pass, const float* weight, float* packed, void* stream) {
+  return geom_pack_weights("fn2_conv_geometry_pack_weights", geom, transposed, pass, weight, packed, stream);
+}
+
+FN2_API int fn2_conv_geometry_forward(const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+                                      const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
+                                      int relu, float negative_slope, void* stream) {
+  return geom_forward("fn2_conv_geometry_forward", geom, transposed, bottom, bottom_channels, bottom_c0, packed_weight, bias, top, top_channels, top_c0,
+                      relu, negative_slope, stream);
+}
+
+FN2_API int fn2_conv_geometry_backward_data(const int* geom, int transposed, const float* top_diff, int top_channels, int top_c0,
+                                            const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
+  return geom_backward_data("fn2_conv_geometry_backward_data", geom, transposed, top_diff, top_channels, top_c0, packed_weight, bottom_diff,
+                            bottom_channels, bottom_c0, stream);
+}
+
+FN2_API int fn2_conv_geometry_backward_weights(const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+                                               const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff,
+                                               int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  return geom_backward_weights("fn2_conv_geometry_backward_weights", geom, transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels,
+                               top_c0, weight_diff, bias_diff, accumulate, workspace, workspace_bytes, stream);
 }

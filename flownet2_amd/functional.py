@@ -42,33 +42,47 @@ def _note_fallback(what, x, w):
         print("library fallback: %s bottom %s weight %s" % (what, tuple(x.shape), tuple(w.shape)), flush=True)
 
 
-def lib_conv2d(x, w, b, stride, pad):
+def _plain_call(stride, pad, dilation, groups):
+    """The arguments lib_conv2d / lib_conv_transpose2d took before they learnt pairs, dilation and groups."""
+    return not isinstance(stride, (tuple, list)) and not isinstance(pad, (tuple, list)) and dilation == 1 and groups == 1
+
+
+def _lib_conv(x, w, b, stride, pad, dilation, groups, transposed):
+    if _plain_call(stride, pad, dilation, groups):
+        desc = _general_desc(x, w, b, stride, pad, transposed)
+        if desc is not None:
+            return _GeneralConv.apply(x, w, b, desc, transposed)
+        kw = dict(stride=stride, padding=pad)
+        what = "%s{stride %d, pad %d}" % ("Deconvolution" if transposed else "Convolution", stride, pad)
+    else:
+        geom = _general_geom(x, w, b, stride, pad, dilation, groups, transposed)
+        if geom is not None:
+            return _GeometryConv.apply(x, w, b, geom, transposed)
+        kw = dict(stride=stride, padding=pad, dilation=dilation, groups=groups)
+        what = "%s{stride %s, pad %s, dilation %s, group %d}" % ("Deconvolution" if transposed else "Convolution", stride, pad, dilation, groups)
+    if x.is_cuda:
+        _note_fallback(what, x, w)
+    f = torch.nn.functional.conv_transpose2d if transposed else torch.nn.functional.conv2d
+    if not _BATCH_INVARIANT[0] or not x.is_cuda:
+        return f(x, w, b, **kw)
+    return torch.cat([f(x[n:n + 1], w, b, **kw) for n in range(x.shape[0])], 0)
+
+
+def lib_conv2d(x, w, b, stride, pad, dilation=1, groups=1):
     """Last resort for a Convolution no own kernel serves (a layer shape outside FlowNet's families, or CPU tensors): the library's
-    convolution through torch, counted in LIBRARY_FALLBACKS for CUDA tensors; sample by sample in batch-invariant mode."""
-    desc = _general_desc(x, w, b, stride, pad, False)
-    if desc is not None:
-        return _GeneralConv.apply(x, w, b, desc, False)
-    if x.is_cuda:
-        _note_fallback("Convolution{stride %d, pad %d}" % (stride, pad), x, w)
-    if not _BATCH_INVARIANT[0] or not x.is_cuda:
-        return torch.nn.functional.conv2d(x, w, b, stride=stride, padding=pad)
-    return torch.cat([torch.nn.functional.conv2d(x[n:n + 1], w, b, stride=stride, padding=pad) for n in range(x.shape[0])], 0)
+    convolution through torch, counted in LIBRARY_FALLBACKS for CUDA tensors; sample by sample in batch-invariant mode.  stride, pad and
+    dilation: an int or a pair (h, w); w: [Cout, Cin / groups, kh, kw]."""
+    return _lib_conv(x, w, b, stride, pad, dilation, groups, False)
 
 
-def lib_conv_transpose2d(x, w, b, stride, pad):
-    desc = _general_desc(x, w, b, stride, pad, True)
-    if desc is not None:
-        return _GeneralConv.apply(x, w, b, desc, True)
-    if x.is_cuda:
-        _note_fallback("Deconvolution{stride %d, pad %d}" % (stride, pad), x, w)
-    if not _BATCH_INVARIANT[0] or not x.is_cuda:
-        return torch.nn.functional.conv_transpose2d(x, w, b, stride=stride, padding=pad)
-    return torch.cat([torch.nn.functional.conv_transpose2d(x[n:n + 1], w, b, stride=stride, padding=pad) for n in range(x.shape[0])], 0)
+def lib_conv_transpose2d(x, w, b, stride, pad, dilation=1, groups=1):
+    """The same for a Deconvolution; w: [Cin, Cout / groups, kh, kw]."""
+    return _lib_conv(x, w, b, stride, pad, dilation, groups, True)
 
 
 # What lib_conv2d / lib_conv_transpose2d run CUDA float32 tensors on: "library" (the default: the library convolution through torch, counted
-# and refused under FN2_STRICT=1 as above) or "own" (the general-geometry kernels, csrc/conv_general.hip: any square-tap geometry, exact
-# fp32, forward and backward; nothing leaves the own kernels, so nothing is counted).  A switch of its own, not one of ARITH_SWITCHES.
+# and refused under FN2_STRICT=1 as above) or "own" (the general-geometry kernels, csrc/conv_general.hip: any taps, per-axis stride, pad and
+# dilation, groups; exact fp32, forward and backward; nothing leaves the own kernels, so nothing is counted).  A switch of its own, not one of ARITH_SWITCHES.
 _GENERAL_CONVOLUTIONS = ("library", "own")
 _GENERAL_CONV = ["library"]
 
@@ -138,6 +152,49 @@ class _GeneralConv(torch.autograd.Function):
         if need_w or need_b:
             xb, x0 = _channel_slice(x)
             gw, gb = ops.conv_general_backward_weights(xb, d, desc, transposed, bias=bool(need_b), bottom_c0=x0)
+        return gx, (gw if need_w else None), gb, None, None
+
+
+def _general_geom(x, w, b, stride, pad, dilation, groups, transposed):
+    """The 14-int geometry of the layer where the switch is "own" and the widened general kernels take the call, else None."""
+    if _GENERAL_CONV[0] != "own" or not (x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float32 and x.dim() == w.dim() == 4):
+        return None
+    if groups < 1 or (b is not None and (not b.is_cuda or b.dtype != torch.float32)):
+        return None
+    Cout = w.shape[1] * groups if transposed else w.shape[0]
+    if (x.shape[1] != w.shape[0]) if transposed else (x.shape[1] != w.shape[1] * groups):
+        return None
+    geom = ops.conv_geometry(x.shape[0], x.shape[1], x.shape[2], x.shape[3], Cout, (w.shape[2], w.shape[3]), stride, pad, dilation, groups)
+    return geom if ops.conv_geometry_supported(geom, transposed) else None
+
+
+class _GeometryConv(torch.autograd.Function):
+    """Convolution / Deconvolution with rectangular taps, per-axis stride / pad / dilation and groups on the general kernels; the operands
+    are packed once per weight version, keyed by the whole geometry."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, geom, transposed):
+        ctx.geom, ctx.transposed, ctx.has_bias = geom, transposed, b is not None
+        ctx.save_for_backward(x, w)
+        packed = _cached_pack(_PACKED_T, w, ("geometry-fwd", transposed) + tuple(geom),
+                              lambda: ops.conv_geometry_pack_weights(w.detach().contiguous(), geom, transposed))
+        xb, x0 = _channel_slice(x)
+        return ops.conv_geometry_forward(xb, packed, b.detach() if b is not None else None, geom, transposed, in_c0=x0)
+
+    @staticmethod
+    def backward(ctx, d):
+        x, w = ctx.saved_tensors
+        geom, transposed = ctx.geom, ctx.transposed
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        d = d.contiguous()
+        gx = gw = gb = None
+        if need_x:
+            packed = _cached_pack(_PACKED_T, w, ("geometry-dgrad", transposed) + tuple(geom),
+                                  lambda: ops.conv_geometry_pack_weights(w.detach().contiguous(), geom, transposed, backward=True))
+            gx = ops.conv_geometry_backward_data(d, packed, geom, transposed)
+        if need_w or need_b:
+            xb, x0 = _channel_slice(x)
+            gw, gb = ops.conv_geometry_backward_weights(xb, d, geom, transposed, bias=bool(need_b), bottom_c0=x0)
         return gx, (gw if need_w else None), gb, None, None
 
 

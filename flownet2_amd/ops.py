@@ -893,6 +893,132 @@ def conv_general_backward_weights(bottom, top_diff, desc, transposed=False, weig
     return weight_diff, (bias_diff if bias else None)
 
 
+def _pair(v, what):
+    """An int or a pair -> (h, w)."""
+    if isinstance(v, (tuple, list)):
+        if len(v) == 1:
+            return int(v[0]), int(v[0])
+        if len(v) != 2:
+            raise ValueError(f"{what}: one value or a pair, not {v!r}")
+        return int(v[0]), int(v[1])
+    return int(v), int(v)
+
+
+def conv_geometry(N, Cin, Hin, Win, Cout, kernel, stride=1, pad=0, dilation=1, group=1):
+    """The 14 ints of include/flownet2_hip_conv_geometry.h: {N, Cin, Hin, Win, Cout, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+    dilation_h, dilation_w, group}; kernel, stride, pad and dilation an int or a pair (h, w)."""
+    vals = (N, Cin, Hin, Win, Cout) + _pair(kernel, "kernel") + _pair(stride, "stride") + _pair(pad, "pad") + _pair(dilation, "dilation") + (group,)
+    return (C.c_int * 14)(*(int(v) for v in vals))
+
+
+def conv_geometry_supported(geom, transposed=False) -> bool:
+    """Whether the general-geometry kernels take this layer (fn2_conv_geometry_supported; host-only)."""
+    return bool(_lib.lib().fn2_conv_geometry_supported(geom, int(bool(transposed))))
+
+
+def conv_geometry_sizes(geom, transposed=False):
+    """(floats of the forward operand, of the data-gradient operand, of the weight-gradient operand (0), bytes of the weight-gradient
+    workspace) (fn2_conv_geometry_sizes; host-only)."""
+    n = [C.c_size_t() for _ in range(4)]
+    check(_lib.lib().fn2_conv_geometry_sizes(geom, int(bool(transposed)), *(C.byref(v) for v in n)))
+    return tuple(int(v.value) for v in n)
+
+
+def conv_geometry_out_shape(geom, transposed=False):
+    """(Hout, Wout) of the layer as the reference computes it with the dilated extent (fn2_conv_geometry_out_shape; host-only)."""
+    h, w = C.c_int(), C.c_int()
+    check(_lib.lib().fn2_conv_geometry_out_shape(geom, int(bool(transposed)), C.byref(h), C.byref(w)))
+    return int(h.value), int(w.value)
+
+
+def _geometry_weight_shape(geom, transposed):
+    N, Cin, Hin, Win, Cout, kh, kw = geom[:7]
+    group = geom[13]
+    return (Cin, Cout // group, kh, kw) if transposed else (Cout, Cin // group, kh, kw)
+
+
+def conv_geometry_pack_weights(weight, geom, transposed=False, backward=False):
+    """The layer's weight blob -> the operand of the forward (backward: data-gradient) kernel (fn2_conv_geometry_pack_weights)."""
+    w = _chk(weight, "weight")
+    sizes = conv_geometry_sizes(geom, transposed)
+    if tuple(w.shape) != _geometry_weight_shape(geom, transposed):
+        raise ValueError("conv_geometry_pack_weights: weight of shape %s is not this layer's" % (tuple(w.shape),))
+    packed = torch.empty(sizes[1 if backward else 0], device=w.device, dtype=torch.float32)
+    check(_lib.lib().fn2_conv_geometry_pack_weights(geom, int(bool(transposed)), 1 if backward else 0, _ptr(w), _ptr(packed), _stream()))
+    return packed
+
+
+def _geometry_blobs(what, geom, transposed, bottom, bottom_c0, top, top_c0):
+    Ho, Wo = conv_geometry_out_shape(geom, transposed)
+    N, Cin, Hin, Win, Cout = geom[:5]
+    for t, c0, Cc, H, W, name in ((bottom, bottom_c0, Cin, Hin, Win, "bottom"), (top, top_c0, Cout, Ho, Wo, "top")):
+        if t is not None and (not t.is_contiguous() or (t.shape[0], t.shape[2], t.shape[3]) != (N, H, W) or c0 < 0 or c0 + Cc > t.shape[1]):
+            raise ValueError(f"{what}: {name} blob {tuple(t.shape)} does not hold the layer's [{N},{Cc},{H},{W}] at channel {c0}")
+    return Ho, Wo
+
+
+def conv_geometry_forward(x, packed, bias, geom, transposed=False, relu=False, negative_slope=0.0, out=None, out_c0=0, in_c0=0):
+    """act(layer(x[:, in_c0:in_c0+Cin]) + bias) -> out[:, out_c0:out_c0+Cout] (a new blob if out is None) (fn2_conv_geometry_forward).
+    packed = conv_geometry_pack_weights(weight, geom, transposed)."""
+    x = _chk(x, "bottom[0]")
+    if out is not None:
+        _chk(out, "top[0]")
+    Ho, Wo = _geometry_blobs("conv_geometry_forward", geom, transposed, x, in_c0, out, out_c0)
+    if out is None:
+        out = torch.empty((geom[0], geom[4], Ho, Wo), device=x.device, dtype=torch.float32)
+    b = _chk_opt(bias, "bias", ndim=1)
+    pw = _chk(packed, "packed weight", ndim=None)
+    if pw.numel() != conv_geometry_sizes(geom, transposed)[0]:
+        raise ValueError("conv_geometry_forward: the operand has %d floats, not what the forward reads for this layer" % pw.numel())
+    check(_lib.lib().fn2_conv_geometry_forward(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(in_c0), _ptr(pw), _ptr(b), _ptr(out),
+                                               out.shape[1], int(out_c0), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
+    return out
+
+
+def conv_geometry_backward_data(top_diff, packed, geom, transposed=False, top_c0=0, out=None, out_c0=0):
+    """bottom_diff [N, Cin, Hin, Win] (or the slice of `out` at out_c0) of the layer (fn2_conv_geometry_backward_data).
+    packed = conv_geometry_pack_weights(weight, geom, transposed, backward=True)."""
+    d = _chk(top_diff, "top_diff")
+    if out is not None:
+        _chk(out, "bottom diff")
+    _geometry_blobs("conv_geometry_backward_data", geom, transposed, out, out_c0, d, top_c0)
+    if out is None:
+        out = torch.empty((geom[0], geom[1], geom[2], geom[3]), device=d.device, dtype=torch.float32)
+    pw = _chk(packed, "packed weight", ndim=None)
+    if pw.numel() != conv_geometry_sizes(geom, transposed)[1]:
+        raise ValueError("conv_geometry_backward_data: the operand has %d floats, not what the data gradient reads for this layer" % pw.numel())
+    check(_lib.lib().fn2_conv_geometry_backward_data(geom, int(bool(transposed)), _ptr(d), d.shape[1], int(top_c0), _ptr(pw), _ptr(out),
+                                                     out.shape[1], int(out_c0), _stream()))
+    return out
+
+
+def conv_geometry_backward_weights(bottom, top_diff, geom, transposed=False, weight_diff=None, bias_diff=None, bias=True, accumulate=False,
+                                   bottom_c0=0, top_c0=0):
+    """(weight_diff, bias_diff) of the layer (fn2_conv_geometry_backward_weights; deterministic).  accumulate adds into the diffs given;
+    bias=False: no bias gradient (None comes back)."""
+    x, d = _chk(bottom, "bottom"), _chk(top_diff, "top_diff")
+    _geometry_blobs("conv_geometry_backward_weights", geom, transposed, x, bottom_c0, d, top_c0)
+    shape, Cout = _geometry_weight_shape(geom, transposed), geom[4]
+    if weight_diff is None:
+        if accumulate:
+            raise ValueError("conv_geometry_backward_weights: accumulate needs the diffs to add into")
+        weight_diff = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif tuple(_chk(weight_diff, "weight diff").shape) != shape or not weight_diff.is_contiguous():
+        raise ValueError("conv_geometry_backward_weights: weight diff has the wrong shape")
+    if bias and bias_diff is None:
+        if accumulate:
+            raise ValueError("conv_geometry_backward_weights: accumulate needs the diffs to add into")
+        bias_diff = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    elif bias and (tuple(_chk(bias_diff, "bias diff", ndim=1).shape) != (Cout,) or not bias_diff.is_contiguous()):
+        raise ValueError("conv_geometry_backward_weights: bias diff has the wrong shape")
+    need = conv_geometry_sizes(geom, transposed)[3]
+    ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
+    check(_lib.lib().fn2_conv_geometry_backward_weights(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1],
+                                                        int(top_c0), _ptr(weight_diff), _ptr(bias_diff if bias else None), int(bool(accumulate)),
+                                                        _ptr(ws), need, _stream()))
+    return weight_diff, (bias_diff if bias else None)
+
+
 def conv_mfma_supported(Cin, Hin, Win, Cout, kernel, stride, pad) -> bool:
     return bool(_lib.lib().fn2_conv_mfma_supported(int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad)))
 

@@ -64,9 +64,22 @@ def fill_blob(blob: Blob, filler: dict, seed_name: str = ""):
         raise CheckError("Unknown filler name: " + t)                                   # filler.hpp:319
 
 
+def _dims(cp, name, default, what=None):
+    """The repeated field `name` of a ConvolutionParameter as (h, w): specified once, or once per spatial dimension
+    (base_conv_layer.cpp:35-44, 59-70, 83-93, 98-108); `default` None: at least one entry is required."""
+    v = cp.get(name)
+    v = [] if v is None else (list(v) if isinstance(v, (list, tuple)) else [v])
+    CHECK(len(v) in ((1, 2) if default is None else (0, 1, 2)),
+          "%s must be specified once, or once per spatial dimension (%s specified %d times; 2 spatial dims)." % (what or name, what or name, len(v)))
+    if not v:
+        return default, default
+    return int(v[0]), int(v[-1])
+
+
 class _ConvBase(Layer):
-    """BaseConvolutionLayer::LayerSetUp / Reshape (base_conv_layer.cpp:15-254): square or h / w kernels, pad, stride; group 1 and
-    dilation 1 only (all a FlowNet uses)."""
+    """BaseConvolutionLayer::LayerSetUp / Reshape (base_conv_layer.cpp:15-254): square or h / w kernels, pads and strides, dilation and
+    group, two spatial axes.  A PLAIN layer (square taps, one stride, one pad, dilation 1, group 1: all a FlowNet uses) runs on the routed
+    kernels of nets.py; every other layer runs forward and backward through functional.lib_conv2d / lib_conv_transpose2d."""
     transposed = False
 
     def MinBottomBlobs(self): return 1
@@ -74,27 +87,48 @@ class _ConvBase(Layer):
     def EqualNumBottomTopBlobs(self): return True                                        # base_conv_layer.hpp:29
 
     def _geom(self):
+        """(num_output, (kh, kw), (ph, pw), (sh, sw), (dh, dw), group, bias_term) as base_conv_layer.cpp:24-124 reads them."""
         cp = self.layer_param_.convolution_param
         CHECK("num_output" in cp, "num_output is required")
-        kh = int(cp["kernel_h"]) if "kernel_h" in cp else int(_first(cp.get("kernel_size"), 0))
-        kw = int(cp["kernel_w"]) if "kernel_w" in cp else int(_first(cp.get("kernel_size"), 0))
-        CHECK(kh > 0 and kw > 0, "Filter dimensions cannot be zero.")                    # base_conv_layer.cpp:45
-        ph = int(cp["pad_h"]) if "pad_h" in cp else int(_first(cp.get("pad"), 0))
-        pw = int(cp["pad_w"]) if "pad_w" in cp else int(_first(cp.get("pad"), 0))
-        sh = int(cp["stride_h"]) if "stride_h" in cp else int(_first(cp.get("stride"), 1))
-        sw = int(cp["stride_w"]) if "stride_w" in cp else int(_first(cp.get("stride"), 1))
-        CHECK(int(cp.get("group", 1)) == 1, "group > 1 is not supported by this mirror")
-        CHECK(int(_first(cp.get("dilation"), 1)) == 1, "dilation > 1 is not supported by this mirror")
-        CHECK(kh == kw and ph == pw and sh == sw, "only square kernels / pads / strides are supported by this mirror")
-        return int(cp["num_output"]), kh, ph, sh, bool(cp.get("bias_term", True))
+        CHECK(int(cp.get("axis", 1)) == 1 and not cp.get("force_nd_im2col", False), "N-dimensional convolution (axis, force_nd_im2col) is not supported")
+        if "kernel_h" in cp or "kernel_w" in cp:
+            CHECK(not cp.get("kernel_size"), "Either kernel_size or kernel_h/w should be specified; not both.")
+            kh, kw = int(cp.get("kernel_h", 0)), int(cp.get("kernel_w", 0))
+        else:
+            kh, kw = _dims(cp, "kernel_size", None)
+        CHECK(kh > 0 and kw > 0, "Filter dimensions must be nonzero.")                   # base_conv_layer.cpp:45-47
+        if "stride_h" in cp or "stride_w" in cp:
+            CHECK(not cp.get("stride"), "Either stride or stride_h/w should be specified; not both.")
+            sh, sw = int(cp.get("stride_h", 1)), int(cp.get("stride_w", 1))
+        else:
+            sh, sw = _dims(cp, "stride", 1)
+        CHECK(sh > 0 and sw > 0, "Stride dimensions must be nonzero.")                   # base_conv_layer.cpp:69
+        if "pad_h" in cp or "pad_w" in cp:
+            CHECK(not cp.get("pad"), "Either pad or pad_h/w should be specified; not both.")
+            ph, pw = int(cp.get("pad_h", 0)), int(cp.get("pad_w", 0))
+        else:
+            ph, pw = _dims(cp, "pad", 0)
+        dh, dw = _dims(cp, "dilation", 1)
+        CHECK(dh >= 1 and dw >= 1, "Dilation dimensions must be nonzero.")
+        group = int(cp.get("group", 1))
+        CHECK(group >= 1, "group must be positive")
+        return int(cp["num_output"]), (kh, kw), (ph, pw), (sh, sw), (dh, dw), group, bool(cp.get("bias_term", True))
 
     def LayerSetUp(self, bottom, top):
-        self.num_output_, self.kernel_, self.pad_, self.stride_, self.bias_term_ = self._geom()
+        self.num_output_, self.kernel_hw_, self.pad_hw_, self.stride_hw_, self.dilation_hw_, self.group_, self.bias_term_ = self._geom()
+        self.plain_ = (self.kernel_hw_[0] == self.kernel_hw_[1] and self.pad_hw_[0] == self.pad_hw_[1] and self.stride_hw_[0] == self.stride_hw_[1]
+                       and self.dilation_hw_ == (1, 1) and self.group_ == 1)
+        # what the plain code paths read; a layer that is not plain never reaches them
+        self.kernel_, self.pad_, self.stride_ = (self.kernel_hw_[0], self.pad_hw_[0], self.stride_hw_[0]) if self.plain_ else (None, None, None)
         self.fused_relu_tops_ = {}              # top index -> negative slope of an in-place ReLU folded in by the executor
         cin = bottom[0].channels()
+        CHECK(self.num_output_ > 0, "num_output must be positive")                       # base_conv_layer.cpp:120
+        CHECK(cin % self.group_ == 0, "Check failed: channels_ % group_ == 0")           # base_conv_layer.cpp:122
+        CHECK(self.num_output_ % self.group_ == 0, "Number of output should be multiples of group.")     # base_conv_layer.cpp:123-124
         cp = self.layer_param_.convolution_param
         if not self.blobs_:                                                               # base_conv_layer.cpp:125-152
-            wshape = [cin, self.num_output_, self.kernel_, self.kernel_] if self.transposed else [self.num_output_, cin, self.kernel_, self.kernel_]
+            kh, kw = self.kernel_hw_
+            wshape = [cin, self.num_output_ // self.group_, kh, kw] if self.transposed else [self.num_output_, cin // self.group_, kh, kw]
             w = Blob(*wshape, device=bottom[0].device)
             fill_blob(w, cp.get("weight_filler", {}), self.layer_param_.name + ".w")
             self.blobs_ = [w]
@@ -104,13 +138,14 @@ class _ConvBase(Layer):
                 self.blobs_.append(b)
 
     def _out_hw(self, h, w):
-        k, p, s = self.kernel_, self.pad_, self.stride_
-        if self.transposed:
-            return s * (h - 1) + k - 2 * p, s * (w - 1) + k - 2 * p                       # deconv_layer.cpp:8-22
-        return (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1                        # conv_layer.cpp:8-23
+        out = []
+        for n, k, p, s, d in zip((h, w), self.kernel_hw_, self.pad_hw_, self.stride_hw_, self.dilation_hw_):
+            ext = d * (k - 1) + 1
+            out.append(s * (n - 1) + ext - 2 * p if self.transposed else (n + 2 * p - ext) // s + 1)      # deconv_layer.cpp:8-22 / conv_layer.cpp:8-23
+        return tuple(out)
 
     def Reshape(self, bottom, top):
-        cin = self.blobs_[0].shape(0) if self.transposed else self.blobs_[0].shape(1)
+        cin = self.blobs_[0].shape(0) if self.transposed else self.blobs_[0].shape(1) * self.group_
         CHECK(bottom[0].channels() == cin, "Input size incompatible with convolution kernel.")   # base_conv_layer.cpp:191-192
         for b in bottom[1:]:                                                                     # base_conv_layer.cpp:194-197
             CHECK(b.shape() == bottom[0].shape(), "All inputs must have the same shape.")
@@ -134,6 +169,7 @@ class _ConvBase(Layer):
         tops) run as ONE launch on the bottoms stacked along the batch axis -- the kernels are per-sample -- and the tops are the
         halves of its output."""
         self._stacked = None
+        self._graphs = []                       # of a layer that is not plain (_general_one), one per call of `one`
         if len(bottom) > 1 and len({self._slope(i) for i in range(len(top))}) == 1 and bottom[0].data.is_cuda:
             n = bottom[0].num()
             x = torch.cat([b.data for b in bottom], 0)
@@ -150,8 +186,35 @@ class _ConvBase(Layer):
         if g is not None:
             self.blobs_[k].mutable_gpu_diff().add_(g.reshape(self.blobs_[k].shape()))
 
-    def _backward_one(self, x, y, g, slope, need_x, head):
+    def _general_one(self, x, slope, be):
+        """A layer that is not plain: lib_conv2d / lib_conv_transpose2d of the backend (the general kernels under
+        set_general_convolution("own"), else the counted library), the folded ReLU as a pass of its own.  The autograd graph of the call is
+        kept for Backward_gpu, in call order."""
+        w, b = self.blobs_[0].data, (self.blobs_[1].data if self.bias_term_ else None)
+        name = "lib_conv_transpose2d" if self.transposed else "lib_conv2d"
+        f = torch.nn.functional.conv_transpose2d if self.transposed else torch.nn.functional.conv2d
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_(True) if t is not None else None for t in (x, w, b)]
+            if hasattr(be, name):
+                y = getattr(be, name)(leaves[0], leaves[1], leaves[2], self.stride_hw_, self.pad_hw_, dilation=self.dilation_hw_, groups=self.group_)
+            else:
+                y = f(leaves[0], leaves[1], leaves[2], stride=self.stride_hw_, padding=self.pad_hw_, dilation=self.dilation_hw_, groups=self.group_)
+            if slope is not None:
+                y = torch.nn.functional.leaky_relu(y, slope)
+        self._graphs.append((leaves, y))
+        return y.detach()
+
+    def _general_backward(self, index, g, need_x):
+        leaves, y = self._graphs[index]
+        wanted = [need_x, self.param_propagate_down(0), self.bias_term_ and self.param_propagate_down(1)]
+        inputs = [t for t, need in zip(leaves, wanted) if need]
+        grads = iter(torch.autograd.grad(y, inputs, g.contiguous(), retain_graph=True) if inputs else ())
+        return tuple(next(grads) if need else None for need in wanted)
+
+    def _backward_one(self, x, y, g, slope, need_x, head, index=0):
         from . import functional as Fn, ops
+        if not self.plain_:
+            return self._general_backward(index, g, need_x)
         w = self.blobs_[0].data
         need_w = self.param_propagate_down(0)
         need_b = self.bias_term_ and self.param_propagate_down(1)
@@ -182,7 +245,7 @@ class _ConvBase(Layer):
                     b.diff = gx[i * n:(i + 1) * n]
             return
         for i, (b, t) in enumerate(zip(bottom, top)):
-            gx, gw, db = self._backward_one(b.data, t.data, t.mutable_gpu_diff(), self._slope(i), bool(propagate_down[i]), head)
+            gx, gw, db = self._backward_one(b.data, t.data, t.mutable_gpu_diff(), self._slope(i), bool(propagate_down[i]), head, i)
             self._accumulate(0, gw)
             if self.bias_term_:
                 self._accumulate(1, db)
@@ -206,6 +269,8 @@ class ConvolutionLayer(_ConvBase):
         k, s, p = self.kernel_, self.stride_, self.pad_
 
         def one(x, slope):
+            if not self.plain_:
+                return self._general_one(x, slope, be)
             if k == 1 and s == 1 and p == 0 and slope is None and getattr(self, "diagonal_", None) is not None:
                 # the deploy tail's SCALE convolution (weight_filler diagonal, run-flownet.py:47-48): y[c] = diag[c] x[c] + 0 x[other]
                 y = x * self.diagonal_.view(1, -1, 1, 1)
@@ -243,6 +308,8 @@ class DeconvolutionLayer(_ConvBase):
         k, s, p = self.kernel_, self.stride_, self.pad_
 
         def one(x, slope):
+            if not self.plain_:
+                return self._general_one(x, slope, be)
             if (k, s, p) == (4, 2, 1) and w.shape[0] == 2 and w.shape[1] == 2 and slope is None and hasattr(be, "upsample_flow_deconv"):
                 return be.upsample_flow_deconv(x, w, b)                                   # the upsample_flow heads (csrc/flow_head.hip)
             if (k, s, p) == (4, 2, 1):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Timing of the general-geometry convolution (csrc/conv_general.hip) next to what it stands in for, on the same tensors in one run:
 the library convolution through torch at three shapes outside FlowNet's kernel families, and the specialised own route at one FlowNet
-shape (the conv3_1 class), which states what generality costs.  Forward, data gradient and weight (+ bias) gradient.  Run on the GPU box:
-    python scripts/conv_general_bench.py [--iters 20] [--repeats 5] [--batch 8]
+shape (the conv3_1 class), which states what generality costs; and (--rows geometry) four layers with groups or dilation
+(include/flownet2_hip_conv_geometry.h) against the library.  Forward, data gradient and weight (+ bias) gradient.  Run on the GPU box:
+    python scripts/conv_general_bench.py [--iters 20] [--repeats 5] [--batch 8] [--rows square|geometry|all]
 Per (shape, pass) one line: the median over the repeats of the mean time per call of each side, the spread (min .. max over the repeats),
 the ratio of the medians, and the largest difference between the two results over the result's scale.  The two sides alternate inside
 every repeat; every shape is warmed up first (operands are packed outside the timed window, as a layer packs once per weight version)."""
@@ -25,6 +26,13 @@ SHAPES = [
     ("deconv 4x4/2 32->16 @40x56", True, 32, 40, 56, 16, 4, 2, 1, "library"),
     ("conv3_1 class 3x3/1 256->256 @40x56", False, 256, 40, 56, 256, 3, 1, 1, "specialised"),
 ]
+# name, transposed, Cin, H, W, Cout, kernel, stride, pad, dilation, group: against the library
+GEOMETRY_SHAPES = [
+    ("depthwise 3x3/1 256 @40x56", False, 256, 40, 56, 256, 3, 1, 1, 1, 256),
+    ("dilated 3x3/1 d2 256->256 @40x56", False, 256, 40, 56, 256, 3, 1, 2, 2, 1),
+    ("group-2 5x5/2 64->128 @160x224", False, 64, 160, 224, 128, 5, 2, 2, 1, 2),
+    ("depthwise deconv 4x4/2 128 @40x56", True, 128, 40, 56, 128, 4, 2, 1, 1, 128),
+]
 
 
 def timeit(fn, iters):
@@ -37,13 +45,19 @@ def timeit(fn, iters):
     return e0.elapsed_time(e1) * 1e3 / iters           # us per call
 
 
-def library_passes(x, w, b, g, tr, s, p):
+def library_passes(x, w, b, g, tr, s, p, d=1, group=1):
     conv = F.conv_transpose2d if tr else F.conv2d
 
     def backward(mask):
-        return torch.ops.aten.convolution_backward(g, x, w, [w.shape[1 if tr else 0]], [s, s], [p, p], [1, 1], tr, [0, 0], 1, mask)
-    return {"forward": lambda: conv(x, w, b, stride=s, padding=p), "data gradient": lambda: backward([True, False, False])[0],
+        return torch.ops.aten.convolution_backward(g, x, w, [b.shape[0]], [s, s], [p, p], [d, d], tr, [0, 0], group, mask)
+    return {"forward": lambda: conv(x, w, b, stride=s, padding=p, dilation=d, groups=group), "data gradient": lambda: backward([True, False, False])[0],
             "weight + bias gradient": lambda: backward([False, True, True])[1]}
+
+
+def geometry_passes(x, w, b, g, geom, tr):
+    pf, pd = ops.conv_geometry_pack_weights(w, geom, tr), ops.conv_geometry_pack_weights(w, geom, tr, backward=True)
+    return {"forward": lambda: ops.conv_geometry_forward(x, pf, b, geom, tr), "data gradient": lambda: ops.conv_geometry_backward_data(g, pd, geom, tr),
+            "weight + bias gradient": lambda: ops.conv_geometry_backward_weights(x, g, geom, tr)[0]}
 
 
 def general_passes(x, w, b, g, desc, tr):
@@ -70,22 +84,27 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--rows", choices=["square", "geometry", "all"], default="all")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("conv_general_bench: needs the GPU (a CPU run measures nothing)")
     gen = torch.Generator(device="cuda").manual_seed(0)
     N = a.batch
-    for name, tr, Cin, H, W, Cout, k, s, p, other in SHAPES:
+    rows = [r[:9] + (1, 1) + r[9:] for r in SHAPES] if a.rows != "geometry" else []
+    rows += [r + ("library",) for r in GEOMETRY_SHAPES] if a.rows != "square" else []
+    for name, tr, Cin, H, W, Cout, k, s, p, d, group, other in rows:
+        square = d == 1 and group == 1
         desc = ops.conv_desc(N, Cin, H, W, Cout, k, s, p)
-        Ho, Wo = ops.conv_general_out_shape(desc, tr)
+        geom = ops.conv_geometry(N, Cin, H, W, Cout, k, s, p, d, group)
+        Ho, Wo = ops.conv_geometry_out_shape(geom, tr)
         x = torch.randn(N, Cin, H, W, device="cuda", generator=gen)
-        w = torch.randn((Cin, Cout, k, k) if tr else (Cout, Cin, k, k), device="cuda", generator=gen) * 0.1
+        w = torch.randn((Cin, Cout // group, k, k) if tr else (Cout, Cin // group, k, k), device="cuda", generator=gen) * 0.1
         b = torch.randn(Cout, device="cuda", generator=gen)
         g = torch.randn(N, Cout, Ho, Wo, device="cuda", generator=gen)
-        gflop = 2.0 * N * Cin * Cout * k * k * (H * W if tr else Ho * Wo) / 1e9
+        gflop = 2.0 * N * Cin * (Cout // group) * k * k * (H * W if tr else Ho * Wo) / 1e9
         print("%s, batch %d: %.2f GFLOP per pass" % (name, N, gflop), flush=True)
-        mine = general_passes(x, w, b, g, desc, tr)
-        theirs = library_passes(x, w, b, g, tr, s, p) if other == "library" else specialised_passes(x, w, b, g, desc, tr)
+        mine = general_passes(x, w, b, g, desc, tr) if square else geometry_passes(x, w, b, g, geom, tr)
+        theirs = library_passes(x, w, b, g, tr, s, p, d, group) if other == "library" else specialised_passes(x, w, b, g, desc, tr)
         for what in mine:
             f, r = mine[what], theirs[what]
             got, want = f(), r()                       # (also the warm-up of both sides at this shape)

@@ -5,6 +5,7 @@
 #include <string>
 #include <climits>
 #include "flownet2_hip_conv_general.h"
+#include "flownet2_hip_conv_geometry.h"
 namespace fn2 { std::string& last_error() { static std::string s; return s; } int& batch_invariant_flag() { static int f = 0; return f; } }
 int main() {
   const int rows[][9] = {
@@ -28,6 +29,30 @@ int main() {
     size_t a=1,b=1,c=1,w=1;
     if (fn2_conv_general_supported(&d, r[0]) != 0 || fn2_conv_general_sizes(&d, r[0], &a, &b, &c, &w) != FN2_ERR_UNSUPPORTED || a || b || c || w) { printf("bad accepted %d %d\n", r[1], r[6]); ++fails; }
   }
+  // the 14-int geometries of include/flownet2_hip_conv_geometry.h: {transposed, N, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group}: rows of
+  // tests/conv_geometry_cases.py, its invalid list, and values at the ends of the int range in every field
+  const int M = INT_MAX;
+  const int grows[][15] = {
+    {0,2,3,6,11,5,1,7,1,1,0,3,1,1,1},{0,2,4,12,9,20,3,3,2,2,1,1,3,1,1},{0,1,2,4,4,3,3,3,1,1,4,4,4,4,1},{0,2,19,8,9,19,3,3,1,1,1,1,1,1,19},
+    {0,2,6,11,14,9,2,3,2,1,1,2,2,3,3},{1,2,5,4,6,3,4,2,2,1,1,0,1,1,1},{1,1,6,3,4,9,3,2,3,2,0,1,1,2,3},{1,1,5,4,4,5,4,4,2,2,1,1,1,1,5}};
+  const int gbad[][15] = {
+    {0,1,4,8,8,4,3,3,1,1,1,1,1,1,0},{0,1,5,8,8,4,3,3,1,1,1,1,1,1,2},{0,1,4,8,8,5,3,3,1,1,1,1,1,1,2},{0,1,4,8,8,4,3,3,1,1,1,1,0,1,1},
+    {0,1,4,8,8,4,3,0,1,1,1,1,1,1,1},{0,1,4,8,8,4,3,3,0,1,1,1,1,1,1},{0,1,4,8,8,4,3,3,1,1,1,-1,1,1,1},{0,1,4,8,8,4,3,3,1,1,1,1,5,1,1},
+    {1,1,4,1,1,4,2,2,1,1,1,1,1,1,2},{0,1,4,1<<20,1<<20,4,3,3,1,1,1,1,1,1,2},
+    {0,M,M,M,M,M,M,M,M,M,M,M,M,M,M},{1,M,M,M,M,M,M,M,M,M,M,M,M,M,1},{0,1,1,8,8,1,M,M,1,1,M,M,M,M,1},{1,1,1,M,M,1,2,2,M,M,0,0,M,M,1},
+    {0,1,M,1,1,M,1,1,1,1,0,0,1,1,M},{0,1,1,8,8,1,3,3,1,1,M/2,M/2,M/2,M/2,1},{1,1,1,1,1,1,M,1,1,1,0,0,M,1,1},{0,1,1,1,1,1,1,1,M,M,M/2,M/2,1,1,1}};
+  for (auto& r : grows) {
+    size_t a=0,b=0,c=1,w=0; int oh=0, ow=0;
+    if (fn2_conv_geometry_supported(r + 1, r[0]) != 1 || fn2_conv_geometry_sizes(r + 1, r[0], &a, &b, &c, &w) != 0 || !a || !b || c || !w ||
+        fn2_conv_geometry_out_shape(r + 1, r[0], &oh, &ow) != 0 || oh < 1 || ow < 1) { printf("geometry row refused\n"); ++fails; }
+    else printf("ok %zu %zu %zu %d x %d\n", a, b, w, oh, ow);
+  }
+  for (auto& r : gbad) {
+    size_t a=1,b=1,c=1,w=1; int oh=1, ow=1;
+    if (fn2_conv_geometry_supported(r + 1, r[0]) != 0 || fn2_conv_geometry_sizes(r + 1, r[0], &a, &b, &c, &w) != FN2_ERR_UNSUPPORTED || a || b || c || w ||
+        fn2_conv_geometry_out_shape(r + 1, r[0], &oh, &ow) != FN2_ERR_UNSUPPORTED || oh || ow) { printf("bad geometry accepted %d %d\n", r[6], r[14]); ++fails; }
+  }
+  if (fn2_conv_geometry_supported(nullptr, 0) != 0 || fn2_conv_geometry_out_shape(nullptr, 1, nullptr, nullptr) != FN2_ERR_UNSUPPORTED) ++fails;
   if (fn2_conv_general_supported(nullptr, 0) != 0 || fn2_conv_general_sizes(nullptr, 1, nullptr, nullptr, nullptr, nullptr) != FN2_ERR_UNSUPPORTED) ++fails;
   printf("%s: %s\n", fails ? "FAILED" : "clean", fn2::last_error().c_str());
   return fails;
