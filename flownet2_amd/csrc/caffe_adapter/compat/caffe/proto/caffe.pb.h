@@ -181,11 +181,14 @@ class ConvolutionParameter {
   const FillerParameter& bias_filler() const { return bias_filler_; }
   FillerParameter* mutable_bias_filler() { return &bias_filler_; }
   Engine engine() const { return ConvolutionParameter_Engine_CAFFE; }
-  int axis() const { return 1; }
-  bool force_nd_im2col() const { return false; }
+  int axis() const { return axis_; }                               // caffe.proto: [default = 1]
+  void set_axis(int v) { axis_ = v; }
+  bool force_nd_im2col() const { return force_nd_im2col_; }        // caffe.proto: [default = false]
+  void set_force_nd_im2col(bool v) { force_nd_im2col_ = v; }
  private:
   unsigned num_output_ = 0, group_ = 1;
-  bool bias_term_ = true;
+  int axis_ = 1;
+  bool bias_term_ = true, force_nd_im2col_ = false;
   std::vector<unsigned> pad_, kernel_size_, stride_, dilation_;
   unsigned pad_h_ = 0, pad_w_ = 0, kernel_h_ = 0, kernel_w_ = 0, stride_h_ = 1, stride_w_ = 1;
   bool has_pad_h_ = false, has_pad_w_ = false, has_kernel_h_ = false, has_kernel_w_ = false, has_stride_h_ = false, has_stride_w_ = false;

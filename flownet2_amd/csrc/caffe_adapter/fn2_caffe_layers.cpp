@@ -28,7 +28,7 @@
 
 #include "flownet2_hip.h"
 #include "flownet2_hip_conv_general.h"
-#include "flownet2_hip_conv_geometry.h"
+#include "flownet2_hip_conv_volume.h"
 
 namespace caffe {
 
@@ -404,13 +404,15 @@ class DownsampleLayer : public Layer<Dtype> {
 //   <- ConvolutionLayer / DeconvolutionLayer (conv_layer.cpp:8-40, deconv_layer.cpp:8-45) over BaseConvolutionLayer::LayerSetUp / Reshape
 //      (base_conv_layer.cpp:14-253): same convolution_param fields (num_output, kernel_size, stride, pad, bias_term, weight / bias fillers),
 //      same blob shapes -- weight [num_output, C, k, k] (Deconvolution: [C, num_output, k, k]), bias [num_output] --, same top shape.
-// Scope: every ConvolutionParameter of a 2D layer the stock layers accept -- kernel_size / kernel_h, kernel_w, stride, pad, dilation with one
-// or two entries, group -- read with the checks and messages of base_conv_layer.cpp:24-124; one bottom / top pair.  Refused, with a message
-// naming the layer: axis != 1, force_nd_im2col, more than two spatial axes.  A PLAIN layer (square taps, one stride, one pad, dilation 1,
-// group 1) takes the path it always took: every Convolution and Deconvolution of the FlowNet graphs runs on its specialised family; a
+// Scope: every ConvolutionParameter the stock layers accept over 0 to 3 spatial axes -- axis (the axes in front of it fold into the batch,
+// base_conv_layer.cpp:17-21, 191), kernel_size, stride, pad, dilation once or once per spatial axis, kernel_h / kernel_w and their kin with two
+// spatial axes, group, force_nd_im2col (it chooses an im2col routine in the reference and nothing here) -- read with the checks and messages
+// of base_conv_layer.cpp:24-124; one bottom / top pair.  Refused, with a message naming the layer and the count: four or more spatial axes.
+// A PLAIN layer (two spatial axes, square taps, one stride, one pad, dilation 1, group 1) takes the path it always took: every Convolution and Deconvolution of the FlowNet graphs runs on its specialised family; a
 // geometry no family takes -- and a gradient pass of a layer whose forward has a family but that pass none -- runs on the general kernels
 // (include/flownet2_hip_conv_general.h: any kernel, stride and pad).  Every other layer runs forward and all three gradient passes on the
-// same kernels through include/flownet2_hip_conv_geometry.h.  Only what fn2_conv_general_supported / fn2_conv_geometry_supported refuse (an
+// same kernels through include/flownet2_hip_conv_volume.h (fewer than three spatial axes with the leading ones trivial: the kernels and the
+// bits of include/flownet2_hip_conv_geometry.h).  Only what fn2_conv_general_supported / fn2_conv_volume_supported refuse (an
 // empty output, a blob beyond the 32-bit index limits) aborts in Reshape with a message naming the layer.
 // The packed weight operand (round 6): packed ONCE and kept while the weights provably have not changed -- Caffe has no "weights changed"
 // signal below Solver::ApplyUpdate, so the layer reads what SyncedMemory already records: the operand is reused iff the layer runs in the
@@ -429,65 +431,74 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
   explicit Fn2ConvolutionLayer(const LayerParameter& param, bool transposed) : Layer<Dtype>(param), transposed_(transposed) {}
   virtual void LayerSetUp(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
     const ConvolutionParameter& cp = this->layer_param_.convolution_param();
-    // base_conv_layer.cpp:14-124 for two spatial axes, with its messages
-    CHECK(cp.axis() == 1 && !cp.force_nd_im2col() && bottom[0]->num_axes() == 4)
-        << this->layer_param_.name() << ": libflownet2_hip runs 2D convolutions only (axis 1, no force_nd_im2col, two spatial axes)";
-    const int num_spatial_axes = 2;
+    // base_conv_layer.cpp:14-124, with its messages
+    channel_axis_ = bottom[0]->CanonicalAxisIndex(cp.axis());
+    num_spatial_axes_ = bottom[0]->num_axes() - channel_axis_ - 1;
+    CHECK_GE(num_spatial_axes_, 0);
+    CHECK_LE(num_spatial_axes_, 3) << this->layer_param_.name() << ": libflownet2_hip runs convolutions over 0 to 3 spatial axes; "
+                                   << num_spatial_axes_ << " were asked for";
+    const int num_spatial_axes = num_spatial_axes_, lead = 3 - num_spatial_axes;
+    // the values per axis (depth, height, width); the axes that are not there are trivial: kernel 1, stride 1, pad 0, dilation 1
+    for (int i = 0; i < 3; ++i) { kernel_3_[i] = 1; stride_3_[i] = 1; pad_3_[i] = 0; dilation_3_[i] = 1; }
     if (cp.has_kernel_h() || cp.has_kernel_w()) {
+      CHECK_EQ(num_spatial_axes, 2) << "kernel_h & kernel_w can only be used for 2D convolution.";
       CHECK_EQ(0, cp.kernel_size_size()) << "Either kernel_size or kernel_h/w should be specified; not both.";
-      kernel_h_ = (int)cp.kernel_h(); kernel_w_ = (int)cp.kernel_w();
+      kernel_3_[1] = (int)cp.kernel_h(); kernel_3_[2] = (int)cp.kernel_w();
     } else {
       const int n = cp.kernel_size_size();
       CHECK(n == 1 || n == num_spatial_axes) << "kernel_size must be specified once, or once per spatial dimension "
                                              << "(kernel_size specified " << n << " times; " << num_spatial_axes << " spatial dims).";
-      kernel_h_ = (int)cp.kernel_size(0); kernel_w_ = (int)cp.kernel_size(n - 1);
+      for (int i = 0; i < num_spatial_axes; ++i) kernel_3_[lead + i] = (int)cp.kernel_size(n == 1 ? 0 : i);
     }
-    CHECK_GT(kernel_h_, 0) << "Filter dimensions must be nonzero.";
-    CHECK_GT(kernel_w_, 0) << "Filter dimensions must be nonzero.";
+    for (int i = 0; i < 3; ++i) CHECK_GT(kernel_3_[i], 0) << "Filter dimensions must be nonzero.";
     if (cp.has_stride_h() || cp.has_stride_w()) {
+      CHECK_EQ(num_spatial_axes, 2) << "stride_h & stride_w can only be used for 2D convolution.";
       CHECK_EQ(0, cp.stride_size()) << "Either stride or stride_h/w should be specified; not both.";
-      stride_h_ = (int)cp.stride_h(); stride_w_ = (int)cp.stride_w();
+      stride_3_[1] = (int)cp.stride_h(); stride_3_[2] = (int)cp.stride_w();
     } else {
       const int n = cp.stride_size();
       CHECK(n == 0 || n == 1 || n == num_spatial_axes) << "stride must be specified once, or once per spatial dimension "
                                                        << "(stride specified " << n << " times; " << num_spatial_axes << " spatial dims).";
-      stride_h_ = n ? (int)cp.stride(0) : 1; stride_w_ = n ? (int)cp.stride(n - 1) : 1;
+      for (int i = 0; i < num_spatial_axes && n; ++i) stride_3_[lead + i] = (int)cp.stride(n == 1 ? 0 : i);
     }
-    CHECK_GT(stride_h_, 0) << "Stride dimensions must be nonzero.";
-    CHECK_GT(stride_w_, 0) << "Stride dimensions must be nonzero.";
+    for (int i = 0; i < 3; ++i) CHECK_GT(stride_3_[i], 0) << "Stride dimensions must be nonzero.";
     if (cp.has_pad_h() || cp.has_pad_w()) {
+      CHECK_EQ(num_spatial_axes, 2) << "pad_h & pad_w can only be used for 2D convolution.";
       CHECK_EQ(0, cp.pad_size()) << "Either pad or pad_h/w should be specified; not both.";
-      pad_h_ = (int)cp.pad_h(); pad_w_ = (int)cp.pad_w();
+      pad_3_[1] = (int)cp.pad_h(); pad_3_[2] = (int)cp.pad_w();
     } else {
       const int n = cp.pad_size();
       CHECK(n == 0 || n == 1 || n == num_spatial_axes) << "pad must be specified once, or once per spatial dimension "
                                                        << "(pad specified " << n << " times; " << num_spatial_axes << " spatial dims).";
-      pad_h_ = n ? (int)cp.pad(0) : 0; pad_w_ = n ? (int)cp.pad(n - 1) : 0;
+      for (int i = 0; i < num_spatial_axes && n; ++i) pad_3_[lead + i] = (int)cp.pad(n == 1 ? 0 : i);
     }
     {
       const int n = cp.dilation_size();
       CHECK(n == 0 || n == 1 || n == num_spatial_axes) << "dilation must be specified once, or once per spatial dimension "
                                                        << "(dilation specified " << n << " times; " << num_spatial_axes << " spatial dims).";
-      dilation_h_ = n ? (int)cp.dilation(0) : 1; dilation_w_ = n ? (int)cp.dilation(n - 1) : 1;
+      for (int i = 0; i < num_spatial_axes && n; ++i) dilation_3_[lead + i] = (int)cp.dilation(n == 1 ? 0 : i);
     }
-    CHECK_GT(dilation_h_, 0) << "Dilation dimensions must be nonzero.";
-    CHECK_GT(dilation_w_, 0) << "Dilation dimensions must be nonzero.";
+    for (int i = 0; i < 3; ++i) CHECK_GT(dilation_3_[i], 0) << "Dilation dimensions must be nonzero.";
+    kernel_h_ = kernel_3_[1]; kernel_w_ = kernel_3_[2]; stride_h_ = stride_3_[1]; stride_w_ = stride_3_[2]; pad_h_ = pad_3_[1]; pad_w_ = pad_3_[2];
+    dilation_h_ = dilation_3_[1]; dilation_w_ = dilation_3_[2];
     num_output_ = (int)cp.num_output();
     CHECK_GT(num_output_, 0);
     bias_term_ = cp.bias_term();
-    channels_ = bottom[0]->channels();
+    channels_ = bottom[0]->shape(channel_axis_);
     group_ = (int)cp.group();
     CHECK_GT(group_, 0);
     CHECK_EQ(channels_ % group_, 0);
     CHECK_EQ(num_output_ % group_, 0) << "Number of output should be multiples of group.";
     // a PLAIN layer (all a FlowNet has) keeps the specialised route and the square-tap general kernels behind it
-    plain_ = kernel_h_ == kernel_w_ && stride_h_ == stride_w_ && pad_h_ == pad_w_ && dilation_h_ == 1 && dilation_w_ == 1 && group_ == 1;
+    plain_ = num_spatial_axes == 2 && kernel_h_ == kernel_w_ && stride_h_ == stride_w_ && pad_h_ == pad_w_ && dilation_h_ == 1 && dilation_w_ == 1 &&
+             group_ == 1;
     kernel_ = kernel_h_; stride_ = stride_h_; pad_ = pad_h_;      // read by the plain paths only
     if (this->blobs_.size() == 0) {
       this->blobs_.resize(bias_term_ ? 2 : 1);
-      // base_conv_layer.cpp:125-139: [conv_out_channels, conv_in_channels / group, kh, kw]; for a Deconvolution the roles are swapped
-      const int d0 = transposed_ ? channels_ : num_output_, d1 = (transposed_ ? num_output_ : channels_) / group_;
-      this->blobs_[0].reset(new Blob<Dtype>(d0, d1, kernel_h_, kernel_w_));
+      // base_conv_layer.cpp:125-139: [conv_out_channels, conv_in_channels / group, k...]; for a Deconvolution the roles are swapped
+      vector<int> wshape{transposed_ ? channels_ : num_output_, (transposed_ ? num_output_ : channels_) / group_};
+      for (int i = 0; i < num_spatial_axes; ++i) wshape.push_back(kernel_3_[lead + i]);
+      this->blobs_[0].reset(new Blob<Dtype>(wshape));
       shared_ptr<Filler<Dtype> > wf(GetFiller<Dtype>(cp.weight_filler()));
       wf->Fill(this->blobs_[0].get());
       if (bias_term_) {
@@ -499,11 +510,15 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     this->param_propagate_down_.resize(this->blobs_.size(), true);
   }
   virtual void Reshape(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
-    CHECK_EQ(bottom[0]->channels(), channels_) << "Input size incompatible with convolution kernel.";
-    desc_.N = bottom[0]->num(); desc_.Cin = channels_; desc_.Hin = bottom[0]->height(); desc_.Win = bottom[0]->width();
+    CHECK_EQ(bottom[0]->num_axes(), channel_axis_ + 1 + num_spatial_axes_) << "bottom num_axes may not change.";
+    CHECK_EQ(bottom[0]->shape(channel_axis_), channels_) << "Input size incompatible with convolution kernel.";
+    // every axis in front of the channels folds into the batch (base_conv_layer.cpp:191); the spatial extents right-aligned in (D, H, W)
+    for (int i = 0; i < 3; ++i) in_3_[i] = 1;
+    for (int i = 0; i < num_spatial_axes_; ++i) in_3_[3 - num_spatial_axes_ + i] = bottom[0]->shape(channel_axis_ + 1 + i);
+    desc_.N = bottom[0]->count(0, channel_axis_); desc_.Cin = channels_; desc_.Hin = in_3_[1]; desc_.Win = in_3_[2];
     desc_.Cout = num_output_; desc_.kernel = kernel_; desc_.stride = stride_; desc_.pad = pad_;
     const int tr = transposed_ ? 1 : 0;
-    if (!plain_) { ReshapeGeometry(top); return; }
+    if (!plain_) { ReshapeGeometry(bottom, top); return; }
     int oh, ow;
     if (transposed_) {      // deconv_layer.cpp:8-24
       oh = stride_ * (desc_.Hin - 1) + kernel_ - 2 * pad_; ow = stride_ * (desc_.Win - 1) + kernel_ - 2 * pad_;
@@ -520,7 +535,8 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no kernel for " << type() << "{kernel " << kernel_ << ", stride " << stride_
                  << ", pad " << pad_ << "} " << channels_ << " -> " << num_output_ << " on " << desc_.Hin << " x " << desc_.Win
                  << " (empty output, or a blob beyond the 32-bit index limits)";
-    top[0]->Reshape(desc_.N, num_output_, oh, ow);
+    out_h_ = oh; out_w_ = ow;
+    top[0]->Reshape(TopShape(bottom, 1, oh, ow));
     const size_t pf = route_ == 0 ? gen_fwd : transposed_ ? fn2_deconv_packed_weight_floats(&desc_, route_) : fn2_conv_packed_weight_floats(&desc_, route_);
     size_t wb = route_ == 0 ? 0 : transposed_ ? fn2_deconv_workspace_bytes(&desc_, route_) : fn2_conv_workspace_bytes(&desc_, route_);
     packed_.Reshape(vector<int>{(int)pf});
@@ -541,33 +557,48 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     }
     workspace_.Reshape(vector<int>{(int)((wb + 3) / 4) + 4});
   }
-  // a layer that is not plain: no specialised route, all four passes on fn2_conv_geometry_* (include/flownet2_hip_conv_geometry.h)
-  void ReshapeGeometry(const vector<Blob<Dtype>*>& top) {
+  // the top shape: the bottom's leading axes, num_output, the output extents of the spatial axes the layer has (base_conv_layer.cpp:198-207)
+  vector<int> TopShape(const vector<Blob<Dtype>*>& bottom, int od, int oh, int ow) const {
+    vector<int> shape(bottom[0]->shape().begin(), bottom[0]->shape().begin() + channel_axis_);
+    shape.push_back(num_output_);
+    const int out[3] = {od, oh, ow};
+    for (int i = 3 - num_spatial_axes_; i < 3; ++i) shape.push_back(out[i]);
+    return shape;
+  }
+  // a layer that is not plain: no specialised route, all four passes on fn2_conv_volume_* (include/flownet2_hip_conv_volume.h)
+  void ReshapeGeometry(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
     const int tr = transposed_ ? 1 : 0;
-    const int g[14] = {desc_.N, channels_, desc_.Hin, desc_.Win, num_output_, kernel_h_, kernel_w_, stride_h_, stride_w_, pad_h_, pad_w_,
-                       dilation_h_, dilation_w_, group_};
-    std::copy(g, g + 14, geom_);
+    const int g[19] = {desc_.N, channels_, in_3_[0], in_3_[1], in_3_[2], num_output_, kernel_3_[0], kernel_3_[1], kernel_3_[2], stride_3_[0], stride_3_[1],
+                       stride_3_[2], pad_3_[0], pad_3_[1], pad_3_[2], dilation_3_[0], dilation_3_[1], dilation_3_[2], group_};
+    std::copy(g, g + 19, geom_);
     route_ = 0; bwd_route_ = FN2_BWD_ROUTE_NONE; bwd_weights_ = false; head_ = false;
-    general_ = fn2_conv_geometry_supported(geom_, tr) != 0;
+    general_ = fn2_conv_volume_supported(geom_, tr) != 0;
+    if (!general_ && num_spatial_axes_ == 3)
+      LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no kernel for " << type() << "{kernel " << kernel_3_[0] << " x " << kernel_h_ << " x "
+                 << kernel_w_ << ", stride " << stride_3_[0] << " x " << stride_h_ << " x " << stride_w_ << ", pad " << pad_3_[0] << " x " << pad_h_ << " x "
+                 << pad_w_ << ", dilation " << dilation_3_[0] << " x " << dilation_h_ << " x " << dilation_w_ << ", group " << group_ << "} " << channels_
+                 << " -> " << num_output_ << " on " << in_3_[0] << " x " << desc_.Hin << " x " << desc_.Win
+                 << " (empty output, or a blob beyond the 32-bit index limits)";
     if (!general_)
       LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no kernel for " << type() << "{kernel " << kernel_h_ << " x " << kernel_w_
                  << ", stride " << stride_h_ << " x " << stride_w_ << ", pad " << pad_h_ << " x " << pad_w_ << ", dilation " << dilation_h_ << " x "
                  << dilation_w_ << ", group " << group_ << "} " << channels_ << " -> " << num_output_ << " on " << desc_.Hin << " x " << desc_.Win
                  << " (empty output, or a blob beyond the 32-bit index limits)";
-    int oh = 0, ow = 0;
+    int od = 0, oh = 0, ow = 0;
     size_t gen_fwd = 0, gen_dgrad = 0, gen_ws = 0;
-    FN2_CALL(fn2_conv_geometry_out_shape(geom_, tr, &oh, &ow));      // conv_layer.cpp:8-23 / deconv_layer.cpp:8-24 with the dilated extent
-    FN2_CALL(fn2_conv_geometry_sizes(geom_, tr, &gen_fwd, &gen_dgrad, nullptr, &gen_ws));
-    top[0]->Reshape(desc_.N, num_output_, oh, ow);
+    FN2_CALL(fn2_conv_volume_out_shape(geom_, tr, &od, &oh, &ow));      // conv_layer.cpp:8-23 / deconv_layer.cpp:8-24 with the dilated extent
+    FN2_CALL(fn2_conv_volume_sizes(geom_, tr, &gen_fwd, &gen_dgrad, nullptr, &gen_ws));
+    out_h_ = od * oh; out_w_ = ow;      // what the bias gradient sums over, per channel
+    top[0]->Reshape(TopShape(bottom, od, oh, ow));
     packed_.Reshape(vector<int>{(int)gen_fwd});
     packed_bwd_.Reshape(vector<int>{(int)gen_dgrad});
-    const size_t wb = std::max(gen_ws, fn2_bias_leaky_relu_backward_workspace_bytes(desc_.N, num_output_, oh, ow));
+    const size_t wb = std::max(gen_ws, fn2_bias_leaky_relu_backward_workspace_bytes(desc_.N, num_output_, out_h_, out_w_));
     workspace_.Reshape(vector<int>{(int)((wb + 3) / 4) + 4});
   }
-  // the general kernels of either header: the square-tap entry points for a plain layer (the bits of before), else the 14-int ones
+  // the general kernels of either header: the square-tap entry points for a plain layer (the bits of before), else the 19-int ones
   int GeneralPack(int pass, const float* w, float* pk) const {
     const int tr = transposed_ ? 1 : 0;
-    return plain_ ? fn2_conv_general_pack_weights(&desc_, tr, pass, w, pk, kStream) : fn2_conv_geometry_pack_weights(geom_, tr, pass, w, pk, kStream);
+    return plain_ ? fn2_conv_general_pack_weights(&desc_, tr, pass, w, pk, kStream) : fn2_conv_volume_pack_weights(geom_, tr, pass, w, pk, kStream);
   }
   virtual inline const char* type() const { return transposed_ ? "Deconvolution" : "Convolution"; }
   virtual inline int ExactNumBottomBlobs() const { return 1; }
@@ -595,8 +626,8 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       fn2_adapter_stats().weight_packs++;
     }
     if (route_ == 0 && !plain_) {
-      FN2_CALL(fn2_conv_geometry_forward(geom_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
-                                         num_output_, 0, 0, 0.f, kStream));
+      FN2_CALL(fn2_conv_volume_forward(geom_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
+                                       num_output_, 0, 0, 0.f, kStream));
     } else if (route_ == 0) {
       FN2_CALL(fn2_conv_general_forward(&desc_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
                                         num_output_, 0, 0, 0.f, kStream));
@@ -631,7 +662,7 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       return;
     }
     if (bias_term_ && this->param_propagate_down_[1])
-      FN2_CALL(fn2_conv_backward_bias(td, num_output_, 0, f32(this->blobs_[1]->mutable_gpu_diff()), desc_.N, num_output_, top[0]->height(), top[0]->width(),
+      FN2_CALL(fn2_conv_backward_bias(td, num_output_, 0, f32(this->blobs_[1]->mutable_gpu_diff()), desc_.N, num_output_, out_h_, out_w_,
                                       1, ws, wsb, kStream));
     if (this->param_propagate_down_[0]) {
       if (!bwd_weights_ && !general_)
@@ -640,8 +671,8 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
         FN2_CALL(fn2_conv_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0, f32(this->blobs_[0]->mutable_gpu_diff()),
                                            1, ws, wsb, kStream));
       } else if (!plain_) {
-        FN2_CALL(fn2_conv_geometry_backward_weights(geom_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
-                                                    f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
+        FN2_CALL(fn2_conv_volume_backward_weights(geom_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
+                                                  f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
       } else {      // the general kernel (the bias gradient was taken above)
         FN2_CALL(fn2_conv_general_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
                                                    f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
@@ -654,7 +685,7 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       if (bwd_route_ == FN2_BWD_ROUTE_NONE) {
         FN2_CALL(GeneralPack(1, f32(this->blobs_[0]->gpu_data()), pk));
         if (plain_) FN2_CALL(fn2_conv_general_backward_data(&desc_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
-        else FN2_CALL(fn2_conv_geometry_backward_data(geom_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
+        else FN2_CALL(fn2_conv_volume_backward_data(geom_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
         return;
       }
       FN2_CALL(fn2_conv_backward_data_pack_weights(&desc_, tr, bwd_route_, f32(this->blobs_[0]->gpu_data()), pk, ws, wsb, kStream));
@@ -665,8 +696,10 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
   bool transposed_, bias_term_ = true, bwd_weights_ = false, head_ = false, general_ = false, plain_ = true;
   int kernel_ = 0, stride_ = 1, pad_ = 0, num_output_ = 0, channels_ = 0, route_ = 0, bwd_route_ = 0;
   int kernel_h_ = 0, kernel_w_ = 0, stride_h_ = 1, stride_w_ = 1, pad_h_ = 0, pad_w_ = 0, dilation_h_ = 1, dilation_w_ = 1, group_ = 1;
+  int channel_axis_ = 1, num_spatial_axes_ = 2, out_h_ = 0, out_w_ = 0;
+  int in_3_[3] = {1, 1, 1}, kernel_3_[3] = {1, 1, 1}, stride_3_[3] = {1, 1, 1}, pad_3_[3] = {0, 0, 0}, dilation_3_[3] = {1, 1, 1};      // (depth, height, width)
   fn2_conv_desc desc_;
-  int geom_[14] = {0};
+  int geom_[19] = {0};
   Blob<Dtype> packed_, packed_bwd_, workspace_;
   const float* packed_for_ = nullptr;      // device pointer of the weights packed_ was built from
   int packed_route_ = -1, packed_count_ = -1;

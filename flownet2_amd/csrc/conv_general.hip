@@ -1,6 +1,7 @@
 // General-geometry Convolution / Deconvolution on v_mfma_f32_16x16x4_f32 (exact fp32): the last resort behind the specialised families.
 // Contract, operand layout and summation order: include/flownet2_hip_conv_general.h (square taps, fn2_conv_desc) and
-// include/flownet2_hip_conv_geometry.h (rectangular taps, per-axis stride / pad / dilation, groups: the same code, widened).
+// include/flownet2_hip_conv_geometry.h (rectangular taps, per-axis stride / pad / dilation, groups: the same code, widened) and
+// include/flownet2_hip_conv_volume.h (a depth axis in front of the two: one more digit of the same pixel and k-row numbers).
 //
 // Everything is stated on the two SIDES of the layer, the larger map L and the smaller map S (Convolution: L = bottom, S = top;
 // Deconvolution: L = top, S = bottom).  The weight blob is [Cs][Cl / group][kh][kw] for both kinds.  Per group (channels Clg = Cl / group,
@@ -9,9 +10,10 @@
 //   transposed gather S -> L   Convolution data gradient, Deconvolution forward      M = Clg, K = Csg kh kw, Wp[cl][(cs, tap)] = W[cs][cl][tap]
 //   weight gradient            dW[cs][(cl, tap)] = sum over (n, S pixels) of S[cs][p] x (forward gather of L)[(cl, tap)][p]
 // so there are two gather kernels (one template), two pack layouts and one weight-gradient kernel for the four layer uses.  The group is a
-// grid factor.  Every kernel that gathers exists twice: GEN = false is the plain geometry (square taps, one stride, one pad, dilation 1,
-// group 1), where the per-axis values, the dilation products and the group offsets compile away; GEN = true is everything else.  Both run
-// the same accumulation chain per output value.
+// grid factor.  Every kernel that gathers exists three times, by the template parameter GEO: kPlain is the plain geometry (square taps, one
+// stride, one pad, dilation 1, group 1), where the per-axis values, the dilation products and the group offsets compile away; kGen is every
+// other geometry with two spatial axes; kVol adds the depth axis (pixels (z, y, x), k-rows (c, kz, ky, kx)) and is run only where the depth
+// axis is not trivial.  All run the same accumulation chain per output value.
 //
 // Tiles.  A workgroup is 4 waves.  Gather kernel: 64 consecutive pixels (flattened y Wout + x, so a tile may wrap rows) of one sample x
 // NG = 1, 2 or 4 groups of 16 output channels (by the channel count alone); per chunk of 16 k-rows every thread gathers 4 values (its
@@ -23,6 +25,7 @@
 
 #include "../../include/flownet2_hip_conv_general.h"
 #include "../../include/flownet2_hip_conv_geometry.h"
+#include "../../include/flownet2_hip_conv_volume.h"
 
 namespace fn2 {
 namespace {
@@ -38,71 +41,106 @@ constexpr long long kMaxElems = 0x7fffffffll;
 constexpr long long kMaxTiles = 0x3fffff00ll;
 
 // ------------------------------------------------------------------------------------------------ host geometry
+enum Geo { kPlain = 0, kGen = 1, kVol = 2 };      // the geometry template parameter of the gathering kernels
+
 struct Sides {
-  int N, Cl, Hl, Wl, Cs, Hs, Ws, kh, kw, sh, sw, ph, pw, dh, dw, group;
+  int N, Cl, Dl, Hl, Wl, Cs, Ds, Hs, Ws, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw, group;
   int Cin, Cout;            // the layer's own names of the two channel counts (the slices of bottom and top)
-  bool plain;               // square taps, one stride, one pad, dilation 1, group 1: the GEN = false kernels
+  bool plain;               // two spatial axes, square taps, one stride, one pad, dilation 1, group 1: the kPlain kernels
+  bool volume;              // a depth axis that is not trivial (not Din = kd = sd = dd = 1, pd = 0): the kVol kernels
+  long long Pl() const { return (long long)Dl * Hl * Wl; }      // voxels of the two maps
+  long long Ps() const { return (long long)Ds * Hs * Ws; }
+  int taps() const { return kd * kh * kw; }
 };
 
-// the 14 ints of include/flownet2_hip_conv_geometry.h
-enum { kGN, kGCin, kGHin, kGWin, kGCout, kGkh, kGkw, kGsh, kGsw, kGph, kGpw, kGdh, kGdw, kGgroup, kGeomInts };
+// the 19 ints of include/flownet2_hip_conv_volume.h: what every entry point is stated on
+enum { kGN, kGCin, kGDin, kGHin, kGWin, kGCout, kGkd, kGkh, kGkw, kGsd, kGsh, kGsw, kGpd, kGph, kGpw, kGdd, kGdh, kGdw, kGgroup, kGeomInts };
+
+// a caller's geometry as the 19 ints: the 19 themselves, or the 14 of include/flownet2_hip_conv_geometry.h with a trivial depth axis
+struct Geom {
+  int v[kGeomInts];
+  bool null, depth;         // depth: stated with a depth axis (what a refusal prints)
+  Geom() : null(true), depth(false) {}
+  static Geom from_volume(const int* w) {
+    Geom g;
+    g.null = !w; g.depth = true;
+    if (w) for (int i = 0; i < kGeomInts; ++i) g.v[i] = w[i];
+    return g;
+  }
+  static Geom from_planar(const int* w) {       // {N, Cin, Hin, Win, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group}
+    Geom g;
+    g.null = !w;
+    if (w) {
+      const int u[kGeomInts] = {w[0], w[1], 1, w[2], w[3], w[4], 1, w[5], w[6], 1, w[7], w[8], 0, w[9], w[10], 1, w[11], w[12], w[13]};
+      for (int i = 0; i < kGeomInts; ++i) g.v[i] = u[i];
+    }
+    return g;
+  }
+  // fn2_conv_desc: (k, k, s, s, p, p, 1, 1, 1)
+  static Geom from_desc(const fn2_conv_desc* d) {
+    if (!d) return Geom();
+    const int w[14] = {d->N, d->Cin, d->Hin, d->Win, d->Cout, d->kernel, d->kernel, d->stride, d->stride, d->pad, d->pad, 1, 1, 1};
+    return from_planar(w);
+  }
+};
 
 inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 
+// a b c where every partial product has to stay inside the 32-bit element limit; false: it does not
+inline bool mul3(long long a, long long b, long long c, long long& out) {
+  out = a * b;              // a, b, c <= kMaxElems: no long long overflow in either step
+  if (out > kMaxElems) return false;
+  out *= c;
+  return out <= kMaxElems;
+}
+
 // the geometry on its two sides; false: invalid, output extent below 1, or a blob beyond the 32-bit index limits
-bool make_sides(const int* v, int transposed, Sides& g) {
-  if (!v) return false;
-  if (v[kGN] < 1 || v[kGCin] < 1 || v[kGHin] < 1 || v[kGWin] < 1 || v[kGCout] < 1 || v[kGkh] < 1 || v[kGkw] < 1 || v[kGsh] < 1 || v[kGsw] < 1 ||
-      v[kGph] < 0 || v[kGpw] < 0 || v[kGdh] < 1 || v[kGdw] < 1 || v[kGgroup] < 1)
-    return false;
+bool make_sides(const Geom& geom, int transposed, Sides& g) {
+  if (geom.null) return false;
+  const int* v = geom.v;
+  for (int i = 0; i < kGeomInts; ++i)
+    if (v[i] < ((i >= kGpd && i <= kGpw) ? 0 : 1)) return false;      // pad >= 0, everything else >= 1
   if (v[kGCin] % v[kGgroup] != 0 || v[kGCout] % v[kGgroup] != 0) return false;
-  // the dilated extent of the taps, per axis
-  const long long eh = (long long)v[kGdh] * (v[kGkh] - 1) + 1, ew = (long long)v[kGdw] * (v[kGkw] - 1) + 1;
-  const long long Hp = (long long)v[kGHin] + 2ll * v[kGph], Wp = (long long)v[kGWin] + 2ll * v[kGpw];
-  if (eh > kMaxElems || ew > kMaxElems) return false;
-  long long Ho, Wo;
-  if (!transposed) {
-    if (Hp < eh || Wp < ew) return false;
-    Ho = (Hp - eh) / v[kGsh] + 1;
-    Wo = (Wp - ew) / v[kGsw] + 1;
-  } else {
-    Ho = (long long)v[kGsh] * (v[kGHin] - 1) + eh - 2ll * v[kGph];
-    Wo = (long long)v[kGsw] * (v[kGWin] - 1) + ew - 2ll * v[kGpw];
+  // per axis (depth, height, width): the dilated extent of the taps and the top extent
+  long long ext[3], out[3];
+  for (int a = 0; a < 3; ++a) {
+    const long long in = v[kGDin + a], k = v[kGkd + a], s = v[kGsd + a], p = v[kGpd + a], d = v[kGdd + a];
+    ext[a] = d * (k - 1) + 1;
+    if (ext[a] > kMaxElems) return false;
+    if (!transposed) {
+      if (in + 2 * p < ext[a]) return false;
+      out[a] = (in + 2 * p - ext[a]) / s + 1;
+    } else {
+      out[a] = s * (in - 1) + ext[a] - 2 * p;
+    }
+    if (out[a] < 1 || out[a] > kMaxElems) return false;
   }
-  if (Ho < 1 || Wo < 1 || Ho > kMaxElems || Wo > kMaxElems) return false;
-  const long long kk = (long long)v[kGkh] * v[kGkw];
-  if (kk > kMaxElems) return false;
+  long long kk, pb, pt;
+  if (!mul3(v[kGkd], v[kGkh], v[kGkw], kk) || !mul3(v[kGDin], v[kGHin], v[kGWin], pb) || !mul3(out[0], out[1], out[2], pt)) return false;
   const long long bottom = (long long)v[kGN] * v[kGCin], top = (long long)v[kGN] * v[kGCout];
   if (bottom > kMaxElems || top > kMaxElems) return false;
-  const long long pb = (long long)v[kGHin] * v[kGWin], pt = Ho * Wo;
-  if (pb > kMaxElems || pt > kMaxElems || bottom * pb > kMaxElems || top * pt > kMaxElems) return false;
+  if (bottom * pb > kMaxElems || top * pt > kMaxElems) return false;
   const long long cc = (long long)v[kGCin] * (v[kGCout] / v[kGgroup]);
   if (cc > kMaxElems || cc * kk > kMaxElems) return false;
   // the padded operands: group x (channels of a group rounded to 16) x (K of a group rounded to 16)
   const long long cmax = (v[kGCin] > v[kGCout] ? v[kGCin] : v[kGCout]) / v[kGgroup];
   if (v[kGgroup] * (cdivll(cmax, 16) * 16) * (cdivll(cmax * kk, kKC) * kKC + kKC) > kMaxElems) return false;
-  g.N = v[kGN]; g.kh = v[kGkh]; g.kw = v[kGkw]; g.sh = v[kGsh]; g.sw = v[kGsw]; g.ph = v[kGph]; g.pw = v[kGpw]; g.dh = v[kGdh]; g.dw = v[kGdw];
+  g.N = v[kGN]; g.kd = v[kGkd]; g.kh = v[kGkh]; g.kw = v[kGkw]; g.sd = v[kGsd]; g.sh = v[kGsh]; g.sw = v[kGsw]; g.pd = v[kGpd]; g.ph = v[kGph];
+  g.pw = v[kGpw]; g.dd = v[kGdd]; g.dh = v[kGdh]; g.dw = v[kGdw];
   g.group = v[kGgroup]; g.Cin = v[kGCin]; g.Cout = v[kGCout];
-  g.plain = g.kh == g.kw && g.sh == g.sw && g.ph == g.pw && g.dh == 1 && g.dw == 1 && g.group == 1;
-  if (!transposed) { g.Cl = v[kGCin]; g.Hl = v[kGHin]; g.Wl = v[kGWin]; g.Cs = v[kGCout]; g.Hs = (int)Ho; g.Ws = (int)Wo; }
-  else { g.Cs = v[kGCin]; g.Hs = v[kGHin]; g.Ws = v[kGWin]; g.Cl = v[kGCout]; g.Hl = (int)Ho; g.Wl = (int)Wo; }
+  g.volume = !(v[kGDin] == 1 && g.kd == 1 && g.sd == 1 && g.pd == 0 && g.dd == 1);
+  g.plain = !g.volume && g.kh == g.kw && g.sh == g.sw && g.ph == g.pw && g.dh == 1 && g.dw == 1 && g.group == 1;
+  if (!transposed) {
+    g.Cl = v[kGCin]; g.Dl = v[kGDin]; g.Hl = v[kGHin]; g.Wl = v[kGWin]; g.Cs = v[kGCout]; g.Ds = (int)out[0]; g.Hs = (int)out[1]; g.Ws = (int)out[2];
+  } else {
+    g.Cs = v[kGCin]; g.Ds = v[kGDin]; g.Hs = v[kGHin]; g.Ws = v[kGWin]; g.Cl = v[kGCout]; g.Dl = (int)out[0]; g.Hl = (int)out[1]; g.Wl = (int)out[2];
+  }
   // the gathers' coordinates (y stride - pad + ky dilation and y + pad - ky dilation over the larger map) stay inside int
-  if ((long long)g.Hl + 2ll * g.ph + eh > kMaxElems || (long long)g.Wl + 2ll * g.pw + ew > kMaxElems) return false;
+  if ((long long)g.Dl + 2ll * g.pd + ext[0] > kMaxElems || (long long)g.Hl + 2ll * g.ph + ext[1] > kMaxElems ||
+      (long long)g.Wl + 2ll * g.pw + ext[2] > kMaxElems)
+    return false;
   return true;
 }
-
-// fn2_conv_desc as the 14 ints: (k, k, s, s, p, p, 1, 1, 1)
-struct DescGeom {
-  int v[kGeomInts];
-  bool null;
-  explicit DescGeom(const fn2_conv_desc* d) : null(!d) {
-    if (d) {
-      const int w[kGeomInts] = {d->N, d->Cin, d->Hin, d->Win, d->Cout, d->kernel, d->kernel, d->stride, d->stride, d->pad, d->pad, 1, 1, 1};
-      for (int i = 0; i < kGeomInts; ++i) v[i] = w[i];
-    }
-  }
-  const int* geom() const { return null ? nullptr : v; }
-};
 
 // one GEMM view of ONE group: M output channels, R reduction channels (K = R kh kw)
 struct Gemm {
@@ -110,10 +148,10 @@ struct Gemm {
   long long K, Kpad;
 };
 
-Gemm make_gemm(int M, int R, int kh, int kw) {
+Gemm make_gemm(int M, int R, int taps) {
   Gemm m;
   m.M = M; m.R = R; m.G = (M + 15) / 16;
-  m.K = (long long)R * kh * kw;
+  m.K = (long long)R * taps;
   m.Kpad = cdivll(m.K, kKC) * kKC;
   m.ksteps = (int)(m.Kpad / 4);
   return m;
@@ -123,7 +161,7 @@ Gemm make_gemm(int M, int R, int kh, int kw) {
 inline bool pass_is_tr(int transposed, int pass) { return (pass == 1) != (transposed != 0); }
 inline Gemm pass_gemm(const Sides& g, bool tr) {
   const int cl = g.Cl / g.group, cs = g.Cs / g.group;
-  return tr ? make_gemm(cl, cs, g.kh, g.kw) : make_gemm(cs, cl, g.kh, g.kw);
+  return tr ? make_gemm(cl, cs, g.taps()) : make_gemm(cs, cl, g.taps());
 }
 inline size_t packed_floats(const Sides& g, const Gemm& m) { return (size_t)g.group * (size_t)m.G * (size_t)m.ksteps * 64; }
 
@@ -137,7 +175,7 @@ struct WgradPlan {
 WgradPlan make_wgrad(const Sides& g) {
   WgradPlan p;
   p.m = pass_gemm(g, false);
-  p.ptiles = (int)cdivll((long long)g.Hs * g.Ws, kPix);
+  p.ptiles = (int)cdivll(g.Ps(), kPix);
   p.chunks = (long long)g.N * p.ptiles;
   const long long out_tiles = (p.m.Kpad / kKC) * ((p.m.G + 3) / 4) * g.group;       // a 64-channel tile stays inside one group
   long long want = 2048 / out_tiles;                   // enough workgroups for the chip when the output has few tiles
@@ -158,11 +196,11 @@ inline int natural_groups(int G) { return G <= 1 ? 1 : G <= 2 ? 2 : 4; }
 inline int groups_per_block(int G) { return forced_groups() ? forced_groups() : natural_groups(G); }
 
 long long gather_tiles(const Sides& g, bool tr, const Gemm& m, int ng) {
-  const long long P = tr ? (long long)g.Hl * g.Wl : (long long)g.Hs * g.Ws;
+  const long long P = tr ? g.Pl() : g.Ps();
   return (long long)g.N * cdivll(P, kPix) * cdivll(m.G, ng) * g.group;
 }
 
-bool supported(const int* geom, int transposed, Sides& g) {
+bool supported(const Geom& geom, int transposed, Sides& g) {
   if (!make_sides(geom, transposed, g)) return false;
   const Gemm mf = pass_gemm(g, false), mt = pass_gemm(g, true);
   if (gather_tiles(g, false, mf, natural_groups(mf.G)) > kMaxTiles || gather_tiles(g, true, mt, natural_groups(mt.G)) > kMaxTiles) return false;
@@ -175,12 +213,19 @@ struct GatherSrc {
   const float* in;          // channel c0 of sample 0 of the input blob
   int ctot, C, IH, IW;      // channels of the blob / of the slice, input map
   int OW;                   // width of the pixel space the tile runs over
-  long long OP;             // its pixels
-  int kh, sh, ph;               // GEN = false reads these alone, for both axes ...
+  long long OP;             // its pixels (voxels)
+  int kh, sh, ph;               // kPlain reads these alone, for both axes ...
   unsigned ow_magic, sh_magic;  // div_magic(OW), div_magic(sh)
-  int kw, sw, pw, dh, dw;       // ... GEN = true these too
+  int kw, sw, pw, dh, dw;       // ... kGen these too ...
   int group;                    // the input channels of group g are [g C, (g + 1) C) from `in`
   unsigned sw_magic;            // div_magic(sw)
+};
+
+// ... and kVol the depth axis as well.  A structure of its own at the END of the kernels' arguments: what the other instantiations read lies
+// where it lay before there was a depth axis
+struct GatherDepth {
+  int ID, OHW, kd, sd, pd, dd;      // input depth, pixels of one output plane, the depth axis of the taps
+  unsigned ohw_magic, sd_magic;     // div_magic(OHW), div_magic(sd)
 };
 
 // n / d for 0 <= n < 2^32 without an integer division: with m = div_magic(d) = floor((2^32 - 1) / d), umulhi(n, m) is the quotient or one
@@ -193,15 +238,22 @@ __device__ __forceinline__ void divmod(unsigned n, unsigned d, unsigned magic, u
   if (r >= d) { ++q; r -= d; }
 }
 
-// the pixel of a thread in its tile, as the gather needs it: forward (y sh - ph, x sw - pw), transposed (y + ph, x + pw)
-struct PixelBase { int by, bx; bool valid; };
+// the pixel of a thread in its tile, as the gather needs it: forward (y sh - ph, x sw - pw), transposed (y + ph, x + pw); kVol: z alike
+struct PixelBase { int bz, by, bx; bool valid; };
 
-template <bool TR, bool GEN>
-__device__ __forceinline__ PixelBase pixel_base(const GatherSrc& a, long long p) {
+template <bool TR, int GEO>
+__device__ __forceinline__ PixelBase pixel_base(const GatherSrc& a, const GatherDepth& z, long long p) {
+  constexpr bool GEN = GEO != kPlain;
   PixelBase b;
   b.valid = p < a.OP;
-  unsigned uy, ux;
-  divmod(b.valid ? (unsigned)p : 0u, (unsigned)a.OW, a.ow_magic, uy, ux);
+  unsigned up = b.valid ? (unsigned)p : 0u, uy, ux;
+  b.bz = 0;
+  if constexpr (GEO == kVol) {
+    unsigned uz;
+    divmod(up, (unsigned)z.OHW, z.ohw_magic, uz, up);
+    b.bz = TR ? (int)uz + z.pd : (int)uz * z.sd - z.pd;
+  }
+  divmod(up, (unsigned)a.OW, a.ow_magic, uy, ux);
   const int y = (int)uy, x = (int)ux;
   const int sw = GEN ? a.sw : a.sh, pw = GEN ? a.pw : a.ph;
   b.by = TR ? y + a.ph : y * a.sh - a.ph;
@@ -209,37 +261,67 @@ __device__ __forceinline__ PixelBase pixel_base(const GatherSrc& a, long long p)
   return b;
 }
 
-// A k-row as (channel, ky, kx), wave-uniform: decomposed once, then advanced by a constant number of rows per chunk with two carries
-// (kx against kw, ky against kh) instead of two divisions
-struct KRow { int c, ky, kx; };
-struct KStep { int dc, dky, dkx; };
+// A k-row as (channel, kz, ky, kx), wave-uniform: decomposed once, then advanced by a constant number of rows per chunk with carries
+// (kx against kw, ky against kh, kVol: kz against kd) instead of divisions.  Without a depth axis kz stays 0 and compiles away.
+struct KRow { int c, kz, ky, kx; };
+struct KStep { int dc, dkz, dky, dkx; };
 
-__device__ __forceinline__ KRow k_row(int kg, int kh, int kw) {
-  const int kk = kh * kw;
+template <bool VOL>
+__device__ __forceinline__ KRow k_row(int kg, int kd, int kh, int kw) {
+  const int kk = kh * kw, kkk = VOL ? kd * kk : kk;
   KRow r;
-  r.c = kg / kk;
-  const int tap = kg - r.c * kk;
+  r.c = kg / kkk;
+  int tap = kg - r.c * kkk;
+  r.kz = 0;
+  if constexpr (VOL) { r.kz = tap / kk; tap -= r.kz * kk; }
   r.ky = tap / kw;
   r.kx = tap - r.ky * kw;
   return r;
 }
 
-__device__ __forceinline__ KStep k_step(int rows, int kh, int kw) {
-  const KRow r = k_row(rows, kh, kw);
-  return KStep{r.c, r.ky, r.kx};
+template <bool VOL>
+__device__ __forceinline__ KStep k_step(int rows, int kd, int kh, int kw) {
+  const KRow r = k_row<VOL>(rows, kd, kh, kw);
+  return KStep{r.c, r.kz, r.ky, r.kx};
 }
 
-__device__ __forceinline__ void k_advance(KRow& r, const KStep& d, int kh, int kw) {
+template <bool VOL>
+__device__ __forceinline__ void k_advance(KRow& r, const KStep& d, int kd, int kh, int kw) {
   r.kx += d.dkx;
   if (r.kx >= kw) { r.kx -= kw; ++r.ky; }
   r.ky += d.dky;
-  if (r.ky >= kh) { r.ky -= kh; ++r.c; }
+  if constexpr (VOL) {
+    if (r.ky >= kh) { r.ky -= kh; ++r.kz; }
+    r.kz += d.dkz;
+    if (r.kz >= kd) { r.kz -= kd; ++r.c; }
+  } else {
+    if (r.ky >= kh) { r.ky -= kh; ++r.c; }
+  }
   r.c += d.dc;
 }
 
+// The depth axis of one tap, for all three passes (they all gather through gather_one): the input plane `zi` of the pixel base bz and the
+// tap kz, and whether the tap contributes -- forward bz + kz dd inside [0, ID); transposed (bz - kz dd) / sd exact, not negative and below ID.
+// An address is formed from `zi` only where this is true.
+template <bool TR>
+__device__ __forceinline__ bool depth_coord(const GatherDepth& z, int bz, int kz, int& zi) {
+  const int oz = kz * z.dd;
+  if constexpr (TR) {
+    const int tz = bz - oz;
+    unsigned qz, rz;
+    divmod((unsigned)max(tz, 0), (unsigned)z.sd, z.sd_magic, qz, rz);
+    zi = (int)qz;
+    return tz >= 0 && rz == 0 && zi < z.ID;
+  } else {
+    zi = bz + oz;
+    return zi >= 0 && zi < z.ID;
+  }
+}
+
 // col[k-row][pixel] of sample slice `src`; 0 outside the image, beyond K and for a pixel beyond the tile's map
-template <bool TR, bool GEN>
-__device__ __forceinline__ float gather_one(const GatherSrc& a, const float* src, const KRow& kr, const PixelBase& b) {
+template <bool TR, int GEO>
+__device__ __forceinline__ float gather_one(const GatherSrc& a, const GatherDepth& z, const float* src, const KRow& kr, const PixelBase& b) {
+  constexpr bool GEN = GEO != kPlain;
   int yi, xi;
   bool ok = b.valid && kr.c < a.C;
   const int oy = GEN ? kr.ky * a.dh : kr.ky, ox = GEN ? kr.kx * a.dw : kr.kx;      // the tap's offset, dilated
@@ -255,7 +337,13 @@ __device__ __forceinline__ float gather_one(const GatherSrc& a, const float* src
     ok = ok && yi >= 0 && yi < a.IH && xi >= 0 && xi < a.IW;
   }
   float v = 0.f;
-  if (ok) v = src[(size_t)kr.c * a.IH * a.IW + (size_t)yi * a.IW + xi];
+  if constexpr (GEO == kVol) {
+    int zi;
+    ok = depth_coord<TR>(z, b.bz, kr.kz, zi) && ok;
+    if (ok) v = src[((size_t)kr.c * z.ID + zi) * a.IH * a.IW + (size_t)yi * a.IW + xi];
+  } else {
+    if (ok) v = src[(size_t)kr.c * a.IH * a.IW + (size_t)yi * a.IW + xi];
+  }
   return v;
 }
 
@@ -268,23 +356,25 @@ struct GatherArgs {
   int out_ctot, M, G, ksteps, ptiles, mblocks;
   int relu;
   float slope;
+  GatherDepth z;
 };
 
-template <bool TR, int NG, bool GEN>
+template <bool TR, int NG, int GEO>
 __global__ __launch_bounds__(kThreads) void conv_general_gather(GatherArgs a) {
   __shared__ float col[kKC * kColStrideG];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   unsigned task = blockIdx.x;
   const int mb = task % a.mblocks; task /= a.mblocks;
+  constexpr bool GEN = GEO != kPlain, VOL = GEO == kVol;
   int grp = 0;                // the layer's group: a grid factor; M, G, ksteps and C are those of one group
   if constexpr (GEN) { grp = task % a.g.group; task /= a.g.group; }
   const int pt = task % a.ptiles;
   const int n = task / a.ptiles;
   const long long p0 = (long long)pt * kPix;
-  const size_t iplane = (size_t)a.g.IH * a.g.IW;
+  const size_t iplane = (size_t)(VOL ? a.z.ID : 1) * a.g.IH * a.g.IW;
   const float* src = a.g.in + ((size_t)n * a.g.ctot + (size_t)grp * a.g.C) * iplane;
-  const PixelBase pb = pixel_base<TR, GEN>(a.g, p0 + lane);
-  const int kh = a.g.kh, kw = GEN ? a.g.kw : a.g.kh;
+  const PixelBase pb = pixel_base<TR, GEO>(a.g, a.z, p0 + lane);
+  const int kd = VOL ? a.z.kd : 1, kh = a.g.kh, kw = GEN ? a.g.kw : a.g.kh;
 
   // this wave's NG row groups of the weights; beyond the last real one of the group the last one again (computed, not stored)
   const float* wl[NG];
@@ -298,13 +388,13 @@ __global__ __launch_bounds__(kThreads) void conv_general_gather(GatherArgs a) {
   for (int j = 0; j < NG; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nchunks = a.ksteps / 4;
-  const KStep kstep = k_step(kKC, kh, kw);
+  const KStep kstep = k_step<VOL>(kKC, kd, kh, kw);
   KRow kr[4];
   float v[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    kr[i] = k_row(wave + 4 * i, kh, kw);
-    v[i] = gather_one<TR, GEN>(a.g, src, kr[i], pb);
+    kr[i] = k_row<VOL>(wave + 4 * i, kd, kh, kw);
+    v[i] = gather_one<TR, GEO>(a.g, a.z, src, kr[i], pb);
   }
   // the weight operand of a chunk (4 k-steps x NG groups) is fetched a chunk ahead, like the col values
   float w[4][NG];
@@ -326,8 +416,8 @@ __global__ __launch_bounds__(kThreads) void conv_general_gather(GatherArgs a) {
       for (int j = 0; j < NG; ++j) wn[ks][j] = wl[j][(size_t)(4 * nx + ks) * 64];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      k_advance(kr[i], kstep, kh, kw);
-      v[i] = gather_one<TR, GEN>(a.g, src, kr[i], pb);
+      k_advance<VOL>(kr[i], kstep, kd, kh, kw);
+      v[i] = gather_one<TR, GEO>(a.g, a.z, src, kr[i], pb);
     }
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -367,18 +457,19 @@ struct WgradArgs {
   int x_ctot, A, G, ablocks, ktiles, ptiles;
   long long chunks, per_part, Kpad;
   float* ws;                // [nsplit][group][16 G][Kpad]; A, G, Kpad and g.C are those of one group
+  GatherDepth z;
 };
 
 // the values of a thread for pixel chunk q: 4 of the col tile (k-rows kr) and 16 of the S blob (channels ch0, ch0 + 4, ... of group grp)
-template <bool GEN>
+template <int GEO>
 __device__ __forceinline__ void wgrad_fetch(const WgradArgs& a, const KRow (&kr)[4], long long q, int grp, int ch0, int lane, float (&cv)[4],
                                             float (&xv)[16]) {
   const int n = (int)(q / a.ptiles);
   const long long p = (q - (long long)n * a.ptiles) * kPix + lane;
-  const float* src = a.g.in + ((size_t)n * a.g.ctot + (size_t)grp * a.g.C) * a.g.IH * a.g.IW;
-  const PixelBase pb = pixel_base<false, GEN>(a.g, p);
+  const float* src = a.g.in + ((size_t)n * a.g.ctot + (size_t)grp * a.g.C) * (GEO == kVol ? a.z.ID : 1) * a.g.IH * a.g.IW;
+  const PixelBase pb = pixel_base<false, GEO>(a.g, a.z, p);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) cv[i] = gather_one<false, GEN>(a.g, src, kr[i], pb);
+  for (int i = 0; i < 4; ++i) cv[i] = gather_one<false, GEO>(a.g, a.z, src, kr[i], pb);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int ch = ch0 + 4 * i;
@@ -386,8 +477,9 @@ __device__ __forceinline__ void wgrad_fetch(const WgradArgs& a, const KRow (&kr)
   }
 }
 
-template <bool GEN>
+template <int GEO>
 __global__ __launch_bounds__(kThreads) void conv_general_wgrad(WgradArgs a) {
+  constexpr bool GEN = GEO != kPlain, VOL = GEO == kVol;
   __shared__ float col[kKC * kColStrideW];
   __shared__ float xs[64 * kColStrideW];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -404,9 +496,9 @@ __global__ __launch_bounds__(kThreads) void conv_general_wgrad(WgradArgs a) {
   float cv[4], xv[16];
   KRow kr[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) kr[i] = k_row(kt * kKC + wave + 4 * i, a.g.kh, GEN ? a.g.kw : a.g.kh);
+  for (int i = 0; i < 4; ++i) kr[i] = k_row<VOL>(kt * kKC + wave + 4 * i, VOL ? a.z.kd : 1, a.g.kh, GEN ? a.g.kw : a.g.kh);
   // chunk q's values are fetched while chunk q - 1 is multiplied (the last chunk of the part is fetched twice: no branch)
-  wgrad_fetch<GEN>(a, kr, q0, grp, 64 * ab + wave, lane, cv, xv);
+  wgrad_fetch<GEO>(a, kr, q0, grp, 64 * ab + wave, lane, cv, xv);
   for (long long q = q0; q < q1; ++q) {
     __syncthreads();      // the previous chunk's reads are done
 #pragma unroll
@@ -414,7 +506,7 @@ __global__ __launch_bounds__(kThreads) void conv_general_wgrad(WgradArgs a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) xs[(wave + 4 * i) * kColStrideW + lane] = xv[i];
     __syncthreads();
-    wgrad_fetch<GEN>(a, kr, min(q + 1, q1 - 1), grp, 64 * ab + wave, lane, cv, xv);
+    wgrad_fetch<GEO>(a, kr, min(q + 1, q1 - 1), grp, 64 * ab + wave, lane, cv, xv);
     if (active) {
       const float* xr = xs + (16 * wave + (lane & 15)) * kColStrideW + (lane >> 4);
       const float* cr = col + (lane & 15) * kColStrideW + (lane >> 4);
@@ -489,20 +581,30 @@ __global__ void conv_general_pack(const float* w, float* wp, int M, int R, int G
 // ------------------------------------------------------------------------------------------------ host entry helpers
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 
-inline void set_taps(GatherSrc& a, const Sides& g) {
+inline void set_taps(GatherSrc& a, GatherDepth& z, const Sides& g) {
   a.kh = g.kh; a.kw = g.kw; a.sh = g.sh; a.sw = g.sw; a.ph = g.ph; a.pw = g.pw; a.dh = g.dh; a.dw = g.dw; a.group = g.group;
   a.sh_magic = div_magic(g.sh); a.sw_magic = div_magic(g.sw);
+  z.kd = g.kd; z.sd = g.sd; z.pd = g.pd; z.dd = g.dd; z.sd_magic = div_magic(g.sd);
+}
+
+// the input map and the pixel space of a gather: in_l: the input is the larger map (the forward gather), else the smaller one
+inline void set_maps(GatherSrc& a, GatherDepth& z, const Sides& g, bool in_l) {
+  z.ID = in_l ? g.Dl : g.Ds; a.IH = in_l ? g.Hl : g.Hs; a.IW = in_l ? g.Wl : g.Ws;
+  const int OH = in_l ? g.Hs : g.Hl;
+  a.OW = in_l ? g.Ws : g.Wl;
+  z.OHW = OH * a.OW;        // (below 2^31: a whole blob is)
+  a.OP = in_l ? g.Ps() : g.Pl();
+  a.ow_magic = div_magic(a.OW); z.ohw_magic = div_magic(z.OHW);
 }
 
 int run_gather(const Sides& g, bool tr, const float* in, int in_ctot, int in_c0, const float* packed, const float* bias, float* out, int out_ctot,
                int out_c0, int relu, float slope, hipStream_t st) {
   const Gemm m = pass_gemm(g, tr);
   GatherArgs a;
-  const int IH = tr ? g.Hs : g.Hl, IW = tr ? g.Ws : g.Wl, OH = tr ? g.Hl : g.Hs, OW = tr ? g.Wl : g.Ws;
-  a.g.in = in + (size_t)in_c0 * IH * IW;
-  a.g.ctot = in_ctot; a.g.C = m.R; a.g.IH = IH; a.g.IW = IW; a.g.OW = OW; a.g.OP = (long long)OH * OW;
-  set_taps(a.g, g);
-  a.g.ow_magic = div_magic(OW);
+  set_maps(a.g, a.z, g, !tr);
+  set_taps(a.g, a.z, g);
+  a.g.in = in + (size_t)in_c0 * (size_t)(tr ? g.Ps() : g.Pl());
+  a.g.ctot = in_ctot; a.g.C = m.R;
   a.wp = packed; a.bias = bias;
   a.out = out + (size_t)out_c0 * a.g.OP;
   a.out_ctot = out_ctot; a.M = m.M; a.G = m.G; a.ksteps = m.ksteps;
@@ -513,8 +615,9 @@ int run_gather(const Sides& g, bool tr, const float* in, int in_ctot, int in_c0,
   if (tiles > kMaxTiles) return fail(FN2_ERR_UNSUPPORTED, "fn2_conv_general: grid too large");
   const dim3 grid((unsigned)tiles), block(kThreads);
 #define FN2_GATHER(TR_, NG_) \
-  do { if (g.plain) hipLaunchKernelGGL((conv_general_gather<TR_, NG_, false>), grid, block, 0, st, a); \
-       else hipLaunchKernelGGL((conv_general_gather<TR_, NG_, true>), grid, block, 0, st, a); } while (0)
+  do { if (g.plain) hipLaunchKernelGGL((conv_general_gather<TR_, NG_, kPlain>), grid, block, 0, st, a); \
+       else if (g.volume) hipLaunchKernelGGL((conv_general_gather<TR_, NG_, kVol>), grid, block, 0, st, a); \
+       else hipLaunchKernelGGL((conv_general_gather<TR_, NG_, kGen>), grid, block, 0, st, a); } while (0)
   if (tr) { if (ng == 1) FN2_GATHER(true, 1); else if (ng == 2) FN2_GATHER(true, 2); else FN2_GATHER(true, 4); }
   else { if (ng == 1) FN2_GATHER(false, 1); else if (ng == 2) FN2_GATHER(false, 2); else FN2_GATHER(false, 4); }
 #undef FN2_GATHER
@@ -528,17 +631,25 @@ int check_slices(const char* what, const Sides& g, int bottom_channels, int bott
   return FN2_OK;
 }
 
-int refuse(const char* what, const int* v, int transposed) {
-  if (!v) return fail(FN2_ERR_UNSUPPORTED, "%s: null descriptor", what);
+int refuse(const char* what, const Geom& geom, int transposed) {
+  if (geom.null) return fail(FN2_ERR_UNSUPPORTED, "%s: null descriptor", what);
+  const int* v = geom.v;
+  const char* kind = transposed ? "Deconvolution" : "Convolution";
+  if (geom.depth)
+    return fail(FN2_ERR_UNSUPPORTED,
+                "%s: no kernel for %s N=%d Cin=%d %dx%dx%d Cout=%d kernel=%dx%dx%d stride=%dx%dx%d pad=%dx%dx%d dilation=%dx%dx%d group=%d (invalid, "
+                "empty output, or beyond the 32-bit index limits)",
+                what, kind, v[kGN], v[kGCin], v[kGDin], v[kGHin], v[kGWin], v[kGCout], v[kGkd], v[kGkh], v[kGkw], v[kGsd], v[kGsh], v[kGsw], v[kGpd],
+                v[kGph], v[kGpw], v[kGdd], v[kGdh], v[kGdw], v[kGgroup]);
   return fail(FN2_ERR_UNSUPPORTED,
               "%s: no kernel for %s N=%d Cin=%d %dx%d Cout=%d kernel=%dx%d stride=%dx%d pad=%dx%d dilation=%dx%d group=%d (invalid, empty output, or beyond "
               "the 32-bit index limits)",
-              what, transposed ? "Deconvolution" : "Convolution", v[kGN], v[kGCin], v[kGHin], v[kGWin], v[kGCout], v[kGkh], v[kGkw], v[kGsh], v[kGsw],
-              v[kGph], v[kGpw], v[kGdh], v[kGdw], v[kGgroup]);
+              what, kind, v[kGN], v[kGCin], v[kGHin], v[kGWin], v[kGCout], v[kGkh], v[kGkw], v[kGsh], v[kGsw], v[kGph], v[kGpw], v[kGdh], v[kGdw],
+              v[kGgroup]);
 }
 
-// ------------------------------------------------------------------------------------------------ the entry points, on the 14 ints
-int geom_sizes(const char* what, const int* geom, int transposed, size_t* forward_packed, size_t* backward_data_packed, size_t* backward_weights_packed,
+// ------------------------------------------------------------------------------------------------ the entry points, on the 19 ints
+int geom_sizes(const char* what, const Geom& geom, int transposed, size_t* forward_packed, size_t* backward_data_packed, size_t* backward_weights_packed,
                size_t* backward_weights_workspace) {
   if (forward_packed) *forward_packed = 0;
   if (backward_data_packed) *backward_data_packed = 0;
@@ -552,7 +663,7 @@ int geom_sizes(const char* what, const int* geom, int transposed, size_t* forwar
   return FN2_OK;
 }
 
-int geom_pack_weights(const char* what, const int* geom, int transposed, int pass, const float* weight, float* packed, void* stream) {
+int geom_pack_weights(const char* what, const Geom& geom, int transposed, int pass, const float* weight, float* packed, void* stream) {
   Sides g;
   if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
   if (pass < 0 || pass > 2) return fail(FN2_ERR_INVALID_ARG, "%s: pass %d (0 forward, 1 data gradient, 2 weight gradient)", what, pass);
@@ -562,12 +673,12 @@ int geom_pack_weights(const char* what, const int* geom, int transposed, int pas
   const bool tr = pass_is_tr(transposed, pass);
   const Gemm m = pass_gemm(g, tr);
   const long long total = (long long)packed_floats(g, m);
-  hipLaunchKernelGGL(conv_general_pack, dim3(blocks_for(total, 256)), dim3(256), 0, as_stream(stream), weight, packed, m.M, m.R, m.G, g.kh * g.kw, m.K,
+  hipLaunchKernelGGL(conv_general_pack, dim3(blocks_for(total, 256)), dim3(256), 0, as_stream(stream), weight, packed, m.M, m.R, m.G, g.taps(), m.K,
                      m.ksteps, total, tr ? 1 : 0);
   return check_launch(what);
 }
 
-int geom_forward(const char* what, const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0, const float* packed_weight,
+int geom_forward(const char* what, const Geom& geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0, const float* packed_weight,
                  const float* bias, float* top, int top_channels, int top_c0, int relu, float negative_slope, void* stream) {
   Sides g;
   if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
@@ -579,7 +690,7 @@ int geom_forward(const char* what, const int* geom, int transposed, const float*
                     negative_slope, as_stream(stream));
 }
 
-int geom_backward_data(const char* what, const int* geom, int transposed, const float* top_diff, int top_channels, int top_c0,
+int geom_backward_data(const char* what, const Geom& geom, int transposed, const float* top_diff, int top_channels, int top_c0,
                        const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
   Sides g;
   if (!supported(geom, transposed, g)) return refuse(what, geom, transposed);
@@ -590,7 +701,7 @@ int geom_backward_data(const char* what, const int* geom, int transposed, const 
                     0.f, as_stream(stream));
 }
 
-int geom_backward_weights(const char* what, const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+int geom_backward_weights(const char* what, const Geom& geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
                           const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff, int accumulate, void* workspace,
                           size_t workspace_bytes, void* stream) {
   Sides g;
@@ -609,22 +720,23 @@ int geom_backward_weights(const char* what, const int* geom, int transposed, con
   const float* lblob = transposed ? top_diff : bottom;
   const int l_ctot = transposed ? top_channels : bottom_channels, l_c0 = transposed ? top_c0 : bottom_c0;
   WgradArgs a;
-  a.g.in = lblob + (size_t)l_c0 * g.Hl * g.Wl;
-  a.g.ctot = l_ctot; a.g.C = p.m.R; a.g.IH = g.Hl; a.g.IW = g.Wl; a.g.OW = g.Ws; a.g.OP = (long long)g.Hs * g.Ws;
-  set_taps(a.g, g);
-  a.g.ow_magic = div_magic(g.Ws);
+  set_maps(a.g, a.z, g, true);
+  set_taps(a.g, a.z, g);
+  a.g.in = lblob + (size_t)l_c0 * (size_t)g.Pl();
+  a.g.ctot = l_ctot; a.g.C = p.m.R;
   a.x = sblob + (size_t)s_c0 * a.g.OP;
   a.x_ctot = s_ctot; a.A = p.m.M; a.G = p.m.G; a.ablocks = (p.m.G + 3) / 4; a.ktiles = (int)(p.m.Kpad / kKC); a.ptiles = p.ptiles;
   a.chunks = p.chunks; a.per_part = p.per_part; a.Kpad = p.m.Kpad;
   a.ws = static_cast<float*>(workspace);
-  if (g.plain) hipLaunchKernelGGL(conv_general_wgrad<false>, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
-  else hipLaunchKernelGGL(conv_general_wgrad<true>, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
+  if (g.plain) hipLaunchKernelGGL(conv_general_wgrad<kPlain>, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
+  else if (g.volume) hipLaunchKernelGGL(conv_general_wgrad<kVol>, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
+  else hipLaunchKernelGGL(conv_general_wgrad<kGen>, dim3((unsigned)p.tiles), dim3(kThreads), 0, st, a);
   if (const int rc = check_launch(what)) return rc;
   hipLaunchKernelGGL(conv_general_wgrad_finalize, dim3(blocks_for((long long)g.Cs * p.m.K, 256)), dim3(256), 0, st, a.ws, weight_diff, p.m.M, g.group,
                      p.m.K, p.m.Kpad, 16 * p.m.G, p.nsplit, accumulate);
   if (const int rc = check_launch(what)) return rc;
   if (bias_diff) {
-    const long long Pt = transposed ? (long long)g.Hl * g.Wl : (long long)g.Hs * g.Ws;
+    const long long Pt = transposed ? g.Pl() : g.Ps();
     hipLaunchKernelGGL(conv_general_bias_grad, dim3((unsigned)g.Cout), dim3(kThreads), 0, st, top_diff + (size_t)top_c0 * Pt, top_channels, g.N, Pt,
                        bias_diff, accumulate);
     if (const int rc = check_launch(what)) return rc;
@@ -639,7 +751,7 @@ using namespace fn2;
 
 FN2_API int fn2_conv_general_supported(const fn2_conv_desc* desc, int transposed) {
   Sides g;
-  return supported(DescGeom(desc).geom(), transposed, g) ? 1 : 0;
+  return supported(Geom::from_desc(desc), transposed, g) ? 1 : 0;
 }
 
 FN2_API int fn2_debug_set_conv_general_groups(int groups) {
@@ -652,50 +764,51 @@ FN2_API int fn2_debug_set_conv_general_groups(int groups) {
 // the square-tap entry points (include/flownet2_hip_conv_general.h): the same code with (k, k, s, s, p, p, 1, 1, 1)
 FN2_API int fn2_conv_general_sizes(const fn2_conv_desc* desc, int transposed, size_t* forward_packed, size_t* backward_data_packed,
                                    size_t* backward_weights_packed, size_t* backward_weights_workspace) {
-  const DescGeom d(desc);
-  return geom_sizes("fn2_conv_general_sizes", d.geom(), transposed, forward_packed, backward_data_packed, backward_weights_packed,
+  const Geom d = Geom::from_desc(desc);
+  return geom_sizes("fn2_conv_general_sizes", d, transposed, forward_packed, backward_data_packed, backward_weights_packed,
                     backward_weights_workspace);
 }
 
 FN2_API int fn2_conv_general_pack_weights(const fn2_conv_desc* desc, int transposed, int pass, const float* weight, float* packed, void* stream) {
-  const DescGeom d(desc);
-  return geom_pack_weights("fn2_conv_general_pack_weights", d.geom(), transposed, pass, weight, packed, stream);
+  const Geom d = Geom::from_desc(desc);
+  return geom_pack_weights("fn2_conv_general_pack_weights", d, transposed, pass, weight, packed, stream);
 }
 
 FN2_API int fn2_conv_general_forward(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
                                      const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
                                      int relu, float negative_slope, void* stream) {
-  const DescGeom d(desc);
-  return geom_forward("fn2_conv_general_forward", d.geom(), transposed, bottom, bottom_channels, bottom_c0, packed_weight, bias, top, top_channels,
+  const Geom d = Geom::from_desc(desc);
+  return geom_forward("fn2_conv_general_forward", d, transposed, bottom, bottom_channels, bottom_c0, packed_weight, bias, top, top_channels,
                       top_c0, relu, negative_slope, stream);
 }
 
 FN2_API int fn2_conv_general_backward_data(const fn2_conv_desc* desc, int transposed, const float* top_diff, int top_channels, int top_c0,
                                            const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
-  const DescGeom d(desc);
-  return geom_backward_data("fn2_conv_general_backward_data", d.geom(), transposed, top_diff, top_channels, top_c0, packed_weight, bottom_diff,
+  const Geom d = Geom::from_desc(desc);
+  return geom_backward_data("fn2_conv_general_backward_data", d, transposed, top_diff, top_channels, top_c0, packed_weight, bottom_diff,
                             bottom_channels, bottom_c0, stream);
 }
 
 FN2_API int fn2_conv_general_backward_weights(const fn2_conv_desc* desc, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
                                               const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff,
                                               int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  const DescGeom d(desc);
-  return geom_backward_weights("fn2_conv_general_backward_weights", d.geom(), transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels,
+  const Geom d = Geom::from_desc(desc);
+  return geom_backward_weights("fn2_conv_general_backward_weights", d, transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels,
                                top_c0, weight_diff, bias_diff, accumulate, workspace, workspace_bytes, stream);
 }
 
 // the 14-int entry points (include/flownet2_hip_conv_geometry.h)
 FN2_API int fn2_conv_geometry_supported(const int* geom, int transposed) {
   Sides g;
-  return supported(geom, transposed, g) ? 1 : 0;
+  return supported(Geom::from_planar(geom), transposed, g) ? 1 : 0;
 }
 
 FN2_API int fn2_conv_geometry_out_shape(const int* geom, int transposed, int* out_h, int* out_w) {
   if (out_h) *out_h = 0;
   if (out_w) *out_w = 0;
   Sides g;
-  if (!supported(geom, transposed, g)) return refuse("fn2_conv_geometry_out_shape", geom, transposed);
+  const Geom d = Geom::from_planar(geom);
+  if (!supported(d, transposed, g)) return refuse("fn2_conv_geometry_out_shape", d, transposed);
   if (out_h) *out_h = transposed ? g.Hl : g.Hs;
   if (out_w) *out_w = transposed ? g.Wl : g.Ws;
   return FN2_OK;
@@ -703,30 +816,79 @@ FN2_API int fn2_conv_geometry_out_shape(const int* geom, int transposed, int* ou
 
 FN2_API int fn2_conv_geometry_sizes(const int* geom, int transposed, size_t* forward_packed, size_t* backward_data_packed,
                                     size_t* backward_weights_packed, size_t* backward_weights_workspace) {
-  return geom_sizes("fn2_conv_geometry_sizes", geom, transposed, forward_packed, backward_data_packed, backward_weights_packed,
+  return geom_sizes("fn2_conv_geometry_sizes", Geom::from_planar(geom), transposed, forward_packed, backward_data_packed, backward_weights_packed,
                     backward_weights_workspace);
 }
 
 FN2_API int fn2_conv_geometry_pack_weights(const int* geom, int transposed, int pass, const float* weight, float* packed, void* stream) {
-  return geom_pack_weights("fn2_conv_geometry_pack_weights", geom, transposed, pass, weight, packed, stream);
+  return geom_pack_weights("fn2_conv_geometry_pack_weights", Geom::from_planar(geom), transposed, pass, weight, packed, stream);
 }
 
 FN2_API int fn2_conv_geometry_forward(const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
                                       const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
                                       int relu, float negative_slope, void* stream) {
-  return geom_forward("fn2_conv_geometry_forward", geom, transposed, bottom, bottom_channels, bottom_c0, packed_weight, bias, top, top_channels, top_c0,
+  return geom_forward("fn2_conv_geometry_forward", Geom::from_planar(geom), transposed, bottom, bottom_channels, bottom_c0, packed_weight, bias, top, top_channels, top_c0,
                       relu, negative_slope, stream);
 }
 
 FN2_API int fn2_conv_geometry_backward_data(const int* geom, int transposed, const float* top_diff, int top_channels, int top_c0,
                                             const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
-  return geom_backward_data("fn2_conv_geometry_backward_data", geom, transposed, top_diff, top_channels, top_c0, packed_weight, bottom_diff,
+  return geom_backward_data("fn2_conv_geometry_backward_data", Geom::from_planar(geom), transposed, top_diff, top_channels, top_c0, packed_weight, bottom_diff,
                             bottom_channels, bottom_c0, stream);
 }
 
 FN2_API int fn2_conv_geometry_backward_weights(const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
                                                const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff,
                                                int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  return geom_backward_weights("fn2_conv_geometry_backward_weights", geom, transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels,
+  return geom_backward_weights("fn2_conv_geometry_backward_weights", Geom::from_planar(geom), transposed, bottom, bottom_channels, bottom_c0, top_diff, top_channels,
                                top_c0, weight_diff, bias_diff, accumulate, workspace, workspace_bytes, stream);
+}
+
+// the 19-int entry points (include/flownet2_hip_conv_volume.h)
+FN2_API int fn2_conv_volume_supported(const int* geom, int transposed) {
+  Sides g;
+  return supported(Geom::from_volume(geom), transposed, g) ? 1 : 0;
+}
+
+FN2_API int fn2_conv_volume_out_shape(const int* geom, int transposed, int* out_d, int* out_h, int* out_w) {
+  if (out_d) *out_d = 0;
+  if (out_h) *out_h = 0;
+  if (out_w) *out_w = 0;
+  Sides g;
+  const Geom d = Geom::from_volume(geom);
+  if (!supported(d, transposed, g)) return refuse("fn2_conv_volume_out_shape", d, transposed);
+  if (out_d) *out_d = transposed ? g.Dl : g.Ds;
+  if (out_h) *out_h = transposed ? g.Hl : g.Hs;
+  if (out_w) *out_w = transposed ? g.Wl : g.Ws;
+  return FN2_OK;
+}
+
+FN2_API int fn2_conv_volume_sizes(const int* geom, int transposed, size_t* forward_packed, size_t* backward_data_packed,
+                                  size_t* backward_weights_packed, size_t* backward_weights_workspace) {
+  return geom_sizes("fn2_conv_volume_sizes", Geom::from_volume(geom), transposed, forward_packed, backward_data_packed, backward_weights_packed,
+                    backward_weights_workspace);
+}
+
+FN2_API int fn2_conv_volume_pack_weights(const int* geom, int transposed, int pass, const float* weight, float* packed, void* stream) {
+  return geom_pack_weights("fn2_conv_volume_pack_weights", Geom::from_volume(geom), transposed, pass, weight, packed, stream);
+}
+
+FN2_API int fn2_conv_volume_forward(const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+                                    const float* packed_weight, const float* bias, float* top, int top_channels, int top_c0,
+                                    int relu, float negative_slope, void* stream) {
+  return geom_forward("fn2_conv_volume_forward", Geom::from_volume(geom), transposed, bottom, bottom_channels, bottom_c0, packed_weight, bias, top,
+                      top_channels, top_c0, relu, negative_slope, stream);
+}
+
+FN2_API int fn2_conv_volume_backward_data(const int* geom, int transposed, const float* top_diff, int top_channels, int top_c0,
+                                          const float* packed_weight, float* bottom_diff, int bottom_channels, int bottom_c0, void* stream) {
+  return geom_backward_data("fn2_conv_volume_backward_data", Geom::from_volume(geom), transposed, top_diff, top_channels, top_c0, packed_weight,
+                            bottom_diff, bottom_channels, bottom_c0, stream);
+}
+
+FN2_API int fn2_conv_volume_backward_weights(const int* geom, int transposed, const float* bottom, int bottom_channels, int bottom_c0,
+                                             const float* top_diff, int top_channels, int top_c0, float* weight_diff, float* bias_diff,
+                                             int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  return geom_backward_weights("fn2_conv_volume_backward_weights", Geom::from_volume(geom), transposed, bottom, bottom_channels, bottom_c0, top_diff,
+                               top_channels, top_c0, weight_diff, bias_diff, accumulate, workspace, workspace_bytes, stream);
 }

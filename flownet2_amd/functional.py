@@ -80,7 +80,32 @@ def lib_conv_transpose2d(x, w, b, stride, pad, dilation=1, groups=1):
     return _lib_conv(x, w, b, stride, pad, dilation, groups, True)
 
 
-# What lib_conv2d / lib_conv_transpose2d run CUDA float32 tensors on: "library" (the default: the library convolution through torch, counted
+def _lib_conv_volume(x, w, b, stride, pad, dilation, groups, transposed):
+    geom = _general_volume(x, w, b, stride, pad, dilation, groups, transposed)
+    if geom is not None:
+        return _VolumeConv.apply(x, w, b, geom, transposed)
+    if x.is_cuda:
+        _note_fallback("%s{stride %s, pad %s, dilation %s, group %d}" % ("Deconvolution" if transposed else "Convolution", stride, pad, dilation, groups), x, w)
+    kw = dict(stride=stride, padding=pad, dilation=dilation, groups=groups)
+    f = torch.nn.functional.conv_transpose3d if transposed else torch.nn.functional.conv3d
+    if not _BATCH_INVARIANT[0] or not x.is_cuda:
+        return f(x, w, b, **kw)
+    return torch.cat([f(x[n:n + 1], w, b, **kw) for n in range(x.shape[0])], 0)
+
+
+def lib_conv3d(x, w, b, stride, pad, dilation=1, groups=1):
+    """lib_conv2d for a volumetric Convolution: x [N, Cin, D, H, W], w [Cout, Cin / groups, kd, kh, kw]; stride, pad and dilation an int or
+    a triple (d, h, w).  Under the same switch: "own" runs the depth tier of the general-geometry kernels, the default the library's
+    conv3d through torch, counted in LIBRARY_FALLBACKS."""
+    return _lib_conv_volume(x, w, b, stride, pad, dilation, groups, False)
+
+
+def lib_conv_transpose3d(x, w, b, stride, pad, dilation=1, groups=1):
+    """The same for a Deconvolution; w: [Cin, Cout / groups, kd, kh, kw]."""
+    return _lib_conv_volume(x, w, b, stride, pad, dilation, groups, True)
+
+
+# What lib_conv2d / lib_conv_transpose2d (and lib_conv3d / lib_conv_transpose3d) run CUDA float32 tensors on: "library" (the default: the library convolution through torch, counted
 # and refused under FN2_STRICT=1 as above) or "own" (the general-geometry kernels, csrc/conv_general.hip: any taps, per-axis stride, pad and
 # dilation, groups; exact fp32, forward and backward; nothing leaves the own kernels, so nothing is counted).  A switch of its own, not one of ARITH_SWITCHES.
 _GENERAL_CONVOLUTIONS = ("library", "own")
@@ -195,6 +220,47 @@ class _GeometryConv(torch.autograd.Function):
         if need_w or need_b:
             xb, x0 = _channel_slice(x)
             gw, gb = ops.conv_geometry_backward_weights(xb, d, geom, transposed, bias=bool(need_b), bottom_c0=x0)
+        return gx, (gw if need_w else None), gb, None, None
+
+
+def _general_volume(x, w, b, stride, pad, dilation, groups, transposed):
+    """The 19-int geometry of the volumetric layer where the switch is "own" and the general kernels take the call, else None."""
+    if _GENERAL_CONV[0] != "own" or not (x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float32 and x.dim() == w.dim() == 5):
+        return None
+    if groups < 1 or (b is not None and (not b.is_cuda or b.dtype != torch.float32)):
+        return None
+    Cout = w.shape[1] * groups if transposed else w.shape[0]
+    if (x.shape[1] != w.shape[0]) if transposed else (x.shape[1] != w.shape[1] * groups):
+        return None
+    geom = ops.conv_volume(x.shape[0], x.shape[1], tuple(x.shape[2:]), Cout, tuple(w.shape[2:]), stride, pad, dilation, groups)
+    return geom if ops.conv_volume_supported(geom, transposed) else None
+
+
+class _VolumeConv(torch.autograd.Function):
+    """Convolution / Deconvolution over three spatial axes on the general kernels; the operands are packed once per weight version, keyed
+    by the whole geometry."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, geom, transposed):
+        ctx.geom, ctx.transposed, ctx.has_bias = geom, transposed, b is not None
+        ctx.save_for_backward(x, w)
+        packed = _cached_pack(_PACKED_T, w, ("volume-fwd", transposed) + tuple(geom),
+                              lambda: ops.conv_volume_pack_weights(w.detach().contiguous(), geom, transposed))
+        return ops.conv_volume_forward(x.contiguous(), packed, b.detach() if b is not None else None, geom, transposed)
+
+    @staticmethod
+    def backward(ctx, d):
+        x, w = ctx.saved_tensors
+        geom, transposed = ctx.geom, ctx.transposed
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        d = d.contiguous()
+        gx = gw = gb = None
+        if need_x:
+            packed = _cached_pack(_PACKED_T, w, ("volume-dgrad", transposed) + tuple(geom),
+                                  lambda: ops.conv_volume_pack_weights(w.detach().contiguous(), geom, transposed, backward=True))
+            gx = ops.conv_volume_backward_data(d, packed, geom, transposed)
+        if need_w or need_b:
+            gw, gb = ops.conv_volume_backward_weights(x.contiguous(), d, geom, transposed, bias=bool(need_b))
         return gx, (gw if need_w else None), gb, None, None
 
 

@@ -1019,6 +1019,139 @@ def conv_geometry_backward_weights(bottom, top_diff, geom, transposed=False, wei
     return weight_diff, (bias_diff if bias else None)
 
 
+def _per_axis(v, axes, what):
+    """An int or one value per spatial axis -> `axes` ints."""
+    if isinstance(v, (tuple, list)):
+        if len(v) == 1:
+            return (int(v[0]),) * axes
+        if len(v) != axes:
+            raise ValueError(f"{what}: one value or one per spatial axis ({axes}), not {v!r}")
+        return tuple(int(s) for s in v)
+    return (int(v),) * axes
+
+
+def conv_volume(N, Cin, size, Cout, kernel, stride=1, pad=0, dilation=1, group=1):
+    """The 19 ints of include/flownet2_hip_conv_volume.h: {N, Cin, Din, Hin, Win, Cout, kernel_d/h/w, stride_d/h/w, pad_d/h/w,
+    dilation_d/h/w, group}.  size: the 0 to 3 spatial extents of the bottom blob, outermost first; kernel, stride, pad and dilation an int
+    or one value per spatial axis.  Fewer than three axes are folded onto the innermost ones (the leading axes trivial: extent 1, kernel 1,
+    stride 1, pad 0, dilation 1); N is the folded batch."""
+    size = tuple(int(s) for s in size)
+    axes = len(size)
+    if axes > 3:
+        raise ValueError(f"conv_volume: {axes} spatial axes asked for; convolution over 0 to 3 spatial axes is supported")
+    lead = 3 - axes
+    vals = ((N, Cin) + (1,) * lead + size + (Cout,) + (1,) * lead + _per_axis(kernel, axes, "kernel") + (1,) * lead + _per_axis(stride, axes, "stride")
+            + (0,) * lead + _per_axis(pad, axes, "pad") + (1,) * lead + _per_axis(dilation, axes, "dilation") + (group,))
+    return (C.c_int * 19)(*(int(v) for v in vals))
+
+
+def conv_volume_supported(geom, transposed=False) -> bool:
+    """Whether the general kernels take this layer (fn2_conv_volume_supported; host-only)."""
+    return bool(_lib.lib().fn2_conv_volume_supported(geom, int(bool(transposed))))
+
+
+def conv_volume_sizes(geom, transposed=False):
+    """(floats of the forward operand, of the data-gradient operand, of the weight-gradient operand (0), bytes of the weight-gradient
+    workspace) (fn2_conv_volume_sizes; host-only)."""
+    n = [C.c_size_t() for _ in range(4)]
+    check(_lib.lib().fn2_conv_volume_sizes(geom, int(bool(transposed)), *(C.byref(v) for v in n)))
+    return tuple(int(v.value) for v in n)
+
+
+def conv_volume_out_shape(geom, transposed=False):
+    """(Dout, Hout, Wout) of the layer as the reference computes it with the dilated extent (fn2_conv_volume_out_shape; host-only)."""
+    d, h, w = C.c_int(), C.c_int(), C.c_int()
+    check(_lib.lib().fn2_conv_volume_out_shape(geom, int(bool(transposed)), C.byref(d), C.byref(h), C.byref(w)))
+    return int(d.value), int(h.value), int(w.value)
+
+
+def _volume_weight_shape(geom, transposed):
+    Cin, Cout, group = geom[1], geom[5], geom[18]
+    return ((Cin, Cout // group) if transposed else (Cout, Cin // group)) + tuple(geom[6:9])
+
+
+def conv_volume_pack_weights(weight, geom, transposed=False, backward=False):
+    """The layer's weight blob [., ., kd, kh, kw] -> the operand of the forward (backward: data-gradient) kernel (fn2_conv_volume_pack_weights)."""
+    w = _chk(weight, "weight", ndim=5)
+    sizes = conv_volume_sizes(geom, transposed)
+    if tuple(w.shape) != _volume_weight_shape(geom, transposed):
+        raise ValueError("conv_volume_pack_weights: weight of shape %s is not this layer's" % (tuple(w.shape),))
+    packed = torch.empty(sizes[1 if backward else 0], device=w.device, dtype=torch.float32)
+    check(_lib.lib().fn2_conv_volume_pack_weights(geom, int(bool(transposed)), 1 if backward else 0, _ptr(w), _ptr(packed), _stream()))
+    return packed
+
+
+def _volume_blobs(what, geom, transposed, bottom, bottom_c0, top, top_c0):
+    out = conv_volume_out_shape(geom, transposed)
+    N, Cin, Cout = geom[0], geom[1], geom[5]
+    for t, c0, Cc, size, name in ((bottom, bottom_c0, Cin, tuple(geom[2:5]), "bottom"), (top, top_c0, Cout, out, "top")):
+        if t is not None and (not t.is_contiguous() or (t.shape[0],) + tuple(t.shape[2:]) != (N,) + size or c0 < 0 or c0 + Cc > t.shape[1]):
+            raise ValueError(f"{what}: {name} blob {tuple(t.shape)} does not hold the layer's {[N, Cc] + list(size)} at channel {c0}")
+    return out
+
+
+def conv_volume_forward(x, packed, bias, geom, transposed=False, relu=False, negative_slope=0.0, out=None, out_c0=0, in_c0=0):
+    """act(layer(x[:, in_c0:in_c0+Cin]) + bias) -> out[:, out_c0:out_c0+Cout] (a new blob if out is None) on [N, C, D, H, W] blobs
+    (fn2_conv_volume_forward).  packed = conv_volume_pack_weights(weight, geom, transposed)."""
+    x = _chk(x, "bottom[0]", ndim=5)
+    if out is not None:
+        _chk(out, "top[0]", ndim=5)
+    size = _volume_blobs("conv_volume_forward", geom, transposed, x, in_c0, out, out_c0)
+    if out is None:
+        out = torch.empty((geom[0], geom[5]) + size, device=x.device, dtype=torch.float32)
+    b = _chk_opt(bias, "bias", ndim=1)
+    pw = _chk(packed, "packed weight", ndim=None)
+    if pw.numel() != conv_volume_sizes(geom, transposed)[0]:
+        raise ValueError("conv_volume_forward: the operand has %d floats, not what the forward reads for this layer" % pw.numel())
+    check(_lib.lib().fn2_conv_volume_forward(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(in_c0), _ptr(pw), _ptr(b), _ptr(out),
+                                             out.shape[1], int(out_c0), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
+    return out
+
+
+def conv_volume_backward_data(top_diff, packed, geom, transposed=False, top_c0=0, out=None, out_c0=0):
+    """bottom_diff [N, Cin, Din, Hin, Win] (or the slice of `out` at out_c0) of the layer (fn2_conv_volume_backward_data).
+    packed = conv_volume_pack_weights(weight, geom, transposed, backward=True)."""
+    d = _chk(top_diff, "top_diff", ndim=5)
+    if out is not None:
+        _chk(out, "bottom diff", ndim=5)
+    _volume_blobs("conv_volume_backward_data", geom, transposed, out, out_c0, d, top_c0)
+    if out is None:
+        out = torch.empty((geom[0], geom[1]) + tuple(geom[2:5]), device=d.device, dtype=torch.float32)
+    pw = _chk(packed, "packed weight", ndim=None)
+    if pw.numel() != conv_volume_sizes(geom, transposed)[1]:
+        raise ValueError("conv_volume_backward_data: the operand has %d floats, not what the data gradient reads for this layer" % pw.numel())
+    check(_lib.lib().fn2_conv_volume_backward_data(geom, int(bool(transposed)), _ptr(d), d.shape[1], int(top_c0), _ptr(pw), _ptr(out),
+                                                   out.shape[1], int(out_c0), _stream()))
+    return out
+
+
+def conv_volume_backward_weights(bottom, top_diff, geom, transposed=False, weight_diff=None, bias_diff=None, bias=True, accumulate=False,
+                                 bottom_c0=0, top_c0=0):
+    """(weight_diff, bias_diff) of the layer (fn2_conv_volume_backward_weights; deterministic).  accumulate adds into the diffs given;
+    bias=False: no bias gradient (None comes back)."""
+    x, d = _chk(bottom, "bottom", ndim=5), _chk(top_diff, "top_diff", ndim=5)
+    _volume_blobs("conv_volume_backward_weights", geom, transposed, x, bottom_c0, d, top_c0)
+    shape, Cout = _volume_weight_shape(geom, transposed), geom[5]
+    if weight_diff is None:
+        if accumulate:
+            raise ValueError("conv_volume_backward_weights: accumulate needs the diffs to add into")
+        weight_diff = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif tuple(_chk(weight_diff, "weight diff", ndim=5).shape) != shape or not weight_diff.is_contiguous():
+        raise ValueError("conv_volume_backward_weights: weight diff has the wrong shape")
+    if bias and bias_diff is None:
+        if accumulate:
+            raise ValueError("conv_volume_backward_weights: accumulate needs the diffs to add into")
+        bias_diff = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    elif bias and (tuple(_chk(bias_diff, "bias diff", ndim=1).shape) != (Cout,) or not bias_diff.is_contiguous()):
+        raise ValueError("conv_volume_backward_weights: bias diff has the wrong shape")
+    need = conv_volume_sizes(geom, transposed)[3]
+    ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
+    check(_lib.lib().fn2_conv_volume_backward_weights(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1],
+                                                      int(top_c0), _ptr(weight_diff), _ptr(bias_diff if bias else None), int(bool(accumulate)),
+                                                      _ptr(ws), need, _stream()))
+    return weight_diff, (bias_diff if bias else None)
+
+
 def conv_mfma_supported(Cin, Hin, Win, Cout, kernel, stride, pad) -> bool:
     return bool(_lib.lib().fn2_conv_mfma_supported(int(Cin), int(Hin), int(Win), int(Cout), int(kernel), int(stride), int(pad)))
 

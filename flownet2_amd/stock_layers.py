@@ -64,71 +64,94 @@ def fill_blob(blob: Blob, filler: dict, seed_name: str = ""):
         raise CheckError("Unknown filler name: " + t)                                   # filler.hpp:319
 
 
-def _dims(cp, name, default, what=None):
-    """The repeated field `name` of a ConvolutionParameter as (h, w): specified once, or once per spatial dimension
+def _dims(cp, name, default, spatial=2):
+    """The repeated field `name` of a ConvolutionParameter, one value per spatial axis: specified once, or once per spatial dimension
     (base_conv_layer.cpp:35-44, 59-70, 83-93, 98-108); `default` None: at least one entry is required."""
     v = cp.get(name)
     v = [] if v is None else (list(v) if isinstance(v, (list, tuple)) else [v])
-    CHECK(len(v) in ((1, 2) if default is None else (0, 1, 2)),
-          "%s must be specified once, or once per spatial dimension (%s specified %d times; 2 spatial dims)." % (what or name, what or name, len(v)))
+    CHECK(len(v) in ((1, spatial) if default is None else (0, 1, spatial)),
+          "%s must be specified once, or once per spatial dimension (%s specified %d times; %d spatial dims)." % (name, name, len(v), spatial))
     if not v:
-        return default, default
-    return int(v[0]), int(v[-1])
+        return (default,) * spatial
+    return tuple(int(v[0 if len(v) == 1 else i]) for i in range(spatial))
+
+
+MAX_SPATIAL_AXES = 3            # what the general kernels state (include/flownet2_hip_conv_volume.h)
 
 
 class _ConvBase(Layer):
-    """BaseConvolutionLayer::LayerSetUp / Reshape (base_conv_layer.cpp:15-254): square or h / w kernels, pads and strides, dilation and
-    group, two spatial axes.  A PLAIN layer (square taps, one stride, one pad, dilation 1, group 1: all a FlowNet uses) runs on the routed
-    kernels of nets.py; every other layer runs forward and backward through functional.lib_conv2d / lib_conv_transpose2d."""
+    """BaseConvolutionLayer::LayerSetUp / Reshape (base_conv_layer.cpp:15-254): `axis` and 0 to 3 spatial axes behind it, kernels, pads
+    and strides once or once per axis (h / w fields with two axes), dilation and group; every axis in front of `axis` folds into the batch
+    (by a view).  force_nd_im2col chooses an im2col routine in the reference and nothing here.  A PLAIN layer (two spatial axes, square
+    taps, one stride, one pad, dilation 1, group 1: all a FlowNet uses) runs on the routed kernels of nets.py; every other layer runs
+    forward and backward through functional.lib_conv2d / lib_conv_transpose2d (0 and 1 spatial axes as a 2-D layer on a map of height 1)
+    or lib_conv3d / lib_conv_transpose3d (3 spatial axes)."""
     transposed = False
 
     def MinBottomBlobs(self): return 1
     def MinTopBlobs(self): return 1
     def EqualNumBottomTopBlobs(self): return True                                        # base_conv_layer.hpp:29
 
-    def _geom(self):
-        """(num_output, (kh, kw), (ph, pw), (sh, sw), (dh, dw), group, bias_term) as base_conv_layer.cpp:24-124 reads them."""
+    def _geom(self, spatial=2):
+        """(num_output, kernel, pad, stride, dilation, group, bias_term) as base_conv_layer.cpp:24-124 reads them, the four geometry
+        values one per spatial axis."""
         cp = self.layer_param_.convolution_param
         CHECK("num_output" in cp, "num_output is required")
-        CHECK(int(cp.get("axis", 1)) == 1 and not cp.get("force_nd_im2col", False), "N-dimensional convolution (axis, force_nd_im2col) is not supported")
-        if "kernel_h" in cp or "kernel_w" in cp:
+
+        def hw(name):
+            if name + "_h" not in cp and name + "_w" not in cp:
+                return False
+            CHECK(spatial == 2, "%s_h & %s_w can only be used for 2D convolution." % (name, name))       # base_conv_layer.cpp:28-29, 52-53, 76-77
+            return True
+        if hw("kernel"):
             CHECK(not cp.get("kernel_size"), "Either kernel_size or kernel_h/w should be specified; not both.")
-            kh, kw = int(cp.get("kernel_h", 0)), int(cp.get("kernel_w", 0))
+            kernel = int(cp.get("kernel_h", 0)), int(cp.get("kernel_w", 0))
         else:
-            kh, kw = _dims(cp, "kernel_size", None)
-        CHECK(kh > 0 and kw > 0, "Filter dimensions must be nonzero.")                   # base_conv_layer.cpp:45-47
-        if "stride_h" in cp or "stride_w" in cp:
+            kernel = _dims(cp, "kernel_size", None, spatial)
+        CHECK(all(k > 0 for k in kernel), "Filter dimensions must be nonzero.")          # base_conv_layer.cpp:45-47
+        if hw("stride"):
             CHECK(not cp.get("stride"), "Either stride or stride_h/w should be specified; not both.")
-            sh, sw = int(cp.get("stride_h", 1)), int(cp.get("stride_w", 1))
+            stride = int(cp.get("stride_h", 1)), int(cp.get("stride_w", 1))
         else:
-            sh, sw = _dims(cp, "stride", 1)
-        CHECK(sh > 0 and sw > 0, "Stride dimensions must be nonzero.")                   # base_conv_layer.cpp:69
-        if "pad_h" in cp or "pad_w" in cp:
+            stride = _dims(cp, "stride", 1, spatial)
+        CHECK(all(v > 0 for v in stride), "Stride dimensions must be nonzero.")          # base_conv_layer.cpp:69
+        if hw("pad"):
             CHECK(not cp.get("pad"), "Either pad or pad_h/w should be specified; not both.")
-            ph, pw = int(cp.get("pad_h", 0)), int(cp.get("pad_w", 0))
+            pad = int(cp.get("pad_h", 0)), int(cp.get("pad_w", 0))
         else:
-            ph, pw = _dims(cp, "pad", 0)
-        dh, dw = _dims(cp, "dilation", 1)
-        CHECK(dh >= 1 and dw >= 1, "Dilation dimensions must be nonzero.")
+            pad = _dims(cp, "pad", 0, spatial)
+        dilation = _dims(cp, "dilation", 1, spatial)
+        CHECK(all(d >= 1 for d in dilation), "Dilation dimensions must be nonzero.")
         group = int(cp.get("group", 1))
         CHECK(group >= 1, "group must be positive")
-        return int(cp["num_output"]), (kh, kw), (ph, pw), (sh, sw), (dh, dw), group, bool(cp.get("bias_term", True))
+        return int(cp["num_output"]), kernel, pad, stride, dilation, group, bool(cp.get("bias_term", True))
 
     def LayerSetUp(self, bottom, top):
-        self.num_output_, self.kernel_hw_, self.pad_hw_, self.stride_hw_, self.dilation_hw_, self.group_, self.bias_term_ = self._geom()
-        self.plain_ = (self.kernel_hw_[0] == self.kernel_hw_[1] and self.pad_hw_[0] == self.pad_hw_[1] and self.stride_hw_[0] == self.stride_hw_[1]
-                       and self.dilation_hw_ == (1, 1) and self.group_ == 1)
+        cp = self.layer_param_.convolution_param
+        num_axes, axis = bottom[0].num_axes(), int(cp.get("axis", 1))
+        CHECK(-num_axes <= axis < num_axes, "axis %d out of range for %d-D Blob with shape %s" % (axis, num_axes, bottom[0].shape_string()))
+        self.channel_axis_ = axis + num_axes if axis < 0 else axis                       # base_conv_layer.cpp:17 (blob.hpp:121-132)
+        self.num_spatial_axes_ = spatial = num_axes - self.channel_axis_ - 1
+        CHECK(spatial >= 0, "Check failed: num_spatial_axes_ >= 0 (%d vs. 0)" % spatial)   # base_conv_layer.cpp:21
+        CHECK(spatial <= MAX_SPATIAL_AXES, "convolution over %d spatial axes is not supported (0 to %d are)" % (spatial, MAX_SPATIAL_AXES))
+        self.folded_ = not (self.channel_axis_ == 1 and spatial == 2)                     # the blobs are viewed as [num, C, ...] around the kernels
+        (self.num_output_, self.kernel_shape_, self.pad_shape_, self.stride_shape_, self.dilation_shape_, self.group_,
+         self.bias_term_) = self._geom(spatial)
+        # 0 and 1 spatial axes: the 2-D layer on a map of height 1 (kernel 1, stride 1, pad 0, dilation 1 on the axes that are not there)
+        lead = max(0, 2 - spatial)
+        self.kernel_hw_, self.stride_hw_, self.dilation_hw_ = ((1,) * lead + v for v in (self.kernel_shape_, self.stride_shape_, self.dilation_shape_))
+        self.pad_hw_ = (0,) * lead + self.pad_shape_
+        self.plain_ = (spatial == 2 and self.kernel_hw_[0] == self.kernel_hw_[1] and self.pad_hw_[0] == self.pad_hw_[1]
+                       and self.stride_hw_[0] == self.stride_hw_[1] and self.dilation_hw_ == (1, 1) and self.group_ == 1)
         # what the plain code paths read; a layer that is not plain never reaches them
         self.kernel_, self.pad_, self.stride_ = (self.kernel_hw_[0], self.pad_hw_[0], self.stride_hw_[0]) if self.plain_ else (None, None, None)
         self.fused_relu_tops_ = {}              # top index -> negative slope of an in-place ReLU folded in by the executor
-        cin = bottom[0].channels()
+        cin = bottom[0].shape(self.channel_axis_)
         CHECK(self.num_output_ > 0, "num_output must be positive")                       # base_conv_layer.cpp:120
         CHECK(cin % self.group_ == 0, "Check failed: channels_ % group_ == 0")           # base_conv_layer.cpp:122
         CHECK(self.num_output_ % self.group_ == 0, "Number of output should be multiples of group.")     # base_conv_layer.cpp:123-124
-        cp = self.layer_param_.convolution_param
         if not self.blobs_:                                                               # base_conv_layer.cpp:125-152
-            kh, kw = self.kernel_hw_
-            wshape = [cin, self.num_output_ // self.group_, kh, kw] if self.transposed else [self.num_output_, cin // self.group_, kh, kw]
+            wshape = ([cin, self.num_output_ // self.group_] if self.transposed else [self.num_output_, cin // self.group_]) + list(self.kernel_shape_)
             w = Blob(*wshape, device=bottom[0].device)
             fill_blob(w, cp.get("weight_filler", {}), self.layer_param_.name + ".w")
             self.blobs_ = [w]
@@ -137,21 +160,37 @@ class _ConvBase(Layer):
                 fill_blob(b, cp.get("bias_filler", {}), self.layer_param_.name + ".b")
                 self.blobs_.append(b)
 
-    def _out_hw(self, h, w):
+    def _out_shape(self, size):
         out = []
-        for n, k, p, s, d in zip((h, w), self.kernel_hw_, self.pad_hw_, self.stride_hw_, self.dilation_hw_):
+        for n, k, p, s, d in zip(size, self.kernel_shape_, self.pad_shape_, self.stride_shape_, self.dilation_shape_):
             ext = d * (k - 1) + 1
             out.append(s * (n - 1) + ext - 2 * p if self.transposed else (n + 2 * p - ext) // s + 1)      # deconv_layer.cpp:8-22 / conv_layer.cpp:8-23
-        return tuple(out)
+        return out
+
+    def _fold(self, t):
+        """A bottom or top tensor as the kernels take it: [num, C, spatial...] with num = count(0, channel_axis) (base_conv_layer.cpp:191) and
+        at least two spatial axes -- a view of a contiguous blob; the tensor itself for a four-axis blob with axis 1."""
+        if not self.folded_:
+            return t
+        ca = self.channel_axis_
+        lead = 1
+        for d in t.shape[:ca]:
+            lead *= d
+        return t.reshape((lead, t.shape[ca]) + (1,) * max(0, 2 - self.num_spatial_axes_) + tuple(t.shape[ca + 1:]))
+
+    def _unfold(self, t, blob):
+        return t.reshape(blob.shape()) if self.folded_ else t
 
     def Reshape(self, bottom, top):
         cin = self.blobs_[0].shape(0) if self.transposed else self.blobs_[0].shape(1) * self.group_
-        CHECK(bottom[0].channels() == cin, "Input size incompatible with convolution kernel.")   # base_conv_layer.cpp:191-192
+        ca = self.channel_axis_
+        CHECK(bottom[0].num_axes() == ca + 1 + self.num_spatial_axes_, "bottom num_axes may not change.")      # base_conv_layer.cpp:189-190
+        CHECK(bottom[0].shape(ca) == cin, "Input size incompatible with convolution kernel.")    # base_conv_layer.cpp:191-192
         for b in bottom[1:]:                                                                     # base_conv_layer.cpp:194-197
             CHECK(b.shape() == bottom[0].shape(), "All inputs must have the same shape.")
-        ho, wo = self._out_hw(bottom[0].height(), bottom[0].width())
+        shape = bottom[0].shape()
         for t in top:                                                                            # one weight blob, applied to every bottom
-            t.Reshape(bottom[0].num(), self.num_output_, ho, wo)
+            t.Reshape(*(shape[:ca] + [self.num_output_] + self._out_shape(shape[ca + 1:])))       # base_conv_layer.cpp:198-207
 
     @property
     def fused_relu_(self):
@@ -171,15 +210,16 @@ class _ConvBase(Layer):
         self._stacked = None
         self._graphs = []                       # of a layer that is not plain (_general_one), one per call of `one`
         if len(bottom) > 1 and len({self._slope(i) for i in range(len(top))}) == 1 and bottom[0].data.is_cuda:
-            n = bottom[0].num()
-            x = torch.cat([b.data for b in bottom], 0)
+            xs = [self._fold(b.data) for b in bottom]
+            n = xs[0].shape[0]
+            x = torch.cat(xs, 0)
             y = one(x, self._slope(0))
             for i, t in enumerate(top):
-                t.data = y[i * n:(i + 1) * n]
+                t.data = self._unfold(y[i * n:(i + 1) * n], t)
             self._stacked = (x, y)              # Backward_gpu runs the stacked batch as ONE launch per gradient, like the forward
             return
         for i, (b, t) in enumerate(zip(bottom, top)):
-            t.data = one(b.data, self._slope(i))
+            t.data = self._unfold(one(self._fold(b.data), self._slope(i)), t)
 
     def _accumulate(self, k, g):
         """Parameter diffs accumulate (weight_gpu_gemm / backward_gpu_bias with beta = 1); Net.ClearParamDiffs zeroes them per iteration."""
@@ -191,14 +231,18 @@ class _ConvBase(Layer):
         set_general_convolution("own"), else the counted library), the folded ReLU as a pass of its own.  The autograd graph of the call is
         kept for Backward_gpu, in call order."""
         w, b = self.blobs_[0].data, (self.blobs_[1].data if self.bias_term_ else None)
-        name = "lib_conv_transpose2d" if self.transposed else "lib_conv2d"
-        f = torch.nn.functional.conv_transpose2d if self.transposed else torch.nn.functional.conv2d
+        nd = "3d" if self.num_spatial_axes_ == 3 else "2d"
+        name = ("lib_conv_transpose" if self.transposed else "lib_conv") + nd
+        f = getattr(torch.nn.functional, ("conv_transpose" if self.transposed else "conv") + nd)
+        stride, pad, dilation = (self.stride_shape_, self.pad_shape_, self.dilation_shape_) if nd == "3d" else (self.stride_hw_, self.pad_hw_, self.dilation_hw_)
+        if w.dim() != x.dim():                  # 0 and 1 spatial axes: the weight blob [., ., k...] as the 2-D layer's [., ., 1, k]
+            w = w.reshape(tuple(w.shape[:2]) + self.kernel_hw_)
         with torch.enable_grad():
             leaves = [t.detach().requires_grad_(True) if t is not None else None for t in (x, w, b)]
             if hasattr(be, name):
-                y = getattr(be, name)(leaves[0], leaves[1], leaves[2], self.stride_hw_, self.pad_hw_, dilation=self.dilation_hw_, groups=self.group_)
+                y = getattr(be, name)(leaves[0], leaves[1], leaves[2], stride, pad, dilation=dilation, groups=self.group_)
             else:
-                y = f(leaves[0], leaves[1], leaves[2], stride=self.stride_hw_, padding=self.pad_hw_, dilation=self.dilation_hw_, groups=self.group_)
+                y = f(leaves[0], leaves[1], leaves[2], stride=stride, padding=pad, dilation=dilation, groups=self.group_)
             if slope is not None:
                 y = torch.nn.functional.leaky_relu(y, slope)
         self._graphs.append((leaves, y))
@@ -234,23 +278,24 @@ class _ConvBase(Layer):
         head = self._head_kind()
         if getattr(self, "_stacked", None) is not None:
             x, y = self._stacked
-            n = bottom[0].num()
-            g = torch.cat([t.mutable_gpu_diff() for t in top], 0)
+            n = x.shape[0] // len(bottom)
+            g = torch.cat([self._fold(t.mutable_gpu_diff()) for t in top], 0)
             gx, gw, db = self._backward_one(x, y, g, self._slope(0), any(propagate_down), head)
             self._accumulate(0, gw)
             if self.bias_term_:
                 self._accumulate(1, db)
             for i, b in enumerate(bottom):
                 if propagate_down[i]:
-                    b.diff = gx[i * n:(i + 1) * n]
+                    b.diff = self._unfold(gx[i * n:(i + 1) * n], b)
             return
         for i, (b, t) in enumerate(zip(bottom, top)):
-            gx, gw, db = self._backward_one(b.data, t.data, t.mutable_gpu_diff(), self._slope(i), bool(propagate_down[i]), head, i)
+            gx, gw, db = self._backward_one(self._fold(b.data), self._fold(t.data), self._fold(t.mutable_gpu_diff()), self._slope(i),
+                                            bool(propagate_down[i]), head, i)
             self._accumulate(0, gw)
             if self.bias_term_:
                 self._accumulate(1, db)
             if propagate_down[i]:
-                b.diff = gx
+                b.diff = self._unfold(gx, b)
 
     def _backend(self):
         if self.backend_ is not None:

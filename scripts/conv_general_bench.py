@@ -2,8 +2,10 @@
 """Timing of the general-geometry convolution (csrc/conv_general.hip) next to what it stands in for, on the same tensors in one run:
 the library convolution through torch at three shapes outside FlowNet's kernel families, and the specialised own route at one FlowNet
 shape (the conv3_1 class), which states what generality costs; and (--rows geometry) four layers with groups or dilation
-(include/flownet2_hip_conv_geometry.h) against the library.  Forward, data gradient and weight (+ bias) gradient.  Run on the GPU box:
-    python scripts/conv_general_bench.py [--iters 20] [--repeats 5] [--batch 8] [--rows square|geometry|all]
+(include/flownet2_hip_conv_geometry.h) against the library; and (--rows volume, batch 4 unless --batch is given) three volumetric layers
+(include/flownet2_hip_conv_volume.h) against the library's conv3d / conv_transpose3d.  Forward, data gradient and weight (+ bias) gradient.
+Run on the GPU box:
+    python scripts/conv_general_bench.py [--iters 20] [--repeats 5] [--batch 8] [--rows square|geometry|volume|all]
 Per (shape, pass) one line: the median over the repeats of the mean time per call of each side, the spread (min .. max over the repeats),
 the ratio of the medians, and the largest difference between the two results over the result's scale.  The two sides alternate inside
 every repeat; every shape is warmed up first (operands are packed outside the timed window, as a layer packs once per weight version)."""
@@ -33,6 +35,12 @@ GEOMETRY_SHAPES = [
     ("group-2 5x5/2 64->128 @160x224", False, 64, 160, 224, 128, 5, 2, 2, 1, 2),
     ("depthwise deconv 4x4/2 128 @40x56", True, 128, 40, 56, 128, 4, 2, 1, 1, 128),
 ]
+# name, transposed, Cin, (D, H, W), Cout, kernel, stride, pad, group: three spatial axes, against the library
+VOLUME_SHAPES = [
+    ("3x3x3/1 32->32 @16x40x56", False, 32, (16, 40, 56), 32, 3, 1, 1, 1),
+    ("deconv 4x4x4/2 32->16 @8x20x28", True, 32, (8, 20, 28), 16, 4, 2, 1, 1),
+    ("depthwise 3x3x3/1 64 @16x40x56", False, 64, (16, 40, 56), 64, 3, 1, 1, 64),
+]
 
 
 def timeit(fn, iters):
@@ -52,6 +60,39 @@ def library_passes(x, w, b, g, tr, s, p, d=1, group=1):
         return torch.ops.aten.convolution_backward(g, x, w, [b.shape[0]], [s, s], [p, p], [d, d], tr, [0, 0], group, mask)
     return {"forward": lambda: conv(x, w, b, stride=s, padding=p, dilation=d, groups=group), "data gradient": lambda: backward([True, False, False])[0],
             "weight + bias gradient": lambda: backward([False, True, True])[1]}
+
+
+def library_volume_passes(x, w, b, g, tr, s, p, group):
+    conv = F.conv_transpose3d if tr else F.conv3d
+
+    def backward(mask):
+        return torch.ops.aten.convolution_backward(g, x, w, [b.shape[0]], [s] * 3, [p] * 3, [1] * 3, tr, [0] * 3, group, mask)
+    return {"forward": lambda: conv(x, w, b, stride=s, padding=p, groups=group), "data gradient": lambda: backward([True, False, False])[0],
+            "weight + bias gradient": lambda: backward([False, True, True])[1]}
+
+
+def volume_passes(x, w, b, g, geom, tr):
+    pf, pd = ops.conv_volume_pack_weights(w, geom, tr), ops.conv_volume_pack_weights(w, geom, tr, backward=True)
+    return {"forward": lambda: ops.conv_volume_forward(x, pf, b, geom, tr), "data gradient": lambda: ops.conv_volume_backward_data(g, pd, geom, tr),
+            "weight + bias gradient": lambda: ops.conv_volume_backward_weights(x, g, geom, tr)[0]}
+
+
+def measure(a, name, N, gflop, mine, theirs, other):
+    print("%s, batch %d: %.2f GFLOP per pass" % (name, N, gflop), flush=True)
+    for what in mine:
+        f, r = mine[what], theirs[what]
+        got, want = f(), r()                       # (also the warm-up of both sides at this shape)
+        for _ in range(2):
+            f(), r()
+        torch.cuda.synchronize()
+        diff = float((got - want[:, :got.shape[1]] if what == "data gradient" else got - want).abs().max()) / max(1.0, float(want.abs().max()))
+        tm, tt = [], []
+        for _ in range(a.repeats):
+            tm.append(timeit(f, a.iters))
+            tt.append(timeit(r, a.iters))
+        m, t = statistics.median(tm), statistics.median(tt)
+        print("   %-22s general %8.1f us (%.1f .. %.1f)  %6.2f TFLOP/s | %s %8.1f us (%.1f .. %.1f) | general / %s = %.2f | max diff / scale %.1e"
+              % (what, m, min(tm), max(tm), gflop / m * 1e3, other, t, min(tt), max(tt), other, m / t, diff), flush=True)
 
 
 def geometry_passes(x, w, b, g, geom, tr):
@@ -83,15 +124,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--rows", choices=["square", "geometry", "all"], default="all")
+    ap.add_argument("--batch", type=int, default=None, help="default: 8, and 4 for the volume rows")
+    ap.add_argument("--rows", choices=["square", "geometry", "volume", "all"], default="all")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("conv_general_bench: needs the GPU (a CPU run measures nothing)")
     gen = torch.Generator(device="cuda").manual_seed(0)
-    N = a.batch
-    rows = [r[:9] + (1, 1) + r[9:] for r in SHAPES] if a.rows != "geometry" else []
-    rows += [r + ("library",) for r in GEOMETRY_SHAPES] if a.rows != "square" else []
+    N = a.batch or 8
+    rows = [r[:9] + (1, 1) + r[9:] for r in SHAPES] if a.rows in ("square", "all") else []
+    rows += [r + ("library",) for r in GEOMETRY_SHAPES] if a.rows in ("geometry", "all") else []
     for name, tr, Cin, H, W, Cout, k, s, p, d, group, other in rows:
         square = d == 1 and group == 1
         desc = ops.conv_desc(N, Cin, H, W, Cout, k, s, p)
@@ -102,24 +143,20 @@ def main():
         b = torch.randn(Cout, device="cuda", generator=gen)
         g = torch.randn(N, Cout, Ho, Wo, device="cuda", generator=gen)
         gflop = 2.0 * N * Cin * (Cout // group) * k * k * (H * W if tr else Ho * Wo) / 1e9
-        print("%s, batch %d: %.2f GFLOP per pass" % (name, N, gflop), flush=True)
         mine = general_passes(x, w, b, g, desc, tr) if square else geometry_passes(x, w, b, g, geom, tr)
         theirs = library_passes(x, w, b, g, tr, s, p, d, group) if other == "library" else specialised_passes(x, w, b, g, desc, tr)
-        for what in mine:
-            f, r = mine[what], theirs[what]
-            got, want = f(), r()                       # (also the warm-up of both sides at this shape)
-            for _ in range(2):
-                f(), r()
-            torch.cuda.synchronize()
-            diff = float((got - want[:, :got.shape[1]] if what == "data gradient" else got - want).abs().max()) / max(1.0, float(want.abs().max()))
-            tm, tt = [], []
-            for _ in range(a.repeats):
-                tm.append(timeit(f, a.iters))
-                tt.append(timeit(r, a.iters))
-            m, t = statistics.median(tm), statistics.median(tt)
-            print("   %-22s general %8.1f us (%.1f .. %.1f)  %6.2f TFLOP/s | %s %8.1f us (%.1f .. %.1f) | general / %s = %.2f | max diff / scale %.1e"
-                  % (what, m, min(tm), max(tm), gflop / m * 1e3, other, t, min(tt), max(tt), other, m / t, diff), flush=True)
-
+        measure(a, name, N, gflop, mine, theirs, other)
+    N = a.batch or 4
+    for name, tr, Cin, size, Cout, k, s, p, group in (VOLUME_SHAPES if a.rows in ("volume", "all") else []):
+        geom = ops.conv_volume(N, Cin, size, Cout, k, s, p, 1, group)
+        out = ops.conv_volume_out_shape(geom, tr)
+        x = torch.randn((N, Cin) + size, device="cuda", generator=gen)
+        w = torch.randn((Cin, Cout // group, k, k, k) if tr else (Cout, Cin // group, k, k, k), device="cuda", generator=gen) * 0.1
+        b = torch.randn(Cout, device="cuda", generator=gen)
+        g = torch.randn((N, Cout) + out, device="cuda", generator=gen)
+        voxels = size[0] * size[1] * size[2] if tr else out[0] * out[1] * out[2]
+        gflop = 2.0 * N * Cin * (Cout // group) * k ** 3 * voxels / 1e9
+        measure(a, name, N, gflop, volume_passes(x, w, b, g, geom, tr), library_volume_passes(x, w, b, g, tr, s, p, group), "library")
 
 if __name__ == "__main__":
     main()

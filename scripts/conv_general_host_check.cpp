@@ -1,4 +1,4 @@
-// Host side of csrc/conv_general.hip (descriptor checks, fn2_conv_general_supported, fn2_conv_general_sizes) as a stand-alone program for
+// Host side of csrc/conv_general.hip (descriptor checks, _supported, _out_shape, _sizes and the weight-gradient plan of all three headers) as a stand-alone program for
 // AddressSanitizer / UndefinedBehaviorSanitizer: the row list of tests/conv_general_cases.py, FlowNet's classes, the invalid descriptors
 // and descriptors at the ends of the int range.  No GPU and no Python involved; built and run by scripts/conv_general_host_check.sh.
 #include <cstdio>
@@ -6,6 +6,7 @@
 #include <climits>
 #include "flownet2_hip_conv_general.h"
 #include "flownet2_hip_conv_geometry.h"
+#include "flownet2_hip_conv_volume.h"
 namespace fn2 { std::string& last_error() { static std::string s; return s; } int& batch_invariant_flag() { static int f = 0; return f; } }
 int main() {
   const int rows[][9] = {
@@ -52,6 +53,37 @@ int main() {
     if (fn2_conv_geometry_supported(r + 1, r[0]) != 0 || fn2_conv_geometry_sizes(r + 1, r[0], &a, &b, &c, &w) != FN2_ERR_UNSUPPORTED || a || b || c || w ||
         fn2_conv_geometry_out_shape(r + 1, r[0], &oh, &ow) != FN2_ERR_UNSUPPORTED || oh || ow) { printf("bad geometry accepted %d %d\n", r[6], r[14]); ++fails; }
   }
+  // the 19-int geometries of include/flownet2_hip_conv_volume.h: {transposed, N, Cin, D, H, W, Cout, kd, kh, kw, sd, sh, sw, pd, ph, pw, dd, dh, dw,
+  // group}: rows of tests/conv_volume_cases.py, its invalid list, and values at the ends of the int range in every field
+  const int vrows[][20] = {
+    {0,2,3,4,5,6,5,3,3,3,1,1,1,1,1,1,1,1,1,1},{0,1,4,3,7,6,6,1,3,2,1,2,1,0,1,0,1,1,1,1},{0,2,3,7,5,8,4,3,2,2,2,1,1,1,0,2,2,1,3,1},
+    {0,1,4,3,4,5,34,2,2,2,1,1,1,0,0,0,1,1,1,2},{0,2,3,4,4,5,3,3,3,3,1,1,1,1,1,1,1,1,1,3},{0,1,20,3,4,4,6,2,2,2,1,1,1,0,0,0,1,1,1,1},
+    {0,2,2,3,5,7,3,3,3,3,1,1,1,1,1,1,1,1,1,1},{0,1,2,3,6,5,3,5,3,3,1,1,1,1,1,1,1,1,1,1},
+    {1,2,5,2,3,4,3,4,4,4,2,2,2,1,1,1,1,1,1,1},{1,1,3,2,3,3,4,3,3,3,3,3,3,1,1,1,2,2,2,1},{1,1,4,3,4,5,3,3,2,2,2,1,1,1,0,2,2,1,3,1},
+    {1,1,4,2,3,3,6,2,3,2,1,2,1,0,1,0,1,1,1,2},
+    {0,2,4,1,1,9,6,1,1,3,1,1,2,0,0,1,1,1,2,2},{1,2,4,1,1,1,6,1,1,1,1,1,1,0,0,0,1,1,1,1}};      // (one and no spatial axis, folded)
+  const int vbad[][20] = {
+    {0,1,5,4,4,4,4,3,3,3,1,1,1,1,1,1,1,1,1,2},{0,1,4,4,4,4,5,3,3,3,1,1,1,1,1,1,1,1,1,2},{0,1,4,4,4,4,4,3,3,3,1,1,1,1,1,1,0,1,1,1},
+    {0,1,4,4,8,8,4,3,3,3,1,1,1,1,1,1,3,1,1,1},{1,1,4,1,4,4,4,2,2,2,1,1,1,1,0,0,1,1,1,2},{0,1,4,4,4,4,4,0,3,3,1,1,1,1,1,1,1,1,1,1},
+    {0,1,4,4,4,4,4,3,3,3,0,1,1,1,1,1,1,1,1,1},{0,1,4,4,4,4,4,3,3,3,1,1,1,-1,1,1,1,1,1,1},{0,1,4,4,4,4,4,3,3,3,1,1,1,1,1,1,1,1,1,0},
+    {0,1,4,1<<10,1<<10,1<<10,4,3,3,3,1,1,1,1,1,1,1,1,1,2},{0,1,4,0,4,4,4,3,3,3,1,1,1,1,1,1,1,1,1,1},
+    {0,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M},{1,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,M,1},{0,1,1,8,8,8,1,M,M,M,1,1,1,M,M,M,M,M,M,1},
+    {1,1,1,M,M,M,1,2,2,2,M,M,M,0,0,0,M,M,M,1},{0,1,M,1,1,1,M,1,1,1,1,1,1,0,0,0,1,1,1,M},{0,1,1,8,8,8,1,3,3,3,1,1,1,M/2,M/2,M/2,M/2,M/2,M/2,1},
+    {1,1,1,1,1,1,1,M,1,1,1,1,1,0,0,0,M,1,1,1},{0,1,1,1,1,1,1,1,1,1,M,M,M,M/2,M/2,M/2,1,1,1,1},{0,1,1,M,2,2,1,1,1,1,1,1,1,0,0,0,1,1,1,1},
+    {0,1,1,1291,1291,1291,1,1,1,1,1,1,1,0,0,0,1,1,1,1},{0,1,1,8,8,8,1,1291,1291,1291,1,1,1,645,645,645,1,1,1,1}};
+  for (auto& r : vrows) {
+    size_t a=0,b=0,c=1,w=0; int od=0, oh=0, ow=0;
+    if (fn2_conv_volume_supported(r + 1, r[0]) != 1 || fn2_conv_volume_sizes(r + 1, r[0], &a, &b, &c, &w) != 0 || !a || !b || c || !w ||
+        fn2_conv_volume_out_shape(r + 1, r[0], &od, &oh, &ow) != 0 || od < 1 || oh < 1 || ow < 1) { printf("volume row refused\n"); ++fails; }
+    else printf("ok %zu %zu %zu %d x %d x %d\n", a, b, w, od, oh, ow);
+  }
+  for (auto& r : vbad) {
+    size_t a=1,b=1,c=1,w=1; int od=1, oh=1, ow=1;
+    if (fn2_conv_volume_supported(r + 1, r[0]) != 0 || fn2_conv_volume_sizes(r + 1, r[0], &a, &b, &c, &w) != FN2_ERR_UNSUPPORTED || a || b || c || w ||
+        fn2_conv_volume_out_shape(r + 1, r[0], &od, &oh, &ow) != FN2_ERR_UNSUPPORTED || od || oh || ow) { printf("bad volume accepted %d %d\n", r[7], r[19]); ++fails; }
+  }
+  if (fn2_conv_volume_supported(nullptr, 0) != 0 || fn2_conv_volume_out_shape(nullptr, 1, nullptr, nullptr, nullptr) != FN2_ERR_UNSUPPORTED ||
+      fn2_conv_volume_sizes(nullptr, 0, nullptr, nullptr, nullptr, nullptr) != FN2_ERR_UNSUPPORTED) ++fails;
   if (fn2_conv_geometry_supported(nullptr, 0) != 0 || fn2_conv_geometry_out_shape(nullptr, 1, nullptr, nullptr) != FN2_ERR_UNSUPPORTED) ++fails;
   if (fn2_conv_general_supported(nullptr, 0) != 0 || fn2_conv_general_sizes(nullptr, 1, nullptr, nullptr, nullptr, nullptr) != FN2_ERR_UNSUPPORTED) ++fails;
   printf("%s: %s\n", fails ? "FAILED" : "clean", fn2::last_error().c_str());
