@@ -5,12 +5,13 @@ _lib/ops   ctypes binding (no fallback: a missing library raises)
 layers     host-side mirror of the reference's Caffe Layer<Dtype> / LayerRegistry interface
 functional torch.autograd glue,  nets: FlowNetC/S graphs,  flo: .flo I/O
 solver     SolverParameter, Solver (SGDSolver / AdamSolver, get_solver) and CaffeOptimizer on the one-launch HIP update
+LpqSchedule  the p / q episodes of LpqLoss (lpq_schedule.py)
 """
 from . import _lib  # noqa: F401
 from ._lib import Fn2Error, version  # noqa: F401
 
 _SOLVER_EXPORTS = ("SolverParameter", "Solver", "SGDSolver", "AdamSolver", "get_solver", "CaffeOptimizer")
-__all__ = ["Fn2Error", "version", *_SOLVER_EXPORTS]
+__all__ = ["Fn2Error", "version", "LpqSchedule", *_SOLVER_EXPORTS]
 
 
 def __getattr__(name):
@@ -18,4 +19,7 @@ def __getattr__(name):
     if name in _SOLVER_EXPORTS:
         from . import solver
         return getattr(solver, name)
+    if name == "LpqSchedule":
+        from .lpq_schedule import LpqSchedule
+        return LpqSchedule
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,6 +1,6 @@
 """ctypes binding of libflownet2_hip.so, derived from the C headers in include/ (they are its one source).
 
-Importing this module parses the six headers: every `fn2_*` function declaration becomes argtypes / restype, every `typedef struct fn2_*`
+Importing this module parses the seven headers: every `fn2_*` function declaration becomes argtypes / restype, every `typedef struct fn2_*`
 a ctypes.Structure (CorrParams, ConvDesc, ...), every `enum { FN2_* }` and `#define FN2_* <integer>` an entry of CONSTANTS.  lib() loads the
 library and applies the prototypes.  A new entry point is declared in a header; nothing is added here.  What the parser does not understand
 is an error that names the declaration, never an `int` by default.
@@ -102,11 +102,11 @@ def parse_header(text, structs=None):
 
 
 def _parse_headers():
-    """The six headers, each read on its own (an #include is not followed: the per-header name lists stay apart); the main one first,
+    """The seven headers, each read on its own (an #include is not followed: the per-header name lists stay apart); the main one first,
     whose structures the others use."""
     per_header, structs, constants = [], {}, {}
     for h in ("flownet2_hip.h", "flownet2_hip_solver.h", "flownet2_hip_corr_route.h", "flownet2_hip_conv_general.h",
-              "flownet2_hip_conv_geometry.h", "flownet2_hip_conv_volume.h"):
+              "flownet2_hip_conv_geometry.h", "flownet2_hip_conv_volume.h", "flownet2_hip_lpq_loss.h"):
         with open(os.path.join(INCLUDE_DIR, h)) as f:
             functions, structs, c = parse_header(f.read(), structs)
         per_header.append(functions)
@@ -115,7 +115,7 @@ def _parse_headers():
 
 
 _PER_HEADER, _STRUCTS, CONSTANTS = _parse_headers()         # CONSTANTS: every FN2_* enumerator and integer #define
-EXPORTS, SOLVER_EXPORTS, CORR_ROUTE_EXPORTS, CONV_GENERAL_EXPORTS, CONV_GEOMETRY_EXPORTS, CONV_VOLUME_EXPORTS = (
+EXPORTS, SOLVER_EXPORTS, CORR_ROUTE_EXPORTS, CONV_GENERAL_EXPORTS, CONV_GEOMETRY_EXPORTS, CONV_VOLUME_EXPORTS, LPQ_LOSS_EXPORTS = (
     list(f) for f in _PER_HEADER)      # per header
 PROTOTYPES = {name: proto for f in _PER_HEADER for name, proto in f.items()}
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})      # CaffemodelEntry, Hdf5Entry, ConvDesc, CorrParams, DatumView, ...

@@ -29,6 +29,8 @@ $HIPCC $FLAGS -DFN2_SHIM_L1LOSS=1 -DFN2_SHIM_CONV_REGISTRY=1 $NETDEF -x hip -c "
 $HIPCC $FLAGS -x hip -c "$HERE/geometry_shim.cpp" -o "$OUT/geometry_shim.o"
 # and the one for blobs of any number of axes (axis, 0 to 3 spatial axes, force_nd_im2col)
 $HIPCC $FLAGS -x hip -c "$HERE/volume_shim.cpp" -o "$OUT/volume_shim.o"
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libfn2_caffe_adapter_test.so" "$OUT/fn2_caffe_layers.o" "$OUT/shim.o" "$OUT/geometry_shim.o" "$OUT/volume_shim.o" $STOCK_OBJS \
+# and the one for the LpqLoss plug-in and its schedule (a net that states its iteration)
+$HIPCC $FLAGS -x hip -c "$HERE/lpq_shim.cpp" -o "$OUT/lpq_shim.o"
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libfn2_caffe_adapter_test.so" "$OUT/fn2_caffe_layers.o" "$OUT/shim.o" "$OUT/geometry_shim.o" "$OUT/volume_shim.o" "$OUT/lpq_shim.o" $STOCK_OBJS \
   -L"$ROOT/flownet2_amd" -lflownet2_hip -Wl,-rpath,'$ORIGIN/../../..'
 echo "built $OUT/libfn2_caffe_adapter_test.so"

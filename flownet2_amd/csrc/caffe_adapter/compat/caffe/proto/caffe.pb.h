@@ -88,6 +88,32 @@ class L1LossParameter {
   float epsilon_ = 1e-2f, plateau_ = 0.f;
 };
 
+class LpqLossParameter {              // caffe.proto:563-602
+ public:
+  bool l2_prescale_by_channels() const { return l2_prescale_by_channels_; }
+  bool normalize_by_num_entries() const { return normalize_by_num_entries_; }
+  float p_epsilon() const { return p_epsilon_; }
+  float q_epsilon() const { return q_epsilon_; }
+  void set_l2_prescale_by_channels(bool v) { l2_prescale_by_channels_ = v; }
+  void set_normalize_by_num_entries(bool v) { normalize_by_num_entries_ = v; }
+  void set_p_epsilon(float v) { p_epsilon_ = v; }
+  void set_q_epsilon(float v) { q_epsilon_ = v; }
+  int pq_episode_starts_at_iter_size() const { return (int)starts_.size(); }
+  unsigned pq_episode_starts_at_iter(int i) const { return starts_[i]; }
+  void add_pq_episode_starts_at_iter(unsigned v) { starts_.push_back(v); }
+  int p_size() const { return (int)p_.size(); }
+  float p(int i) const { return p_[i]; }
+  void add_p(float v) { p_.push_back(v); }
+  int q_size() const { return (int)q_.size(); }
+  float q(int i) const { return q_[i]; }
+  void add_q(float v) { q_.push_back(v); }
+ private:
+  bool l2_prescale_by_channels_ = false, normalize_by_num_entries_ = false;
+  float p_epsilon_ = 0.f, q_epsilon_ = 1e-2f;
+  std::vector<unsigned> starts_;
+  std::vector<float> p_, q_;
+};
+
 class DownsampleParameter {
  public:
   unsigned top_height() const { return top_height_; }
@@ -520,6 +546,9 @@ class AugmentationParameter {
 };
 
 enum Phase { TRAIN = 0, TEST = 1 };
+class NetParameter;                  // named by the declarations of the reference's net.hpp (the LpqLoss plug-in includes it for Net::iter)
+class NetState;
+class NetStateRule;
 
 class LayerParameter {
  public:
@@ -544,6 +573,8 @@ class LayerParameter {
   CorrelationParameter* mutable_correlation_param() { return &correlation_param_; }
   const L1LossParameter& l1_loss_param() const { return l1_loss_param_; }                   // = 151
   L1LossParameter* mutable_l1_loss_param() { return &l1_loss_param_; }
+  const LpqLossParameter& lpq_loss_param() const { return lpq_loss_param_; }                // = 158
+  LpqLossParameter* mutable_lpq_loss_param() { return &lpq_loss_param_; }
   const ResampleParameter& resample_param() const { return resample_param_; }               // = 155
   ResampleParameter* mutable_resample_param() { return &resample_param_; }
   const DownsampleParameter& downsample_param() const { return downsample_param_; }         // = 156
@@ -580,6 +611,7 @@ class LayerParameter {
   Phase phase_ = TEST;
   CorrelationParameter correlation_param_;
   L1LossParameter l1_loss_param_;
+  LpqLossParameter lpq_loss_param_;
   ResampleParameter resample_param_;
   DownsampleParameter downsample_param_;
   FlowWarpParameter flow_warp_param_;

@@ -17,6 +17,7 @@
 // Only Dtype = float is instantiated: the C ABI is fp32 (the reference's tools use float, tools/caffe.cpp:203).
 #include <algorithm>
 #include <cmath>
+#include <sstream>
 #include <type_traits>
 #include <vector>
 
@@ -24,11 +25,13 @@
 #include "caffe/filler.hpp"
 #include "caffe/layer.hpp"
 #include "caffe/layer_factory.hpp"
+#include "caffe/net.hpp"
 #include "caffe/proto/caffe.pb.h"
 
 #include "flownet2_hip.h"
 #include "flownet2_hip_conv_general.h"
 #include "flownet2_hip_conv_volume.h"
+#include "flownet2_hip_lpq_loss.h"
 
 namespace caffe {
 
@@ -325,6 +328,90 @@ class L1LossLayer : public Layer<Dtype> {
                                  workspace_.count() * sizeof(Dtype), kStream));
   }
   fn2_l1loss_params params_;
+  Blob<Dtype> workspace_, loss_dev_;
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// LpqLoss (include/caffe/layers/lpq_loss_layer.hpp; lpq_loss_layer.cpp:14-173, lpq_loss_layer.cu:97-245) on the fused kernels of
+// include/flownet2_hip_lpq_loss.h.  No state between forward and backward but the workspace ({loss, normalize_coeff} stay on the
+// device): p and q are picked from the schedule by the net's iteration in both passes -- a pure function of it, where the reference pops a
+// queue and never steps back.
+template <typename Dtype>
+class LpqLossLayer : public Layer<Dtype> {
+ public:
+  explicit LpqLossLayer(const LayerParameter& param) : Layer<Dtype>(param) {}
+  virtual void LayerSetUp(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
+    if (this->layer_param_.loss_weight_size() == 0) this->layer_param_.add_loss_weight(Dtype(1));   // LossLayer::LayerSetUp, loss_layer.cpp:8-13
+    const LpqLossParameter& lp = this->layer_param_.lpq_loss_param();
+    const int ns = lp.pq_episode_starts_at_iter_size(), np = lp.p_size(), nq = lp.q_size();
+    starts_.clear(); ps_.clear(); qs_.clear();
+    if (ns == 0 && np == 1 && nq == 1) {                                                            // lpq_loss_layer.cpp:29-37
+      starts_.push_back(0);
+    } else {
+      if (ns != np || np != nq)                                                                     // cpp:41-47
+        LOG(FATAL) << "Incompatible sizes: (pq_episode_starts_at_iter -> " << ns << ", p -> " << np << ", q -> " << nq << ")";
+      if (ns < 1) LOG(FATAL) << "Lpq schedule parameters must not be empty";                        // cpp:49-51
+      for (int i = 0; i + 1 < ns; ++i)                                                              // cpp:53-64
+        if (lp.pq_episode_starts_at_iter(i) >= lp.pq_episode_starts_at_iter(i + 1)) {
+          std::ostringstream oss;
+          for (int j = 0; j < ns; ++j) oss << " " << lp.pq_episode_starts_at_iter(j);
+          LOG(FATAL) << "pq_episode_starts_at_frame is not ordered or contains duplicates:" << oss.str();
+        }
+      if (lp.pq_episode_starts_at_iter(0) != 0)                                                     // cpp:66-69
+        LOG(FATAL) << "First entry in pq_episode_starts_at_frame is not 0, this is probably a mistake.";
+      for (int i = 0; i < ns; ++i) starts_.push_back((int)lp.pq_episode_starts_at_iter(i));
+    }
+    for (int i = 0; i < np; ++i) { ps_.push_back(lp.p(i)); qs_.push_back(lp.q(i)); }
+    if (bottom.size() != 1 && bottom.size() != 2) LOG(FATAL) << "LpqLossLayer needs one or two input blobs.";   // cpp:98-100
+  }
+  virtual void Reshape(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
+    top[0]->Reshape(vector<int>());   // Loss layers output a scalar; 0 axes.
+    size_t need = 0;
+    FN2_CALL(fn2_lpq_loss_sizes(1, &need, nullptr, nullptr));
+    workspace_.Reshape(vector<int>{(int)((need + sizeof(Dtype) - 1) / sizeof(Dtype))});
+    loss_dev_.Reshape(vector<int>{1});
+  }
+  virtual inline const char* type() const { return "LpqLoss"; }
+  virtual inline int ExactNumBottomBlobs() const { return -1; }
+  virtual inline int MinBottomBlobs() const { return 1; }
+  virtual inline int MaxBottomBlobs() const { return 2; }
+  virtual inline int ExactNumTopBlobs() const { return 1; }
+  virtual inline bool AutoTopBlobs() const { return true; }
+  virtual inline bool AllowForceBackward(const int) const { return true; }
+
+ protected:
+  // the episode in force at the net's iteration (lpq_loss_layer.cu:100-135; 0 without a net)
+  int Episode() {
+    Net<Dtype>* net = this->GetNet();
+    const int step = fn2_lpq_loss_schedule_step((int)starts_.size(), starts_.data(), net ? net->iter() : 0);
+    return step < 0 ? 0 : step;
+  }
+  virtual void Forward_cpu(const vector<Blob<Dtype>*>&, const vector<Blob<Dtype>*>&) { NOT_IMPLEMENTED; }
+  virtual void Backward_cpu(const vector<Blob<Dtype>*>&, const vector<bool>&, const vector<Blob<Dtype>*>&) { NOT_IMPLEMENTED; }
+  virtual void Forward_gpu(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
+    const LpqLossParameter& lp = this->layer_param_.lpq_loss_param();
+    const int e = Episode();
+    FN2_CALL(fn2_lpq_loss_forward(f32(bottom[0]->gpu_data()), bottom.size() > 1 ? f32(bottom[1]->gpu_data()) : nullptr,
+                                  f32(loss_dev_.mutable_gpu_data()), bottom[0]->num(), bottom[0]->channels(), bottom[0]->height(),
+                                  bottom[0]->width(), ps_[e], qs_[e], lp.p_epsilon(), lp.q_epsilon(), lp.l2_prescale_by_channels(),
+                                  lp.normalize_by_num_entries(), f32(workspace_.mutable_gpu_data()), workspace_.count() * sizeof(Dtype), kStream));
+    top[0]->mutable_cpu_data()[0] = loss_dev_.cpu_data()[0];   // the reference also writes the scalar on the host (lpq_loss_layer.cu:197)
+  }
+  virtual void Backward_gpu(const vector<Blob<Dtype>*>& top, const vector<bool>& propagate_down, const vector<Blob<Dtype>*>& bottom) {
+    bool prop_down = propagate_down[0];
+    if (bottom.size() > 1) prop_down |= propagate_down[1];
+    if (!prop_down) return;
+    const LpqLossParameter& lp = this->layer_param_.lpq_loss_param();
+    const int e = Episode();
+    FN2_CALL(fn2_lpq_loss_backward(f32(bottom[0]->gpu_data()), bottom.size() > 1 ? f32(bottom[1]->gpu_data()) : nullptr,
+                                   top[0]->cpu_diff()[0], f32(bottom[0]->mutable_gpu_diff()),
+                                   bottom.size() > 1 ? f32(bottom[1]->mutable_gpu_diff()) : nullptr, bottom[0]->num(), bottom[0]->channels(),
+                                   bottom[0]->height(), bottom[0]->width(), ps_[e], qs_[e], lp.p_epsilon(), lp.q_epsilon(),
+                                   lp.l2_prescale_by_channels(), lp.normalize_by_num_entries(), f32(workspace_.mutable_gpu_data()),
+                                   workspace_.count() * sizeof(Dtype), kStream));
+  }
+  vector<int> starts_;
+  vector<float> ps_, qs_;
   Blob<Dtype> workspace_, loss_dev_;
 };
 
@@ -719,6 +806,8 @@ INSTANTIATE_CLASS(ResampleLayer);
 REGISTER_LAYER_CLASS(Resample);
 INSTANTIATE_CLASS(L1LossLayer);
 REGISTER_LAYER_CLASS(L1Loss);
+INSTANTIATE_CLASS(LpqLossLayer);
+REGISTER_LAYER_CLASS(LpqLoss);
 INSTANTIATE_CLASS(ChannelNormLayer);
 REGISTER_LAYER_CLASS(ChannelNorm);
 INSTANTIATE_CLASS(DownsampleLayer);

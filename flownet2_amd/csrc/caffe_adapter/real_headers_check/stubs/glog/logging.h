@@ -24,6 +24,7 @@ struct Voidify { void operator&(std::ostream&) {} };
 #define DLOG(sev) LOG(sev)
 #define LOG_IF(sev, cond) !(cond) ? (void)0 : ::fn2_glog::Voidify() & LOG(sev)
 #define LOG_FIRST_N(sev, n) LOG(sev)
+#define LOG_EVERY_N(sev, n) LOG(sev)
 #define CHECK(cond) (cond) ? (void)0 : ::fn2_glog::Voidify() & ::fn2_glog::Msg(true).stream() << "Check failed: " #cond " "
 #define FN2_GLOG_OP(a, b, op) ((a) op (b)) ? (void)0 : ::fn2_glog::Voidify() & ::fn2_glog::Msg(true).stream() << "Check failed: " #a " " #op " " #b " "
 #define CHECK_EQ(a, b) FN2_GLOG_OP(a, b, ==)

@@ -474,6 +474,78 @@ def l1_loss_multi(preds, targets, weights, l2_per_location=False, l2_prescale_by
     return _L1LossMulti.apply(p, tuple(float(w) for w in weights), len(preds), *blobs)
 
 
+class _LpqLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, b0, b1, params):
+        loss, ws = ops.lpq_loss_forward(params, b0, b1)
+        ctx.params, ctx.ws = params, ws
+        ctx.save_for_backward(b0, b1)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        b0, b1 = ctx.saved_tensors
+        # the C ABI takes the loss weight as a host float, like top[0]->cpu_diff()[0] (lpq_loss_layer.cu:215)
+        d0, d1 = ops.lpq_loss_backward(ctx.params, b0, b1, float(g), ctx.ws)
+        return (d0 if ctx.needs_input_grad[0] else None), (d1 if (b1 is not None and ctx.needs_input_grad[1]) else None), None
+
+
+def lpq_loss(b0, b1=None, p=1.0, q=1.0, p_epsilon=0.0, q_epsilon=1e-2, l2_prescale_by_channels=False, normalize_by_num_entries=False):
+    """LpqLoss: sum over (n, y, x) of (sum_c w (|b0 - b1| + p_epsilon)^p + q_epsilon)^q / normalize_coeff (csrc/lpq_loss.hip);
+    p = 2, q = 0.5 is the l2_per_location form of l1_loss.  The defaults are caffe.proto:563-602's."""
+    params = ops.lpq_params(p, q, p_epsilon, q_epsilon, l2_prescale_by_channels, normalize_by_num_entries)
+    return _LpqLoss.apply(b0.contiguous(), b1.contiguous() if b1 is not None else None, params)
+
+
+class _LpqLossMulti(torch.autograd.Function):
+    """All LpqLoss layers of a net: forward and backward one launch each, the weighted sum included; the upstream gradient stays on
+    the device (as _L1LossMulti)."""
+
+    @staticmethod
+    def forward(ctx, params, weights, n, *blobs):
+        b0, b1 = list(blobs[:n]), list(blobs[n:])
+        total, losses, ws = ops.lpq_loss_forward_multi(params, b0, b1, weights)
+        ctx.params, ctx.weights, ctx.n, ctx.ws = params, weights, n, ws
+        ctx.save_for_backward(*blobs)
+        ctx.mark_non_differentiable(losses)
+        return total, losses
+
+    @staticmethod
+    def backward(ctx, g, _g_losses):
+        n = ctx.n
+        blobs = ctx.saved_tensors
+        b0, b1 = list(blobs[:n]), list(blobs[n:])
+        need1 = any(ctx.needs_input_grad[3 + n:])
+        d0, d1 = ops.lpq_loss_backward_multi(ctx.params, b0, b1, ctx.weights, g.contiguous(), ctx.ws, need1=need1)
+        grads = [d if ctx.needs_input_grad[3 + k] else None for k, d in enumerate(d0)]
+        grads += [d if ctx.needs_input_grad[3 + n + k] else None for k, d in enumerate(d1)]
+        return (None, None, None) + tuple(grads)
+
+
+def lpq_loss_multi(preds, targets, weights, p=1.0, q=1.0, p_epsilon=0.0, q_epsilon=1e-2, l2_prescale_by_channels=False,
+                   normalize_by_num_entries=False):
+    """sum_k weights[k] * LpqLoss(preds[k], targets[k]) -- the loss layers of a training net -- as (total, per-scale losses)."""
+    params = ops.lpq_params(p, q, p_epsilon, q_epsilon, l2_prescale_by_channels, normalize_by_num_entries)
+    blobs = [t.contiguous() for t in preds] + [t.contiguous() for t in targets]
+    return _LpqLossMulti.apply(params, tuple(float(w) for w in weights), len(preds), *blobs)
+
+
+def add_loss_flags(ap):
+    """--loss l1 | lpq and the Lpq schedule of a training script (scripts/train_pipeline.py, scripts/train_prototxt_step.py)."""
+    ap.add_argument("--loss", choices=("l1", "lpq"), default="l1", help="l1: L1Loss{l2_per_location} (the default); lpq: LpqLoss with --lpq-p / --lpq-q")
+    ap.add_argument("--lpq-p", type=float, nargs="+", default=[2.0], metavar="P", help="p of every episode (one value: constant)")
+    ap.add_argument("--lpq-q", type=float, nargs="+", default=[0.2], metavar="Q", help="q of every episode")
+    ap.add_argument("--lpq-starts", type=int, nargs="+", default=[], metavar="ITER", help="iteration at which each episode starts (the first is 0)")
+    ap.add_argument("--lpq-p-epsilon", type=float, default=0.0)
+    ap.add_argument("--lpq-q-epsilon", type=float, default=1e-2)
+
+
+def loss_schedule(args):
+    """None for --loss l1, else the LpqSchedule of the flags (its checks are LpqLossLayer::LayerSetUp's)."""
+    from .lpq_schedule import LpqSchedule
+    return LpqSchedule(args.lpq_starts, args.lpq_p, args.lpq_q) if args.loss == "lpq" else None
+
+
 class _PredictFlow(torch.autograd.Function):
     """predict_flow (Convolution{3,1,1} C -> 2): own forward (csrc/flow_head.hip) and own backward (csrc/flow_head_bwd.hip: weight,
     bias and bottom gradients as streaming kernels over NCHW -- a 2-channel side cannot feed a matrix tile)."""

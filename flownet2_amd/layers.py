@@ -13,6 +13,7 @@ The C++ twin of this file for a real Caffe tree is flownet2_amd/csrc/caffe_adapt
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -119,6 +120,7 @@ class LayerParameter:
     flow_warp_param: Dict = field(default_factory=dict)
     resample_param: Dict = field(default_factory=dict)
     l1_loss_param: Dict = field(default_factory=dict)
+    lpq_loss_param: Dict = field(default_factory=dict)        # LpqLossParameter, caffe.proto:563-602
     downsample_param: Dict = field(default_factory=dict)
     data_param: Dict = field(default_factory=dict)      # DataParameter, caffe.proto:918-986 (CustomData)
     augmentation_param: Dict = field(default_factory=dict)   # AugmentationParameter, caffe.proto:489-546 (crop sizes, mean, generators as dicts)
@@ -160,6 +162,10 @@ class Layer:
         self.blobs_: List[Blob] = []          # learnable parameters (layer.hpp:288-291)
         self.param_propagate_down_: List[bool] = []       # layer.hpp:327-341, set by Net::Init (net.cpp:173-185)
         self.backend_ = None                  # flownet2_amd.functional unless the Net was given another one (stock layers only)
+        self.net_ = None                      # the Net that owns the layer (layer.hpp:123-128), set by Net as net.cpp:90 does
+
+    def SetNet(self, net): self.net_ = net                # layer.hpp:123-125
+    def GetNet(self): return self.net_                    # layer.hpp:126-128
 
     def blobs(self):
         return self.blobs_
@@ -433,6 +439,60 @@ class L1LossLayer(Layer):
         d0, d1 = _wrap(ops.l1loss_backward, self.params_, bottom[0].data, b1, top_diff, self.ws_)
         if len(bottom) > 1:
             # Eltwise backward honours propagate_down per bottom (eltwise_layer.cu Backward)
+            if propagate_down[0]: bottom[0].diff = d0
+            if propagate_down[1]: bottom[1].diff = d1
+        else:
+            bottom[0].diff = d0
+
+
+class LpqLossLayer(Layer):
+    """include/caffe/layers/lpq_loss_layer.hpp; lpq_loss_layer.cpp:14-173, lpq_loss_layer.cu:97-245.  Not in the default registry:
+    Net(..., extra_layers=("LpqLoss",)) registers it while that net is built (OPTIONAL_LAYER_CLASSES)."""
+
+    def type(self): return "LpqLoss"
+    def MinBottomBlobs(self): return 1
+    def MaxBottomBlobs(self): return 2
+    def ExactNumTopBlobs(self): return 1
+    def AutoTopBlobs(self): return True                   # LossLayer, loss_layer.hpp:40
+
+    def LayerSetUp(self, bottom, top):
+        from .lpq_schedule import LpqSchedule
+        if not self.layer_param_.loss_weight:        # LossLayer::LayerSetUp, loss_layer.cpp:8-13
+            self.layer_param_.loss_weight = [1.0]
+        lp = self.layer_param_.lpq_loss_param
+        as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v]
+        self.schedule_ = LpqSchedule(as_list(lp.get("pq_episode_starts_at_iter", [])), as_list(lp.get("p", [])), as_list(lp.get("q", [])),
+                                     error=CheckError)
+        CHECK(len(bottom) in (1, 2), "LpqLossLayer needs one or two input blobs.")               # cpp:98-100
+        self.flags_ = (float(lp.get("p_epsilon", 0.0)), float(lp.get("q_epsilon", 1e-2)), bool(lp.get("l2_prescale_by_channels", False)),
+                       bool(lp.get("normalize_by_num_entries", False)))
+        self.pq_ = self.schedule_.at(0)
+        self.ws_ = None
+
+    def Reshape(self, bottom, top):
+        top[0].Reshape()                              # 0-axis scalar, cpp:149-150
+
+    def params_(self):
+        return ops.lpq_params(self.pq_[0], self.pq_[1], *self.flags_)
+
+    def Forward_gpu(self, bottom, top):
+        net = self.GetNet()                           # cu:100-135: the episode of the net's iteration, 0 without a net
+        self.pq_ = self.schedule_.at(net.iter() if net is not None else 0)
+        b1 = bottom[1].data if len(bottom) > 1 else None
+        loss, self.ws_ = _wrap(ops.lpq_loss_forward, self.params_(), bottom[0].data, b1, self.ws_)
+        top[0].data = loss
+
+    def normalize_coeff(self) -> float:
+        return float(self.ws_[:8].view(torch.float32)[1])
+
+    def Backward_gpu(self, top, propagate_down, bottom):
+        prop = bool(propagate_down[0]) or (len(bottom) > 1 and bool(propagate_down[1]))       # cu:209-210
+        if not prop:
+            return
+        top_diff = float(top[0].mutable_gpu_diff())       # top[0]->cpu_diff()[0], cu:215
+        b1 = bottom[1].data if len(bottom) > 1 else None
+        d0, d1 = _wrap(ops.lpq_loss_backward, self.params_(), bottom[0].data, b1, top_diff, self.ws_)
+        if len(bottom) > 1:
             if propagate_down[0]: bottom[0].diff = d0
             if propagate_down[1]: bottom[1].diff = d1
         else:
@@ -909,6 +969,28 @@ class LayerRegistry:
 
 def REGISTER_LAYER_CLASS(type_: str, klass):
     LayerRegistry.AddCreator(type_, klass)
+
+
+# layer types that are implemented but not registered by default (the default type list is what a stock build of the reference's FlowNet
+# nets needs): Net(..., extra_layers=(...)) and a Solver built with extra_layers= register them while their net is constructed
+OPTIONAL_LAYER_CLASSES: Dict[str, Callable[[LayerParameter], Layer]] = {"LpqLoss": LpqLossLayer}         # lpq_loss_layer.cpp:194-195
+
+
+@contextlib.contextmanager
+def registered(extra_layers: Sequence[str] = ()):
+    """The registry with the named OPTIONAL_LAYER_CLASSES added for the duration of the block; restored afterwards, also on an error."""
+    for t in extra_layers:
+        CHECK(t in OPTIONAL_LAYER_CLASSES, f"Unknown optional layer type: {t} (optional types: {', '.join(sorted(OPTIONAL_LAYER_CLASSES))})")
+    added = []
+    try:
+        for t in extra_layers:
+            if t not in LayerRegistry._registry:
+                LayerRegistry.AddCreator(t, OPTIONAL_LAYER_CLASSES[t])
+                added.append(t)
+        yield
+    finally:
+        for t in added:
+            LayerRegistry._registry.pop(t, None)
 
 
 REGISTER_LAYER_CLASS("Correlation", CorrelationLayer)      # correlation_layer.cpp:102-103

@@ -34,6 +34,7 @@ import torch
 
 from . import prototxt
 from .layers import Blob, CHECK, CheckError, Layer, LayerParameter, LayerRegistry
+from .layers import registered as registered_layers
 
 
 def _state_meets_rule(state: Dict, rule: Dict) -> bool:
@@ -121,7 +122,10 @@ def _insert_splits(lps: List[LayerParameter], net_inputs: List[str], phase: str)
 
 
 class Net:
-    def __init__(self, proto_text: str, phase: str = "TEST", device=None, backend=None, level: int = 0, stages=(), with_backward=None):
+    def __init__(self, proto_text: str, phase: str = "TEST", device=None, backend=None, level: int = 0, stages=(), with_backward=None,
+                 extra_layers=()):
+        """extra_layers: names of layers.OPTIONAL_LAYER_CLASSES (e.g. "LpqLoss") registered while this net is constructed."""
+        self.iter_ = 0                                   # net.hpp:230-231: the solver's iteration, for layers with a schedule
         self.phase_ = phase
         self.with_backward_ = (phase == "TRAIN") if with_backward is None else bool(with_backward)
         self.device_ = torch.device(device) if device is not None else torch.device("cuda")
@@ -157,11 +161,15 @@ class Net:
         self.bottom_need_backward_: List[List[bool]] = []
         self.bottom_names_: List[List[str]] = []
         self.top_names_: List[List[str]] = []
-        for lp in lps:
-            self._append_layer(lp, last_writer)
+        with registered_layers(extra_layers):
+            for lp in lps:
+                self._append_layer(lp, last_writer)
         self.outputs = list(self._available)            # blobs nobody consumed (net.cpp:221-230)
         self._finish_backward_flags()
         self.loss_ = None
+
+    def iter(self) -> int: return self.iter_              # net.hpp:230
+    def set_iter(self, iteration: int): self.iter_ = int(iteration)     # net.hpp:231
 
     # ---- construction --------------------------------------------------------------------------------------------------
     def _init_inputs(self):
@@ -205,6 +213,7 @@ class Net:
                 self._available.append(t)
         layer = LayerRegistry.CreateLayer(lp)
         layer.backend_ = self.backend_
+        layer.SetNet(self)                               # net.cpp:90
         if lp.type == "Input":
             for t in lp.top:
                 self.inputs.append(t)

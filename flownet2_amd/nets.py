@@ -440,19 +440,34 @@ def loss_targets_ahead(gt_flow, backend, divisors=None):
 FINAL_FLOW_GT_SCALE = {"SD": 1.0 / SD_FLOW_SCALE, "fusion": 1.0}     # pixels -> the units of the final flow of flownet_sd_core / fusion_core
 
 
-def final_flow_loss(flow, gt_flow, backend, scale):
+def _lpq_kwargs(loss):
+    """loss = ("lpq", p, q[, p_epsilon[, q_epsilon]]) -> the keyword arguments of the backend's lpq_loss / lpq_loss_multi with the flags the
+    L1Loss path uses (normalize_by_num_entries; p_epsilon 0 and q_epsilon 1e-2, the proto's defaults, when left out)."""
+    if not (isinstance(loss, (tuple, list)) and 3 <= len(loss) <= 5 and loss[0] == "lpq"):
+        raise ValueError('loss: None or ("lpq", p, q[, p_epsilon[, q_epsilon]]), got %r' % (loss,))
+    p_eps, q_eps = (tuple(loss[3:]) + (0.0, 1e-2)[len(loss) - 3:])
+    return dict(p=float(loss[1]), q=float(loss[2]), p_epsilon=float(p_eps), q_epsilon=float(q_eps), normalize_by_num_entries=True)
+
+
+def final_flow_loss(flow, gt_flow, backend, scale, loss=None):
     """Training loss of a core that returns only its final flow (flownet_sd_core, fusion_core): Downsample(GT * scale) to that flow's size
-    -> L1Loss{l2_per_location, normalize_by_num_entries}, the loss layer multiscale_loss uses per scale."""
+    -> L1Loss{l2_per_location, normalize_by_num_entries}, the loss layer multiscale_loss uses per scale; loss=("lpq", p, q, p_epsilon,
+    q_epsilon): LpqLoss{normalize_by_num_entries} in its place."""
     backend = backend_of(backend)
     tgt = backend.downsample(gt_flow * scale, flow.shape[2], flow.shape[3])
+    if loss is not None:
+        return backend.lpq_loss(flow, tgt, **_lpq_kwargs(loss))
     return backend.l1_loss(flow, tgt, l2_per_location=True, normalize_by_num_entries=True)
 
 
-def multiscale_loss(flows, gt_flow, backend, targets=None):
+def multiscale_loss(flows, gt_flow, backend, targets=None, loss=None):
     """Training loss: per scale Downsample(GT * 0.05) -> L1Loss{l2_per_location, normalize_by_num_entries}.  `targets`: the handle of
-    loss_targets_ahead (the same Downsample launches, issued at the start of the step on a second stream)."""
+    loss_targets_ahead (the same Downsample launches, issued at the start of the step on a second stream).  loss=("lpq", p, q, p_epsilon,
+    q_epsilon): LpqLoss{normalize_by_num_entries} per scale instead (p = 2, q = 0.5 is the L1Loss form), in one launch where the backend
+    has lpq_loss_multi."""
     backend = backend_of(backend)
-    if backend.has_multi_loss and gt_flow.is_cuda:
+    lpq = _lpq_kwargs(loss) if loss is not None else None
+    if (backend.has_multi_loss if lpq is None else backend.has_multi_lpq_loss) and gt_flow.is_cuda:
         # the five loss layers in one launch per direction, the weighted sum (Net::ForwardFromTo's loss += ...) included
         scales = list(LOSS_WEIGHTS.items())
         preds = [flows[s] for s, _ in scales]
@@ -462,13 +477,18 @@ def multiscale_loss(flows, gt_flow, backend, targets=None):
         else:
             gt = gt_flow * (1.0 / FLOW_SCALE)
             tgts = [backend.downsample(gt, p.shape[2], p.shape[3]) for p in preds]
+        if lpq is not None:
+            return backend.lpq_loss_multi(preds, tgts, [w for _, w in scales], **lpq)[0]
         return backend.l1_loss_multi(preds, tgts, [w for _, w in scales], l2_per_location=True, normalize_by_num_entries=True)[0]
     gt = gt_flow * (1.0 / FLOW_SCALE)
     total = 0.0
     for s, w in LOSS_WEIGHTS.items():
         pred = flows[s]
         tgt = backend.downsample(gt, pred.shape[2], pred.shape[3])
-        total = total + w * backend.l1_loss(pred, tgt, l2_per_location=True, normalize_by_num_entries=True)
+        if lpq is not None:
+            total = total + w * backend.lpq_loss(pred, tgt, **lpq)
+        else:
+            total = total + w * backend.l1_loss(pred, tgt, l2_per_location=True, normalize_by_num_entries=True)
     return total
 
 

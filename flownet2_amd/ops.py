@@ -351,6 +351,94 @@ def l1loss_backward_multi(p: L1LossParams, bottoms0, bottoms1, weights, total_di
     return d0, d1
 
 
+def lpq_params(p, q, p_epsilon=0.0, q_epsilon=1e-2, l2_prescale_by_channels=False, normalize_by_num_entries=False):
+    """The per-call arguments of the fn2_lpq_loss_* entry points, in their order (include/flownet2_hip_lpq_loss.h)."""
+    return (C.c_float(float(p)), C.c_float(float(q)), C.c_float(float(p_epsilon)), C.c_float(float(q_epsilon)),
+            int(bool(l2_prescale_by_channels)), int(bool(normalize_by_num_entries)))
+
+
+def lpq_loss_sizes(nscales: int = 1):
+    """(workspace bytes of one layer, of `nscales` layers in one launch, bytes of the arrival counters)."""
+    one, multi, sync = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    check(_lib.lib().fn2_lpq_loss_sizes(int(nscales), C.byref(one), C.byref(multi), C.byref(sync)))
+    return one.value, multi.value, sync.value
+
+
+def lpq_loss_forward(params, bottom0, bottom1=None, workspace=None):
+    """LpqLoss forward (csrc/lpq_loss.hip); params = lpq_params(...).  Returns (loss [0-axis device tensor], workspace);
+    workspace[:8] viewed as float32 = {loss, normalize_coeff}."""
+    b0 = _chk(bottom0, "bottom[0]")
+    b1 = _chk_opt(bottom1, "bottom[1]")
+    if b1 is not None and b1.shape != b0.shape:
+        raise ValueError("LpqLoss: bottom blobs must have the same shape")
+    N, Cc, H, W = b0.shape
+    ws = workspace if workspace is not None else torch.empty(lpq_loss_sizes()[0], dtype=torch.uint8, device=b0.device)
+    loss = torch.empty((), device=b0.device, dtype=torch.float32)
+    check(_lib.lib().fn2_lpq_loss_forward(_ptr(b0), _ptr(b1), _ptr(loss), N, Cc, H, W, *params, _ptr(ws), ws.numel(), _stream()))
+    return loss, ws
+
+
+def lpq_loss_backward(params, bottom0, bottom1, top_diff: float, workspace):
+    b0 = _chk(bottom0, "bottom[0]")
+    b1 = _chk_opt(bottom1, "bottom[1]")
+    N, Cc, H, W = b0.shape
+    d0 = torch.empty_like(b0)
+    d1 = torch.empty_like(b0) if b1 is not None else None
+    check(_lib.lib().fn2_lpq_loss_backward(_ptr(b0), _ptr(b1), C.c_float(float(top_diff)), _ptr(d0), _ptr(d1), N, Cc, H, W, *params,
+                                           _ptr(workspace), workspace.numel(), _stream()))
+    return d0, d1
+
+
+_LPQ_SYNC = {}      # (device, stream) -> the zeroed arrival counters of fn2_lpq_loss_forward_multi (every call leaves them zero)
+
+
+def _lpq_scales(bottoms0, bottoms1, weights):
+    """The host arrays of a _multi call: (b0 pointers, b1 pointers, shapes [4 n], loss weights) and the checked tensors they point into."""
+    n = len(bottoms0)
+    b0s = [_chk(b, "bottom[0]") for b in bottoms0]
+    b1s = [_chk_opt(bottoms1[k], "bottom[1]") if bottoms1 is not None else None for k in range(n)]
+    for b0, b1 in zip(b0s, b1s):
+        if b1 is not None and b1.shape != b0.shape:
+            raise ValueError("LpqLoss: bottom blobs must have the same shape")
+    shapes = (C.c_int * (4 * n))(*[int(d) for b in b0s for d in b.shape])
+    return _ptr_array(b0s), _ptr_array(b1s), shapes, (C.c_float * n)(*[float(w) for w in weights]), b0s, b1s
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
+def lpq_loss_forward_multi(params, bottoms0, bottoms1, weights):
+    """Every LpqLoss layer of a net in one launch (csrc/lpq_loss.hip: lpq_fwd_multi).  Returns (total [0-axis device tensor] =
+    sum_k weights[k] * loss_k in list order, losses [n], workspace); per scale bit-identical to lpq_loss_forward."""
+    n = len(bottoms0)
+    dev = bottoms0[0].device
+    _, ws_bytes, sync_bytes = lpq_loss_sizes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    key = (dev.index, int(torch.cuda.current_stream().cuda_stream))
+    sync = _LPQ_SYNC.get(key)
+    if sync is None:
+        sync = _LPQ_SYNC[key] = torch.zeros(sync_bytes, dtype=torch.uint8, device=dev)
+    losses = torch.empty((n,), device=dev, dtype=torch.float32)
+    total = torch.empty((), device=dev, dtype=torch.float32)
+    p0, p1, shapes, lw, _b0s, _b1s = _lpq_scales(bottoms0, bottoms1, weights)
+    check(_lib.lib().fn2_lpq_loss_forward_multi(n, p0, p1, shapes, lw, *params, _ptr(losses), _ptr(total), _ptr(ws), ws.numel(), _ptr(sync),
+                                                _stream()))
+    return total, losses, ws
+
+
+def lpq_loss_backward_multi(params, bottoms0, bottoms1, weights, total_diff, workspace, need1=False):
+    """Gradients of every scale for d(objective) / d(total) = total_diff (a DEVICE scalar tensor, or None for 1) in one launch."""
+    n = len(bottoms0)
+    p0, p1, shapes, lw, b0s, b1s = _lpq_scales(bottoms0, bottoms1, weights)
+    d0 = [torch.empty_like(b) for b in b0s]
+    d1 = [torch.empty_like(b) if (need1 and b1s[k] is not None) else None for k, b in enumerate(b0s)]
+    td = _chk(total_diff.reshape(1), "total_diff", ndim=1) if total_diff is not None else None
+    check(_lib.lib().fn2_lpq_loss_backward_multi(n, p0, p1, _ptr_array(d0), _ptr_array(d1), shapes, lw, *params, _ptr(td), _ptr(workspace),
+                                                 workspace.numel(), _stream()))
+    return d0, d1
+
+
 def channel_norm_forward(x):
     x = _chk(x, "bottom[0]")
     N, Cc, H, W = x.shape

@@ -338,8 +338,10 @@ class Solver(_Schedule):
 
     solver_type: Optional[str] = None
 
-    def __init__(self, param, net=None, device=None, write_update: bool = False):
+    def __init__(self, param, net=None, device=None, write_update: bool = False, extra_layers=()):
+        """extra_layers: handed on to the train net this solver builds (Net(..., extra_layers=...))."""
         param = param if isinstance(param, SolverParameter) else SolverParameter(param)
+        self.extra_layers_ = tuple(extra_layers)
         self._init_schedule(param)
         CHECK(self.solver_type is None or param.type == self.solver_type, f"{type(self).__name__} built with a SolverParameter of type {param.type}")
         self.write_update_ = bool(write_update)
@@ -373,7 +375,8 @@ class Solver(_Schedule):
             with open(path) as f:
                 text = f.read()
         st = prototxt.to_dict(p.train_state, "state") if p.has("train_state") else {}
-        return Net(text, phase="TRAIN", device=device, level=int(st.get("level", 0)), stages=tuple(st.get("stage", [])))
+        return Net(text, phase="TRAIN", device=device, level=int(st.get("level", 0)), stages=tuple(st.get("stage", [])),
+                   extra_layers=self.extra_layers_)
 
     def _pre_solve(self):
         """SGDSolver::PreSolve (sgd_solver.cpp:65-78) and AdamPreSolve (adam_solver.cpp:7-17): history_ = one zero blob per learnable blob,
@@ -416,6 +419,8 @@ class Solver(_Schedule):
         self.smoothed_loss_ = np.float32(0)
         p = self.param_
         while self.iter_ < stop_iter:
+            if hasattr(self.net_, "set_iter"):
+                self.net_.set_iter(self.iter_)                                                            # solver.cpp:202
             self.net_.ClearParamDiffs()
             for cb in self.callbacks_:
                 cb.on_start()

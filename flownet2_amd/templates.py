@@ -160,11 +160,19 @@ def flownet_c_template() -> str:
     return b.text()
 
 
-def flownet_c_train_prototxt(batch: int, height: int, width: int) -> str:
+def flownet_c_train_prototxt(batch: int, height: int, width: int, lpq=None) -> str:
     """A TRAIN-phase FlowNetC in the reference's format (nets.flownet_c_core + nets.multiscale_loss as layers): pre-processed images and the
     ground-truth flow as net inputs, the flow scaled by 1 / 20 (Eltwise), per prediction scale a Downsample to the prediction's size and an
     L1Loss{l2_per_location, normalize_by_num_entries} with the scale's loss_weight.  Not a file of the reference tree (it ships no
-    prototxt): the layer types, parameter messages and the loss wiring are the reference's."""
+    prototxt): the layer types, parameter messages and the loss wiring are the reference's.
+    lpq = (starts, ps, qs[, p_epsilon[, q_epsilon]]): LpqLoss{normalize_by_num_entries} with that schedule in place of every L1Loss (build
+    the net with extra_layers=("LpqLoss",))."""
+    if lpq is not None:
+        starts, ps, qs = lpq[:3]
+        p_eps, q_eps = (tuple(lpq[3:]) + (0.0, 1e-2)[len(lpq) - 3:])
+        lpq_param = "lpq_loss_param { %s%s%sp_epsilon: %r q_epsilon: %r normalize_by_num_entries: true } include { phase: TRAIN }" % (
+            "".join("pq_episode_starts_at_iter: %d " % int(v) for v in starts), "".join("p: %r " % float(v) for v in ps),
+            "".join("q: %r " % float(v) for v in qs), float(p_eps), float(q_eps))
     b = _Builder("FlowNetC_train")
     for n, c in (("img0_nomean", 3), ("img1_nomean", 3), ("flow_gt", 2)):
         b.lines += ['input: "%s"' % n, "input_shape { dim: %d dim: %d dim: %d dim: %d }" % (batch, c, height, width)]
@@ -173,8 +181,8 @@ def flownet_c_train_prototxt(batch: int, height: int, width: int) -> str:
     for lvl, pred in b.preds:
         ds = "flow_gt_scaled_%d" % lvl
         b.layer("Downsample%d" % lvl, "Downsample", [gt, pred], [ds], "", "propagate_down: false propagate_down: false")
-        b.layer("flow_loss%d" % lvl, "L1Loss", [pred, ds], ["flow_loss%d" % lvl],
-                "l1_loss_param { l2_per_location: true normalize_by_num_entries: true } include { phase: TRAIN }",
+        b.layer("flow_loss%d" % lvl, "L1Loss" if lpq is None else "LpqLoss", [pred, ds], ["flow_loss%d" % lvl],
+                "l1_loss_param { l2_per_location: true normalize_by_num_entries: true } include { phase: TRAIN }" if lpq is None else lpq_param,
                 "loss_weight: %r propagate_down: true propagate_down: false" % float(nets.LOSS_WEIGHTS[lvl]))
     return b.text()
 

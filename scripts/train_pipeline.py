@@ -75,7 +75,9 @@ def main():
                          "biases, clip_gradients) instead of torch.optim.Adam")
     Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
     Fn.add_general_convolution_flag(ap)
+    Fn.add_loss_flags(ap)
     a = ap.parse_args()
+    schedule = Fn.loss_schedule(a)
     Fn.apply_arithmetic_flags(a, ARITH)
     Fn.apply_general_convolution_flag(a)
     dev = torch.device("cuda")
@@ -142,7 +144,9 @@ def main():
             # gradients handed over, not zero-filled + accumulated (as bench.py --mode train); with --solver they are zero-filled in place so
             # that the .grad tensors, and with them the optimizer's device table, stay where they are
             opt.zero_grad(set_to_none=not a.solver)
-            loss = nets.multiscale_loss(nets.flownet_c_core(P, t_img0[0].data, t_img1[0].data, Fn), t_flow[0].data, Fn)
+            # --loss lpq: the episode of this iteration (the solver's, with --solver), as Solver::Step hands it to the net
+            spec = None if schedule is None else ("lpq",) + schedule.at(opt.iter_ if a.solver else it) + (a.lpq_p_epsilon, a.lpq_q_epsilon)
+            loss = nets.multiscale_loss(nets.flownet_c_core(P, t_img0[0].data, t_img1[0].data, Fn), t_flow[0].data, Fn, loss=spec)
             loss.backward()
             opt.step()
         marks[8].record()

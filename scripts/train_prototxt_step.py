@@ -10,7 +10,9 @@ ap = argparse.ArgumentParser()
 ARITH = ("dgrad", "wgrad", "wino")
 Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
 Fn.add_general_convolution_flag(ap)
+Fn.add_loss_flags(ap)
 args = ap.parse_args()
+schedule = Fn.loss_schedule(args)
 Fn.apply_arithmetic_flags(args, ARITH)
 Fn.apply_general_convolution_flag(args)
 
@@ -19,7 +21,12 @@ P = {k: v.cuda() for k, v in nets.init_params("C", seed=0).items()}
 g = torch.Generator().manual_seed(1)
 img0, img1 = (torch.rand((N, 3, H, W), generator=g) - 0.43).cuda(), (torch.rand((N, 3, H, W), generator=g) - 0.43).cuda()
 gt = (torch.randn((N, 2, H, W), generator=g) * 5).cuda()
-net = fnet.Net(templates.flownet_c_train_prototxt(N, H, W), phase="TRAIN", device="cuda")
+if schedule is None:
+    net, spec = fnet.Net(templates.flownet_c_train_prototxt(N, H, W), phase="TRAIN", device="cuda"), None
+else:       # LpqLoss layers with the schedule of the flags; both steps run at iteration 0
+    lpq = (schedule.starts, schedule.ps, schedule.qs, args.lpq_p_epsilon, args.lpq_q_epsilon)
+    net = fnet.Net(templates.flownet_c_train_prototxt(N, H, W, lpq=lpq), phase="TRAIN", device="cuda", extra_layers=("LpqLoss",))
+    spec = ("lpq",) + schedule.at(net.iter()) + (args.lpq_p_epsilon, args.lpq_q_epsilon)
 assert net.load_param_dict(P) == []
 Pg = {k: v.clone().requires_grad_(True) for k, v in P.items()}
 
@@ -32,7 +39,7 @@ def proto_step():
 def autograd_step():
     for p in Pg.values():
         p.grad = None
-    loss = nets.multiscale_loss(nets.flownet_c_core(Pg, img0, img1, Fn), gt, Fn)
+    loss = nets.multiscale_loss(nets.flownet_c_core(Pg, img0, img1, Fn), gt, Fn, loss=spec)
     loss.backward()
     return loss
 
