@@ -29,7 +29,6 @@
 #include "caffe/proto/caffe.pb.h"
 
 #include "flownet2_hip.h"
-#include "flownet2_hip_conv_general.h"
 #include "flownet2_hip_conv_volume.h"
 #include "flownet2_hip_lpq_loss.h"
 
@@ -497,10 +496,10 @@ class DownsampleLayer : public Layer<Dtype> {
 // of base_conv_layer.cpp:24-124; one bottom / top pair.  Refused, with a message naming the layer and the count: four or more spatial axes.
 // A PLAIN layer (two spatial axes, square taps, one stride, one pad, dilation 1, group 1) takes the path it always took: every Convolution and Deconvolution of the FlowNet graphs runs on its specialised family; a
 // geometry no family takes -- and a gradient pass of a layer whose forward has a family but that pass none -- runs on the general kernels
-// (include/flownet2_hip_conv_general.h: any kernel, stride and pad).  Every other layer runs forward and all three gradient passes on the
-// same kernels through include/flownet2_hip_conv_volume.h (fewer than three spatial axes with the leading ones trivial: the kernels and the
-// bits of include/flownet2_hip_conv_geometry.h).  Only what fn2_conv_general_supported / fn2_conv_volume_supported refuse (an
-// empty output, a blob beyond the 32-bit index limits) aborts in Reshape with a message naming the layer.
+// (csrc/conv_general.hip).  Every other layer runs forward and all three gradient passes on the same kernels.  Both reach them through
+// the 19 ints of include/flownet2_hip_conv_volume.h (fewer than three spatial axes with the leading ones trivial: the kernels and the bits of
+// include/flownet2_hip_conv_general.h for a plain layer, of include/flownet2_hip_conv_geometry.h for the others).  Only what
+// fn2_conv_volume_supported refuses (an empty output, a blob beyond the 32-bit index limits) aborts in Reshape with a message naming the layer.
 // The packed weight operand (round 6): packed ONCE and kept while the weights provably have not changed -- Caffe has no "weights changed"
 // signal below Solver::ApplyUpdate, so the layer reads what SyncedMemory already records: the operand is reused iff the layer runs in the
 // TEST phase, the weight blob's memory is SYNCED on entry (no mutable_cpu_data / mutable_gpu_data since the last const access: a
@@ -605,7 +604,14 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     desc_.N = bottom[0]->count(0, channel_axis_); desc_.Cin = channels_; desc_.Hin = in_3_[1]; desc_.Win = in_3_[2];
     desc_.Cout = num_output_; desc_.kernel = kernel_; desc_.stride = stride_; desc_.pad = pad_;
     const int tr = transposed_ ? 1 : 0;
-    if (!plain_) { ReshapeGeometry(bottom, top); return; }
+    // what the general kernels are called with, for every layer (a plain one: depth trivial, dilation 1, group 1)
+    const int g[19] = {desc_.N, channels_, in_3_[0], in_3_[1], in_3_[2], num_output_, kernel_3_[0], kernel_3_[1], kernel_3_[2], stride_3_[0], stride_3_[1],
+                       stride_3_[2], pad_3_[0], pad_3_[1], pad_3_[2], dilation_3_[0], dilation_3_[1], dilation_3_[2], group_};
+    std::copy(g, g + 19, geom_);
+    general_ = fn2_conv_volume_supported(geom_, tr) != 0;
+    size_t gen_fwd = 0, gen_dgrad = 0, gen_ws = 0;
+    if (general_) FN2_CALL(fn2_conv_volume_sizes(geom_, tr, &gen_fwd, &gen_dgrad, nullptr, &gen_ws));
+    if (!plain_) { ReshapeGeometry(bottom, top, gen_fwd, gen_dgrad, gen_ws); return; }
     int oh, ow;
     if (transposed_) {      // deconv_layer.cpp:8-24
       oh = stride_ * (desc_.Hin - 1) + kernel_ - 2 * pad_; ow = stride_ * (desc_.Win - 1) + kernel_ - 2 * pad_;
@@ -615,9 +621,6 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       route_ = fn2_conv_route(&desc_, 0);
     }
     // the general kernels: the forward of a geometry no family takes, and below the gradient passes that have no route of their own
-    size_t gen_fwd = 0, gen_dgrad = 0, gen_ws = 0;
-    general_ = fn2_conv_general_supported(&desc_, tr) != 0;
-    if (general_) FN2_CALL(fn2_conv_general_sizes(&desc_, tr, &gen_fwd, &gen_dgrad, nullptr, &gen_ws));
     if (route_ == 0 && !general_)
       LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no kernel for " << type() << "{kernel " << kernel_ << ", stride " << stride_
                  << ", pad " << pad_ << "} " << channels_ << " -> " << num_output_ << " on " << desc_.Hin << " x " << desc_.Win
@@ -652,14 +655,9 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     for (int i = 3 - num_spatial_axes_; i < 3; ++i) shape.push_back(out[i]);
     return shape;
   }
-  // a layer that is not plain: no specialised route, all four passes on fn2_conv_volume_* (include/flownet2_hip_conv_volume.h)
-  void ReshapeGeometry(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top) {
-    const int tr = transposed_ ? 1 : 0;
-    const int g[19] = {desc_.N, channels_, in_3_[0], in_3_[1], in_3_[2], num_output_, kernel_3_[0], kernel_3_[1], kernel_3_[2], stride_3_[0], stride_3_[1],
-                       stride_3_[2], pad_3_[0], pad_3_[1], pad_3_[2], dilation_3_[0], dilation_3_[1], dilation_3_[2], group_};
-    std::copy(g, g + 19, geom_);
+  // a layer that is not plain: no specialised route, all four passes on the general kernels
+  void ReshapeGeometry(const vector<Blob<Dtype>*>& bottom, const vector<Blob<Dtype>*>& top, size_t gen_fwd, size_t gen_dgrad, size_t gen_ws) {
     route_ = 0; bwd_route_ = FN2_BWD_ROUTE_NONE; bwd_weights_ = false; head_ = false;
-    general_ = fn2_conv_volume_supported(geom_, tr) != 0;
     if (!general_ && num_spatial_axes_ == 3)
       LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no kernel for " << type() << "{kernel " << kernel_3_[0] << " x " << kernel_h_ << " x "
                  << kernel_w_ << ", stride " << stride_3_[0] << " x " << stride_h_ << " x " << stride_w_ << ", pad " << pad_3_[0] << " x " << pad_h_ << " x "
@@ -672,20 +670,13 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
                  << dilation_w_ << ", group " << group_ << "} " << channels_ << " -> " << num_output_ << " on " << desc_.Hin << " x " << desc_.Win
                  << " (empty output, or a blob beyond the 32-bit index limits)";
     int od = 0, oh = 0, ow = 0;
-    size_t gen_fwd = 0, gen_dgrad = 0, gen_ws = 0;
-    FN2_CALL(fn2_conv_volume_out_shape(geom_, tr, &od, &oh, &ow));      // conv_layer.cpp:8-23 / deconv_layer.cpp:8-24 with the dilated extent
-    FN2_CALL(fn2_conv_volume_sizes(geom_, tr, &gen_fwd, &gen_dgrad, nullptr, &gen_ws));
+    FN2_CALL(fn2_conv_volume_out_shape(geom_, transposed_ ? 1 : 0, &od, &oh, &ow));      // conv_layer.cpp:8-23 / deconv_layer.cpp:8-24 with the dilated extent
     out_h_ = od * oh; out_w_ = ow;      // what the bias gradient sums over, per channel
     top[0]->Reshape(TopShape(bottom, od, oh, ow));
     packed_.Reshape(vector<int>{(int)gen_fwd});
     packed_bwd_.Reshape(vector<int>{(int)gen_dgrad});
     const size_t wb = std::max(gen_ws, fn2_bias_leaky_relu_backward_workspace_bytes(desc_.N, num_output_, out_h_, out_w_));
     workspace_.Reshape(vector<int>{(int)((wb + 3) / 4) + 4});
-  }
-  // the general kernels of either header: the square-tap entry points for a plain layer (the bits of before), else the 19-int ones
-  int GeneralPack(int pass, const float* w, float* pk) const {
-    const int tr = transposed_ ? 1 : 0;
-    return plain_ ? fn2_conv_general_pack_weights(&desc_, tr, pass, w, pk, kStream) : fn2_conv_volume_pack_weights(geom_, tr, pass, w, pk, kStream);
   }
   virtual inline const char* type() const { return transposed_ ? "Deconvolution" : "Convolution"; }
   virtual inline int ExactNumBottomBlobs() const { return 1; }
@@ -706,18 +697,15 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
     if (reuse) {
       fn2_adapter_stats().weight_pack_reuses++;
     } else {
-      if (route_ == 0) FN2_CALL(GeneralPack(0, w, pk));
+      if (route_ == 0) FN2_CALL(fn2_conv_volume_pack_weights(geom_, transposed_ ? 1 : 0, 0, w, pk, kStream));
       else if (transposed_) FN2_CALL(fn2_deconv_pack_weights(&desc_, route_, w, pk, kStream));
       else FN2_CALL(fn2_conv_pack_weights(&desc_, route_, w, pk, kStream));
       packed_for_ = w; packed_route_ = route_; packed_count_ = packed_.count();
       fn2_adapter_stats().weight_packs++;
     }
-    if (route_ == 0 && !plain_) {
+    if (route_ == 0) {
       FN2_CALL(fn2_conv_volume_forward(geom_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
                                        num_output_, 0, 0, 0.f, kStream));
-    } else if (route_ == 0) {
-      FN2_CALL(fn2_conv_general_forward(&desc_, transposed_ ? 1 : 0, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()),
-                                        num_output_, 0, 0, 0.f, kStream));
     } else if (transposed_) {
       FN2_CALL(fn2_deconv_forward(&desc_, route_, f32(bottom[0]->gpu_data()), channels_, 0, pk, b, f32(top[0]->mutable_gpu_data()), num_output_, 0,
                                   0, 0.f, ws, wsb, kStream));
@@ -757,12 +745,9 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
       if (bwd_weights_) {
         FN2_CALL(fn2_conv_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0, f32(this->blobs_[0]->mutable_gpu_diff()),
                                            1, ws, wsb, kStream));
-      } else if (!plain_) {
+      } else {      // the general kernel (the bias gradient was taken above)
         FN2_CALL(fn2_conv_volume_backward_weights(geom_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
                                                   f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
-      } else {      // the general kernel (the bias gradient was taken above)
-        FN2_CALL(fn2_conv_general_backward_weights(&desc_, tr, f32(bottom[0]->gpu_data()), channels_, 0, td, num_output_, 0,
-                                                   f32(this->blobs_[0]->mutable_gpu_diff()), nullptr, 1, ws, wsb, kStream));
       }
     }
     if (propagate_down[0]) {
@@ -770,9 +755,8 @@ class Fn2ConvolutionLayer : public Layer<Dtype> {
         LOG(FATAL) << this->layer_param_.name() << ": libflownet2_hip has no data-gradient kernel for this " << type();
       float* pk = f32(packed_bwd_.mutable_gpu_data());
       if (bwd_route_ == FN2_BWD_ROUTE_NONE) {
-        FN2_CALL(GeneralPack(1, f32(this->blobs_[0]->gpu_data()), pk));
-        if (plain_) FN2_CALL(fn2_conv_general_backward_data(&desc_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
-        else FN2_CALL(fn2_conv_volume_backward_data(geom_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
+        FN2_CALL(fn2_conv_volume_pack_weights(geom_, tr, 1, f32(this->blobs_[0]->gpu_data()), pk, kStream));
+        FN2_CALL(fn2_conv_volume_backward_data(geom_, tr, td, num_output_, 0, pk, f32(bottom[0]->mutable_gpu_diff()), channels_, 0, kStream));
         return;
       }
       FN2_CALL(fn2_conv_backward_data_pack_weights(&desc_, tr, bwd_route_, f32(this->blobs_[0]->gpu_data()), pk, ws, wsb, kStream));

@@ -47,22 +47,21 @@ def _plain_call(stride, pad, dilation, groups):
     return not isinstance(stride, (tuple, list)) and not isinstance(pad, (tuple, list)) and dilation == 1 and groups == 1
 
 
-def _lib_conv(x, w, b, stride, pad, dilation, groups, transposed):
-    if _plain_call(stride, pad, dilation, groups):
-        desc = _general_desc(x, w, b, stride, pad, transposed)
-        if desc is not None:
-            return _GeneralConv.apply(x, w, b, desc, transposed)
+def _lib_conv(x, w, b, stride, pad, dilation, groups, transposed, axes=4):
+    """lib_conv2d and its kin on blobs of `axes` axes: the general kernels where _general_layer gives them the call, else the library."""
+    layer = _general_layer(x, w, b, stride, pad, dilation, groups, transposed, axes)
+    if layer is not None:
+        return _GeneralConv.apply(x, w, b, layer[0], layer[1], transposed)
+    name = "Deconvolution" if transposed else "Convolution"
+    if axes == 4 and _plain_call(stride, pad, dilation, groups):
         kw = dict(stride=stride, padding=pad)
-        what = "%s{stride %d, pad %d}" % ("Deconvolution" if transposed else "Convolution", stride, pad)
+        what = "%s{stride %d, pad %d}" % (name, stride, pad)
     else:
-        geom = _general_geom(x, w, b, stride, pad, dilation, groups, transposed)
-        if geom is not None:
-            return _GeometryConv.apply(x, w, b, geom, transposed)
         kw = dict(stride=stride, padding=pad, dilation=dilation, groups=groups)
-        what = "%s{stride %s, pad %s, dilation %s, group %d}" % ("Deconvolution" if transposed else "Convolution", stride, pad, dilation, groups)
+        what = "%s{stride %s, pad %s, dilation %s, group %d}" % (name, stride, pad, dilation, groups)
     if x.is_cuda:
         _note_fallback(what, x, w)
-    f = torch.nn.functional.conv_transpose2d if transposed else torch.nn.functional.conv2d
+    f = getattr(torch.nn.functional, ("conv_transpose%dd" if transposed else "conv%dd") % (axes - 2))
     if not _BATCH_INVARIANT[0] or not x.is_cuda:
         return f(x, w, b, **kw)
     return torch.cat([f(x[n:n + 1], w, b, **kw) for n in range(x.shape[0])], 0)
@@ -80,29 +79,16 @@ def lib_conv_transpose2d(x, w, b, stride, pad, dilation=1, groups=1):
     return _lib_conv(x, w, b, stride, pad, dilation, groups, True)
 
 
-def _lib_conv_volume(x, w, b, stride, pad, dilation, groups, transposed):
-    geom = _general_volume(x, w, b, stride, pad, dilation, groups, transposed)
-    if geom is not None:
-        return _VolumeConv.apply(x, w, b, geom, transposed)
-    if x.is_cuda:
-        _note_fallback("%s{stride %s, pad %s, dilation %s, group %d}" % ("Deconvolution" if transposed else "Convolution", stride, pad, dilation, groups), x, w)
-    kw = dict(stride=stride, padding=pad, dilation=dilation, groups=groups)
-    f = torch.nn.functional.conv_transpose3d if transposed else torch.nn.functional.conv3d
-    if not _BATCH_INVARIANT[0] or not x.is_cuda:
-        return f(x, w, b, **kw)
-    return torch.cat([f(x[n:n + 1], w, b, **kw) for n in range(x.shape[0])], 0)
-
-
 def lib_conv3d(x, w, b, stride, pad, dilation=1, groups=1):
     """lib_conv2d for a volumetric Convolution: x [N, Cin, D, H, W], w [Cout, Cin / groups, kd, kh, kw]; stride, pad and dilation an int or
     a triple (d, h, w).  Under the same switch: "own" runs the depth tier of the general-geometry kernels, the default the library's
     conv3d through torch, counted in LIBRARY_FALLBACKS."""
-    return _lib_conv_volume(x, w, b, stride, pad, dilation, groups, False)
+    return _lib_conv(x, w, b, stride, pad, dilation, groups, False, axes=5)
 
 
 def lib_conv_transpose3d(x, w, b, stride, pad, dilation=1, groups=1):
     """The same for a Deconvolution; w: [Cin, Cout / groups, kd, kh, kw]."""
-    return _lib_conv_volume(x, w, b, stride, pad, dilation, groups, True)
+    return _lib_conv(x, w, b, stride, pad, dilation, groups, True, axes=5)
 
 
 # What lib_conv2d / lib_conv_transpose2d (and lib_conv3d / lib_conv_transpose3d) run CUDA float32 tensors on: "library" (the default: the library convolution through torch, counted
@@ -137,131 +123,57 @@ def apply_general_convolution_flag(args):
         set_general_convolution(args.general_conv)
 
 
-def _general_desc(x, w, b, stride, pad, transposed):
-    """The descriptor of the layer where the switch is "own" and the general kernels take the call, else None."""
-    if _GENERAL_CONV[0] != "own" or not (x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float32 and x.dim() == w.dim() == 4):
+def _general_layer(x, w, b, stride, pad, dilation, groups, transposed, axes):
+    """(ABI, geometry) of the layer (ops.conv_general_abi and a descriptor for a _plain_call on 4 axes, which keeps to square taps; else
+    ops.conv_geometry_abi and the 14 ints on 4 axes, ops.conv_volume_abi and the 19 ints on 5) where the switch is "own" and the general kernels
+    take the call, else None."""
+    if _GENERAL_CONV[0] != "own" or not (x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float32 and x.dim() == w.dim() == axes):
         return None
-    if w.shape[2] != w.shape[3] or x.shape[1] != w.shape[0 if transposed else 1] or (b is not None and (not b.is_cuda or b.dtype != torch.float32)):
+    if groups < 1 or (b is not None and (not b.is_cuda or b.dtype != torch.float32)):
         return None
-    if isinstance(stride, (tuple, list)) or isinstance(pad, (tuple, list)):
+    Cout = w.shape[1] * groups if transposed else w.shape[0]
+    if (x.shape[1] != w.shape[0]) if transposed else (x.shape[1] != w.shape[1] * groups):
         return None
-    desc = ops.conv_desc(x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[1 if transposed else 0], w.shape[2], stride, pad)
-    return desc if ops.conv_general_supported(desc, transposed) else None
+    N, Cin, size, taps = x.shape[0], x.shape[1], tuple(x.shape[2:]), tuple(w.shape[2:])
+    if axes == 5:
+        abi, g = ops.conv_volume_abi, ops.conv_volume(N, Cin, size, Cout, taps, stride, pad, dilation, groups)
+    elif not _plain_call(stride, pad, dilation, groups):
+        abi, g = ops.conv_geometry_abi, ops.conv_geometry(N, Cin, size[0], size[1], Cout, taps, stride, pad, dilation, groups)
+    elif taps[0] == taps[1]:
+        abi, g = ops.conv_general_abi, ops.conv_desc(N, Cin, size[0], size[1], Cout, taps[0], stride, pad)
+    else:
+        return None
+    return (abi, g) if abi.supported(g, transposed) else None
 
 
 class _GeneralConv(torch.autograd.Function):
-    """Convolution / Deconvolution of any square-tap geometry on the general kernels; the operands are packed once per weight version."""
+    """Convolution / Deconvolution of any geometry on the general kernels, through the ABI _general_layer chose; the operands are packed
+    once per weight version, keyed by the ABI and by what of the geometry they depend on."""
 
     @staticmethod
-    def forward(ctx, x, w, b, desc, transposed):
-        ctx.desc, ctx.transposed, ctx.has_bias = desc, transposed, b is not None
+    def forward(ctx, x, w, b, abi, g, transposed):
+        ctx.layer, ctx.has_bias = (abi, g, transposed), b is not None
         ctx.save_for_backward(x, w)
-        key = (desc.kernel, desc.stride, desc.pad)
-        packed = _cached_pack(_PACKED_T, w, ("general-fwd", transposed) + key,
-                              lambda: ops.conv_general_pack_weights(w.detach().contiguous(), desc, transposed))
+        packed = _cached_pack(_PACKED_T, w, (abi.tag + "-fwd", transposed) + abi.key(g),
+                              lambda: abi.pack_weights(w.detach().contiguous(), g, transposed))
         xb, x0 = _channel_slice(x)
-        return ops.conv_general_forward(xb, packed, b.detach() if b is not None else None, desc, transposed, in_c0=x0)
+        return abi.forward(xb, packed, b.detach() if b is not None else None, g, transposed, in_c0=x0)
 
     @staticmethod
     def backward(ctx, d):
         x, w = ctx.saved_tensors
-        desc, transposed = ctx.desc, ctx.transposed
+        abi, g, transposed = ctx.layer
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         d = d.contiguous()
         gx = gw = gb = None
         if need_x:
-            key = (desc.kernel, desc.stride, desc.pad)
-            packed = _cached_pack(_PACKED_T, w, ("general-dgrad", transposed) + key,
-                                  lambda: ops.conv_general_pack_weights(w.detach().contiguous(), desc, transposed, backward=True))
-            gx = ops.conv_general_backward_data(d, packed, desc, transposed)
+            packed = _cached_pack(_PACKED_T, w, (abi.tag + "-dgrad", transposed) + abi.key(g),
+                                  lambda: abi.pack_weights(w.detach().contiguous(), g, transposed, backward=True))
+            gx = abi.backward_data(d, packed, g, transposed)
         if need_w or need_b:
             xb, x0 = _channel_slice(x)
-            gw, gb = ops.conv_general_backward_weights(xb, d, desc, transposed, bias=bool(need_b), bottom_c0=x0)
-        return gx, (gw if need_w else None), gb, None, None
-
-
-def _general_geom(x, w, b, stride, pad, dilation, groups, transposed):
-    """The 14-int geometry of the layer where the switch is "own" and the widened general kernels take the call, else None."""
-    if _GENERAL_CONV[0] != "own" or not (x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float32 and x.dim() == w.dim() == 4):
-        return None
-    if groups < 1 or (b is not None and (not b.is_cuda or b.dtype != torch.float32)):
-        return None
-    Cout = w.shape[1] * groups if transposed else w.shape[0]
-    if (x.shape[1] != w.shape[0]) if transposed else (x.shape[1] != w.shape[1] * groups):
-        return None
-    geom = ops.conv_geometry(x.shape[0], x.shape[1], x.shape[2], x.shape[3], Cout, (w.shape[2], w.shape[3]), stride, pad, dilation, groups)
-    return geom if ops.conv_geometry_supported(geom, transposed) else None
-
-
-class _GeometryConv(torch.autograd.Function):
-    """Convolution / Deconvolution with rectangular taps, per-axis stride / pad / dilation and groups on the general kernels; the operands
-    are packed once per weight version, keyed by the whole geometry."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, geom, transposed):
-        ctx.geom, ctx.transposed, ctx.has_bias = geom, transposed, b is not None
-        ctx.save_for_backward(x, w)
-        packed = _cached_pack(_PACKED_T, w, ("geometry-fwd", transposed) + tuple(geom),
-                              lambda: ops.conv_geometry_pack_weights(w.detach().contiguous(), geom, transposed))
-        xb, x0 = _channel_slice(x)
-        return ops.conv_geometry_forward(xb, packed, b.detach() if b is not None else None, geom, transposed, in_c0=x0)
-
-    @staticmethod
-    def backward(ctx, d):
-        x, w = ctx.saved_tensors
-        geom, transposed = ctx.geom, ctx.transposed
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        d = d.contiguous()
-        gx = gw = gb = None
-        if need_x:
-            packed = _cached_pack(_PACKED_T, w, ("geometry-dgrad", transposed) + tuple(geom),
-                                  lambda: ops.conv_geometry_pack_weights(w.detach().contiguous(), geom, transposed, backward=True))
-            gx = ops.conv_geometry_backward_data(d, packed, geom, transposed)
-        if need_w or need_b:
-            xb, x0 = _channel_slice(x)
-            gw, gb = ops.conv_geometry_backward_weights(xb, d, geom, transposed, bias=bool(need_b), bottom_c0=x0)
-        return gx, (gw if need_w else None), gb, None, None
-
-
-def _general_volume(x, w, b, stride, pad, dilation, groups, transposed):
-    """The 19-int geometry of the volumetric layer where the switch is "own" and the general kernels take the call, else None."""
-    if _GENERAL_CONV[0] != "own" or not (x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float32 and x.dim() == w.dim() == 5):
-        return None
-    if groups < 1 or (b is not None and (not b.is_cuda or b.dtype != torch.float32)):
-        return None
-    Cout = w.shape[1] * groups if transposed else w.shape[0]
-    if (x.shape[1] != w.shape[0]) if transposed else (x.shape[1] != w.shape[1] * groups):
-        return None
-    geom = ops.conv_volume(x.shape[0], x.shape[1], tuple(x.shape[2:]), Cout, tuple(w.shape[2:]), stride, pad, dilation, groups)
-    return geom if ops.conv_volume_supported(geom, transposed) else None
-
-
-class _VolumeConv(torch.autograd.Function):
-    """Convolution / Deconvolution over three spatial axes on the general kernels; the operands are packed once per weight version, keyed
-    by the whole geometry."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, geom, transposed):
-        ctx.geom, ctx.transposed, ctx.has_bias = geom, transposed, b is not None
-        ctx.save_for_backward(x, w)
-        packed = _cached_pack(_PACKED_T, w, ("volume-fwd", transposed) + tuple(geom),
-                              lambda: ops.conv_volume_pack_weights(w.detach().contiguous(), geom, transposed))
-        return ops.conv_volume_forward(x.contiguous(), packed, b.detach() if b is not None else None, geom, transposed)
-
-    @staticmethod
-    def backward(ctx, d):
-        x, w = ctx.saved_tensors
-        geom, transposed = ctx.geom, ctx.transposed
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        d = d.contiguous()
-        gx = gw = gb = None
-        if need_x:
-            packed = _cached_pack(_PACKED_T, w, ("volume-dgrad", transposed) + tuple(geom),
-                                  lambda: ops.conv_volume_pack_weights(w.detach().contiguous(), geom, transposed, backward=True))
-            gx = ops.conv_volume_backward_data(d, packed, geom, transposed)
-        if need_w or need_b:
-            gw, gb = ops.conv_volume_backward_weights(x.contiguous(), d, geom, transposed, bias=bool(need_b))
-        return gx, (gw if need_w else None), gb, None, None
+            gw, gb = abi.backward_weights(xb, d, g, transposed, bias=bool(need_b), bottom_c0=x0)
+        return gx, (gw if need_w else None), gb, None, None, None
 
 
 def scale_shift(x, scale, shift=None, out=None, out_c0=0):

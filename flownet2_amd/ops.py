@@ -870,22 +870,125 @@ def conv_backward_bias(top_diff, C_, top_c0=0, out=None, accumulate=False):
     return out
 
 
-def conv_general_supported(desc, transposed=False) -> bool:
-    """Whether the general-geometry kernels (csrc/conv_general.hip) take this layer (fn2_conv_general_supported; host-only)."""
-    return bool(_lib.lib().fn2_conv_general_supported(C.byref(desc), int(bool(transposed))))
+class _ConvAbi:
+    """The wrappers of the general-geometry kernels (csrc/conv_general.hip), written once over what differs between their three C ABIs:
+    name = the public prefix (the C one is "fn2_" + name, the word after "conv_" tags the family's cached operands); axes = axes of its
+    blobs; arg(g) = the geometry as C takes it; read(g) = (N, Cin, bottom size, Cout, kernel, group), sizes as tuples; key(g) = what of
+    the geometry a packed operand depends on beside the weight; out_shape(g, transposed) (default: the ABI's C function); sep: between
+    the numbers of a layer's extent in a message; shape_first: pack_weights checks the weight's shape before it asks C for the sizes."""
+
+    def __init__(self, name, axes, arg, read, key=tuple, out_shape=None, sep=",", shape_first=False):
+        self.name, self.axes, self.arg, self.read, self.key, self.sep, self.shape_first = name, axes, arg, read, key, sep, shape_first
+        self.tag = name[len("conv_"):]
+        self.out_shape = out_shape or self.c_out_shape
+        self._c = {}
+
+    def c(self, fn):
+        """The ABI's C entry point `fn`, looked up once (a call of these wrappers is a few microseconds of host time)."""
+        f = self._c.get(fn)
+        if f is None:
+            f = self._c[fn] = getattr(_lib.lib(), "fn2_%s_%s" % (self.name, fn))
+        return f
+
+    def supported(self, g, transposed=False):
+        return bool(self.c("supported")(self.arg(g), int(bool(transposed))))
+
+    def sizes(self, g, transposed=False):
+        n = [C.c_size_t() for _ in range(4)]
+        check(self.c("sizes")(self.arg(g), int(bool(transposed)), *(C.byref(v) for v in n)))
+        return tuple(int(v.value) for v in n)
+
+    def c_out_shape(self, g, transposed=False):
+        n = [C.c_int() for _ in range(self.axes - 2)]
+        check(self.c("out_shape")(self.arg(g), int(bool(transposed)), *[C.byref(v) for v in n]))
+        return tuple([v.value for v in n])
+
+    @staticmethod
+    def weight_shape(layer, transposed):
+        N, Cin, size, Cout, kernel, group = layer
+        return ((Cin, Cout // group) if transposed else (Cout, Cin // group)) + kernel
+
+    def blobs(self, what, g, transposed, bottom, bottom_c0, top, top_c0):
+        """Check that the blobs given hold the layer's bottom and top slices; -> (read(g), top size)."""
+        out = self.out_shape(g, transposed)
+        layer = N, Cin, size, Cout, _, _ = self.read(g)
+        for t, c0, Cc, ext, name in ((bottom, bottom_c0, Cin, size, "bottom"), (top, top_c0, Cout, out, "top")):
+            if t is not None and (not t.is_contiguous() or (t.shape[0],) + tuple(t.shape[2:]) != (N,) + ext or c0 < 0 or c0 + Cc > t.shape[1]):
+                layer = "[" + self.sep.join(str(v) for v in (N, Cc) + ext) + "]"
+                raise ValueError(f"{what}: {name} blob {tuple(t.shape)} does not hold the layer's {layer} at channel {c0}")
+        return layer, out
+
+    def pack_weights(self, weight, g, transposed=False, backward=False):
+        w = _chk(weight, "weight", ndim=self.axes)
+        sizes = None if self.shape_first else self.sizes(g, transposed)
+        if tuple(w.shape) != self.weight_shape(self.read(g), transposed):
+            raise ValueError("%s_pack_weights: weight of shape %s is not this layer's" % (self.name, tuple(w.shape)))
+        sizes = sizes or self.sizes(g, transposed)
+        packed = torch.empty(sizes[1 if backward else 0], device=w.device, dtype=torch.float32)
+        check(self.c("pack_weights")(self.arg(g), int(bool(transposed)), 1 if backward else 0, _ptr(w), _ptr(packed), _stream()))
+        return packed
+
+    def forward(self, x, packed, bias, g, transposed=False, relu=False, negative_slope=0.0, out=None, out_c0=0, in_c0=0):
+        what = self.name + "_forward"
+        x = _chk(x, "bottom[0]", ndim=self.axes)
+        if out is not None:
+            _chk(out, "top[0]", ndim=self.axes)
+        (N, _, _, Cout, _, _), size = self.blobs(what, g, transposed, x, in_c0, out, out_c0)
+        b = _chk_opt(bias, "bias", ndim=1)
+        pw = _chk(packed, "packed weight", ndim=None)
+        if pw.numel() != self.sizes(g, transposed)[0]:
+            raise ValueError("%s: the operand has %d floats, not what the forward reads for this layer" % (what, pw.numel()))
+        if out is None:
+            out = torch.empty((N, Cout) + size, device=x.device, dtype=torch.float32)
+        check(self.c("forward")(self.arg(g), int(bool(transposed)), _ptr(x), x.shape[1], int(in_c0), _ptr(pw), _ptr(b), _ptr(out), out.shape[1],
+                                int(out_c0), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
+        return out
+
+    def backward_data(self, top_diff, packed, g, transposed=False, top_c0=0, out=None, out_c0=0):
+        what = self.name + "_backward_data"
+        d = _chk(top_diff, "top_diff", ndim=self.axes)
+        if out is not None:
+            _chk(out, "bottom diff", ndim=self.axes)
+        (N, Cin, size, _, _, _), _ = self.blobs(what, g, transposed, out, out_c0, d, top_c0)
+        pw = _chk(packed, "packed weight", ndim=None)
+        if pw.numel() != self.sizes(g, transposed)[1]:
+            raise ValueError("%s: the operand has %d floats, not what the data gradient reads for this layer" % (what, pw.numel()))
+        if out is None:
+            out = torch.empty((N, Cin) + size, device=d.device, dtype=torch.float32)
+        check(self.c("backward_data")(self.arg(g), int(bool(transposed)), _ptr(d), d.shape[1], int(top_c0), _ptr(pw), _ptr(out), out.shape[1],
+                                      int(out_c0), _stream()))
+        return out
+
+    def backward_weights(self, bottom, top_diff, g, transposed=False, weight_diff=None, bias_diff=None, bias=True, accumulate=False,
+                         bottom_c0=0, top_c0=0):
+        what = self.name + "_backward_weights"
+        x, d = _chk(bottom, "bottom", ndim=self.axes), _chk(top_diff, "top_diff", ndim=self.axes)
+        layer, _ = self.blobs(what, g, transposed, x, bottom_c0, d, top_c0)
+        shape, Cout = self.weight_shape(layer, transposed), layer[3]
+        if weight_diff is None:
+            if accumulate:
+                raise ValueError(what + ": accumulate needs the diffs to add into")
+        elif tuple(_chk(weight_diff, "weight diff", ndim=self.axes).shape) != shape or not weight_diff.is_contiguous():
+            raise ValueError(what + ": weight diff has the wrong shape")
+        if bias and bias_diff is None:
+            if accumulate:
+                raise ValueError(what + ": accumulate needs the diffs to add into")
+        elif bias and (tuple(_chk(bias_diff, "bias diff", ndim=1).shape) != (Cout,) or not bias_diff.is_contiguous()):
+            raise ValueError(what + ": bias diff has the wrong shape")
+        need = self.sizes(g, transposed)[3]
+        if weight_diff is None:
+            weight_diff = torch.empty(shape, device=x.device, dtype=torch.float32)
+        if bias and bias_diff is None:
+            bias_diff = torch.empty(Cout, device=x.device, dtype=torch.float32)
+        ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
+        check(self.c("backward_weights")(self.arg(g), int(bool(transposed)), _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1], int(top_c0),
+                                         _ptr(weight_diff), _ptr(bias_diff if bias else None), int(bool(accumulate)), _ptr(ws), need, _stream()))
+        return weight_diff, (bias_diff if bias else None)
 
 
 def set_conv_general_groups(groups: int = 0):
     """Test hook (fn2_debug_set_conv_general_groups): 16-channel groups per workgroup of the general gather kernels; 0 = by geometry."""
     check(_lib.lib().fn2_debug_set_conv_general_groups(int(groups)))
-
-
-def conv_general_sizes(desc, transposed=False):
-    """(floats of the forward operand, of the data-gradient operand, of the weight-gradient operand (0), bytes of the weight-gradient
-    workspace) of the general kernels (fn2_conv_general_sizes; host-only)."""
-    n = [C.c_size_t() for _ in range(4)]
-    check(_lib.lib().fn2_conv_general_sizes(C.byref(desc), int(bool(transposed)), *(C.byref(v) for v in n)))
-    return tuple(int(v.value) for v in n)
 
 
 def conv_general_out_shape(desc, transposed=False):
@@ -896,89 +999,47 @@ def conv_general_out_shape(desc, transposed=False):
     return (desc.Hin + 2 * p - k) // s + 1, (desc.Win + 2 * p - k) // s + 1
 
 
-def _general_weight_shape(desc, transposed):
-    k = desc.kernel
-    return (desc.Cin, desc.Cout, k, k) if transposed else (desc.Cout, desc.Cin, k, k)
+# the square-tap ABI on fn2_conv_desc (include/flownet2_hip_conv_general.h), the 14 ints (flownet2_hip_conv_geometry.h), the 19 ints
+# (flownet2_hip_conv_volume.h)
+conv_general_abi = _ConvAbi("conv_general", 4, C.byref, lambda d: (d.N, d.Cin, (d.Hin, d.Win), d.Cout, (d.kernel, d.kernel), 1),
+                        key=lambda d: (d.kernel, d.stride, d.pad), out_shape=conv_general_out_shape, shape_first=True)
+conv_geometry_abi = _ConvAbi("conv_geometry", 4, lambda g: g, lambda g: (g[0], g[1], (g[2], g[3]), g[4], (g[5], g[6]), g[13]))
+conv_volume_abi = _ConvAbi("conv_volume", 5, lambda g: g, lambda g: (g[0], g[1], tuple(g[2:5]), g[5], tuple(g[6:9]), g[18]), sep=", ")
+
+
+def conv_general_supported(desc, transposed=False) -> bool:
+    """Whether the general-geometry kernels (csrc/conv_general.hip) take this layer (fn2_conv_general_supported; host-only)."""
+    return conv_general_abi.supported(desc, transposed)
+
+
+def conv_general_sizes(desc, transposed=False):
+    """(floats of the forward operand, of the data-gradient operand, of the weight-gradient operand (0), bytes of the weight-gradient
+    workspace) of the general kernels (fn2_conv_general_sizes; host-only)."""
+    return conv_general_abi.sizes(desc, transposed)
 
 
 def conv_general_pack_weights(weight, desc, transposed=False, backward=False):
     """The layer's weight blob -> the operand of the general forward (backward: data-gradient) kernel (fn2_conv_general_pack_weights)."""
-    w = _chk(weight, "weight")
-    if tuple(w.shape) != _general_weight_shape(desc, transposed):
-        raise ValueError("conv_general_pack_weights: weight of shape %s is not this layer's" % (tuple(w.shape),))
-    packed = torch.empty(conv_general_sizes(desc, transposed)[1 if backward else 0], device=w.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_general_pack_weights(C.byref(desc), int(bool(transposed)), 1 if backward else 0, _ptr(w), _ptr(packed), _stream()))
-    return packed
-
-
-def _general_blobs(what, desc, transposed, bottom, bottom_c0, top, top_c0):
-    Ho, Wo = conv_general_out_shape(desc, transposed)
-    for t, c0, Cc, H, W, name in ((bottom, bottom_c0, desc.Cin, desc.Hin, desc.Win, "bottom"), (top, top_c0, desc.Cout, Ho, Wo, "top")):
-        if t is not None and (not t.is_contiguous() or (t.shape[0], t.shape[2], t.shape[3]) != (desc.N, H, W) or c0 < 0 or c0 + Cc > t.shape[1]):
-            raise ValueError(f"{what}: {name} blob {tuple(t.shape)} does not hold the layer's [{desc.N},{Cc},{H},{W}] at channel {c0}")
-    return Ho, Wo
+    return conv_general_abi.pack_weights(weight, desc, transposed, backward)
 
 
 def conv_general_forward(x, packed, bias, desc, transposed=False, relu=False, negative_slope=0.0, out=None, out_c0=0, in_c0=0):
     """act(layer(x[:, in_c0:in_c0+Cin]) + bias) -> out[:, out_c0:out_c0+Cout] (a new blob if out is None) on the general kernel
     (fn2_conv_general_forward).  packed = conv_general_pack_weights(weight, desc, transposed)."""
-    x = _chk(x, "bottom[0]")
-    if out is not None:
-        _chk(out, "top[0]")
-    Ho, Wo = _general_blobs("conv_general_forward", desc, transposed, x, in_c0, out, out_c0)
-    if out is None:
-        out = torch.empty((desc.N, desc.Cout, Ho, Wo), device=x.device, dtype=torch.float32)
-    b = _chk_opt(bias, "bias", ndim=1)
-    pw = _chk(packed, "packed weight", ndim=None)
-    if pw.numel() != conv_general_sizes(desc, transposed)[0]:
-        raise ValueError("conv_general_forward: the operand has %d floats, not what the forward reads for this layer" % pw.numel())
-    check(_lib.lib().fn2_conv_general_forward(C.byref(desc), int(bool(transposed)), _ptr(x), x.shape[1], int(in_c0), _ptr(pw), _ptr(b), _ptr(out),
-                                              out.shape[1], int(out_c0), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
-    return out
+    return conv_general_abi.forward(x, packed, bias, desc, transposed, relu, negative_slope, out, out_c0, in_c0)
 
 
 def conv_general_backward_data(top_diff, packed, desc, transposed=False, top_c0=0, out=None, out_c0=0):
     """bottom_diff [N, Cin, Hin, Win] (or the slice of `out` at out_c0) of the layer on the general kernel (fn2_conv_general_backward_data).
     packed = conv_general_pack_weights(weight, desc, transposed, backward=True)."""
-    d = _chk(top_diff, "top_diff")
-    if out is not None:
-        _chk(out, "bottom diff")
-    _general_blobs("conv_general_backward_data", desc, transposed, out, out_c0, d, top_c0)
-    if out is None:
-        out = torch.empty((desc.N, desc.Cin, desc.Hin, desc.Win), device=d.device, dtype=torch.float32)
-    pw = _chk(packed, "packed weight", ndim=None)
-    if pw.numel() != conv_general_sizes(desc, transposed)[1]:
-        raise ValueError("conv_general_backward_data: the operand has %d floats, not what the data gradient reads for this layer" % pw.numel())
-    check(_lib.lib().fn2_conv_general_backward_data(C.byref(desc), int(bool(transposed)), _ptr(d), d.shape[1], int(top_c0), _ptr(pw), _ptr(out),
-                                                    out.shape[1], int(out_c0), _stream()))
-    return out
+    return conv_general_abi.backward_data(top_diff, packed, desc, transposed, top_c0, out, out_c0)
 
 
 def conv_general_backward_weights(bottom, top_diff, desc, transposed=False, weight_diff=None, bias_diff=None, bias=True, accumulate=False,
                                   bottom_c0=0, top_c0=0):
     """(weight_diff, bias_diff) of the layer on the general kernels (fn2_conv_general_backward_weights; deterministic).  accumulate adds
     into the diffs given; bias=False: no bias gradient (None comes back)."""
-    x, d = _chk(bottom, "bottom"), _chk(top_diff, "top_diff")
-    _general_blobs("conv_general_backward_weights", desc, transposed, x, bottom_c0, d, top_c0)
-    shape = _general_weight_shape(desc, transposed)
-    if weight_diff is None:
-        if accumulate:
-            raise ValueError("conv_general_backward_weights: accumulate needs the diffs to add into")
-        weight_diff = torch.empty(shape, device=x.device, dtype=torch.float32)
-    elif tuple(_chk(weight_diff, "weight diff").shape) != shape or not weight_diff.is_contiguous():
-        raise ValueError("conv_general_backward_weights: weight diff has the wrong shape")
-    if bias and bias_diff is None:
-        if accumulate:
-            raise ValueError("conv_general_backward_weights: accumulate needs the diffs to add into")
-        bias_diff = torch.empty(desc.Cout, device=x.device, dtype=torch.float32)
-    elif bias and (tuple(_chk(bias_diff, "bias diff", ndim=1).shape) != (desc.Cout,) or not bias_diff.is_contiguous()):
-        raise ValueError("conv_general_backward_weights: bias diff has the wrong shape")
-    need = conv_general_sizes(desc, transposed)[3]
-    ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_general_backward_weights(C.byref(desc), int(bool(transposed)), _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1],
-                                                       int(top_c0), _ptr(weight_diff), _ptr(bias_diff if bias else None), int(bool(accumulate)),
-                                                       _ptr(ws), need, _stream()))
-    return weight_diff, (bias_diff if bias else None)
+    return conv_general_abi.backward_weights(bottom, top_diff, desc, transposed, weight_diff, bias_diff, bias, accumulate, bottom_c0, top_c0)
 
 
 def _pair(v, what):
@@ -1001,110 +1062,42 @@ def conv_geometry(N, Cin, Hin, Win, Cout, kernel, stride=1, pad=0, dilation=1, g
 
 def conv_geometry_supported(geom, transposed=False) -> bool:
     """Whether the general-geometry kernels take this layer (fn2_conv_geometry_supported; host-only)."""
-    return bool(_lib.lib().fn2_conv_geometry_supported(geom, int(bool(transposed))))
+    return conv_geometry_abi.supported(geom, transposed)
 
 
 def conv_geometry_sizes(geom, transposed=False):
     """(floats of the forward operand, of the data-gradient operand, of the weight-gradient operand (0), bytes of the weight-gradient
     workspace) (fn2_conv_geometry_sizes; host-only)."""
-    n = [C.c_size_t() for _ in range(4)]
-    check(_lib.lib().fn2_conv_geometry_sizes(geom, int(bool(transposed)), *(C.byref(v) for v in n)))
-    return tuple(int(v.value) for v in n)
+    return conv_geometry_abi.sizes(geom, transposed)
 
 
 def conv_geometry_out_shape(geom, transposed=False):
     """(Hout, Wout) of the layer as the reference computes it with the dilated extent (fn2_conv_geometry_out_shape; host-only)."""
-    h, w = C.c_int(), C.c_int()
-    check(_lib.lib().fn2_conv_geometry_out_shape(geom, int(bool(transposed)), C.byref(h), C.byref(w)))
-    return int(h.value), int(w.value)
-
-
-def _geometry_weight_shape(geom, transposed):
-    N, Cin, Hin, Win, Cout, kh, kw = geom[:7]
-    group = geom[13]
-    return (Cin, Cout // group, kh, kw) if transposed else (Cout, Cin // group, kh, kw)
+    return conv_geometry_abi.c_out_shape(geom, transposed)
 
 
 def conv_geometry_pack_weights(weight, geom, transposed=False, backward=False):
     """The layer's weight blob -> the operand of the forward (backward: data-gradient) kernel (fn2_conv_geometry_pack_weights)."""
-    w = _chk(weight, "weight")
-    sizes = conv_geometry_sizes(geom, transposed)
-    if tuple(w.shape) != _geometry_weight_shape(geom, transposed):
-        raise ValueError("conv_geometry_pack_weights: weight of shape %s is not this layer's" % (tuple(w.shape),))
-    packed = torch.empty(sizes[1 if backward else 0], device=w.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_geometry_pack_weights(geom, int(bool(transposed)), 1 if backward else 0, _ptr(w), _ptr(packed), _stream()))
-    return packed
-
-
-def _geometry_blobs(what, geom, transposed, bottom, bottom_c0, top, top_c0):
-    Ho, Wo = conv_geometry_out_shape(geom, transposed)
-    N, Cin, Hin, Win, Cout = geom[:5]
-    for t, c0, Cc, H, W, name in ((bottom, bottom_c0, Cin, Hin, Win, "bottom"), (top, top_c0, Cout, Ho, Wo, "top")):
-        if t is not None and (not t.is_contiguous() or (t.shape[0], t.shape[2], t.shape[3]) != (N, H, W) or c0 < 0 or c0 + Cc > t.shape[1]):
-            raise ValueError(f"{what}: {name} blob {tuple(t.shape)} does not hold the layer's [{N},{Cc},{H},{W}] at channel {c0}")
-    return Ho, Wo
+    return conv_geometry_abi.pack_weights(weight, geom, transposed, backward)
 
 
 def conv_geometry_forward(x, packed, bias, geom, transposed=False, relu=False, negative_slope=0.0, out=None, out_c0=0, in_c0=0):
     """act(layer(x[:, in_c0:in_c0+Cin]) + bias) -> out[:, out_c0:out_c0+Cout] (a new blob if out is None) (fn2_conv_geometry_forward).
     packed = conv_geometry_pack_weights(weight, geom, transposed)."""
-    x = _chk(x, "bottom[0]")
-    if out is not None:
-        _chk(out, "top[0]")
-    Ho, Wo = _geometry_blobs("conv_geometry_forward", geom, transposed, x, in_c0, out, out_c0)
-    if out is None:
-        out = torch.empty((geom[0], geom[4], Ho, Wo), device=x.device, dtype=torch.float32)
-    b = _chk_opt(bias, "bias", ndim=1)
-    pw = _chk(packed, "packed weight", ndim=None)
-    if pw.numel() != conv_geometry_sizes(geom, transposed)[0]:
-        raise ValueError("conv_geometry_forward: the operand has %d floats, not what the forward reads for this layer" % pw.numel())
-    check(_lib.lib().fn2_conv_geometry_forward(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(in_c0), _ptr(pw), _ptr(b), _ptr(out),
-                                               out.shape[1], int(out_c0), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
-    return out
+    return conv_geometry_abi.forward(x, packed, bias, geom, transposed, relu, negative_slope, out, out_c0, in_c0)
 
 
 def conv_geometry_backward_data(top_diff, packed, geom, transposed=False, top_c0=0, out=None, out_c0=0):
     """bottom_diff [N, Cin, Hin, Win] (or the slice of `out` at out_c0) of the layer (fn2_conv_geometry_backward_data).
     packed = conv_geometry_pack_weights(weight, geom, transposed, backward=True)."""
-    d = _chk(top_diff, "top_diff")
-    if out is not None:
-        _chk(out, "bottom diff")
-    _geometry_blobs("conv_geometry_backward_data", geom, transposed, out, out_c0, d, top_c0)
-    if out is None:
-        out = torch.empty((geom[0], geom[1], geom[2], geom[3]), device=d.device, dtype=torch.float32)
-    pw = _chk(packed, "packed weight", ndim=None)
-    if pw.numel() != conv_geometry_sizes(geom, transposed)[1]:
-        raise ValueError("conv_geometry_backward_data: the operand has %d floats, not what the data gradient reads for this layer" % pw.numel())
-    check(_lib.lib().fn2_conv_geometry_backward_data(geom, int(bool(transposed)), _ptr(d), d.shape[1], int(top_c0), _ptr(pw), _ptr(out),
-                                                     out.shape[1], int(out_c0), _stream()))
-    return out
+    return conv_geometry_abi.backward_data(top_diff, packed, geom, transposed, top_c0, out, out_c0)
 
 
 def conv_geometry_backward_weights(bottom, top_diff, geom, transposed=False, weight_diff=None, bias_diff=None, bias=True, accumulate=False,
                                    bottom_c0=0, top_c0=0):
     """(weight_diff, bias_diff) of the layer (fn2_conv_geometry_backward_weights; deterministic).  accumulate adds into the diffs given;
     bias=False: no bias gradient (None comes back)."""
-    x, d = _chk(bottom, "bottom"), _chk(top_diff, "top_diff")
-    _geometry_blobs("conv_geometry_backward_weights", geom, transposed, x, bottom_c0, d, top_c0)
-    shape, Cout = _geometry_weight_shape(geom, transposed), geom[4]
-    if weight_diff is None:
-        if accumulate:
-            raise ValueError("conv_geometry_backward_weights: accumulate needs the diffs to add into")
-        weight_diff = torch.empty(shape, device=x.device, dtype=torch.float32)
-    elif tuple(_chk(weight_diff, "weight diff").shape) != shape or not weight_diff.is_contiguous():
-        raise ValueError("conv_geometry_backward_weights: weight diff has the wrong shape")
-    if bias and bias_diff is None:
-        if accumulate:
-            raise ValueError("conv_geometry_backward_weights: accumulate needs the diffs to add into")
-        bias_diff = torch.empty(Cout, device=x.device, dtype=torch.float32)
-    elif bias and (tuple(_chk(bias_diff, "bias diff", ndim=1).shape) != (Cout,) or not bias_diff.is_contiguous()):
-        raise ValueError("conv_geometry_backward_weights: bias diff has the wrong shape")
-    need = conv_geometry_sizes(geom, transposed)[3]
-    ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_geometry_backward_weights(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1],
-                                                        int(top_c0), _ptr(weight_diff), _ptr(bias_diff if bias else None), int(bool(accumulate)),
-                                                        _ptr(ws), need, _stream()))
-    return weight_diff, (bias_diff if bias else None)
+    return conv_geometry_abi.backward_weights(bottom, top_diff, geom, transposed, weight_diff, bias_diff, bias, accumulate, bottom_c0, top_c0)
 
 
 def _per_axis(v, axes, what):
@@ -1135,109 +1128,42 @@ def conv_volume(N, Cin, size, Cout, kernel, stride=1, pad=0, dilation=1, group=1
 
 def conv_volume_supported(geom, transposed=False) -> bool:
     """Whether the general kernels take this layer (fn2_conv_volume_supported; host-only)."""
-    return bool(_lib.lib().fn2_conv_volume_supported(geom, int(bool(transposed))))
+    return conv_volume_abi.supported(geom, transposed)
 
 
 def conv_volume_sizes(geom, transposed=False):
     """(floats of the forward operand, of the data-gradient operand, of the weight-gradient operand (0), bytes of the weight-gradient
     workspace) (fn2_conv_volume_sizes; host-only)."""
-    n = [C.c_size_t() for _ in range(4)]
-    check(_lib.lib().fn2_conv_volume_sizes(geom, int(bool(transposed)), *(C.byref(v) for v in n)))
-    return tuple(int(v.value) for v in n)
+    return conv_volume_abi.sizes(geom, transposed)
 
 
 def conv_volume_out_shape(geom, transposed=False):
     """(Dout, Hout, Wout) of the layer as the reference computes it with the dilated extent (fn2_conv_volume_out_shape; host-only)."""
-    d, h, w = C.c_int(), C.c_int(), C.c_int()
-    check(_lib.lib().fn2_conv_volume_out_shape(geom, int(bool(transposed)), C.byref(d), C.byref(h), C.byref(w)))
-    return int(d.value), int(h.value), int(w.value)
-
-
-def _volume_weight_shape(geom, transposed):
-    Cin, Cout, group = geom[1], geom[5], geom[18]
-    return ((Cin, Cout // group) if transposed else (Cout, Cin // group)) + tuple(geom[6:9])
+    return conv_volume_abi.c_out_shape(geom, transposed)
 
 
 def conv_volume_pack_weights(weight, geom, transposed=False, backward=False):
     """The layer's weight blob [., ., kd, kh, kw] -> the operand of the forward (backward: data-gradient) kernel (fn2_conv_volume_pack_weights)."""
-    w = _chk(weight, "weight", ndim=5)
-    sizes = conv_volume_sizes(geom, transposed)
-    if tuple(w.shape) != _volume_weight_shape(geom, transposed):
-        raise ValueError("conv_volume_pack_weights: weight of shape %s is not this layer's" % (tuple(w.shape),))
-    packed = torch.empty(sizes[1 if backward else 0], device=w.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_volume_pack_weights(geom, int(bool(transposed)), 1 if backward else 0, _ptr(w), _ptr(packed), _stream()))
-    return packed
-
-
-def _volume_blobs(what, geom, transposed, bottom, bottom_c0, top, top_c0):
-    out = conv_volume_out_shape(geom, transposed)
-    N, Cin, Cout = geom[0], geom[1], geom[5]
-    for t, c0, Cc, size, name in ((bottom, bottom_c0, Cin, tuple(geom[2:5]), "bottom"), (top, top_c0, Cout, out, "top")):
-        if t is not None and (not t.is_contiguous() or (t.shape[0],) + tuple(t.shape[2:]) != (N,) + size or c0 < 0 or c0 + Cc > t.shape[1]):
-            raise ValueError(f"{what}: {name} blob {tuple(t.shape)} does not hold the layer's {[N, Cc] + list(size)} at channel {c0}")
-    return out
+    return conv_volume_abi.pack_weights(weight, geom, transposed, backward)
 
 
 def conv_volume_forward(x, packed, bias, geom, transposed=False, relu=False, negative_slope=0.0, out=None, out_c0=0, in_c0=0):
     """act(layer(x[:, in_c0:in_c0+Cin]) + bias) -> out[:, out_c0:out_c0+Cout] (a new blob if out is None) on [N, C, D, H, W] blobs
     (fn2_conv_volume_forward).  packed = conv_volume_pack_weights(weight, geom, transposed)."""
-    x = _chk(x, "bottom[0]", ndim=5)
-    if out is not None:
-        _chk(out, "top[0]", ndim=5)
-    size = _volume_blobs("conv_volume_forward", geom, transposed, x, in_c0, out, out_c0)
-    if out is None:
-        out = torch.empty((geom[0], geom[5]) + size, device=x.device, dtype=torch.float32)
-    b = _chk_opt(bias, "bias", ndim=1)
-    pw = _chk(packed, "packed weight", ndim=None)
-    if pw.numel() != conv_volume_sizes(geom, transposed)[0]:
-        raise ValueError("conv_volume_forward: the operand has %d floats, not what the forward reads for this layer" % pw.numel())
-    check(_lib.lib().fn2_conv_volume_forward(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(in_c0), _ptr(pw), _ptr(b), _ptr(out),
-                                             out.shape[1], int(out_c0), int(bool(relu)), C.c_float(float(negative_slope)), _stream()))
-    return out
+    return conv_volume_abi.forward(x, packed, bias, geom, transposed, relu, negative_slope, out, out_c0, in_c0)
 
 
 def conv_volume_backward_data(top_diff, packed, geom, transposed=False, top_c0=0, out=None, out_c0=0):
     """bottom_diff [N, Cin, Din, Hin, Win] (or the slice of `out` at out_c0) of the layer (fn2_conv_volume_backward_data).
     packed = conv_volume_pack_weights(weight, geom, transposed, backward=True)."""
-    d = _chk(top_diff, "top_diff", ndim=5)
-    if out is not None:
-        _chk(out, "bottom diff", ndim=5)
-    _volume_blobs("conv_volume_backward_data", geom, transposed, out, out_c0, d, top_c0)
-    if out is None:
-        out = torch.empty((geom[0], geom[1]) + tuple(geom[2:5]), device=d.device, dtype=torch.float32)
-    pw = _chk(packed, "packed weight", ndim=None)
-    if pw.numel() != conv_volume_sizes(geom, transposed)[1]:
-        raise ValueError("conv_volume_backward_data: the operand has %d floats, not what the data gradient reads for this layer" % pw.numel())
-    check(_lib.lib().fn2_conv_volume_backward_data(geom, int(bool(transposed)), _ptr(d), d.shape[1], int(top_c0), _ptr(pw), _ptr(out),
-                                                   out.shape[1], int(out_c0), _stream()))
-    return out
+    return conv_volume_abi.backward_data(top_diff, packed, geom, transposed, top_c0, out, out_c0)
 
 
 def conv_volume_backward_weights(bottom, top_diff, geom, transposed=False, weight_diff=None, bias_diff=None, bias=True, accumulate=False,
                                  bottom_c0=0, top_c0=0):
     """(weight_diff, bias_diff) of the layer (fn2_conv_volume_backward_weights; deterministic).  accumulate adds into the diffs given;
     bias=False: no bias gradient (None comes back)."""
-    x, d = _chk(bottom, "bottom", ndim=5), _chk(top_diff, "top_diff", ndim=5)
-    _volume_blobs("conv_volume_backward_weights", geom, transposed, x, bottom_c0, d, top_c0)
-    shape, Cout = _volume_weight_shape(geom, transposed), geom[5]
-    if weight_diff is None:
-        if accumulate:
-            raise ValueError("conv_volume_backward_weights: accumulate needs the diffs to add into")
-        weight_diff = torch.empty(shape, device=x.device, dtype=torch.float32)
-    elif tuple(_chk(weight_diff, "weight diff", ndim=5).shape) != shape or not weight_diff.is_contiguous():
-        raise ValueError("conv_volume_backward_weights: weight diff has the wrong shape")
-    if bias and bias_diff is None:
-        if accumulate:
-            raise ValueError("conv_volume_backward_weights: accumulate needs the diffs to add into")
-        bias_diff = torch.empty(Cout, device=x.device, dtype=torch.float32)
-    elif bias and (tuple(_chk(bias_diff, "bias diff", ndim=1).shape) != (Cout,) or not bias_diff.is_contiguous()):
-        raise ValueError("conv_volume_backward_weights: bias diff has the wrong shape")
-    need = conv_volume_sizes(geom, transposed)[3]
-    ws = torch.empty((need + 3) // 4, device=x.device, dtype=torch.float32)
-    check(_lib.lib().fn2_conv_volume_backward_weights(geom, int(bool(transposed)), _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1],
-                                                      int(top_c0), _ptr(weight_diff), _ptr(bias_diff if bias else None), int(bool(accumulate)),
-                                                      _ptr(ws), need, _stream()))
-    return weight_diff, (bias_diff if bias else None)
+    return conv_volume_abi.backward_weights(bottom, top_diff, geom, transposed, weight_diff, bias_diff, bias, accumulate, bottom_c0, top_c0)
 
 
 def conv_mfma_supported(Cin, Hin, Win, Cout, kernel, stride, pad) -> bool:

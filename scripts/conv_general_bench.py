@@ -5,7 +5,7 @@ shape (the conv3_1 class), which states what generality costs; and (--rows geome
 (include/flownet2_hip_conv_geometry.h) against the library; and (--rows volume, batch 4 unless --batch is given) three volumetric layers
 (include/flownet2_hip_conv_volume.h) against the library's conv3d / conv_transpose3d.  Forward, data gradient and weight (+ bias) gradient.
 Run on the GPU box:
-    python scripts/conv_general_bench.py [--iters 20] [--repeats 5] [--batch 8] [--rows square|geometry|volume|all]
+    python scripts/conv_general_bench.py [--iters 20] [--repeats 5] [--batch 8] [--rows square|geometry|volume|all|launch]
 Per (shape, pass) one line: the median over the repeats of the mean time per call of each side, the spread (min .. max over the repeats),
 the ratio of the medians, and the largest difference between the two results over the result's scale.  The two sides alternate inside
 every repeat; every shape is warmed up first (operands are packed outside the timed window, as a layer packs once per weight version)."""
@@ -13,6 +13,7 @@ import argparse
 import os
 import statistics
 import sys
+import time
 
 import torch
 import torch.nn.functional as F
@@ -120,16 +121,55 @@ def specialised_passes(x, w, b, g, desc, tr):
             "weight + bias gradient": wgrad}
 
 
+def launch_rows(a, gen):
+    """The host side alone: one tiny layer (1 x 2 x 4 x 5 -> 3, 2x2 taps, stride 1, pad 0; the volumetric one with a depth of 2) through
+    flownet2_amd.functional under set_general_convolution("own"), where the kernels take a few microseconds and the Python wrappers the
+    rest.  Wall time per call over --calls calls with one synchronise at the end, after a warm-up; median over the repeats."""
+    from flownet2_amd import functional as Fn
+    Fn.set_general_convolution("own")
+    layers = [("lib_conv2d", Fn.lib_conv2d, (1, 2, 4, 5), (3, 2, 2, 2), 3), ("lib_conv_transpose2d", Fn.lib_conv_transpose2d, (1, 2, 4, 5), (2, 3, 2, 2), 3),
+              ("lib_conv3d", Fn.lib_conv3d, (1, 2, 2, 4, 5), (3, 2, 2, 2, 2), 3)]
+    for name, f, xs, ws, Cout in layers:
+        x, w, b = (torch.randn(s, device="cuda", generator=gen).requires_grad_(True) for s in (xs, ws, (Cout,)))
+        with torch.no_grad():
+            g = torch.ones_like(f(x, w, b, 1, 0))
+
+        def forward():
+            with torch.no_grad():
+                f(x, w, b, 1, 0)
+
+        def both():
+            torch.autograd.grad(f(x, w, b, 1, 0), (x, w, b), g)
+        for what, fn in (("forward", forward), ("forward + backward", both)):
+            for _ in range(a.calls // 10):
+                fn()
+            torch.cuda.synchronize()
+            t = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                for _ in range(a.calls):
+                    fn()
+                torch.cuda.synchronize()
+                t.append((time.perf_counter() - t0) * 1e6 / a.calls)
+            print("launch %-22s %-18s %8.1f us per call (%.1f .. %.1f)" % (name, what, statistics.median(t), min(t), max(t)), flush=True)
+    if Fn.LIBRARY_FALLBACKS[0]:
+        raise SystemExit("conv_general_bench: %d calls left the own kernels" % Fn.LIBRARY_FALLBACKS[0])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None, help="default: 8, and 4 for the volume rows")
-    ap.add_argument("--rows", choices=["square", "geometry", "volume", "all"], default="all")
+    ap.add_argument("--rows", choices=["square", "geometry", "volume", "all", "launch"], default="all",
+                    help="launch: the host time of the opt-in path on one tiny layer (not part of all)")
+    ap.add_argument("--calls", type=int, default=2000, help="calls per repeat of the launch rows")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("conv_general_bench: needs the GPU (a CPU run measures nothing)")
     gen = torch.Generator(device="cuda").manual_seed(0)
+    if a.rows == "launch":
+        return launch_rows(a, gen)
     N = a.batch or 8
     rows = [r[:9] + (1, 1) + r[9:] for r in SHAPES] if a.rows in ("square", "all") else []
     rows += [r + ("library",) for r in GEOMETRY_SHAPES] if a.rows in ("geometry", "all") else []
