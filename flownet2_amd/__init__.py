@@ -6,6 +6,7 @@ layers     host-side mirror of the reference's Caffe Layer<Dtype> / LayerRegistr
 functional torch.autograd glue,  nets: FlowNetC/S graphs,  flo: .flo I/O
 solver     SolverParameter, Solver (SGDSolver / AdamSolver, get_solver) and CaffeOptimizer on the one-launch HIP update
 LpqSchedule  the p / q episodes of LpqLoss (lpq_schedule.py)
+evaluate   FlowMetrics (the rows of the metrics kernel, summary()), ground-truth readers incl. the KITTI flow PNG, the data-set loop
 """
 from . import _lib  # noqa: F401
 from ._lib import Fn2Error, version  # noqa: F401

@@ -1,7 +1,8 @@
 """ctypes binding of libflownet2_hip.so, derived from the C headers in include/ (they are its one source).
 
-Importing this module parses the seven headers: every `fn2_*` function declaration becomes argtypes / restype, every `typedef struct fn2_*`
-a ctypes.Structure (CorrParams, ConvDesc, ...), every `enum { FN2_* }` and `#define FN2_* <integer>` an entry of CONSTANTS.  lib() loads the
+Importing this module parses the eight headers: every `fn2_*` function declaration becomes argtypes / restype, every `typedef struct fn2_*`
+a ctypes.Structure (CorrParams, ConvDesc, ...), every `enum { FN2_* }` and `#define FN2_* <integer>` an entry of CONSTANTS (of
+FLOW_METRICS_CONSTANTS for include/flownet2_hip_flow_metrics.h).  lib() loads the
 library and applies the prototypes.  A new entry point is declared in a header; nothing is added here.  What the parser does not understand
 is an error that names the declaration, never an `int` by default.
 
@@ -20,7 +21,7 @@ INCLUDE_DIR = os.path.join(_HERE, "..", "include")
 _SCALARS = {"int": C.c_int, "float": C.c_float, "size_t": C.c_size_t, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
             "char": C.c_char}
 # what a pointer to each base type travels as: buffers (device or host) as plain addresses, out-parameters and host arrays typed
-_POINTERS = {"float": C.c_void_p, "void": C.c_void_p, "unsigned char": C.c_void_p, "char": C.c_char_p, "int": C.POINTER(C.c_int),
+_POINTERS = {"float": C.c_void_p, "double": C.c_void_p, "void": C.c_void_p, "unsigned char": C.c_void_p, "char": C.c_char_p, "int": C.POINTER(C.c_int),
              "unsigned": C.POINTER(C.c_uint), "size_t": C.POINTER(C.c_size_t)}
 _STRUCT_NAMES = {"fn2_l1loss_params": "L1LossParams", "fn2_l1loss_scale": "L1LossScale"}     # the others: fn2_conv_desc -> ConvDesc
 _DECLARATOR = re.compile(r"^([\w\s*]*?)(\w+)\s*(?:\[(\d+)\])?$")
@@ -102,21 +103,23 @@ def parse_header(text, structs=None):
 
 
 def _parse_headers():
-    """The seven headers, each read on its own (an #include is not followed: the per-header name lists stay apart); the main one first,
-    whose structures the others use."""
-    per_header, structs, constants = [], {}, {}
+    """The eight headers, each read on its own (an #include is not followed: the per-header name lists stay apart); the main one first,
+    whose structures the others use.  The last header's enumerators (the result columns of fn2_flow_metrics) are kept in a table of their own,
+    as its functions are in a list of their own."""
+    per_header, structs, constants, metrics = [], {}, {}, {}
     for h in ("flownet2_hip.h", "flownet2_hip_solver.h", "flownet2_hip_corr_route.h", "flownet2_hip_conv_general.h",
-              "flownet2_hip_conv_geometry.h", "flownet2_hip_conv_volume.h", "flownet2_hip_lpq_loss.h"):
+              "flownet2_hip_conv_geometry.h", "flownet2_hip_conv_volume.h", "flownet2_hip_lpq_loss.h", "flownet2_hip_flow_metrics.h"):
         with open(os.path.join(INCLUDE_DIR, h)) as f:
             functions, structs, c = parse_header(f.read(), structs)
         per_header.append(functions)
-        constants.update(c)
-    return per_header, structs, constants
+        (metrics if h == "flownet2_hip_flow_metrics.h" else constants).update(c)
+    return per_header, structs, constants, metrics
 
 
-_PER_HEADER, _STRUCTS, CONSTANTS = _parse_headers()         # CONSTANTS: every FN2_* enumerator and integer #define
-EXPORTS, SOLVER_EXPORTS, CORR_ROUTE_EXPORTS, CONV_GENERAL_EXPORTS, CONV_GEOMETRY_EXPORTS, CONV_VOLUME_EXPORTS, LPQ_LOSS_EXPORTS = (
-    list(f) for f in _PER_HEADER)      # per header
+# CONSTANTS: every FN2_* enumerator and integer #define of the first seven headers; FLOW_METRICS_CONSTANTS: the FN2_FLOW_METRICS_* enum
+_PER_HEADER, _STRUCTS, CONSTANTS, FLOW_METRICS_CONSTANTS = _parse_headers()
+(EXPORTS, SOLVER_EXPORTS, CORR_ROUTE_EXPORTS, CONV_GENERAL_EXPORTS, CONV_GEOMETRY_EXPORTS, CONV_VOLUME_EXPORTS, LPQ_LOSS_EXPORTS,
+ FLOW_METRICS_EXPORTS) = (list(f) for f in _PER_HEADER)      # per header
 PROTOTYPES = {name: proto for f in _PER_HEADER for name, proto in f.items()}
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})      # CaffemodelEntry, Hdf5Entry, ConvDesc, CorrParams, DatumView, ...
 # debug hooks the library may export without declaring them in a header (FN2_ABLATION builds have the trace)

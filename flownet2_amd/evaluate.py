@@ -1,0 +1,369 @@
+"""Flow evaluation: the per-sample rows of the metrics kernel (csrc/flow_metrics.hip, include/flownet2_hip_flow_metrics.h), the numbers
+a FlowNet user quotes computed from them, ground-truth readers, and the data-set loop of scripts/eval_flownet.py.
+
+FlowMetrics holds one float64 row per sample in data-set order.  summary() is a pure function of those ordered rows, and a sample's row
+does not depend on the batch it was computed in (the kernel's summation order follows (H, W) alone), so an evaluation gives the same
+numbers, to the bit, for any batch size and any number of processes.
+
+The KITTI flow PNG reader is written from the format's published description (the devkit's readme: 16-bit RGB, u = (R - 2^15) / 64,
+v = (G - 2^15) / 64, valid = B != 0) and the PNG specification; no KITTI file was at hand to read with it.
+"""
+from __future__ import annotations
+
+import math
+import queue
+import struct
+import threading
+import zlib
+
+import numpy as np
+
+from . import _lib, flo
+
+_PREFIX = "FN2_FLOW_METRICS_"
+_ENUM = _lib.FLOW_METRICS_CONSTANTS                                        # the header's enum, as the binding's parser read it
+K = _ENUM[_PREFIX + "K"]
+COLUMNS = tuple(sorted((n[len(_PREFIX):] for n in _ENUM if n != _PREFIX + "K"), key=lambda n: _ENUM[_PREFIX + n]))      # names in column order
+COL = {name: i for i, name in enumerate(COLUMNS)}
+
+
+def _ratio(num, den):
+    return float(num) / float(den) if den != 0 else math.nan
+
+
+class FlowMetrics:
+    """The [n, K] float64 rows (columns COLUMNS) of n samples in data-set order; epe_map: the [n,1,H,W] map of the call that made them,
+    where it was asked for."""
+
+    def __init__(self, rows=None, epe_map=None):
+        rows = np.zeros((0, K), np.float64) if rows is None else np.array(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != K:
+            raise ValueError(f"FlowMetrics: rows must be [n, {K}], got {rows.shape}")
+        self.rows = rows
+        self.epe_map = epe_map
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def column(self, name):
+        return self.rows[:, COL[name]]
+
+    def merge(self, others):
+        """This object's samples followed by those of `others`, in the order given."""
+        return FlowMetrics(np.concatenate([self.rows] + [o.rows for o in others], axis=0))
+
+    def summary(self):
+        """The quoted numbers, in float64 from the rows:
+          epe            mean over samples of each sample's mean EPE (Chairs, Sintel); samples without a counted pixel are left out
+          epe_pixel      sum of EPE over the counted pixels of all samples / their number (KITTI; L1Loss's normalize_by_num_entries)
+          fl_all         percent of counted pixels with EPE > outlier_abs and > outlier_rel |gt|
+          ae_deg         mean angular error in degrees
+          s0_10, s10_40, s40plus   mean EPE of the counted pixels in each band of |gt|
+          epe_matched, epe_unmatched   mean EPE of the counted pixels outside / inside the occlusion mask
+          epe_max, pixels (counted), samples, nonfinite (valid pixels with a NaN or Inf prediction: in no sum),
+          samples_without_ground_truth (no valid pixel at all)
+        A quotient with a zero denominator is nan (null in to_json's text)."""
+        c = lambda name: self.column(name)
+        tot = lambda name: float(np.sum(c(name)))
+        valid = c("VALID")
+        counted = valid > 0
+        per_sample = c("EPE_SUM")[counted] / valid[counted]
+        pixels, occ = tot("VALID"), tot("OCC_COUNT")
+        return {
+            "epe": _ratio(np.sum(per_sample), per_sample.size),
+            "epe_pixel": _ratio(tot("EPE_SUM"), pixels),
+            "fl_all": 100.0 * _ratio(tot("OUTLIERS"), pixels),
+            "ae_deg": math.degrees(_ratio(tot("AE_SUM"), pixels)),
+            "s0_10": _ratio(tot("BAND_EPE_SUM0"), tot("BAND_COUNT0")),
+            "s10_40": _ratio(tot("BAND_EPE_SUM1"), tot("BAND_COUNT1")),
+            "s40plus": _ratio(tot("BAND_EPE_SUM2"), tot("BAND_COUNT2")),
+            "epe_matched": _ratio(tot("EPE_SUM") - tot("OCC_EPE_SUM"), pixels - occ),
+            "epe_unmatched": _ratio(tot("OCC_EPE_SUM"), occ),
+            "epe_max": float(np.max(c("EPE_MAX"))) if len(self) else math.nan,
+            "pixels": int(pixels),
+            "samples": len(self),
+            "nonfinite": int(tot("NONFINITE")),
+            "samples_without_ground_truth": int(np.sum((valid + c("NONFINITE")) == 0)),
+        }
+
+    def to_json(self):
+        """The summary and the per-sample rows as strict JSON; floats are written by repr, so the text is a function of the bits."""
+        import json
+        return json.dumps({"summary": json_ready(self.summary()), "columns": list(COLUMNS), "rows": self.rows.tolist()}, indent=1,
+                          allow_nan=False) + "\n"
+
+
+def json_ready(summary):
+    """A summary with null where a quotient had a zero denominator: JSON has no NaN, and a strict parser refuses the bare token."""
+    return {k: None if isinstance(v, float) and math.isnan(v) else v for k, v in summary.items()}
+
+
+def exit_status(summary, allow_nonfinite=False):
+    """What scripts/eval_flownet.py exits with: 1 when a valid pixel had a NaN or Inf prediction (such pixels are in no sum, so the
+    numbers look fine without them) unless that was allowed, else 0."""
+    return 1 if summary["nonfinite"] > 0 and not allow_nonfinite else 0
+
+
+# ---- the KITTI flow PNG -------------------------------------------------------------------------------------------------------------
+_PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+
+
+def _chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def _paeth(a, b, c):
+    p = a + b - c
+    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+    return a if pa <= pb and pa <= pc else b if pb <= pc else c
+
+
+def _filter_row(ftype, row, prev, bpp):
+    """PNG filter `ftype` of one scanline (bytes) given the unfiltered previous one (the writer is for fixtures: a Python step per byte)."""
+    out = bytearray(len(row))
+    for i, x in enumerate(row):
+        a = row[i - bpp] if i >= bpp else 0
+        b = prev[i]
+        c = prev[i - bpp] if i >= bpp else 0
+        pred = (0, a, b, (a + b) >> 1, _paeth(a, b, c))[ftype]
+        out[i] = (x - pred) & 255
+    return out
+
+
+def _unfilter(filtered, h, w, bpp):
+    """The scanlines of a non-interlaced image (h rows of 1 filter-type byte + w * bpp bytes) -> uint8 [h, w, bpp], all five filter types.
+    A byte depends on its left, upper and upper-left neighbours, so the pixels of one anti-diagonal x + y = d are independent: the image is
+    rebuilt diagonal by diagonal, h + w - 1 NumPy steps in place of a Python step per byte (libpng picks Paeth for most lines of a
+    photograph-like map; a 1242 x 375 KITTI map is 2.8 M bytes)."""
+    lines = np.frombuffer(filtered, np.uint8).reshape(h, 1 + w * bpp)
+    ftype = lines[:, 0].astype(np.int32)
+    if ftype.max(initial=0) > 4:
+        raise ValueError(f"PNG: unknown filter type {int(ftype.max())}")
+    data = lines[:, 1:].reshape(h, w, bpp).astype(np.int32)
+    out = np.zeros((h + 1, w + 1, bpp), np.int32)               # pixel (y, x) at out[y + 1, x + 1]; row 0 and column 0 are the zeros outside
+    rows = np.arange(h)
+    for d in range(h + w - 1):
+        y = rows[max(0, d - w + 1):min(h, d + 1)]
+        x = d - y
+        a, b, c = out[y + 1, x], out[y, x + 1], out[y, x]       # left, up, upper left
+        f = ftype[y][:, np.newaxis]
+        p = a + b - c
+        pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+        paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+        pred = np.where(f == 1, a, np.where(f == 2, b, np.where(f == 3, (a + b) >> 1, np.where(f == 4, paeth, 0))))
+        out[y + 1, x + 1] = (data[y, x] + pred) & 255
+    return out[1:, 1:].astype(np.uint8)
+
+
+def read_png16_rgb(path):
+    """A non-interlaced 16-bit RGB PNG -> uint16 [H, W, 3].  (PIL hands 16-bit RGB back as 8 bits per channel, so this is read here, on
+    zlib: colour type 2, bit depth 16, all five filter types.)  Anything else is refused by name."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != _PNG_MAGIC:
+        raise ValueError(f"{path}: not a PNG file")
+    pos, idat, head = 8, [], None
+    while pos + 8 <= len(data):
+        n, kind = struct.unpack(">I", data[pos:pos + 4])[0], data[pos + 4:pos + 8]
+        body = data[pos + 8:pos + 8 + n]
+        pos += 12 + n
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+    if head is None:
+        raise ValueError(f"{path}: no IHDR chunk")
+    w, h, depth, colour, _, _, interlace = head
+    if depth != 16 or colour != 2:
+        raise ValueError(f"{path}: bit depth {depth}, colour type {colour}: a KITTI flow map is 16-bit RGB (bit depth 16, colour type 2)")
+    if interlace != 0:
+        raise ValueError(f"{path}: interlaced PNG (Adam7) is not supported")
+    bpp, stride = 6, 6 * w
+    raw = zlib.decompress(b"".join(idat))
+    if len(raw) != h * (stride + 1):
+        raise ValueError(f"{path}: {len(raw)} bytes of image data, expected {h * (stride + 1)}")
+    return np.frombuffer(_unfilter(raw, h, w, bpp).tobytes(), ">u2").reshape(h, w, 3).astype(np.uint16)
+
+
+def write_png16_rgb(path, rgb, filter_type=0):
+    """uint16 [H, W, 3] -> a non-interlaced 16-bit RGB PNG, every scanline with PNG filter `filter_type` (0 .. 4)."""
+    rgb = np.asarray(rgb)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.dtype != np.uint16:
+        raise ValueError(f"write_png16_rgb: need uint16 [H,W,3], got {rgb.dtype} {rgb.shape}")
+    h, w = rgb.shape[:2]
+    lines, prev = [], bytearray(6 * w)
+    for y in range(h):
+        row = bytearray(rgb[y].astype(">u2").tobytes())
+        lines.append(bytes([filter_type]) + bytes(_filter_row(filter_type, row, prev, 6)))
+        prev = row
+    with open(path, "wb") as f:
+        f.write(_PNG_MAGIC + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 2, 0, 0, 0)) + _chunk(b"IDAT", zlib.compress(b"".join(lines)))
+                + _chunk(b"IEND", b""))
+
+
+def read_kitti_flow(path):
+    """KITTI flow PNG -> (flow [2,H,W] float32, valid [1,H,W] float32)."""
+    rgb = read_png16_rgb(path)
+    uv = (rgb[:, :, :2].astype(np.float32) - np.float32(2 ** 15)) / np.float32(64)      # exact: a 16-bit integer over a power of two
+    return np.ascontiguousarray(uv.transpose(2, 0, 1)), (rgb[:, :, 2] != 0).astype(np.float32)[np.newaxis]
+
+
+def write_kitti_flow(path, flow, valid=None, filter_type=0):
+    """The writer that matches read_kitti_flow (fixtures): flow [2,H,W] in steps of 1 / 64 within +-512, valid [1,H,W] or [H,W] or None."""
+    flow = np.asarray(flow, np.float64)
+    q = np.rint(flow * 64.0 + 2 ** 15)
+    if q.min() < 0 or q.max() > 65535:
+        raise ValueError("write_kitti_flow: flow outside the format's range of -512 .. 511.98")
+    v = np.ones(flow.shape[1:], bool) if valid is None else np.asarray(valid).reshape(flow.shape[1:]) != 0
+    rgb = np.stack([q[0], q[1], v.astype(np.float64)], axis=-1).astype(np.uint16)
+    rgb[~v, :2] = 0                                                                       # the devkit writes an invalid pixel as (0, 0, 0)
+    write_png16_rgb(path, rgb, filter_type)
+
+
+# ---- ground truth and lists --------------------------------------------------------------------------------------------------------
+def _plane(a, what):
+    a = np.asarray(a)
+    if a.ndim == 3 and a.shape[0] == 1:
+        a = a[0]
+    if a.ndim == 3:                     # a colour mask image: any channel set
+        a = a.any(axis=2)
+    if a.ndim != 2:
+        raise ValueError(f"{what}: expected a [H,W] mask, got {a.shape}")
+    return (a != 0).astype(np.float32)[np.newaxis]
+
+
+def read_mask(path):
+    """A mask file -> [1,H,W] float32 of 0 / 1: .npy, or any image PIL reads (non-zero = set)."""
+    if path.endswith(".npy"):
+        return _plane(np.load(path), path)
+    from PIL import Image
+    return _plane(np.asarray(Image.open(path)), path)
+
+
+def read_ground_truth(path, mask=None, mask_as="valid"):
+    """-> (flow [2,H,W] float32, valid [1,H,W] float32 or None, occ [1,H,W] float32 or None) from a .flo, a .npz (`flow` as [2,H,W] or
+    [H,W,2], optional `valid` / `occ`) or a KITTI flow .png; `mask`: a mask file read as `valid` or, with mask_as="occ", as `occ`."""
+    if mask_as not in ("valid", "occ"):
+        raise ValueError(f"mask_as: 'valid' or 'occ', got {mask_as!r}")
+    valid = occ = None
+    if path.endswith(".flo"):
+        flow = flo.read_flo(path).transpose(2, 0, 1)
+    elif path.endswith(".npz"):
+        with np.load(path) as z:
+            flow = np.asarray(z["flow"], np.float32)
+            if flow.ndim != 3 or 2 not in (flow.shape[0], flow.shape[2]):
+                raise ValueError(f"{path}: flow must be [2,H,W] or [H,W,2], got {flow.shape}")
+            if flow.shape[2] == 2:                                                      # [H,W,2], as flo.write_flo reads a [2,H,2] array
+                flow = flow.transpose(2, 0, 1)
+            valid = _plane(z["valid"], path + ":valid") if "valid" in z else None
+            occ = _plane(z["occ"], path + ":occ") if "occ" in z else None
+    elif path.endswith(".png"):
+        flow, valid = read_kitti_flow(path)
+    else:
+        raise ValueError(f"{path}: ground truth must be .flo, .npz or a KITTI flow .png")
+    flow = np.ascontiguousarray(flow, np.float32)
+    if mask is not None:
+        m = read_mask(mask)
+        if m.shape[1:] != flow.shape[1:]:
+            raise ValueError(f"{mask}: mask {m.shape[1:]} does not match the flow {flow.shape[1:]}")
+        if mask_as == "valid":
+            valid = m if valid is None else valid * m
+        else:
+            occ = m
+    return flow, valid, occ
+
+
+def parse_list(lines):
+    """List lines `img0 img1 gt [mask]` -> [(img0, img1, gt, mask or None)]; blank lines and lines starting with # are skipped."""
+    out = []
+    for no, line in enumerate(lines, 1):
+        tok = line.split()
+        if not tok or tok[0].startswith("#"):
+            continue
+        if len(tok) not in (3, 4):
+            raise ValueError(f"list line {no}: expected `img0 img1 gt [mask]`, got {len(tok)} fields")
+        out.append((tok[0], tok[1], tok[2], tok[3] if len(tok) == 4 else None))
+    return out
+
+
+# ---- the data-set loop -------------------------------------------------------------------------------------------------------------
+def prefetched(items, depth):
+    """Iterate `items` on a thread of its own that stays up to `depth` items ahead; its exception is raised here."""
+    q, end = queue.Queue(maxsize=max(1, depth)), object()
+
+    def run():
+        try:
+            for it in items:
+                q.put(it)
+            q.put(end)
+        except BaseException as e:      # noqa: BLE001 -- surfaced on the consumer's thread
+            q.put(e)
+
+    threading.Thread(target=run, daemon=True).start()
+    while True:
+        it = q.get()
+        if it is end:
+            return
+        if isinstance(it, BaseException):
+            raise it
+        yield it
+
+
+def _stack(planes, shape, absent):
+    """[n,1,H,W] from per-sample [1,H,W] masks; None when no sample has one, `absent` everywhere for a sample without where others have."""
+    if all(p is None for p in planes):
+        return None
+    return np.stack([p if p is not None else np.full(shape, absent, np.float32) for p in planes])
+
+
+def gather(total, parts):
+    """parts: this rank's [(list indices, FlowMetrics)].  Over the process group (gloo: Python objects) every rank's parts go to rank 0,
+    which returns the FlowMetrics of all `total` samples in list order; the other ranks return None."""
+    from . import parallel
+    mine = [(list(idx), m.rows) for idx, m in parts]
+    if parallel.world() > 1:
+        import torch.distributed as dist
+        every = [None] * parallel.world() if parallel.rank() == 0 else None
+        dist.gather_object(mine, every, dst=0)
+        if parallel.rank() != 0:
+            return None
+        mine = [p for r in every for p in r]
+    rows, seen = np.zeros((total, K), np.float64), np.zeros(total, bool)
+    for idx, r in mine:
+        rows[idx] = r
+        seen[idx] = True
+    if not seen.all():
+        raise RuntimeError(f"evaluate.gather: no result for list entries {np.flatnonzero(~seen).tolist()}")
+    return FlowMetrics(rows)
+
+
+def evaluate(entries, groups_of, read_image, predict, metrics, batch=8, prefetch=2, mask_as="valid", on_group=None):
+    """Score a list.  entries: parse_list's tuples.  This rank takes its shard (parallel.shard), groups it into batches of at most `batch`
+    consecutive pairs of equal image size (groups_of: scripts/run_flownet_many.py's), reads images and ground truth `prefetch` groups
+    ahead, and for every group calls pred = predict(img0 [n,3,H,W], img1) and metrics(pred, gt, valid, occ) -> FlowMetrics (both given
+    NumPy arrays; what predict returns is handed to metrics as it is).  on_group(entries, FlowMetrics) sees every group (the epe maps).
+    Returns gather()'s result: all samples in list order on rank 0, None on the other ranks."""
+    from . import parallel
+    mine = parallel.shard([e + (i,) for i, e in enumerate(entries)])
+
+    def staged():
+        for ents, i0, i1 in groups_of(mine, batch, read_image):
+            gts = [read_ground_truth(e[2], e[3], mask_as) for e in ents]
+            hw = gts[0][0].shape[1:]
+            for e, g in zip(ents, gts):
+                if g[0].shape[1:] != hw or tuple(i0.shape[2:]) != tuple(hw):
+                    raise ValueError(f"{e[2]}: ground truth {g[0].shape[1:]} does not match the images {tuple(i0.shape[2:])}")
+            yield (ents, i0, i1, np.stack([g[0] for g in gts]), _stack([g[1] for g in gts], (1,) + hw, 1.0),
+                   _stack([g[2] for g in gts], (1,) + hw, 0.0))
+
+    parts = []
+    for ents, i0, i1, gt, valid, occ in prefetched(staged(), prefetch):
+        m = metrics(predict(i0, i1), gt, valid, occ)
+        if len(m) != len(ents):
+            raise RuntimeError(f"evaluate: {len(m)} rows for {len(ents)} samples")
+        if on_group is not None:
+            on_group(ents, m)
+        parts.append(([e[4] for e in ents], m))
+    return gather(len(entries), parts)

@@ -442,6 +442,20 @@ def lpq_loss_multi(preds, targets, weights, p=1.0, q=1.0, p_epsilon=0.0, q_epsil
     return _LpqLossMulti.apply(params, tuple(float(w) for w in weights), len(preds), *blobs)
 
 
+def flow_metrics(pred, gt, valid=None, occ=None, *, outlier=(3.0, 0.05), bands=(10.0, 40.0), epe_map=False):
+    """Error metrics of a predicted flow against ground truth, both [N,2,H,W] (csrc/flow_metrics.hip; the arithmetic is stated in
+    include/flownet2_hip_flow_metrics.h): per sample the counted pixels, the EPE sum / sum of squares / max, the outliers (EPE > outlier[0]
+    and > outlier[1] |gt|), the angular error, the EPE per band of |gt| (edges `bands`) and inside the `occ` mask.  valid / occ: [N,1,H,W],
+    non-zero = use the pixel / occluded.  Returns an evaluate.FlowMetrics of N rows (its summary() gives the quoted numbers), with the
+    [N,1,H,W] EPE map (NaN where a pixel is not counted) as .epe_map where epe_map is set.  Not differentiable: a metric, not a loss."""
+    from .evaluate import FlowMetrics
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (pred, gt, valid, occ)):
+        raise RuntimeError("flow_metrics is not differentiable: detach the inputs or call it under torch.no_grad() (the training loss is "
+                           "l1_loss / lpq_loss)")
+    results, emap = ops.flow_metrics(pred, gt, valid, occ, outlier=outlier, bands=bands, epe_map=epe_map)
+    return FlowMetrics(results[:-1].cpu().numpy(), epe_map=emap)
+
+
 def add_loss_flags(ap):
     """--loss l1 | lpq and the Lpq schedule of a training script (scripts/train_pipeline.py, scripts/train_prototxt_step.py)."""
     ap.add_argument("--loss", choices=("l1", "lpq"), default="l1", help="l1: L1Loss{l2_per_location} (the default); lpq: LpqLoss with --lpq-p / --lpq-q")

@@ -439,6 +439,36 @@ def lpq_loss_backward_multi(params, bottoms0, bottoms1, weights, total_diff, wor
     return d0, d1
 
 
+_FLOW_METRICS_K = _lib.FLOW_METRICS_CONSTANTS["FN2_FLOW_METRICS_K"]      # columns of a results row (evaluate.COLUMNS names them)
+
+
+def flow_metrics_sizes(N: int, H: int, W: int):
+    """(workspace bytes for [N,2,H,W], K) of fn2_flow_metrics (include/flownet2_hip_flow_metrics.h)."""
+    nbytes, k = C.c_size_t(), C.c_int()
+    check(_lib.lib().fn2_flow_metrics_sizes(int(N), int(H), int(W), C.byref(nbytes), C.byref(k)))
+    return nbytes.value, k.value
+
+
+def flow_metrics(pred, gt, valid=None, occ=None, outlier=(3.0, 0.05), bands=(10.0, 40.0), epe_map=False):
+    """Flow error metrics (csrc/flow_metrics.hip) of pred against gt [N,2,H,W]; valid / occ [N,1,H,W] or None.  Returns (results
+    [N + 1, K] float64 on the device: one row per sample and the totals row, columns evaluate.COLUMNS; the epe map [N,1,H,W] or None)."""
+    p, g = _chk(pred, "pred"), _chk(gt, "gt")
+    if p.shape != g.shape or p.shape[1] != 2:
+        raise ValueError(f"flow_metrics: pred {tuple(p.shape)} and gt {tuple(g.shape)} must both be [N,2,H,W]")
+    N, _, H, W = p.shape
+    v, o = _chk_opt(valid, "valid"), _chk_opt(occ, "occ")
+    for name, m in (("valid", v), ("occ", o)):
+        if m is not None and tuple(m.shape) != (N, 1, H, W):
+            raise ValueError(f"flow_metrics: {name} {tuple(m.shape)} must be [{N},1,{H},{W}]")
+    ws = torch.empty(flow_metrics_sizes(N, H, W)[0], dtype=torch.uint8, device=p.device)
+    results = torch.empty((N + 1, _FLOW_METRICS_K), dtype=torch.float64, device=p.device)
+    emap = torch.empty((N, 1, H, W), dtype=torch.float32, device=p.device) if epe_map else None
+    check(_lib.lib().fn2_flow_metrics(_ptr(p), _ptr(g), _ptr(v), _ptr(o), N, H, W, C.c_float(float(outlier[0])), C.c_float(float(outlier[1])),
+                                      C.c_float(float(bands[0])), C.c_float(float(bands[1])), _ptr(results), _ptr(emap), _ptr(ws), ws.numel(),
+                                      _stream()))
+    return results, emap
+
+
 def channel_norm_forward(x):
     x = _chk(x, "bottom[0]")
     N, Cc, H, W = x.shape
