@@ -246,14 +246,14 @@ FN2_API int fn2_bias_leaky_relu_forward(float* data, const float* bias, int N, i
   const unsigned per = (unsigned)(vec ? hw / 4 : hw);
   unsigned bx = (per + 255) / 256;
   if (bx > 64) bx = 64;
-  // gridDim.y is limited to 65535: fold planes in chunks
+  // gridDim.y is limited to 65535: fold planes in chunks.  plane % C in the kernel needs every chunk to start on a multiple of C; the
+  // blob is processed in place, so that is decided before the first launch (a refused call leaves the blob as it was)
+  if (planes > 65535 && 65535 % C != 0) return fail(FN2_ERR_UNSUPPORTED, "bias_leaky_relu: N*C > 65535 with C not dividing 65535");
   for (long long p0 = 0; p0 < planes; p0 += 65535) {
     const unsigned py = (unsigned)((planes - p0) < 65535 ? (planes - p0) : 65535);
     float* base = data + (size_t)p0 * hw;
-    const float* bb = bias;     // plane % C below needs the chunk to start on a multiple of C ...
-    if (p0 % C != 0) return fail(FN2_ERR_UNSUPPORTED, "bias_leaky_relu: N*C > 65535 with C not dividing 65535");
-    if (vec) hipLaunchKernelGGL(bias_leaky_relu<true>, dim3(bx, py), dim3(256), 0, st, base, bb, C, (unsigned)hw, negative_slope);
-    else     hipLaunchKernelGGL(bias_leaky_relu<false>, dim3(bx, py), dim3(256), 0, st, base, bb, C, (unsigned)hw, negative_slope);
+    if (vec) hipLaunchKernelGGL(bias_leaky_relu<true>, dim3(bx, py), dim3(256), 0, st, base, bias, C, (unsigned)hw, negative_slope);
+    else     hipLaunchKernelGGL(bias_leaky_relu<false>, dim3(bx, py), dim3(256), 0, st, base, bias, C, (unsigned)hw, negative_slope);
   }
   return check_launch("bias_leaky_relu_forward");
 }

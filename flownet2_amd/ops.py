@@ -597,36 +597,54 @@ def predict_flow_conv_backward_supported(N, C, H, W) -> bool:
     return bool(_lib.lib().fn2_predict_flow_conv_backward_supported(int(N), int(C), int(H), int(W)))
 
 
-def predict_flow_conv_backward(x, weight, top_diff, need_x=True, need_w=True, need_b=True):
+def _head_diffs(what, out, needs, shapes, device):
+    """The (bottom_diff, weight_diff, bias_diff) blobs of a flow head's backward: new ones, or those of `out` (a triple, None where the
+    gradient is not needed), checked against their shapes."""
+    if out is None:
+        return tuple(torch.empty(s, device=device, dtype=torch.float32) if need else None for need, s in zip(needs, shapes))
+    if len(out) != 3:
+        raise ValueError(what + ": out must be (bottom_diff, weight_diff, bias_diff)")
+    for t, need, s, name in zip(out, needs, shapes, ("bottom.diff", "weight.diff", "bias.diff")):
+        if (t is not None) != bool(need):
+            raise ValueError(f"{what}: out holds a {name} exactly where that gradient is needed")
+        if t is not None and (_chk(t, name, ndim=len(s)) is not t or tuple(t.shape) != tuple(s)):
+            raise ValueError(f"{what}: {name} must be a contiguous {list(s)} blob")
+    return tuple(out)
+
+
+def predict_flow_conv_backward(x, weight, top_diff, need_x=True, need_w=True, need_b=True, out=None, accumulate=False):
     """Backward of predict_flow (Convolution{3,1,1} C -> 2): (bottom_diff, weight_diff, bias_diff), None where not needed.  `x` may be a
-    channel slice (blob, c0, C)."""
+    channel slice (blob, c0, C).  `out` = the three gradient blobs to write (None where not needed); with `accumulate` the weight and
+    bias gradients are added to what `out` holds (the bottom gradient is always overwritten)."""
     xb, xctot, xc0, Cc = _as_slice(x, "bottom[0]")
     w, g = _chk(weight, "weight"), _chk(top_diff, "top.diff")
     N, _, H, W = xb.shape
     if tuple(w.shape) != (2, Cc, 3, 3) or tuple(g.shape) != (N, 2, H, W):
         raise ValueError("predict_flow_conv_backward: weight must be [2,C,3,3] and top_diff [N,2,H,W]")
-    dx = torch.empty((N, Cc, H, W), device=g.device, dtype=torch.float32) if need_x else None
-    dw = torch.empty_like(w) if need_w else None
-    db = torch.empty(2, device=g.device, dtype=torch.float32) if need_b else None
+    if accumulate and out is None:
+        raise ValueError("predict_flow_conv_backward: accumulate needs the gradients to add to (out)")
+    dx, dw, db = _head_diffs("predict_flow_conv_backward", out, (need_x, need_w, need_b), ((N, Cc, H, W), tuple(w.shape), (2,)), g.device)
     nbytes = _lib.lib().fn2_predict_flow_conv_backward_workspace_bytes(N, Cc, H, W) if (need_w or need_b) else 0
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=g.device)
-    check(_lib.lib().fn2_predict_flow_conv_backward(_ptr(xb), xctot, xc0, _ptr(w), _ptr(g), _ptr(dx), _ptr(dw), _ptr(db), N, Cc, H, W, 0,
-                                                    _ptr(ws), nbytes, _stream()))
+    check(_lib.lib().fn2_predict_flow_conv_backward(_ptr(xb), xctot, xc0, _ptr(w), _ptr(g), _ptr(dx), _ptr(dw), _ptr(db), N, Cc, H, W,
+                                                    int(bool(accumulate)), _ptr(ws), nbytes, _stream()))
     return dx, dw, db
 
 
-def upsample_flow_deconv_backward(x, weight, top_diff, need_x=True, need_w=True, need_b=True):
-    """Backward of upsample_flow (Deconvolution{4,2,1} 2 -> 2): (bottom_diff, weight_diff, bias_diff), None where not needed."""
+def upsample_flow_deconv_backward(x, weight, top_diff, need_x=True, need_w=True, need_b=True, out=None, accumulate=False):
+    """Backward of upsample_flow (Deconvolution{4,2,1} 2 -> 2): (bottom_diff, weight_diff, bias_diff), None where not needed; `out` and
+    `accumulate` as for predict_flow_conv_backward."""
     x, w, g = _chk(x, "bottom[0]"), _chk(weight, "weight"), _chk(top_diff, "top.diff")
     N, Cc, H, W = x.shape
     if Cc != 2 or tuple(w.shape) != (2, 2, 4, 4) or tuple(g.shape) != (N, 2, 2 * H, 2 * W):
         raise ValueError("upsample_flow_deconv_backward: bottom [N,2,H,W], weight [2,2,4,4], top_diff [N,2,2H,2W]")
-    dx = torch.empty_like(x) if need_x else None
-    dw = torch.empty_like(w) if need_w else None
-    db = torch.empty(2, device=g.device, dtype=torch.float32) if need_b else None
+    if accumulate and out is None:
+        raise ValueError("upsample_flow_deconv_backward: accumulate needs the gradients to add to (out)")
+    dx, dw, db = _head_diffs("upsample_flow_deconv_backward", out, (need_x, need_w, need_b), (tuple(x.shape), (2, 2, 4, 4), (2,)), g.device)
     nbytes = _lib.lib().fn2_upsample_flow_deconv_backward_workspace_bytes(N, H, W) if (need_w or need_b) else 0
     ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=g.device)
-    check(_lib.lib().fn2_upsample_flow_deconv_backward(_ptr(x), _ptr(w), _ptr(g), _ptr(dx), _ptr(dw), _ptr(db), N, H, W, 0, _ptr(ws), nbytes, _stream()))
+    check(_lib.lib().fn2_upsample_flow_deconv_backward(_ptr(x), _ptr(w), _ptr(g), _ptr(dx), _ptr(dw), _ptr(db), N, H, W, int(bool(accumulate)),
+                                                       _ptr(ws), nbytes, _stream()))
     return dx, dw, db
 
 
