@@ -7,12 +7,13 @@ functional torch.autograd glue,  nets: FlowNetC/S graphs,  flo: .flo I/O
 solver     SolverParameter, Solver (SGDSolver / AdamSolver, get_solver) and CaffeOptimizer on the one-launch HIP update
 LpqSchedule  the p / q episodes of LpqLoss (lpq_schedule.py)
 evaluate   FlowMetrics (the rows of the metrics kernel, summary()), ground-truth readers incl. the KITTI flow PNG, the data-set loop
+flow_consistency  forward-backward consistency of two flows -> FlowConsistency (occlusion masks, rows, summary()) in one launch
 """
 from . import _lib  # noqa: F401
 from ._lib import Fn2Error, version  # noqa: F401
 
 _SOLVER_EXPORTS = ("SolverParameter", "Solver", "SGDSolver", "AdamSolver", "get_solver", "CaffeOptimizer")
-__all__ = ["Fn2Error", "version", "LpqSchedule", *_SOLVER_EXPORTS]
+__all__ = ["Fn2Error", "version", "LpqSchedule", "flow_consistency", "FlowConsistency", *_SOLVER_EXPORTS]
 
 
 def __getattr__(name):
@@ -23,4 +24,10 @@ def __getattr__(name):
     if name == "LpqSchedule":
         from .lpq_schedule import LpqSchedule
         return LpqSchedule
+    if name == "flow_consistency":
+        from .functional import flow_consistency
+        return flow_consistency
+    if name == "FlowConsistency":
+        from .evaluate import FlowConsistency
+        return FlowConsistency
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

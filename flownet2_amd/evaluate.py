@@ -86,10 +86,11 @@ class FlowMetrics:
             "samples_without_ground_truth": int(np.sum((valid + c("NONFINITE")) == 0)),
         }
 
-    def to_json(self):
-        """The summary and the per-sample rows as strict JSON; floats are written by repr, so the text is a function of the bits."""
+    def to_json(self, extra=None):
+        """The summary and the per-sample rows as strict JSON; floats are written by repr, so the text is a function of the bits.
+        extra: further top-level entries, written after the three."""
         import json
-        return json.dumps({"summary": json_ready(self.summary()), "columns": list(COLUMNS), "rows": self.rows.tolist()}, indent=1,
+        return json.dumps({"summary": json_ready(self.summary()), "columns": list(COLUMNS), "rows": self.rows.tolist(), **(extra or {})}, indent=1,
                           allow_nan=False) + "\n"
 
 
@@ -102,6 +103,102 @@ def exit_status(summary, allow_nonfinite=False):
     """What scripts/eval_flownet.py exits with: 1 when a valid pixel had a NaN or Inf prediction (such pixels are in no sum, so the
     numbers look fine without them) unless that was allowed, else 0."""
     return 1 if summary["nonfinite"] > 0 and not allow_nonfinite else 0
+
+
+# ---- forward-backward consistency -------------------------------------------------------------------------------------------------
+_C_PREFIX = "FN2_FLOW_CONSISTENCY_"
+_C_ENUM = _lib.FLOW_CONSISTENCY_CONSTANTS                                   # include/flownet2_hip_flow_consistency.h: columns and flag bits
+CONSISTENCY_K = _C_ENUM[_C_PREFIX + "K"]
+CONSISTENCY_FLAGS = {n[len(_C_PREFIX + "FLAG_"):]: v for n, v in _C_ENUM.items() if n.startswith(_C_PREFIX + "FLAG_")}      # name -> bit
+CONSISTENCY_COLUMNS = tuple(sorted((n[len(_C_PREFIX):] for n in _C_ENUM if n != _C_PREFIX + "K" and not n.startswith(_C_PREFIX + "FLAG_")),
+                                   key=lambda n: _C_ENUM[_C_PREFIX + n]))
+CONSISTENCY_COL = {name: i for i, name in enumerate(CONSISTENCY_COLUMNS)}
+
+
+class FlowConsistency:
+    """The [n, K] float64 rows (columns CONSISTENCY_COLUMNS) of n samples per direction, in data-set order, and the maps of the call that
+    made them: occ, flags, err, warped are (forward, backward) pairs or None.  Direction fw checks the forward flow against the backward
+    one (occ_fw lives in frame 0, where the forward flow and its ground truth live), bw the reverse."""
+
+    def __init__(self, rows_fw=None, rows_bw=None, occ=None, flags=None, err=None, warped=None, alpha=(0.01, 0.5), beta=(0.01, 0.002)):
+        def rows(r, what):
+            r = np.zeros((0, CONSISTENCY_K), np.float64) if r is None else np.array(r, dtype=np.float64)
+            if r.ndim != 2 or r.shape[1] != CONSISTENCY_K:
+                raise ValueError(f"FlowConsistency: {what} must be [n, {CONSISTENCY_K}], got {r.shape}")
+            return r
+        self.rows_fw, self.rows_bw = rows(rows_fw, "rows_fw"), rows(rows_bw, "rows_bw")
+        if self.rows_fw.shape != self.rows_bw.shape:
+            raise ValueError(f"FlowConsistency: {self.rows_fw.shape[0]} forward rows, {self.rows_bw.shape[0]} backward rows")
+        pair = lambda p: (None, None) if p is None else tuple(p)
+        (self.occ_fw, self.occ_bw), (self.flags_fw, self.flags_bw) = pair(occ), pair(flags)
+        (self.err_fw, self.err_bw), (self.warped_fw, self.warped_bw) = pair(err), pair(warped)
+        self.alpha, self.beta = (float(alpha[0]), float(alpha[1])), (float(beta[0]), float(beta[1]))
+
+    def __len__(self):
+        return self.rows_fw.shape[0]
+
+    def merge(self, others):
+        """This object's samples followed by those of `others`, in the order given (the rows; the maps stay with their calls)."""
+        for o in others:
+            if (o.alpha, o.beta) != (self.alpha, self.beta):
+                raise ValueError(f"FlowConsistency.merge: thresholds differ ({o.alpha}, {o.beta} against {self.alpha}, {self.beta})")
+        return FlowConsistency(np.concatenate([self.rows_fw] + [o.rows_fw for o in others], axis=0),
+                               np.concatenate([self.rows_bw] + [o.rows_bw for o in others], axis=0), alpha=self.alpha, beta=self.beta)
+
+    def sample(self, i):
+        """Sample i alone (its rows)."""
+        return FlowConsistency(self.rows_fw[i:i + 1], self.rows_bw[i:i + 1], alpha=self.alpha, beta=self.beta)
+
+    @staticmethod
+    def _direction(rows):
+        tot = lambda name: float(np.sum(rows[:, CONSISTENCY_COL[name]]))
+        pixels = tot("PIXELS")
+        with_err = pixels - tot("OUTSIDE") - tot("NONFINITE")                   # the three flags that leave err NaN exclude one another
+        return {
+            "occluded": _ratio(tot("OCCLUDED"), pixels),
+            "outside": _ratio(tot("OUTSIDE"), pixels),
+            "inconsistent": _ratio(tot("INCONSISTENT"), pixels),
+            "nonfinite": _ratio(tot("NONFINITE"), pixels),
+            "boundary": _ratio(tot("BOUNDARY"), pixels),
+            "err_mean": _ratio(tot("ERR_SUM"), with_err),
+            "err_max": float(np.max(rows[:, CONSISTENCY_COL["ERR_MAX"]])) if rows.shape[0] else math.nan,
+            "pixels": int(pixels),
+        }
+
+    def summary(self):
+        """Per direction the fractions of all pixels that are occluded (outside, inconsistent or non-finite), outside, inconsistent,
+        non-finite and on a motion boundary, the mean of err over the pixels that have one, the largest err and the pixel count; then
+        the sample count and the thresholds.  A quotient with a zero denominator is nan (null in to_json's text)."""
+        return {"fw": self._direction(self.rows_fw), "bw": self._direction(self.rows_bw), "samples": len(self), "alpha": list(self.alpha),
+                "beta": list(self.beta)}
+
+    def to_json(self):
+        """The summary, one summary per sample (`lines`, in order) and the rows as strict JSON; floats are written by repr, so the text is
+        a function of the bits."""
+        import json
+        ready = lambda s: {k: json_ready(v) if isinstance(v, dict) else v for k, v in s.items()}
+        return json.dumps({"summary": ready(self.summary()), "lines": [ready(self.sample(i).summary()) for i in range(len(self))],
+                           "columns": list(CONSISTENCY_COLUMNS), "rows_fw": self.rows_fw.tolist(), "rows_bw": self.rows_bw.tolist()}, indent=1,
+                          allow_nan=False) + "\n"
+
+
+def write_pgm(path, plane):
+    """A [H,W] (or [1,H,W]) plane -> 8-bit binary PGM (P5, maxval 255): 255 where the plane is non-zero, else 0."""
+    a = np.asarray(plane)
+    if a.ndim == 3 and a.shape[0] == 1:
+        a = a[0]
+    if a.ndim != 2:
+        raise ValueError(f"write_pgm: expected a [H,W] plane, got {a.shape}")
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
+        f.write(np.where(a != 0, 255, 0).astype(np.uint8).tobytes())
+
+
+def bidirectional_names(out):
+    """What the runners write beside the forward flow `out` (x.flo): (x.bw.flo, x.occ.pgm, x.bw.occ.pgm); a name without the .flo
+    suffix is extended as it stands."""
+    stem = out[:-4] if out.endswith(".flo") else out
+    return stem + ".bw.flo", stem + ".occ.pgm", stem + ".bw.occ.pgm"
 
 
 # ---- the KITTI flow PNG -------------------------------------------------------------------------------------------------------------
@@ -339,11 +436,34 @@ def gather(total, parts):
     return FlowMetrics(rows)
 
 
-def evaluate(entries, groups_of, read_image, predict, metrics, batch=8, prefetch=2, mask_as="valid", on_group=None):
+def gather_consistency(total, parts, alpha=(0.01, 0.5), beta=(0.01, 0.002)):
+    """gather() for FlowConsistency: parts is this rank's [(list indices, FlowConsistency)]; rank 0 returns the FlowConsistency of all
+    `total` samples in list order, the other ranks None."""
+    from . import parallel
+    mine = [(list(idx), c.rows_fw, c.rows_bw) for idx, c in parts]
+    if parallel.world() > 1:
+        import torch.distributed as dist
+        every = [None] * parallel.world() if parallel.rank() == 0 else None
+        dist.gather_object(mine, every, dst=0)
+        if parallel.rank() != 0:
+            return None
+        mine = [p for r in every for p in r]
+    fw, bw, seen = np.zeros((total, CONSISTENCY_K), np.float64), np.zeros((total, CONSISTENCY_K), np.float64), np.zeros(total, bool)
+    for idx, rf, rb in mine:
+        fw[idx], bw[idx] = rf, rb
+        seen[idx] = True
+    if not seen.all():
+        raise RuntimeError(f"evaluate.gather_consistency: no result for list entries {np.flatnonzero(~seen).tolist()}")
+    return FlowConsistency(fw, bw, alpha=alpha, beta=beta)
+
+
+def evaluate(entries, groups_of, read_image, predict, metrics, batch=8, prefetch=2, mask_as="valid", on_group=None, occ_present=False):
     """Score a list.  entries: parse_list's tuples.  This rank takes its shard (parallel.shard), groups it into batches of at most `batch`
     consecutive pairs of equal image size (groups_of: scripts/run_flownet_many.py's), reads images and ground truth `prefetch` groups
     ahead, and for every group calls pred = predict(img0 [n,3,H,W], img1) and metrics(pred, gt, valid, occ) -> FlowMetrics (both given
     NumPy arrays; what predict returns is handed to metrics as it is).  on_group(entries, FlowMetrics) sees every group (the epe maps).
+    With occ_present, metrics gets a fifth argument: per sample, whether its ground truth came with an occlusion mask (where some do and
+    some do not, `occ` is 0 for those that do not).
     Returns gather()'s result: all samples in list order on rank 0, None on the other ranks."""
     from . import parallel
     mine = parallel.shard([e + (i,) for i, e in enumerate(entries)])
@@ -356,11 +476,11 @@ def evaluate(entries, groups_of, read_image, predict, metrics, batch=8, prefetch
                 if g[0].shape[1:] != hw or tuple(i0.shape[2:]) != tuple(hw):
                     raise ValueError(f"{e[2]}: ground truth {g[0].shape[1:]} does not match the images {tuple(i0.shape[2:])}")
             yield (ents, i0, i1, np.stack([g[0] for g in gts]), _stack([g[1] for g in gts], (1,) + hw, 1.0),
-                   _stack([g[2] for g in gts], (1,) + hw, 0.0))
+                   _stack([g[2] for g in gts], (1,) + hw, 0.0), [g[2] is not None for g in gts])
 
     parts = []
-    for ents, i0, i1, gt, valid, occ in prefetched(staged(), prefetch):
-        m = metrics(predict(i0, i1), gt, valid, occ)
+    for ents, i0, i1, gt, valid, occ, has_occ in prefetched(staged(), prefetch):
+        m = metrics(predict(i0, i1), gt, valid, occ, has_occ) if occ_present else metrics(predict(i0, i1), gt, valid, occ)
         if len(m) != len(ents):
             raise RuntimeError(f"evaluate: {len(m)} rows for {len(ents)} samples")
         if on_group is not None:

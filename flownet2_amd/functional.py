@@ -456,6 +456,22 @@ def flow_metrics(pred, gt, valid=None, occ=None, *, outlier=(3.0, 0.05), bands=(
     return FlowMetrics(results[:-1].cpu().numpy(), epe_map=emap)
 
 
+def flow_consistency(fw, bw, *, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=False, err=False, warped=False):
+    """Forward-backward consistency of two flows [N,2,H,W], fw from frame 0 to frame 1 and bw back (csrc/flow_consistency.hip; the
+    arithmetic is stated in include/flownet2_hip_flow_consistency.h): a pixel is occluded where its target lies outside the image, where
+    the other flow sampled at its target does not cancel its own (|a + b|^2 > alpha[0] (|a|^2 + |b|^2) + alpha[1]) or where a value is not
+    finite; it lies on a motion boundary where |grad u|^2 + |grad v|^2 > beta[0] |a|^2 + beta[1].  Both directions in one launch.  Returns
+    an evaluate.FlowConsistency: .occ_fw / .occ_bw [N,1,H,W] float planes of 0 / 1 (what flow_metrics takes as `occ`), the rows per
+    direction (summary() gives the fractions), and where asked for the uint8 flag maps, the err maps |a + b| (NaN where there is none) and
+    the other flow warped to the pixel.  Not differentiable: a check, not a loss."""
+    from .evaluate import FlowConsistency
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (fw, bw)):
+        raise RuntimeError("flow_consistency is not differentiable: detach the inputs or call it under torch.no_grad()")
+    results, occ, fl, er, wa = ops.flow_consistency(fw, bw, alpha=alpha, beta=beta, flags=flags, err=err, warped=warped)
+    rows = results[:, :-1].cpu().numpy()
+    return FlowConsistency(rows[0], rows[1], occ=occ, flags=fl, err=er, warped=wa, alpha=alpha, beta=beta)
+
+
 def add_loss_flags(ap):
     """--loss l1 | lpq and the Lpq schedule of a training script (scripts/train_pipeline.py, scripts/train_prototxt_step.py)."""
     ap.add_argument("--loss", choices=("l1", "lpq"), default="l1", help="l1: L1Loss{l2_per_location} (the default); lpq: LpqLoss with --lpq-p / --lpq-q")

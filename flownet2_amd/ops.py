@@ -469,6 +469,37 @@ def flow_metrics(pred, gt, valid=None, occ=None, outlier=(3.0, 0.05), bands=(10.
     return results, emap
 
 
+_FLOW_CONSISTENCY_K = _lib.FLOW_CONSISTENCY_CONSTANTS["FN2_FLOW_CONSISTENCY_K"]      # columns of a results row (evaluate.CONSISTENCY_COLUMNS)
+
+
+def flow_consistency_sizes(N: int, H: int, W: int):
+    """(workspace bytes for [N,2,H,W], K) of fn2_flow_consistency (include/flownet2_hip_flow_consistency.h)."""
+    nbytes, k = C.c_size_t(), C.c_int()
+    check(_lib.lib().fn2_flow_consistency_sizes(int(N), int(H), int(W), C.byref(nbytes), C.byref(k)))
+    return nbytes.value, k.value
+
+
+def flow_consistency(fw, bw, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=False, err=False, warped=False):
+    """Forward-backward consistency (csrc/flow_consistency.hip) of fw (frame 0 -> 1) and bw (frame 1 -> 0), both [N,2,H,W].  Returns
+    (results [2, N + 1, K] float64 on the device: per direction one row per sample and the totals row, columns
+    evaluate.CONSISTENCY_COLUMNS; occ, flags, err, warped: each a (forward, backward) pair of maps, or None where not asked for)."""
+    f, b = _chk(fw, "fw"), _chk(bw, "bw")
+    if f.shape != b.shape or f.shape[1] != 2:
+        raise ValueError(f"flow_consistency: fw {tuple(f.shape)} and bw {tuple(b.shape)} must both be [N,2,H,W]")
+    if f.device != b.device:
+        raise ValueError(f"flow_consistency: fw on {f.device}, bw on {b.device}")
+    N, _, H, W = f.shape
+    ws = torch.empty(flow_consistency_sizes(N, H, W)[0], dtype=torch.uint8, device=f.device)
+    results = torch.empty((2, N + 1, _FLOW_CONSISTENCY_K), dtype=torch.float64, device=f.device)
+    pair = lambda want, ch, dtype: tuple(torch.empty((N, ch, H, W), dtype=dtype, device=f.device) for _ in range(2)) if want else None
+    occ, fl, er, wa = pair(True, 1, torch.float32), pair(flags, 1, torch.uint8), pair(err, 1, torch.float32), pair(warped, 2, torch.float32)
+    two = lambda p: (_ptr(p[0]), _ptr(p[1])) if p is not None else (_ptr(None), _ptr(None))
+    check(_lib.lib().fn2_flow_consistency(_ptr(f), _ptr(b), N, H, W, C.c_float(float(alpha[0])), C.c_float(float(alpha[1])),
+                                          C.c_float(float(beta[0])), C.c_float(float(beta[1])), _ptr(results), *two(fl), *two(occ), *two(er),
+                                          *two(wa), _ptr(ws), ws.numel(), _stream()))
+    return results, occ, fl, er, wa
+
+
 def channel_norm_forward(x):
     x = _chk(x, "bottom[0]")
     N, Cc, H, W = x.shape

@@ -15,6 +15,9 @@ run_flownet_many.py's grouping into batches of equal image size and its sharding
 ahead of the GPU on a thread).  The kernel compares that prediction with the ground truth; each rank scores its shard, the rows are
 gathered over gloo, rank 0 merges them in list order and prints one summary (strict JSON: a mean over no pixel is null).  --json OUT holds
 the summary and the per-sample rows: in the default batch-invariant mode the file has the same bytes for any --batch and any number of processes.
+--occ-from-consistency: for list lines that bring no occlusion mask, the net also runs backwards, (img1, img0), in the same step, and the
+forward-backward check (functional.flow_consistency, thresholds --alpha) gives the `occ` plane, so the matched / unmatched split exists for
+such data too (FlyingChairs, KITTI without its noc maps); the JSON then records "occ_source": "consistency" and the thresholds.
 Exits with status 1 when a valid pixel had a NaN or Inf prediction (they are in no sum), unless --allow-nonfinite."""
 import argparse
 import json
@@ -52,6 +55,8 @@ def main():
     ap.add_argument("--bands", type=float, nargs=2, default=[10.0, 40.0], metavar=("B0", "B1"), help="edges of the three |gt| bands")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the summary and the per-sample rows")
     ap.add_argument("--epe-maps", default=None, metavar="DIR", help="write every pair's EPE map as DIR/<list index>.npy")
+    ap.add_argument("--occ-from-consistency", action="store_true", help="lines without an occlusion mask: occ from the forward-backward check")
+    ap.add_argument("--alpha", type=float, nargs=2, default=[0.01, 0.5], metavar=("A1", "A2"), help="inconsistent: |a+b|^2 > A1 (|a|^2+|b|^2) + A2")
     ap.add_argument("--allow-nonfinite", action="store_true")
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection depend on the batch size (see run_flownet_many.py)")
     ap.add_argument("--gpu", type=int, default=None, help="device index (default: LOCAL_RANK)")
@@ -88,9 +93,21 @@ def main():
         P, mean = RF.load_params(a.net, a.weights, dev)
         predict = lambda i0, i1: RF.infer(a.net, P, up(i0), up(i1), mean)
 
-    def metrics(pred, gt, valid, occ):
+    if a.occ_from_consistency:
+        one_way = predict
+        predict = lambda i0, i1: one_way(np.concatenate([i0, i1]), np.concatenate([i1, i0]))      # rows 0 .. n-1 forward, n .. 2n-1 backward
+
+    def metrics(pred, gt, valid, occ, has_occ=None):
         with torch.no_grad():
-            return Fn.flow_metrics(pred, up(gt), up(valid), up(occ), outlier=tuple(a.outlier), bands=tuple(a.bands), epe_map=bool(a.epe_maps))
+            occ = up(occ)
+            if a.occ_from_consistency:
+                n = pred.shape[0] // 2
+                pred, back = pred[:n].contiguous(), pred[n:].contiguous()
+                if not all(has_occ):
+                    found = Fn.flow_consistency(pred, back, alpha=tuple(a.alpha)).occ_fw
+                    given = torch.tensor(has_occ, device=dev).view(n, 1, 1, 1)
+                    occ = found if occ is None else torch.where(given, occ, found)
+            return Fn.flow_metrics(pred, up(gt), up(valid), occ, outlier=tuple(a.outlier), bands=tuple(a.bands), epe_map=bool(a.epe_maps))
 
     def save_maps(ents, m):
         maps = m.epe_map.cpu().numpy()
@@ -98,13 +115,13 @@ def main():
             np.save(os.path.join(a.epe_maps, "%06d.npy" % e[4]), maps[k, 0])
 
     result = evaluate.evaluate(entries, RM.groups_of, RF.read_image, predict, metrics, batch=a.batch, prefetch=a.prefetch, mask_as=a.mask,
-                               on_group=save_maps if a.epe_maps else None)
+                               on_group=save_maps if a.epe_maps else None, occ_present=a.occ_from_consistency)
     status = 0
     if parallel.rank() == 0:
         s = result.summary()
         if a.json:
             with open(a.json, "w") as f:
-                f.write(result.to_json())
+                f.write(result.to_json({"occ_source": "consistency", "alpha": list(a.alpha)} if a.occ_from_consistency else None))
         print(json.dumps(evaluate.json_ready(s), allow_nan=False))
         status = evaluate.exit_status(s, a.allow_nonfinite)
         if status:

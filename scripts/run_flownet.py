@@ -14,8 +14,13 @@ Same behaviour as the reference script: images are read as RGB, fed as BGR raw 0
 ADAPTED (x64) size and the flow is resampled / rescaled back to the TARGET size, and the result is written as .flo.
 Differences: no prototxt template / .caffemodel (neither is in the reference tree; the graph is flownet2_amd/nets.py,
 weights are a .caffemodel / .caffemodel.h5 read by flownet2_amd.caffemodel, a name->array .npz in Caffe blob layout, or seeded random), and no "retry up to 5x on NaN" loop -- the
-reference needs it for a race in its kernels (run-flownet.py:72-96); these kernels are deterministic."""
+reference needs it for a race in its kernels (run-flownet.py:72-96); these kernels are deterministic.
+
+`--backward OUT_BW.flo` (either form) also runs (img1, img0) and writes that flow -- the bytes of a plain run on the swapped pair; with
+`--occlusion OUT.pgm` the forward-backward check of the two flows (functional.flow_consistency) is written as an 8-bit binary PGM, 255
+where the forward flow's pixel is occluded.  `out` keeps the bytes it has without these flags."""
 import argparse
+import json
 import os
 import sys
 
@@ -96,7 +101,7 @@ ARITH = ("conv", "deconv", "wino", "corr")          # the switches of functional
 
 def _positionals(argv):
     """Positional arguments of either form: the values of the value-taking options are not positionals."""
-    takes_value = {"--gpu", "--weights", "--net", "--general-conv", *Fn.arithmetic_flags(ARITH)}
+    takes_value = {"--gpu", "--weights", "--net", "--general-conv", "--backward", "--occlusion", *Fn.arithmetic_flags(ARITH)}
     out, skip = [], False
     for a in argv:
         if skip:
@@ -106,6 +111,28 @@ def _positionals(argv):
         elif not a.startswith("-"):
             out.append(a)
     return out
+
+
+def add_backward_flags(ap):
+    ap.add_argument("--backward", default=None, metavar="OUT_BW.flo", help="also run (img1, img0) and write that flow")
+    ap.add_argument("--occlusion", default=None, metavar="OUT.pgm", help="with --backward: the forward flow's occlusion mask (255 = occluded)")
+
+
+def write_backward(a, flow, infer_swapped):
+    """--backward / --occlusion: flow is the forward result [1,2,H,W]; infer_swapped() runs the same net on (img1, img0)."""
+    if a.occlusion and not a.backward:
+        raise SystemExit("--occlusion needs --backward")
+    if not a.backward:
+        return
+    from flownet2_amd import evaluate
+    bw = infer_swapped()
+    flo.write_flo(a.backward, bw[0].cpu().numpy())
+    print("wrote", a.backward, tuple(bw.shape[2:]))
+    if a.occlusion:
+        with torch.no_grad():
+            c = Fn.flow_consistency(flow.detach().contiguous(), bw.detach().contiguous())
+        evaluate.write_pgm(a.occlusion, c.occ_fw[0, 0].cpu().numpy())
+        print("wrote", a.occlusion, json.dumps(evaluate.json_ready(c.summary()["fw"])))
 
 
 def main():
@@ -122,6 +149,7 @@ def main():
         ap.add_argument("--no-batch-invariant", action="store_true")
         Fn.add_arithmetic_flags(ap, ARITH)
         Fn.add_general_convolution_flag(ap)
+        add_backward_flags(ap)
         a = ap.parse_args()
         if not a.caffemodel.startswith("seed:") and not os.path.exists(a.caffemodel):
             raise SystemExit("caffemodel does not exist: " + a.caffemodel)                   # run-flownet.py:20
@@ -139,6 +167,7 @@ def main():
         flow = infer_prototxt(a.caffemodel, a.deployproto, i0, i1, dev)
         flo.write_flo(a.out, flow[0].cpu().numpy())
         print("wrote", a.out, tuple(flow.shape[2:]))
+        write_backward(a, flow, lambda: infer_prototxt(a.caffemodel, a.deployproto, i1, i0, dev))
         return
     ap = argparse.ArgumentParser()
     ap.add_argument("img0"); ap.add_argument("img1"); ap.add_argument("out")
@@ -148,6 +177,7 @@ def main():
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection follow the work size (see run_flownet_many.py)")
     Fn.add_arithmetic_flags(ap, ARITH)
     Fn.add_general_convolution_flag(ap)
+    add_backward_flags(ap)
     a = ap.parse_args()
     for f in (a.img0, a.img1):
         if not os.path.exists(f):
@@ -162,6 +192,7 @@ def main():
     flow = infer(a.net, P, i0, i1, mean)
     flo.write_flo(a.out, flow[0].cpu().numpy())                                         # predict_flow_final -> (H,W,2)
     print("wrote", a.out, tuple(flow.shape[2:]))
+    write_backward(a, flow, lambda: infer(a.net, P, i1, i0, mean))
 
 
 if __name__ == "__main__":

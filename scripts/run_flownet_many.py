@@ -15,6 +15,11 @@ entry (:77-81 inside the loop at :38); here each rank builds the net once, takes
   thread that stays `--prefetch` groups ahead of the GPU and hands over pinned staging buffers (asynchronous H2D copies);
   the .flo files are written by a second thread, so decode, compute and encode of consecutive groups overlap.
 * The process group (only a final barrier -- the data path has no exchange) uses gloo: ranks may even share one GPU.
+* `--bidirectional`: every pair also runs backwards, (img1, img0), in the same step, and the two flows are checked against each other
+  (functional.flow_consistency, one launch).  Beside out.flo the script then writes out.bw.flo (the bytes of a plain run on the swapped
+  line), out.occ.pgm and out.bw.occ.pgm (8-bit binary PGM, 255 = occluded, in frame 0 and in frame 1); `--consistency-json PATH` holds
+  the per-line summaries, with the same bytes for any --batch and any number of processes.  out.flo keeps the bytes it has without
+  the flag (batch-invariant mode).
 """
 import argparse
 import os
@@ -29,7 +34,7 @@ import torch.distributed as dist
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from flownet2_amd import flo, parallel  # noqa: E402
+from flownet2_amd import evaluate, flo, parallel  # noqa: E402
 from flownet2_amd import functional as Fn  # noqa: E402
 import run_flownet as RF  # noqa: E402
 
@@ -69,9 +74,15 @@ def main():
     ap.add_argument("--no-batch-invariant", action="store_true", help="let kernel selection depend on the batch size (faster library "
                     "calls; a pair's bits then depend on the batch it was computed in)")
     ap.add_argument("--gpu", type=int, default=None, help="device index (default: LOCAL_RANK)")
+    ap.add_argument("--bidirectional", action="store_true", help="also run (img1, img0); write out.bw.flo, out.occ.pgm and out.bw.occ.pgm")
+    ap.add_argument("--consistency-json", default=None, metavar="PATH", help="with --bidirectional: the per-line consistency summaries")
+    ap.add_argument("--alpha", type=float, nargs=2, default=[0.01, 0.5], metavar=("A1", "A2"), help="inconsistent: |a+b|^2 > A1 (|a|^2+|b|^2) + A2")
+    ap.add_argument("--beta", type=float, nargs=2, default=[0.01, 0.002], metavar=("B1", "B2"), help="motion boundary: |grad|^2 > B1 |a|^2 + B2")
     Fn.add_arithmetic_flags(ap, ARITH)
     Fn.add_general_convolution_flag(ap)
     a = ap.parse_args()
+    if a.consistency_json and not a.bidirectional:
+        ap.error("--consistency-json needs --bidirectional")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -82,7 +93,8 @@ def main():
     Fn.apply_arithmetic_flags(a, ARITH)
     Fn.apply_general_convolution_flag(a)
     entries = [l.split() for l in open(a.listfile) if l.strip()]
-    mine = parallel.shard(entries)
+    mine = parallel.shard([e + [i] for i, e in enumerate(entries)])      # the list index travels with the entry (the JSON is in list order)
+    parts = []                                                            # --bidirectional: (list indices, FlowConsistency) per group
     P, mean = RF.load_params(a.net, a.weights, dev)
 
     staged = queue.Queue(maxsize=max(1, a.prefetch))
@@ -104,11 +116,17 @@ def main():
                 item = done.get()
                 if item is None:
                     return
-                ents, flow, ev = item
+                ents, flow, occ, ev = item
                 ev.synchronize()
                 arr = flow.numpy()
+                n = len(ents)
                 for k, e in enumerate(ents):
                     flo.write_flo(e[2], arr[k])
+                    if occ is not None:
+                        bw_name, occ_name, bw_occ_name = evaluate.bidirectional_names(e[2])
+                        flo.write_flo(bw_name, arr[n + k])
+                        evaluate.write_pgm(occ_name, occ[k, 0].numpy())
+                        evaluate.write_pgm(bw_occ_name, occ[n + k, 0].numpy())
         except BaseException as e:      # noqa: BLE001
             errors.append(e)
 
@@ -120,17 +138,33 @@ def main():
             break
         ents, h0, h1 = item
         i0, i1 = h0.to(dev, non_blocking=True), h1.to(dev, non_blocking=True)
-        flow = RF.infer(a.net, P, i0, i1, mean)
+        occ_host = None
+        if a.bidirectional:
+            n = i0.shape[0]
+            flow = RF.infer(a.net, P, torch.cat([i0, i1]), torch.cat([i1, i0]), mean)      # rows 0 .. n-1 forward, n .. 2n-1 backward
+            with torch.no_grad():
+                c = Fn.flow_consistency(flow[:n], flow[n:], alpha=tuple(a.alpha), beta=tuple(a.beta))
+            occ = torch.cat([c.occ_fw, c.occ_bw])
+            occ_host = torch.empty(occ.shape, dtype=occ.dtype, pin_memory=True)
+            occ_host.copy_(occ, non_blocking=True)
+            parts.append(([e[-1] for e in ents], c))
+        else:
+            flow = RF.infer(a.net, P, i0, i1, mean)
         host = torch.empty(flow.shape, dtype=flow.dtype, pin_memory=True)
         host.copy_(flow, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        done.put((ents, host, ev))
+        done.put((ents, host, occ_host, ev))
     done.put(None)
     tw.join(); tp.join()
     if errors:
         raise errors[0]
     my_rank = parallel.rank()
+    if a.consistency_json:
+        result = evaluate.gather_consistency(len(entries), parts, alpha=a.alpha, beta=a.beta)
+        if my_rank == 0:
+            with open(a.consistency_json, "w") as f:
+                f.write(result.to_json())
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
