@@ -8,12 +8,13 @@ solver     SolverParameter, Solver (SGDSolver / AdamSolver, get_solver) and Caff
 LpqSchedule  the p / q episodes of LpqLoss (lpq_schedule.py)
 evaluate   FlowMetrics (the rows of the metrics kernel, summary()), ground-truth readers incl. the KITTI flow PNG, the data-set loop
 flow_consistency  forward-backward consistency of two flows -> FlowConsistency (occlusion masks, rows, summary()) in one launch
+visualize  flow_to_color (Middlebury colour coding) and flow_error_map (KITTI-style error image) on fused kernels, color_wheel, write_png
 """
 from . import _lib  # noqa: F401
 from ._lib import Fn2Error, version  # noqa: F401
 
 _SOLVER_EXPORTS = ("SolverParameter", "Solver", "SGDSolver", "AdamSolver", "get_solver", "CaffeOptimizer")
-__all__ = ["Fn2Error", "version", "LpqSchedule", "flow_consistency", "FlowConsistency", *_SOLVER_EXPORTS]
+__all__ = ["Fn2Error", "version", "LpqSchedule", "flow_consistency", "FlowConsistency", "flow_to_color", "flow_error_map", *_SOLVER_EXPORTS]
 
 
 def __getattr__(name):
@@ -27,6 +28,9 @@ def __getattr__(name):
     if name == "flow_consistency":
         from .functional import flow_consistency
         return flow_consistency
+    if name in ("flow_to_color", "flow_error_map"):
+        from . import functional
+        return getattr(functional, name)
     if name == "FlowConsistency":
         from .evaluate import FlowConsistency
         return FlowConsistency

@@ -472,6 +472,32 @@ def flow_consistency(fw, bw, *, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=Fal
     return FlowConsistency(rows[0], rows[1], occ=occ, flags=fl, err=er, warped=wa, alpha=alpha, beta=beta)
 
 
+def _no_grad_inputs(what, tensors):
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{what} is not differentiable: detach the inputs or call it under torch.no_grad()")
+
+
+def flow_to_color(flow, max_flow=None, norm="sample"):
+    """The Middlebury colour coding of a flow [N,2,H,W] as uint8 [N,H,W,3] on the device (csrc/flow_visualize.hip; the arithmetic is stated
+    in include/flownet2_hip_flow_visualize.h): hue from the direction, saturation from the radius over a normalising radius, unknown flow
+    (a value above 1e9, NaN, Inf) black.  With max_flow the radius is divided by it, so pictures of different runs compare (a pixel beyond
+    it is drawn at three quarters of its hue's brightness); without, by the largest radius of the sample (norm="sample": a sample's picture
+    is the same alone and in any batch) or of the whole batch (norm="batch").  No host readback.  Not differentiable: a picture."""
+    _no_grad_inputs("flow_to_color", (flow,))
+    if norm not in ("sample", "batch"):
+        raise ValueError(f"flow_to_color: norm must be 'sample' or 'batch', got {norm!r}")
+    return ops.flow_color(flow, norm="fixed" if max_flow is not None else norm, max_flow=max_flow)[0]
+
+
+def flow_error_map(pred, gt, valid=None, occ=None, abs_thresh=3.0, rel_thresh=0.05):
+    """The KITTI-style error image of a predicted flow against ground truth, both [N,2,H,W], as uint8 [N,H,W,3] on the device
+    (csrc/flow_visualize.hip): the colour of the bin of n = min(EPE / abs_thresh, EPE / |gt| / rel_thresh), blue below 1 and red above -- 1
+    is the Fl outlier criterion of flow_metrics --, black where there is no ground truth (gt unknown, or valid [N,1,H,W] zero), dimmed to
+    half where occ [N,1,H,W] is non-zero (flow_consistency(...).occ_fw goes in as it is).  Not differentiable: a picture."""
+    _no_grad_inputs("flow_error_map", (pred, gt, valid, occ))
+    return ops.flow_error_map(pred, gt, valid, occ, abs_thresh=abs_thresh, rel_thresh=rel_thresh)
+
+
 def add_loss_flags(ap):
     """--loss l1 | lpq and the Lpq schedule of a training script (scripts/train_pipeline.py, scripts/train_prototxt_step.py)."""
     ap.add_argument("--loss", choices=("l1", "lpq"), default="l1", help="l1: L1Loss{l2_per_location} (the default); lpq: LpqLoss with --lpq-p / --lpq-q")

@@ -500,6 +500,55 @@ def flow_consistency(fw, bw, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=False,
     return results, occ, fl, er, wa
 
 
+_FLOW_COLOR_NORMS = {n[len("FN2_FLOW_COLOR_NORM_"):].lower(): v for n, v in _lib.FLOW_VISUALIZE_CONSTANTS.items()}      # sample, batch, fixed
+
+
+def flow_visualize_sizes(N: int, H: int, W: int):
+    """Workspace bytes of fn2_flow_color for [N,2,H,W] (include/flownet2_hip_flow_visualize.h)."""
+    nbytes = C.c_size_t()
+    check(_lib.lib().fn2_flow_visualize_sizes(int(N), int(H), int(W), C.byref(nbytes)))
+    return nbytes.value
+
+
+def flow_color(flow, norm="sample", max_flow=None, maxrad=False):
+    """Middlebury colour coding (csrc/flow_visualize.hip) of flow [N,2,H,W] -> (uint8 [N,H,W,3] on the device; the float [N] of the
+    radius each sample was normalised by, or None).  norm: sample | batch | fixed, the last with max_flow > 0."""
+    f = _chk(flow, "flow")
+    if f.shape[1] != 2:
+        raise ValueError(f"flow_color: flow {tuple(f.shape)} must be [N,2,H,W]")
+    if norm not in _FLOW_COLOR_NORMS:
+        raise ValueError(f"flow_color: norm must be one of {sorted(_FLOW_COLOR_NORMS)}, got {norm!r}")
+    fixed = norm == "fixed"
+    if fixed and max_flow is None:
+        raise ValueError("flow_color: norm='fixed' needs max_flow")
+    N, _, H, W = f.shape
+    ws = None if fixed else torch.empty(flow_visualize_sizes(N, H, W), dtype=torch.uint8, device=f.device)
+    rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device=f.device)
+    used = torch.empty((N,), dtype=torch.float32, device=f.device) if maxrad else None
+    check(_lib.lib().fn2_flow_color(_ptr(f), N, H, W, _FLOW_COLOR_NORMS[norm], C.c_float(float(max_flow) if fixed else 0.0), _ptr(rgb), _ptr(used),
+                                    _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
+    return rgb, used
+
+
+def flow_error_map(pred, gt, valid=None, occ=None, abs_thresh=3.0, rel_thresh=0.05):
+    """KITTI-style error image (csrc/flow_visualize.hip) of pred against gt [N,2,H,W]; valid / occ [N,1,H,W] or None -> uint8 [N,H,W,3]
+    on the device."""
+    p, g = _chk(pred, "pred"), _chk(gt, "gt")
+    if p.shape != g.shape or p.shape[1] != 2:
+        raise ValueError(f"flow_error_map: pred {tuple(p.shape)} and gt {tuple(g.shape)} must both be [N,2,H,W]")
+    if p.device != g.device:
+        raise ValueError(f"flow_error_map: pred on {p.device}, gt on {g.device}")
+    N, _, H, W = p.shape
+    v, o = _chk_opt(valid, "valid"), _chk_opt(occ, "occ")
+    for name, m in (("valid", v), ("occ", o)):
+        if m is not None and tuple(m.shape) != (N, 1, H, W):
+            raise ValueError(f"flow_error_map: {name} {tuple(m.shape)} must be [{N},1,{H},{W}]")
+    rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device=p.device)
+    check(_lib.lib().fn2_flow_error_map(_ptr(p), _ptr(g), _ptr(v), _ptr(o), N, H, W, C.c_float(float(abs_thresh)), C.c_float(float(rel_thresh)),
+                                        _ptr(rgb), _stream()))
+    return rgb
+
+
 def channel_norm_forward(x):
     x = _chk(x, "bottom[0]")
     N, Cc, H, W = x.shape

@@ -18,6 +18,10 @@ the summary and the per-sample rows: in the default batch-invariant mode the fil
 --occ-from-consistency: for list lines that bring no occlusion mask, the net also runs backwards, (img1, img0), in the same step, and the
 forward-backward check (functional.flow_consistency, thresholds --alpha) gives the `occ` plane, so the matched / unmatched split exists for
 such data too (FlyingChairs, KITTI without its noc maps); the JSON then records "occ_source": "consistency" and the thresholds.
+--error-maps DIR writes every pair's KITTI-style error image (functional.flow_error_map with --outlier's thresholds: blue below the Fl
+criterion, red above, black without ground truth, dimmed to half where the pair's occlusion mask -- the data's, or with
+--occ-from-consistency the check's -- is set) as DIR/<list index>.png; --color-maps DIR the colour-coded prediction, normalised per pair
+or with --color-max F by F.  Neither changes a byte of the JSON.
 Exits with status 1 when a valid pixel had a NaN or Inf prediction (they are in no sum), unless --allow-nonfinite."""
 import argparse
 import json
@@ -55,6 +59,10 @@ def main():
     ap.add_argument("--bands", type=float, nargs=2, default=[10.0, 40.0], metavar=("B0", "B1"), help="edges of the three |gt| bands")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the summary and the per-sample rows")
     ap.add_argument("--epe-maps", default=None, metavar="DIR", help="write every pair's EPE map as DIR/<list index>.npy")
+    ap.add_argument("--error-maps", default=None, metavar="DIR", help="write every pair's error image as DIR/<list index>.png")
+    ap.add_argument("--color-maps", default=None, metavar="DIR", help="write every pair's colour-coded prediction as DIR/<list index>.png")
+    ap.add_argument("--color-max", type=float, default=None, metavar="F", help="with --color-maps: the radius drawn at full saturation "
+                    "(default: each prediction's own largest radius)")
     ap.add_argument("--occ-from-consistency", action="store_true", help="lines without an occlusion mask: occ from the forward-backward check")
     ap.add_argument("--alpha", type=float, nargs=2, default=[0.01, 0.5], metavar=("A1", "A2"), help="inconsistent: |a+b|^2 > A1 (|a|^2+|b|^2) + A2")
     ap.add_argument("--allow-nonfinite", action="store_true")
@@ -83,8 +91,11 @@ def main():
         for path in e:
             if path is not None and not os.path.exists(path):
                 raise SystemExit("file does not exist: " + path)
-    if a.epe_maps:
-        os.makedirs(a.epe_maps, exist_ok=True)
+    if a.color_max is not None and not a.color_maps:
+        raise SystemExit("--color-max needs --color-maps")
+    for d in (a.epe_maps, a.error_maps, a.color_maps):
+        if d:
+            os.makedirs(d, exist_ok=True)
 
     up = lambda x: None if x is None else torch.from_numpy(x).to(dev, non_blocking=True)
     if proto:
@@ -107,15 +118,29 @@ def main():
                     found = Fn.flow_consistency(pred, back, alpha=tuple(a.alpha)).occ_fw
                     given = torch.tensor(has_occ, device=dev).view(n, 1, 1, 1)
                     occ = found if occ is None else torch.where(given, occ, found)
-            return Fn.flow_metrics(pred, up(gt), up(valid), occ, outlier=tuple(a.outlier), bands=tuple(a.bands), epe_map=bool(a.epe_maps))
+            gt, valid = up(gt), up(valid)
+            m = Fn.flow_metrics(pred, gt, valid, occ, outlier=tuple(a.outlier), bands=tuple(a.bands), epe_map=bool(a.epe_maps))
+            # the pictures of this group, for save_maps
+            m.error_rgb = Fn.flow_error_map(pred, gt, valid, occ, abs_thresh=a.outlier[0], rel_thresh=a.outlier[1]) if a.error_maps else None
+            m.color_rgb = Fn.flow_to_color(pred.contiguous(), max_flow=a.color_max) if a.color_maps else None
+            return m
 
     def save_maps(ents, m):
+        from flownet2_amd import visualize
+        for directory, rgb in ((a.error_maps, m.error_rgb), (a.color_maps, m.color_rgb)):
+            if directory:
+                rgb = rgb.cpu().numpy()
+                for k, e in enumerate(ents):
+                    visualize.write_png(os.path.join(directory, "%06d.png" % e[4]), rgb[k])
+        m.error_rgb = m.color_rgb = None                        # written: the rows stay until the gather, the pictures need not
+        if not a.epe_maps:
+            return
         maps = m.epe_map.cpu().numpy()
         for k, e in enumerate(ents):
             np.save(os.path.join(a.epe_maps, "%06d.npy" % e[4]), maps[k, 0])
 
     result = evaluate.evaluate(entries, RM.groups_of, RF.read_image, predict, metrics, batch=a.batch, prefetch=a.prefetch, mask_as=a.mask,
-                               on_group=save_maps if a.epe_maps else None, occ_present=a.occ_from_consistency)
+                               on_group=save_maps if (a.epe_maps or a.error_maps or a.color_maps) else None, occ_present=a.occ_from_consistency)
     status = 0
     if parallel.rank() == 0:
         s = result.summary()

@@ -18,7 +18,9 @@ reference needs it for a race in its kernels (run-flownet.py:72-96); these kerne
 
 `--backward OUT_BW.flo` (either form) also runs (img1, img0) and writes that flow -- the bytes of a plain run on the swapped pair; with
 `--occlusion OUT.pgm` the forward-backward check of the two flows (functional.flow_consistency) is written as an 8-bit binary PGM, 255
-where the forward flow's pixel is occluded.  `out` keeps the bytes it has without these flags."""
+where the forward flow's pixel is occluded.  `--color OUT.png` (either form) writes the Middlebury colour coding of the flow
+(functional.flow_to_color, on the device) as an 8-bit PNG: normalised by the flow's own largest radius, or with `--color-max F` by F, so
+that pictures of different pairs compare.  `out` keeps the bytes it has without these flags."""
 import argparse
 import json
 import os
@@ -101,7 +103,7 @@ ARITH = ("conv", "deconv", "wino", "corr")          # the switches of functional
 
 def _positionals(argv):
     """Positional arguments of either form: the values of the value-taking options are not positionals."""
-    takes_value = {"--gpu", "--weights", "--net", "--general-conv", "--backward", "--occlusion", *Fn.arithmetic_flags(ARITH)}
+    takes_value = {"--gpu", "--weights", "--net", "--general-conv", "--backward", "--occlusion", "--color", "--color-max", *Fn.arithmetic_flags(ARITH)}
     out, skip = [], False
     for a in argv:
         if skip:
@@ -116,6 +118,25 @@ def _positionals(argv):
 def add_backward_flags(ap):
     ap.add_argument("--backward", default=None, metavar="OUT_BW.flo", help="also run (img1, img0) and write that flow")
     ap.add_argument("--occlusion", default=None, metavar="OUT.pgm", help="with --backward: the forward flow's occlusion mask (255 = occluded)")
+
+
+def add_color_flags(ap):
+    ap.add_argument("--color", default=None, metavar="OUT.png", help="also write the flow's Middlebury colour coding as an 8-bit PNG")
+    ap.add_argument("--color-max", type=float, default=None, metavar="F", help="with --color: the radius drawn at full saturation "
+                    "(default: the flow's own largest radius)")
+
+
+def write_color(a, flow):
+    """--color / --color-max: flow is the forward result [1,2,H,W] on the device."""
+    if a.color_max is not None and not a.color:
+        raise SystemExit("--color-max needs --color")
+    if not a.color:
+        return
+    from flownet2_amd import visualize
+    with torch.no_grad():
+        rgb = Fn.flow_to_color(flow.detach().contiguous(), max_flow=a.color_max)
+    visualize.write_png(a.color, rgb[0])
+    print("wrote", a.color, tuple(rgb.shape[1:3]))
 
 
 def write_backward(a, flow, infer_swapped):
@@ -150,6 +171,7 @@ def main():
         Fn.add_arithmetic_flags(ap, ARITH)
         Fn.add_general_convolution_flag(ap)
         add_backward_flags(ap)
+        add_color_flags(ap)
         a = ap.parse_args()
         if not a.caffemodel.startswith("seed:") and not os.path.exists(a.caffemodel):
             raise SystemExit("caffemodel does not exist: " + a.caffemodel)                   # run-flownet.py:20
@@ -167,6 +189,7 @@ def main():
         flow = infer_prototxt(a.caffemodel, a.deployproto, i0, i1, dev)
         flo.write_flo(a.out, flow[0].cpu().numpy())
         print("wrote", a.out, tuple(flow.shape[2:]))
+        write_color(a, flow)
         write_backward(a, flow, lambda: infer_prototxt(a.caffemodel, a.deployproto, i1, i0, dev))
         return
     ap = argparse.ArgumentParser()
@@ -178,6 +201,7 @@ def main():
     Fn.add_arithmetic_flags(ap, ARITH)
     Fn.add_general_convolution_flag(ap)
     add_backward_flags(ap)
+    add_color_flags(ap)
     a = ap.parse_args()
     for f in (a.img0, a.img1):
         if not os.path.exists(f):
@@ -192,6 +216,7 @@ def main():
     flow = infer(a.net, P, i0, i1, mean)
     flo.write_flo(a.out, flow[0].cpu().numpy())                                         # predict_flow_final -> (H,W,2)
     print("wrote", a.out, tuple(flow.shape[2:]))
+    write_color(a, flow)
     write_backward(a, flow, lambda: infer(a.net, P, i1, i0, mean))
 
 

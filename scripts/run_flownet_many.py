@@ -20,6 +20,11 @@ entry (:77-81 inside the loop at :38); here each rank builds the net once, takes
   line), out.occ.pgm and out.bw.occ.pgm (8-bit binary PGM, 255 = occluded, in frame 0 and in frame 1); `--consistency-json PATH` holds
   the per-line summaries, with the same bytes for any --batch and any number of processes.  out.flo keeps the bytes it has without
   the flag (batch-invariant mode).
+* `--color`: beside out.flo the script writes out.png, the Middlebury colour coding of the flow (functional.flow_to_color, on the device;
+  with --bidirectional also out.bw.png).  Without `--color-max F` every picture is normalised by its own flow's largest radius, so a
+  pair's picture does not depend on --batch or on the number of processes; with it, by F, and pictures compare.  `--color-norm batch`
+  (the largest radius of the group a pair was computed in) depends on the grouping by construction: it is refused with more than one
+  process unless --color-max is given, which then decides.
 """
 import argparse
 import os
@@ -34,12 +39,19 @@ import torch.distributed as dist
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from flownet2_amd import evaluate, flo, parallel  # noqa: E402
+from flownet2_amd import evaluate, flo, parallel, visualize  # noqa: E402
 from flownet2_amd import functional as Fn  # noqa: E402
 import run_flownet as RF  # noqa: E402
 
 
 ARITH = ("conv", "deconv", "wino", "corr")          # the switches of functional.ARITH_SWITCHES this script offers, as --<key>-arith
+
+
+def color_names(out):
+    """What --color writes beside the forward flow `out` (x.flo): (x.png, x.bw.png); a name without the .flo suffix is extended as it
+    stands."""
+    stem = out[:-4] if out.endswith(".flo") else out
+    return stem + ".png", stem + ".bw.png"
 
 
 def groups_of(entries, batch, read):
@@ -78,12 +90,22 @@ def main():
     ap.add_argument("--consistency-json", default=None, metavar="PATH", help="with --bidirectional: the per-line consistency summaries")
     ap.add_argument("--alpha", type=float, nargs=2, default=[0.01, 0.5], metavar=("A1", "A2"), help="inconsistent: |a+b|^2 > A1 (|a|^2+|b|^2) + A2")
     ap.add_argument("--beta", type=float, nargs=2, default=[0.01, 0.002], metavar=("B1", "B2"), help="motion boundary: |grad|^2 > B1 |a|^2 + B2")
+    ap.add_argument("--color", action="store_true", help="also write out.png (with --bidirectional: out.bw.png), the flow's colour coding")
+    ap.add_argument("--color-max", type=float, default=None, metavar="F", help="with --color: the radius drawn at full saturation, the same "
+                    "for every picture (default: see --color-norm)")
+    ap.add_argument("--color-norm", choices=["sample", "batch"], default="sample", help="with --color and without --color-max: normalise by "
+                    "the largest radius of the pair's own flow (sample), or of the group it was computed in (batch: the picture then depends "
+                    "on --batch and on the sharding, so it is refused with more than one process unless --color-max is given)")
     Fn.add_arithmetic_flags(ap, ARITH)
     Fn.add_general_convolution_flag(ap)
     a = ap.parse_args()
     if a.consistency_json and not a.bidirectional:
         ap.error("--consistency-json needs --bidirectional")
+    if (a.color_max is not None or a.color_norm != "sample") and not a.color:
+        ap.error("--color-max and --color-norm need --color")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if a.color and a.color_norm == "batch" and a.color_max is None and world > 1:
+        ap.error("--color-norm batch depends on how the list is sharded: give --color-max, or run one process")
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo")              # control plane only; the data path has no collective
@@ -116,12 +138,17 @@ def main():
                 item = done.get()
                 if item is None:
                     return
-                ents, flow, occ, ev = item
+                ents, flow, occ, rgb, ev = item
                 ev.synchronize()
                 arr = flow.numpy()
                 n = len(ents)
                 for k, e in enumerate(ents):
                     flo.write_flo(e[2], arr[k])
+                    if rgb is not None:
+                        png_name, bw_png_name = color_names(e[2])
+                        visualize.write_png(png_name, rgb[k].numpy())
+                        if occ is not None:
+                            visualize.write_png(bw_png_name, rgb[n + k].numpy())
                     if occ is not None:
                         bw_name, occ_name, bw_occ_name = evaluate.bidirectional_names(e[2])
                         flo.write_flo(bw_name, arr[n + k])
@@ -150,11 +177,17 @@ def main():
             parts.append(([e[-1] for e in ents], c))
         else:
             flow = RF.infer(a.net, P, i0, i1, mean)
+        rgb_host = None
+        if a.color:
+            with torch.no_grad():
+                rgb = Fn.flow_to_color(flow.detach().contiguous(), max_flow=a.color_max, norm=a.color_norm)
+            rgb_host = torch.empty(rgb.shape, dtype=rgb.dtype, pin_memory=True)
+            rgb_host.copy_(rgb, non_blocking=True)
         host = torch.empty(flow.shape, dtype=flow.dtype, pin_memory=True)
         host.copy_(flow, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        done.put((ents, host, occ_host, ev))
+        done.put((ents, host, occ_host, rgb_host, ev))
     done.put(None)
     tw.join(); tp.join()
     if errors:
