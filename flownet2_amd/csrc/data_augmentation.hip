@@ -362,12 +362,12 @@ FN2_API int fn2_data_augmentation_forward(const fn2_data_aug_params* p, const fl
     if (!workspace || workspace_bytes < fn2_data_augmentation_workspace_bytes(N))
       return fail(FN2_ERR_WORKSPACE, "data_augmentation: workspace of %zu bytes needed", fn2_data_augmentation_workspace_bytes(N));
     if (N > kStatRowsMax) return fail(FN2_ERR_UNSUPPORTED, "data_augmentation: more than %d samples per call", kStatRowsMax);
+    if ((long long)H * W >= (1ll << 31) || N > 65535) return fail(FN2_ERR_UNSUPPORTED, "data_augmentation: blob too large for the statistics pass");   // every refusal before the first launch
     // :488-536 without the reference's two device <-> host round trips: initialise, reduce and finish on the device
     EigVec ev;
     for (int i = 0; i < 9; ++i) ev.v[i] = p->chromatic_eigvec[i];                                         // :496-497
     EigenSpace* es = static_cast<EigenSpace*>(workspace);
     hipLaunchKernelGGL(eigenspace_init, dim3(1), dim3(1), 0, st, es, ev);
-    if ((long long)H * W >= (1ll << 31) || N > 65535) return fail(FN2_ERR_UNSUPPORTED, "data_augmentation: blob too large for the statistics pass");
     const int vec4 = ((long long)H * W) % 4 == 0 && (reinterpret_cast<uintptr_t>(bottom) & 15) == 0;
     float* partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + 256);
     const unsigned per_sample = (unsigned)(kStatRowsMax / N > 0 ? kStatRowsMax / N : 1);

@@ -919,7 +919,11 @@ typedef struct fn2_data_aug_params {
   unsigned long long noise_seed;   /* key of the counter-based generator behind the noise effect (ours: the reference uses cuRAND's global stream) */
   unsigned long long noise_stream; /* high counter words: the layer's iteration count */
 } fn2_data_aug_params;
-/* Device scratch for the chromatic-eigen statistics of the batch. */
+/* Device scratch for the chromatic-eigen statistics of the batch.  When a sample has chromatic-eigen coefficients the call leaves the
+ * batch's tChromaticEigenSpace (augmentation_layer_base.hpp:115-127) at the start of the workspace, 25 floats in this order:
+ *   mean_eig[3], mean_rgb[3], max_abs_eig[3], max_rgb[3], min_rgb[3], max_l, eigvec[9]
+ * and from byte 256 on one row of 12 partial results (3 sums, 3 max |eig|, 3 max rgb, 3 min rgb) per workgroup of the statistics pass,
+ * at most 1024 rows.  Without such coefficients, and on every refusal, the workspace is not written. */
 size_t fn2_data_augmentation_workspace_bytes(int N);
 /* bottom [N,C,H,W] device; coeffs_host [N,42] HOST (coeff_to_array layout) or NULL = all defaults; mean device or NULL. */
 int fn2_data_augmentation_forward(const fn2_data_aug_params* p, const float* bottom, const float* coeffs_host, const float* mean,
