@@ -201,6 +201,142 @@ def bidirectional_names(out):
     return stem + ".bw.flo", stem + ".occ.pgm", stem + ".bw.occ.pgm"
 
 
+# ---- point trajectories -------------------------------------------------------------------------------------------------------------
+_T_PREFIX = "FN2_FLOW_TRACK_"
+_T_ENUM = _lib.FLOW_TRACK_CONSTANTS                                         # include/flownet2_hip_flow_track.h: columns and stop reasons
+TRACK_K = _T_ENUM[_T_PREFIX + "K"]
+TRACK_STOP = {n[len(_T_PREFIX + "STOP_"):]: v for n, v in _T_ENUM.items() if n.startswith(_T_PREFIX + "STOP_")}      # name -> state value
+TRACK_COLUMNS = tuple(sorted((n[len(_T_PREFIX):] for n in _T_ENUM if n != _T_PREFIX + "K" and not n.startswith(_T_PREFIX + "STOP_")),
+                             key=lambda n: _T_ENUM[_T_PREFIX + n]))
+TRACK_COL = {name: i for i, name in enumerate(TRACK_COLUMNS)}
+UNKNOWN_FLOW = 1e10                                                          # the .flo unknown-flow value (flow_metrics, flow_to_color skip it)
+
+
+def _host(t):
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+
+class FlowTracks:
+    """What one call of functional.flow_track (or several consecutive ones, merged) knows of P points per sample: rows [n, K] float64
+    (columns TRACK_COLUMNS), tracks [n,F,2,P] (the position in every frame reached, NaN after; None where not asked for), start [n,2,P] the
+    positions in the first frame, points [n,2,P] the last position reached, state uint8 [n,P] (0 = alive, else a TRACK_STOP value), steps
+    int32 [n,P], size = (H, W) of the plane.  The arrays are torch tensors (on the device of the call) or NumPy arrays."""
+
+    def __init__(self, rows=None, tracks=None, points=None, state=None, steps=None, start=None, size=None, alpha=(0.01, 0.5)):
+        rows = np.zeros((0, TRACK_K), np.float64) if rows is None else np.array(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != TRACK_K:
+            raise ValueError(f"FlowTracks: rows must be [n, {TRACK_K}], got {rows.shape}")
+        self.rows, self.tracks, self.points, self.state, self.steps, self.start = rows, tracks, points, state, steps, start
+        self.size = None if size is None else (int(size[0]), int(size[1]))
+        self.alpha = (float(alpha[0]), float(alpha[1]))
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def column(self, name):
+        return self.rows[:, TRACK_COL[name]]
+
+    def merge(self, others):
+        """This call followed by `others`, consecutive calls on the SAME points (each started from the points and state the one before
+        returned): one object over all their frames.  tracks are joined along the frame axis (a later call's first frame is the earlier
+        one's last), steps add, points and state are the last call's, start is the first one's.  Rows: POINTS the first call's, ALIVE the
+        last one's, the stop reasons and STEPS_SUM add (exact integers), STEPS_MAX, DISP_SUM and DISP_MAX are computed anew from the
+        merged steps, start and points -- the displacement in float32 as the kernel does, its sum in float64 in index order."""
+        import torch
+        calls = [self] + list(others)
+        for o in calls:
+            if o.alpha != self.alpha or o.size != self.size:
+                raise ValueError(f"FlowTracks.merge: calls differ (alpha {o.alpha}, size {o.size} against {self.alpha}, {self.size})")
+            if o.points is None or o.state is None or o.steps is None or o.start is None:
+                raise ValueError("FlowTracks.merge: needs the points, state, steps and start of every call")
+            if tuple(o.points.shape) != tuple(self.points.shape):
+                raise ValueError(f"FlowTracks.merge: points {tuple(o.points.shape)} against {tuple(self.points.shape)}: not the same points")
+        t = lambda a: torch.as_tensor(a)
+        steps = t(calls[0].steps).clone()
+        for o in calls[1:]:
+            steps = steps + t(o.steps)
+        tracks = None
+        if all(o.tracks is not None for o in calls):
+            tracks = torch.cat([t(calls[0].tracks)] + [t(o.tracks)[:, 1:] for o in calls[1:]], dim=1)
+        last = calls[-1]
+        rows = self.rows.copy()
+        rows[:, TRACK_COL["ALIVE"]] = last.rows[:, TRACK_COL["ALIVE"]]
+        for name in ("NONFINITE", "OUTSIDE", "INCONSISTENT", "MARKED", "STEPS_SUM"):
+            rows[:, TRACK_COL[name]] = sum(o.rows[:, TRACK_COL[name]] for o in calls)
+        s, p0, p1, alive = _host(steps), _host(self.start).astype(np.float32), _host(last.points).astype(np.float32), _host(last.state) == 0
+        n = rows.shape[0]
+        rows[:, TRACK_COL["STEPS_MAX"]] = s.reshape(n, -1).max(1) if s.size else 0
+        with np.errstate(invalid="ignore", over="ignore"):
+            dx, dy = p1[:, 0] - p0[:, 0], p1[:, 1] - p0[:, 1]
+            d = np.where(alive, np.sqrt(dx * dx + dy * dy), np.float32(0)).astype(np.float64)
+        rows[:, TRACK_COL["DISP_SUM"]] = [float(np.cumsum(r)[-1]) if r.size else 0.0 for r in d.reshape(n, -1)]
+        rows[:, TRACK_COL["DISP_MAX"]] = d.reshape(n, -1).max(1) if d.size else 0
+        return FlowTracks(rows, tracks=tracks, points=last.points, state=last.state, steps=steps, start=self.start, size=self.size, alpha=self.alpha)
+
+    def summary(self):
+        """Over all samples: the fraction of the points alive at the end and stopped by each reason, the mean and largest number of frames
+        a point advanced, the mean (over the alive points) and largest displacement between the first and the last position, the point
+        and sample counts.  A quotient with a zero denominator is nan."""
+        tot = lambda name: float(np.sum(self.column(name)))
+        points, alive = tot("POINTS"), tot("ALIVE")
+        top = lambda name: float(np.max(self.column(name))) if len(self) else math.nan
+        return {
+            "alive": _ratio(alive, points),
+            "nonfinite": _ratio(tot("NONFINITE"), points),
+            "outside": _ratio(tot("OUTSIDE"), points),
+            "inconsistent": _ratio(tot("INCONSISTENT"), points),
+            "marked": _ratio(tot("MARKED"), points),
+            "steps_mean": _ratio(tot("STEPS_SUM"), points),
+            "steps_max": top("STEPS_MAX"),
+            "disp_mean": _ratio(tot("DISP_SUM"), alive),
+            "disp_max": top("DISP_MAX"),
+            "points": int(points),
+            "samples": len(self),
+            "alpha": list(self.alpha),
+        }
+
+    def long_range_flow(self):
+        """For a dense grid (P = H W, start = the pixel grid): the flow [n,2,H,W] from the first frame to the last, last position minus
+        start, and 1e10 -- the .flo unknown-flow value, which flow_metrics and flow_to_color leave out -- where the point stopped."""
+        if self.size is None or self.points is None or self.start is None or self.state is None:
+            raise ValueError("FlowTracks.long_range_flow: needs size, start, points and state")
+        H, W = self.size
+        if tuple(self.points.shape[1:]) != (2, H * W):
+            raise ValueError(f"FlowTracks.long_range_flow: points {tuple(self.points.shape)} are no dense grid on a {H} x {W} plane")
+        if hasattr(self.points, "detach"):
+            import torch
+            d = torch.as_tensor(self.points) - torch.as_tensor(self.start).to(self.points.device)
+            stopped = (torch.as_tensor(self.state).to(self.points.device) != 0).unsqueeze(1).expand_as(d)
+            return torch.where(stopped, torch.full_like(d, UNKNOWN_FLOW), d).reshape(-1, 2, H, W)
+        d = np.asarray(self.points, np.float32) - np.asarray(self.start, np.float32)
+        stopped = np.broadcast_to((np.asarray(self.state) != 0)[:, None], d.shape)
+        return np.where(stopped, np.float32(UNKNOWN_FLOW), d).astype(np.float32).reshape(-1, 2, H, W)
+
+
+def track_names(out_dir):
+    """What scripts/track_flownet.py writes into OUT_DIR: the trajectories (tracks.npz: pos float32 [F,2,P], NaN where a slot is empty;
+    track_id int32 [F,P], -1 where empty; state uint8 [P])."""
+    import os
+    return os.path.join(out_dir, "tracks.npz")
+
+
+def write_tracks_npz(path, pos, track_id, state):
+    """tracks.npz with bytes that are a function of the arrays alone: the three of them in this order and with these types, stored
+    uncompressed, every zip entry dated 1980-01-01 (np.savez would stamp them with the time of day).  np.load reads it."""
+    import io
+    import zipfile
+    pos, track_id, state = np.ascontiguousarray(pos, np.float32), np.ascontiguousarray(track_id, np.int32), np.ascontiguousarray(state, np.uint8)
+    if pos.ndim != 3 or pos.shape[1] != 2 or track_id.shape != (pos.shape[0], pos.shape[2]) or state.shape != (pos.shape[2],):
+        raise ValueError(f"write_tracks_npz: pos {pos.shape} [F,2,P], track_id {track_id.shape} [F,P], state {state.shape} [P]")
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+        for name, a in (("pos", pos), ("track_id", track_id), ("state", state)):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, a, version=(1, 0), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
 # ---- the KITTI flow PNG -------------------------------------------------------------------------------------------------------------
 _PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
 

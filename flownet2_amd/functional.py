@@ -477,6 +477,54 @@ def _no_grad_inputs(what, tensors):
         raise RuntimeError(f"{what} is not differentiable: detach the inputs or call it under torch.no_grad()")
 
 
+def flow_track_grid(N, H, W, cell=1, device=None):
+    """The initial points of a tracker on a [H,W] plane cut into cells of `cell` pixels: float32 [N,2,P], P = ceil(H / cell) ceil(W / cell),
+    x plane then y plane, one point at every cell's centre (cell = 1: the pixel grid) -- flow_track_reseed on an all-stopped state."""
+    P = -(-int(H) // int(cell)) * -(-int(W) // int(cell))
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    points = torch.zeros((int(N), 2, P), dtype=torch.float32, device=device)
+    state = torch.ones((int(N), P), dtype=torch.uint8, device=device)
+    ops.flow_track_reseed(points, state, (H, W), cell, born=False)
+    return points
+
+
+def flow_track_reseed(points, state, size, cell):
+    """Fill the gaps in a tracker's coverage, IN PLACE (fn2_flow_track_reseed, include/flownet2_hip_flow_track.h): points [N,2,P] and
+    state uint8 [N,P] on a plane size = (H, W) cut into cells of `cell` pixels, slot c owning cell c.  Every stopped slot whose home cell
+    holds no alive point starts anew at the cell's centre.  Returns born uint8 [N,P], 1 at exactly those slots."""
+    _no_grad_inputs("flow_track_reseed", (points,))
+    return ops.flow_track_reseed(points, state, size, cell, born=True)
+
+
+def flow_track(fw, bw, points=None, state=None, stop=None, stop_mask=None, alpha=(0.01, 0.5), tracks=True):
+    """Carry points through a sequence of flows (csrc/flow_track.hip; the arithmetic is stated in include/flownet2_hip_flow_track.h): fw, bw
+    [N,T,2,H,W], fw[:,t] from frame t to t+1 and bw[:,t] back, or [N,2,H,W] for one step.  points [N,2,P] (x plane, y plane; [N,2,H,W] is
+    taken as P = H W) or None for the dense pixel grid; state uint8 [N,P], non-zero = already stopped; stop uint8 [N,T,1,H,W] (or
+    [N,1,H,W]): a point stops where stop & stop_mask is non-zero at its nearest pixel -- by default the BOUNDARY bit, so
+    flow_consistency(..., flags=True).flags_fw goes in as it is.  A point also stops where its target leaves the image, where the backward
+    flow at its target does not cancel the forward one (alpha, as in flow_consistency) and where a value is not finite.  One launch for all
+    T frames.  Returns an evaluate.FlowTracks.  Not differentiable."""
+    from .evaluate import CONSISTENCY_FLAGS, FlowTracks
+    _no_grad_inputs("flow_track", (fw, bw, points))
+    if isinstance(fw, torch.Tensor) and fw.dim() == 4:
+        fw = fw.unsqueeze(1)
+    if isinstance(bw, torch.Tensor) and bw.dim() == 4:
+        bw = bw.unsqueeze(1)
+    if isinstance(stop, torch.Tensor) and stop.dim() == 4:
+        stop = stop.unsqueeze(1)
+    if not isinstance(fw, torch.Tensor) or fw.dim() != 5:
+        raise ValueError("flow_track: fw must be [N,T,2,H,W] or [N,2,H,W]")
+    N, T, _, H, W = fw.shape
+    if points is None:
+        ops._chk(fw, "fw", 5)
+        points = flow_track_grid(N, H, W, 1, device=fw.device)
+    elif isinstance(points, torch.Tensor) and points.dim() == 4:
+        points = points.reshape(points.shape[0], points.shape[1], -1)
+    mask = CONSISTENCY_FLAGS["BOUNDARY"] if stop_mask is None else int(stop_mask)
+    results, tr, p_out, s_out, st = ops.flow_track(fw, bw, points, state=state, stop=stop, stop_mask=mask, alpha=alpha, tracks=tracks)
+    return FlowTracks(results[:-1].cpu().numpy(), tracks=tr, points=p_out, state=s_out, steps=st, start=points.contiguous(), size=(H, W), alpha=alpha)
+
+
 def flow_to_color(flow, max_flow=None, norm="sample"):
     """The Middlebury colour coding of a flow [N,2,H,W] as uint8 [N,H,W,3] on the device (csrc/flow_visualize.hip; the arithmetic is stated
     in include/flownet2_hip_flow_visualize.h): hue from the direction, saturation from the radius over a normalising radius, unknown flow

@@ -500,6 +500,75 @@ def flow_consistency(fw, bw, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=False,
     return results, occ, fl, er, wa
 
 
+_FLOW_TRACK_K = _lib.FLOW_TRACK_CONSTANTS["FN2_FLOW_TRACK_K"]      # columns of a results row (evaluate.TRACK_COLUMNS)
+
+
+def flow_track_sizes(N: int, T: int, H: int, W: int, P: int):
+    """(workspace bytes, K) of fn2_flow_track / fn2_flow_track_reseed for [N,T,2,H,W] flows and P points (include/flownet2_hip_flow_track.h)."""
+    nbytes, k = C.c_size_t(), C.c_int()
+    check(_lib.lib().fn2_flow_track_sizes(int(N), int(T), int(H), int(W), int(P), C.byref(nbytes), C.byref(k)))
+    return nbytes.value, k.value
+
+
+def _chk_bytes(t, name: str, shape):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA (HIP) tensor; flownet2_amd has no CPU path")
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected uint8 {list(shape)}, got {t.dtype} {list(t.shape)}")
+    return t.contiguous()
+
+
+def flow_track(fw, bw, points, state=None, stop=None, stop_mask=8, alpha=(0.01, 0.5), tracks=True, steps=True):
+    """Point trajectories (csrc/flow_track.hip) through fw, bw [N,T,2,H,W] from points [N,2,P] (a dense grid: [N,2,H,W]); state uint8 [N,P]
+    or None, stop uint8 [N,T,1,H,W] or None.  Returns (results [N + 1, K] float64 on the device, columns evaluate.TRACK_COLUMNS; tracks
+    [N,T+1,2,P] or None; points_out [N,2,P]; state_out uint8 [N,P]; steps int32 [N,P] or None)."""
+    f, b = _chk(fw, "fw", 5), _chk(bw, "bw", 5)
+    if f.shape != b.shape or f.shape[2] != 2:
+        raise ValueError(f"flow_track: fw {tuple(f.shape)} and bw {tuple(b.shape)} must both be [N,T,2,H,W]")
+    N, T, _, H, W = f.shape
+    p = _chk(points, "points", None)
+    if p.dim() < 3 or p.shape[0] != N or p.shape[1] != 2:
+        raise ValueError(f"flow_track: points {tuple(p.shape)} must be [{N},2,P]")
+    if f.device != b.device or f.device != p.device:
+        raise ValueError(f"flow_track: fw on {f.device}, bw on {b.device}, points on {p.device}")
+    P = p[0, 0].numel()
+    s_in = _chk_bytes(state, "state", (N, P)) if state is not None else None
+    s_map = _chk_bytes(stop, "stop", (N, T, 1, H, W)) if stop is not None else None
+    ws = torch.empty(flow_track_sizes(N, T, H, W, P)[0], dtype=torch.uint8, device=f.device)
+    results = torch.empty((N + 1, _FLOW_TRACK_K), dtype=torch.float64, device=f.device)
+    tr = torch.empty((N, T + 1, 2, P), dtype=torch.float32, device=f.device) if tracks else None
+    p_out = torch.empty((N, 2, P), dtype=torch.float32, device=f.device)
+    s_out = torch.empty((N, P), dtype=torch.uint8, device=f.device)
+    st = torch.empty((N, P), dtype=torch.int32, device=f.device) if steps else None
+    check(_lib.lib().fn2_flow_track(_ptr(f), _ptr(b), _ptr(s_map), int(stop_mask), _ptr(p), _ptr(s_in), N, T, H, W, P, C.c_float(float(alpha[0])),
+                                    C.c_float(float(alpha[1])), _ptr(results), _ptr(tr), _ptr(p_out), _ptr(s_out),
+                                    C.cast(_ptr(st), C.POINTER(C.c_int)), _ptr(ws), ws.numel(), _stream()))
+    return results, tr, p_out, s_out, st
+
+
+def flow_track_reseed(points, state, size, cell, born=True):
+    """fn2_flow_track_reseed on points [N,2,P] and state uint8 [N,P], IN PLACE, for a plane size = (H, W) cut into cells of `cell` pixels
+    (P = ceil(H / cell) ceil(W / cell)): every stopped slot whose home cell no alive point covers starts anew at the cell's centre.
+    Returns born uint8 [N,P] (or None)."""
+    H, W = int(size[0]), int(size[1])
+    cell = int(cell)
+    if cell < 1 or H < 1 or W < 1:
+        raise ValueError(f"flow_track_reseed: bad size ({H}, {W}) or cell {cell}")
+    P = -(-H // cell) * -(-W // cell)
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise ValueError("points: expected a CUDA (HIP) tensor; flownet2_amd has no CPU path")
+    N = points.shape[0]
+    if points.dtype != torch.float32 or tuple(points.shape) != (N, 2, P) or not points.is_contiguous():
+        raise ValueError(f"flow_track_reseed: points must be contiguous float32 [N,2,{P}] for size ({H}, {W}) and cell {cell}, got {tuple(points.shape)}")
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or tuple(state.shape) != (N, P) or not state.is_contiguous() \
+            or state.device != points.device:
+        raise ValueError(f"flow_track_reseed: state must be contiguous uint8 [{N},{P}] on {points.device}")
+    ws = torch.empty(max(N * P, 1), dtype=torch.uint8, device=points.device)
+    b = torch.empty((N, P), dtype=torch.uint8, device=points.device) if born else None
+    check(_lib.lib().fn2_flow_track_reseed(_ptr(points), _ptr(state), _ptr(b), N, H, W, cell, _ptr(ws), ws.numel(), _stream()))
+    return b
+
+
 _FLOW_COLOR_NORMS = {n[len("FN2_FLOW_COLOR_NORM_"):].lower(): v for n, v in _lib.FLOW_VISUALIZE_CONSTANTS.items()}      # sample, batch, fixed
 
 
