@@ -33,6 +33,7 @@ struct Args {
   int Cout, Hout, Wout, out_ctot, out_c0;
   int pad;
   int nchunks;        // chunks of CQ channel quads
+  int kquads;         // live channel quads, cdiv(Cin, 4): the 1x1 tiles execute no k-step beyond them (the packed weights are padded to whole chunks)
   int ksteps;         // k-steps of the packed weights per 64-channel group (= quads * KS * KS), multiple of the chunk length
   int tx, ty;         // workgroup tiles per sample along x / y
   int ng;             // Cout / (16 * MW * WM)
@@ -59,6 +60,104 @@ struct Cfg : Window<((P16_ ? 1 : 4) * WNY_ - 1) * S_ + KS_,                  // 
   static_assert(KSC % NBUFA == 0, "ring phase must repeat per chunk");
   static_assert(2 * Cfg::BUF * 4 <= 160 * 1024, "LDS");
 };
+
+// ---- 1x1 tiles (a plain GEMM over the channels).  The packed weights pad K to whole chunks of 8 channel quads, but only cdiv(Cin, 4)
+// quads are live: the k-steps behind them multiply zeros by zeros (7 of 104 for the 386 channels of deconv2) and are not executed.
+//
+// gemm_chunk: a whole chunk with another one behind it, whose window DMA was issued at the top of this one.  `ahead` = the k-steps the next
+// chunk executes (>= 1): its k-step i is prefetched only when i < ahead.  Where ahead < R, the last k-steps have fewer loads behind their
+// operand than R; they then wait as if only the next chunk's k-step 0 had been fetched -- never more than are in flight.
+// ks is the counter of an unrolled loop in both functions: the ring phase and every wait immediate fold to constants.
+template <class K>
+__device__ __forceinline__ void gemm_chunk(f32x4 (&acc)[K::MW][K::NP], typename WVec<K::MW>::T (&wreg)[K::NBUFA], const float* win,
+                                           const float* wk, unsigned wlane, int ahead) {
+  static_assert(K::KS == 1 && K::S == 1, "1x1 tiles");
+  constexpr int MW = K::MW, NP = K::NP, KSC = K::KSC, PW = K::P16 ? 16 : 4;
+  constexpr int R = K::NBUFA - 1, DMA = K::NRUN / K::NW;
+  using WV = typename WVec<MW>::T;
+  auto weight_step = [&](int ks) -> WV {
+    const float* wks = wk + (size_t)(ks + R) * 256;
+    if (ks + R < KSC) wreg[(ks + R) % K::NBUFA] = weight_fetch<MW>(wks, wlane);
+    else wreg[(ks + R) % K::NBUFA] = weight_fetch_unless_last<MW>(ahead, ks + R - KSC, wks, wlane);
+    const int behind = ks < R ? R + DMA : R;      // loads younger than this k-step's weight when every prefetch was issued
+    const int next = ks + R - KSC + 1;            // of them, the next chunk's
+    if (next >= 2) ring_wait_either(ahead, R, behind - (next - 1), behind);
+    else ring_wait(behind);
+    weight_landed(wreg[ks % K::NBUFA]);
+    return wreg[ks % K::NBUFA];
+  };
+  if constexpr (K::PIN) {      // (the two loop forms of conv_body)
+    float b[2][NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) b[0][p] = win[PW * p];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < KSC; ++ks) {
+      const WV w = weight_step(ks);
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+#pragma unroll
+        for (int j = 0; j < MW; ++j) acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ks & 1][p], wget<MW>(w, j), acc[j][p], 0, 0, 0);
+        if (ks + 1 < KSC) b[(ks + 1) & 1][p] = win[(ks + 1 < KSC ? ks + 1 : ks) * 4 * K::CS + PW * p];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int ks = 0; ks < KSC; ++ks) {
+      const WV w = weight_step(ks);
+      float b[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) b[p] = win[ks * 4 * K::CS + PW * p];
+#pragma unroll
+      for (int j = 0; j < MW; ++j)
+#pragma unroll
+        for (int p = 0; p < NP; ++p) acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[p], wget<MW>(w, j), acc[j][p], 0, 0, 0);
+    }
+  }
+}
+
+// gemm_last_chunk: the last chunk, which executes its `live` k-steps (1 .. KSC) and leaves behind k-step live - 1.  ONE unrolled body with
+// an exit behind every k-step, not a block per live count: the accumulators and the ring keep their registers (a switch over eight unrolled
+// blocks doubled the VGPRs and copied ring registers whose loads were in flight on the way into the blocks).  It issues no window and no
+// weight beyond k-step live - 1; min(live, R) of its weights were fetched ahead, so at most that many loads are younger than its window and
+// that is what its top may leave in flight.  k-step ks leaves min(R, live - 1 - ks) loads in flight, the last one none: nothing of the ring
+// or the window is in flight when the epilogue starts.  The operand reads run a k-step ahead in both loop forms (an exit ends a basic
+// block: the compiler cannot lift them over it by itself); the read behind the last live k-step stays inside the window buffer.
+template <class K>
+__device__ __forceinline__ void gemm_last_chunk(f32x4 (&acc)[K::MW][K::NP], typename WVec<K::MW>::T (&wreg)[K::NBUFA], const float* win,
+                                                const float* wk, unsigned wlane, int live) {
+  static_assert(K::KS == 1 && K::S == 1, "1x1 tiles");
+  constexpr int MW = K::MW, NP = K::NP, KSC = K::KSC, PW = K::P16 ? 16 : 4;
+  constexpr int R = K::NBUFA - 1;
+  using WV = typename WVec<MW>::T;
+  const int last = live - 1;
+  wait_vmcnt<R>();
+#pragma unroll
+  for (int j = R - 1; j >= 1; --j) ring_wait_if_le(live, j, j);
+  __builtin_amdgcn_s_barrier();
+  float b[2][NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) b[0][p] = win[PW * p];
+  if constexpr (K::PIN) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ks = 0; ks < KSC; ++ks) {
+    if (ks + R < KSC) wreg[(ks + R) % K::NBUFA] = weight_fetch_unless_last<MW>(live, ks + R, wk + (size_t)(ks + R) * 256, wlane);
+    ring_wait(KSC - 1 - ks < R ? KSC - 1 - ks : R);
+#pragma unroll
+    for (int j = (KSC - 1 - ks < R ? KSC - 1 - ks : R) - 1; j >= 0; --j) ring_wait_if_le(last, ks + j, j);
+    weight_landed(wreg[ks % K::NBUFA]);
+    const WV w = wreg[ks % K::NBUFA];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+#pragma unroll
+      for (int j = 0; j < MW; ++j) acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ks & 1][p], wget<MW>(w, j), acc[j][p], 0, 0, 0);
+      if (ks + 1 < KSC) b[(ks + 1) & 1][p] = win[(ks + 1 < KSC ? ks + 1 : ks) * 4 * K::CS + PW * p];
+      if constexpr (K::PIN) __builtin_amdgcn_sched_barrier(0);
+    }
+    if (ks + 1 < KSC && last == ks) return;
+  }
+}
 
 // One workgroup tile: channel group g (of 16 * MW * WM channels), pixel tile (bx, by) of sample n.
 template <class K>
@@ -106,68 +205,85 @@ __device__ __forceinline__ void conv_body(const Args& a, int g, int bx, int by, 
   static_assert(R + DMA <= 63, "vmcnt has 6 bits");
   WV wreg[K::NBUFA];
   stage(0, 0);
-  if (a.nchunks > 0) {
+  if constexpr (KS == 1) {
+    // whole chunks, then the last chunk with only its live k-steps (gemm_chunk, gemm_last_chunk above)
+    const int nfull = a.nchunks - 1;                     // (nchunks >= 1: Cin >= 1)
+    const int live = a.kquads - nfull * K::KSC;          // k-steps of the last chunk, 1 .. KSC
 #pragma unroll
-    for (int i = 0; i < R; ++i) wreg[i] = weight_fetch<MW>(wb + (size_t)i * 256, wlane);
-  }
-  // the k-step's weight: fetch the one R k-steps ahead, wait for this one
-  auto weight_step = [&](int ks0, int ks, int rest) -> WV {
-    const float* wks = wb + (size_t)(ks0 + ks + R) * 256;
-    if (ks + R < K::KSC) wreg[(ks + R) % K::NBUFA] = weight_fetch<MW>(wks, wlane);
-    else wreg[(ks + R) % K::NBUFA] = weight_fetch_unless_last<MW>(rest, wks, wlane);
-    const int left = K::KSC - 1 - ks < R ? K::KSC - 1 - ks : R;
-    if (ks < R) ring_wait_either(rest, left, R + DMA);
-    else if (left < R) ring_wait_either(rest, left, R);
-    else ring_wait(R);
-    weight_landed(wreg[ks % K::NBUFA]);
-    return wreg[ks % K::NBUFA];
-  };
+    for (int i = 0; i < R; ++i) wreg[i] = weight_fetch_unless_last<MW>(nfull ? K::KSC : live, i, wb + (size_t)i * 256, wlane);
+    for (int c = 0; c < nfull; ++c) {
+      const int buf = c & 1;
+      wait_vmcnt<R>();      // as below: R or more weights were fetched behind the window of chunk c
+      __builtin_amdgcn_s_barrier();
+      stage(c + 1, buf ^ 1);
+      gemm_chunk<K>(acc, wreg, smem + buf * K::BUF + bbase, wb + (size_t)c * K::KSC * 256, wlane, c + 1 < nfull ? K::KSC : live);
+    }
+    gemm_last_chunk<K>(acc, wreg, smem + (nfull & 1) * K::BUF + bbase, wb + (size_t)nfull * K::KSC * 256, wlane, live);
+  } else {
+    if (a.nchunks > 0) {
+#pragma unroll
+      for (int i = 0; i < R; ++i) wreg[i] = weight_fetch<MW>(wb + (size_t)i * 256, wlane);
+    }
+    // the k-step's weight: fetch the one R k-steps ahead, wait for this one
+    auto weight_step = [&](int ks0, int ks, int rest) -> WV {
+      const float* wks = wb + (size_t)(ks0 + ks + R) * 256;
+      if (ks + R < K::KSC) wreg[(ks + R) % K::NBUFA] = weight_fetch<MW>(wks, wlane);
+      else wreg[(ks + R) % K::NBUFA] = weight_fetch_unless_last<MW>(rest, 0, wks, wlane);
+      const int left = K::KSC - 1 - ks < R ? K::KSC - 1 - ks : R;
+      if (ks < R) ring_wait_either(rest, 1, left, R + DMA);
+      else if (left < R) ring_wait_either(rest, 1, left, R);
+      else ring_wait(R);
+      weight_landed(wreg[ks % K::NBUFA]);
+      return wreg[ks % K::NBUFA];
+    };
 
-  for (int c = 0; c < a.nchunks; ++c) {
-    const int buf = c & 1;
-    const int rest = a.nchunks - 1 - c;      // chunks still to come
-    // in flight: the window of chunk c (issued at the top of the chunk before) and, younger than it, the weight prefetch of the last R
-    // k-steps; loads retire in order, so the window has landed once at most R loads remain -- no need to drain the ring
-    wait_vmcnt<R>();
-    __builtin_amdgcn_s_barrier();
-    if (rest) stage(c + 1, buf ^ 1);
-    const float* win = smem + buf * K::BUF + bbase;
-    const int ks0 = c * K::KSC;
-    if constexpr (K::PIN) {
-      // operand reads one k-step ahead, ONE read behind the MW MFMAs of every patch, order pinned (a block of NP reads in front of a
-      // k-step's MFMAs leaves the matrix pipe a single queued instruction deep while it issues: csrc/conv_plane.hip, DESIGN 3.4 c).
-      // A variant of its own: conv3 [16,128,80,112] gains (434 -> 412 us), conv2 [16,64,160,224] loses (428 -> 490): the autotuner
-      // decides per layer, the bits are the same.
-      float b[2][NP];
-      auto tap_off = [](int ks) { const int cq = ks / (KS * KS), ky = (ks / KS) % KS, kx = ks % KS; return cq * 4 * K::CS + ky * K::RS + kx; };
+    for (int c = 0; c < a.nchunks; ++c) {
+      const int buf = c & 1;
+      const int rest = a.nchunks - 1 - c;      // chunks still to come
+      // in flight: the window of chunk c (issued at the top of the chunk before) and, younger than it, the weight prefetch of the last R
+      // k-steps; loads retire in order, so the window has landed once at most R loads remain -- no need to drain the ring
+      wait_vmcnt<R>();
+      __builtin_amdgcn_s_barrier();
+      if (rest) stage(c + 1, buf ^ 1);
+      const float* win = smem + buf * K::BUF + bbase;
+      const int ks0 = c * K::KSC;
+      if constexpr (K::PIN) {
+        // operand reads one k-step ahead, ONE read behind the MW MFMAs of every patch, order pinned (a block of NP reads in front of a
+        // k-step's MFMAs leaves the matrix pipe a single queued instruction deep while it issues: csrc/conv_plane.hip, DESIGN 3.4 c).
+        // A variant of its own: conv3 [16,128,80,112] gains (434 -> 412 us), conv2 [16,64,160,224] loses (428 -> 490): the autotuner
+        // decides per layer, the bits are the same.
+        float b[2][NP];
+        auto tap_off = [](int ks) { const int cq = ks / (KS * KS), ky = (ks / KS) % KS, kx = ks % KS; return cq * 4 * K::CS + ky * K::RS + kx; };
 #pragma unroll
-      for (int p = 0; p < NP; ++p) b[0][p] = win[tap_off(0) + PW * S * p];
-      __builtin_amdgcn_sched_barrier(0);
+        for (int p = 0; p < NP; ++p) b[0][p] = win[tap_off(0) + PW * S * p];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ks = 0; ks < K::KSC; ++ks) {
+          const WV w = weight_step(ks0, ks, rest);
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+#pragma unroll
+            for (int j = 0; j < MW; ++j) acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ks & 1][p], wget<MW>(w, j), acc[j][p], 0, 0, 0);
+            if (ks + 1 < K::KSC) b[(ks + 1) & 1][p] = win[tap_off(ks + 1 < K::KSC ? ks + 1 : ks) + PW * S * p];
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      } else {
 #pragma unroll
       for (int ks = 0; ks < K::KSC; ++ks) {
         const WV w = weight_step(ks0, ks, rest);
+        const int cq = ks / (KS * KS), ky = (ks / KS) % KS, kx = ks % KS;
+        float b[NP];
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
+        for (int p = 0; p < NP; ++p) b[p] = win[cq * 4 * K::CS + ky * K::RS + kx + PW * S * p];
 #pragma unroll
-          for (int j = 0; j < MW; ++j) acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ks & 1][p], wget<MW>(w, j), acc[j][p], 0, 0, 0);
-          if (ks + 1 < K::KSC) b[(ks + 1) & 1][p] = win[tap_off(ks + 1 < K::KSC ? ks + 1 : ks) + PW * S * p];
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        for (int j = 0; j < MW; ++j)
+#pragma unroll
+          for (int p = 0; p < NP; ++p) acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[p], wget<MW>(w, j), acc[j][p], 0, 0, 0);
       }
-    } else {
-#pragma unroll
-    for (int ks = 0; ks < K::KSC; ++ks) {
-      const WV w = weight_step(ks0, ks, rest);
-      const int cq = ks / (KS * KS), ky = (ks / KS) % KS, kx = ks % KS;
-      float b[NP];
-#pragma unroll
-      for (int p = 0; p < NP; ++p) b[p] = win[cq * 4 * K::CS + ky * K::RS + kx + PW * S * p];
-#pragma unroll
-      for (int j = 0; j < MW; ++j)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) acc[j][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[p], wget<MW>(w, j), acc[j][p], 0, 0, 0);
+      }
     }
-    }
+
   }
 
   wait_vmcnt<0>();      // (nothing is in flight behind a last chunk)
@@ -332,7 +448,8 @@ static void set_geometry(Args& a) {
   }
   a.tx = cdiv(a.Wout, K::TW); a.ty = cdiv(a.Hout, K::TH);
   a.ng = a.Cout / (16 * K::MW * K::WM);
-  a.nchunks = cdiv(cdiv(a.Cin, 4), K::CQ);
+  a.kquads = cdiv(a.Cin, 4);
+  a.nchunks = cdiv(a.kquads, K::CQ);
 }
 
 inline long long tiles_of(const Args& a) { return (long long)a.N * a.tx * a.ty * a.ng; }
@@ -415,7 +532,10 @@ static const Variant kVariants[] = {FN2_CV_LIST(FN2_CV_ROW)
   FN2_CV_PIN(1, 1, 2, 7, 2, 2, 1, 8, 1, 1) FN2_CV_PIN(1, 1, 2, 3, 2, 2, 1, 8, 1, 1)
   FN2_CV_PIN(3, 1, 2, 7, 2, 2, 1, 2, 0, 1) FN2_CV_PIN(3, 1, 2, 6, 2, 2, 1, 2, 0, 1) FN2_CV_PIN(3, 2, 2, 7, 2, 1, 2, 2, 0, 1) FN2_CV_PIN(3, 2, 2, 6, 2, 2, 1, 2, 0, 1)
   FN2_CV_PIN(4, 2, 2, 7, 2, 2, 1, 2, 0, 1) FN2_CV_PIN(4, 2, 2, 6, 2, 2, 1, 2, 0, 1) FN2_CV_PIN(5, 2, 2, 6, 2, 2, 1, 1, 0, 1)
-  FN2_CV_PIN(7, 2, 2, 6, 2, 2, 1, 1, 0, 1) FN2_CV_PIN(7, 2, 4, 6, 1, 2, 2, 1, 0, 0)};
+  FN2_CV_PIN(7, 2, 2, 6, 2, 2, 1, 1, 0, 1) FN2_CV_PIN(7, 2, 4, 6, 1, 2, 2, 1, 0, 0)
+  /* 32-channel GEMMs on planes too small to fill the chip with the tiles above (conv_redir, [8,256,40,56] -> 32: 72 workgroups of 256
+     pixels): 64- and 128-pixel tiles, 280 / 144 workgroups there.  (New variants go to the end: the forced-variant numbers stay.) */
+  FN2_CV_ROW16(2, 1, 1, 4, 1, 0) FN2_CV_ROW16(2, 2, 1, 4, 1, 0) FN2_CV_PIN(1, 1, 2, 1, 1, 4, 1, 8, 1, 0) FN2_CV_PIN(1, 1, 2, 2, 1, 4, 1, 8, 1, 0)};
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 int g_forced_variant = -1;       // >= 0: plain launch of that variant; >= 1000: its split-tail launch

@@ -16,6 +16,7 @@
 //   conv3x3_c2_gather : the 9-tap shift-sum of P (+ bias, + the splits in a fixed order): deterministic.
 //   deconv4x4s2_c2 : one thread per output pixel; each output touches 2x2 input taps per input channel.
 #include "fn2_common.hpp"
+#include "../../include/flownet2_hip_flow_head.h"
 
 namespace fn2 {
 
@@ -76,15 +77,11 @@ __global__ void __launch_bounds__(kHeadPix* G) conv3x3_c2_taps(const float* __re
 }
 
 // Pass 2: out[n, o, y, x] = bias[o] + sum_split sum_t P[split][n][o*9 + t][y + dy - 1][x + dx - 1]   (zero outside the image)
-template <int NSPLIT>       // compile-time: all 9 * NSPLIT loads are in flight together (one memory round trip, not NSPLIT)
-__global__ void __launch_bounds__(256) conv3x3_c2_gather(const float* __restrict__ P, const float* __restrict__ bias,
-                                                          float* __restrict__ out, int N, int H, int W) {
+// NSPLIT is compile-time: all 9 * NSPLIT loads are in flight together (one memory round trip, not NSPLIT)
+template <int NSPLIT>
+__device__ __forceinline__ float gather_flow(const float* __restrict__ P, const float* __restrict__ bias, int N, int H, int W,
+                                             unsigned n, unsigned o, int y, int x) {
   const unsigned plane = (unsigned)H * W;
-  const unsigned pix = blockIdx.x * 256u + threadIdx.x;
-  if (pix >= plane) return;
-  const int y = pix / W, x = pix - y * W;
-  const unsigned no = blockIdx.y;                  // n * 2 + o
-  const unsigned n = no >> 1, o = no & 1;
   float v[NSPLIT][9];
 #pragma unroll
   for (int sp = 0; sp < NSPLIT; ++sp) {
@@ -103,7 +100,18 @@ __global__ void __launch_bounds__(256) conv3x3_c2_gather(const float* __restrict
   for (int sp = 0; sp < NSPLIT; ++sp)
 #pragma unroll
     for (int t = 0; t < 9; ++t) sacc += v[sp][t];
-  out[(size_t)no * plane + pix] = sacc;
+  return sacc;
+}
+
+template <int NSPLIT>
+__global__ void __launch_bounds__(256) conv3x3_c2_gather(const float* __restrict__ P, const float* __restrict__ bias,
+                                                          float* __restrict__ out, int N, int H, int W) {
+  const unsigned plane = (unsigned)H * W;
+  const unsigned pix = blockIdx.x * 256u + threadIdx.x;
+  if (pix >= plane) return;
+  const int y = pix / W, x = pix - y * W;
+  const unsigned no = blockIdx.y;                  // n * 2 + o
+  out[(size_t)no * plane + pix] = gather_flow<NSPLIT>(P, bias, N, H, W, no >> 1, no & 1, y, x);
 }
 
 // Caffe Deconvolution 4x4, stride 2, pad 1 (weight [Cin=2, Cout=2, 4, 4], base_conv_layer.cpp:125-139):
@@ -137,6 +145,62 @@ __global__ void __launch_bounds__(256) deconv4x4s2_c2(const float* __restrict__ 
     out[(((size_t)n * out_ctot + out_c0 + 0) * Ho + Y) * Wo + X] = a0;
     out[(((size_t)n * out_ctot + out_c0 + 1) * Ho + Y) * Wo + X] = a1;
   }
+}
+
+// conv3x3_c2_gather and deconv4x4s2_c2 in one launch, for the decoder stages whose flow is up-sampled at once.  A block takes a tile of
+// kFuseT x kFuseT flow pixels of one sample: its first 2 (kFuseT + 2)^2 threads gather the tile's flows and a border of one pixel around it
+// (both channels) with the gather's own expression -- one round trip with 9 NSPLIT loads per thread in flight, as in conv3x3_c2_gather --
+// into LDS, the tile's own pixels also into `flow`; then every thread up-samples one of the tile's 2 kFuseT x 2 kFuseT output pixels from
+// LDS with the deconvolution's fma chain as written there.  Both results have the bits of the two launches; what goes is a launch and the
+// flow's trip through memory, for 1.56 x the gathers.  (A first form, one thread per up-sampled pixel gathering its 2 x 2 flows itself,
+// ran 8 dependent rounds of 9 NSPLIT loads per thread: 19 us against 6.3 + 4.8 us of the two launches at NSPLIT = 8.)
+constexpr int kFuseT = 8, kFuseB = kFuseT + 2;
+static_assert(2 * kFuseB * kFuseB <= 256 && 4 * kFuseT * kFuseT == 256, "one gather and one up-sampled pixel per thread");
+
+template <int NSPLIT>
+__global__ void __launch_bounds__(256) conv3x3_c2_gather_deconv4x4s2(const float* __restrict__ P, const float* __restrict__ bias,
+                                                                      const float* __restrict__ wup, const float* __restrict__ bias_up,
+                                                                      float* __restrict__ flow, float* __restrict__ up,
+                                                                      int N, int H, int W, int tiles_x, int up_ctot, int up_c0) {
+  __shared__ float sflow[2][kFuseB][kFuseB];
+  const int t = threadIdx.x;
+  const int y0 = (int)(blockIdx.x / tiles_x) * kFuseT, x0 = (int)(blockIdx.x % tiles_x) * kFuseT;
+  const unsigned n = blockIdx.y;
+  if (t < 2 * kFuseB * kFuseB) {
+    const int c = t / (kFuseB * kFuseB), r = t % (kFuseB * kFuseB), ly = r / kFuseB, lx = r % kFuseB;
+    const int iy = y0 - 1 + ly, ix = x0 - 1 + lx;
+    float v = 0.f;                                  // (outside the image: the up-sampling never reads it)
+    if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+      v = gather_flow<NSPLIT>(P, bias, N, H, W, n, c, iy, ix);
+      if (ly >= 1 && ly <= kFuseT && lx >= 1 && lx <= kFuseT) flow[(((size_t)n * 2 + c) * H + iy) * W + ix] = v;
+    }
+    sflow[c][ly][lx] = v;
+  }
+  __syncthreads();
+  const int Ho = 2 * H, Wo = 2 * W;
+  const int Y = 2 * y0 + t / (2 * kFuseT), X = 2 * x0 + t % (2 * kFuseT);
+  if (Y >= Ho || X >= Wo) return;
+  float a0 = bias_up ? bias_up[0] : 0.f, a1 = bias_up ? bias_up[1] : 0.f;
+#pragma unroll
+  for (int ty = 0; ty < 2; ++ty) {
+    const int ky = ((Y + 1) & 1) + 2 * ty;            // kernel rows with (Y + 1 - ky) even
+    const int iy = (Y + 1 - ky) / 2;
+    if (Y + 1 - ky < 0 || iy >= H) continue;
+#pragma unroll
+    for (int tx = 0; tx < 2; ++tx) {
+      const int kx = ((X + 1) & 1) + 2 * tx;
+      const int ix = (X + 1 - kx) / 2;
+      if (X + 1 - kx < 0 || ix >= W) continue;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float v = sflow[c][iy - y0 + 1][ix - x0 + 1];
+        a0 = fmaf(wup[((c * 2 + 0) * 4 + ky) * 4 + kx], v, a0);
+        a1 = fmaf(wup[((c * 2 + 1) * 4 + ky) * 4 + kx], v, a1);
+      }
+    }
+  }
+  up[(((size_t)n * up_ctot + up_c0 + 0) * Ho + Y) * Wo + X] = a0;
+  up[(((size_t)n * up_ctot + up_c0 + 1) * Ho + Y) * Wo + X] = a1;
 }
 
 }  // namespace fn2
@@ -204,4 +268,39 @@ FN2_API int fn2_upsample_flow_deconv_forward_into(const float* in, const float* 
   const long long total = (long long)N * 4 * H * W;
   hipLaunchKernelGGL(deconv4x4s2_c2, dim3(blocks_for(total, 256, 4096)), dim3(256), 0, as_stream(stream), in, weight, bias, top, N, H, W, top_channels, top_c0);
   return check_launch("upsample_flow_deconv_forward_into");
+}
+
+// predict_flow and the upsample_flow behind it in two launches instead of three (conv3x3_c2_gather_deconv4x4s2): flow [N,2,H,W] and
+// channels [top_c0, top_c0 + 2) of top [N, top_channels, 2H, 2W], both with the bits of fn2_predict_flow_conv_forward followed by
+// fn2_upsample_flow_deconv_forward_into.  Same workspace as fn2_predict_flow_conv_forward.
+FN2_API int fn2_predict_upsample_flow_supported(int N, int C, int H, int W) {
+  return N >= 1 && C >= 1 && H >= 1 && W >= 1 && 2ll * N <= 65535 && 4ll * H * W < (1ll << 31);
+}
+
+FN2_API int fn2_predict_upsample_flow_forward_into(const float* in, const float* weight, const float* bias, float* flow,
+                                                   const float* up_weight, const float* up_bias, float* top,
+                                                   int N, int C, int H, int W, int top_channels, int top_c0,
+                                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (N < 0 || C < 1 || H < 1 || W < 1) return fail(FN2_ERR_INVALID_ARG, "predict_upsample_flow: bad shape [%d,%d,%d,%d]", N, C, H, W);
+  if (top_c0 < 0 || top_c0 + 2 > top_channels) return fail(FN2_ERR_INVALID_ARG, "predict_upsample_flow: channel slice outside the blob");
+  if (N == 0) return FN2_OK;
+  if (!in || !weight || !flow || !up_weight || !top) return fail(FN2_ERR_INVALID_ARG, "predict_upsample_flow: NULL blob pointer");
+  if (!fn2_predict_upsample_flow_supported(N, C, H, W)) return fail(FN2_ERR_UNSUPPORTED, "predict_upsample_flow: blob too large");
+  const size_t need = fn2_predict_flow_conv_workspace_bytes(N, C, H, W);
+  if (!workspace || workspace_bytes < need) return fail(FN2_ERR_WORKSPACE, "predict_upsample_flow: workspace too small (%zu < %zu)", workspace_bytes, need);
+  const long long total = (long long)N * H * W;
+  const unsigned blocks = (unsigned)((total + kHeadPix - 1) / kHeadPix);
+  const int nsplit = head_splits(N, C, H, W);
+  hipStream_t st = as_stream(stream);
+  float* P = reinterpret_cast<float*>(workspace);
+  hipLaunchKernelGGL(conv3x3_c2_taps<kHeadG>, dim3(blocks, nsplit), dim3(kHeadPix * kHeadG), 0, st, in, weight, P, N, C, H, W, nsplit);
+  const int tiles_x = (W + kFuseT - 1) / kFuseT;
+  const dim3 g2((unsigned)tiles_x * ((H + kFuseT - 1) / kFuseT), N);
+  switch (nsplit) {
+    case 1: hipLaunchKernelGGL(conv3x3_c2_gather_deconv4x4s2<1>, g2, dim3(256), 0, st, P, bias, up_weight, up_bias, flow, top, N, H, W, tiles_x, top_channels, top_c0); break;
+    case 2: hipLaunchKernelGGL(conv3x3_c2_gather_deconv4x4s2<2>, g2, dim3(256), 0, st, P, bias, up_weight, up_bias, flow, top, N, H, W, tiles_x, top_channels, top_c0); break;
+    case 4: hipLaunchKernelGGL(conv3x3_c2_gather_deconv4x4s2<4>, g2, dim3(256), 0, st, P, bias, up_weight, up_bias, flow, top, N, H, W, tiles_x, top_channels, top_c0); break;
+    default: hipLaunchKernelGGL(conv3x3_c2_gather_deconv4x4s2<8>, g2, dim3(256), 0, st, P, bias, up_weight, up_bias, flow, top, N, H, W, tiles_x, top_channels, top_c0); break;
+  }
+  return check_launch("predict_upsample_flow_forward_into");
 }

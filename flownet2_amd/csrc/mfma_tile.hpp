@@ -126,6 +126,7 @@ __device__ __forceinline__ typename WVec<MW>::T weight_load(const float* wl, int
 //   ring_wait          s_waitcnt vmcnt(n), n = the loads YOUNGER than the operand that may stay in flight (a smaller n is always
 //                      correct, only slower).  n must fold to a constant (an unrolled loop's counter does; it does not compile otherwise)
 //   ring_wait_either   one of two such waits, chosen at run time (the last chunk has fewer loads behind the operand)
+//   ring_wait_if_le    a further, tighter wait, taken or not at run time
 //   weight_landed      ties the operand to the waits in front of it: the MFMAs that read it stay behind them.  The waits themselves name
 //                      no register and branch inside one asm block: the k loop stays one basic block for the compiler, which therefore
 //                      never copies an operand that is still in flight on the way into a branch.
@@ -146,27 +147,43 @@ constexpr int vmcnt_clamp(int n) { return n < 63 ? n : 63; }      // the counter
 
 __device__ __forceinline__ void ring_wait(int n) { asm volatile("s_waitcnt vmcnt(%0)" ::"i"(vmcnt_clamp(n))); }
 
-// vmcnt(n_last) in the last chunk (`rest`, the chunks still to come, is 0), else vmcnt(n_else)
-__device__ __forceinline__ void ring_wait_either(int rest, int n_last, int n_else) {
+// vmcnt(n_short) when s < below, else vmcnt(n_full).  With s = the chunks still to come and below = 1: the last chunk, which has fewer
+// loads behind the operand.  below must fold to a constant.
+__device__ __forceinline__ void ring_wait_either(int s, int below, int n_short, int n_full) {
   asm volatile(
-      "s_cmp_eq_u32 %0, 0\n\t"
+      "s_cmp_lt_u32 %0, %1\n\t"
       "s_cbranch_scc1 .Lrwt_%=\n\t"
-      "s_waitcnt vmcnt(%2)\n\t"
+      "s_waitcnt vmcnt(%3)\n\t"
       "s_branch .Lrwe_%=\n"
       ".Lrwt_%=:\n\t"
-      "s_waitcnt vmcnt(%1)\n"
+      "s_waitcnt vmcnt(%2)\n"
       ".Lrwe_%=:"
       :
-      : "s"(rest), "i"(vmcnt_clamp(n_last)), "i"(vmcnt_clamp(n_else))
+      : "s"(s), "i"(below), "i"(vmcnt_clamp(n_short)), "i"(vmcnt_clamp(n_full))
       : "scc");
 }
 
-// weight_fetch unless this is the last chunk (rest == 0), which fetches nothing beyond its own k-steps
+// vmcnt(n) when s <= most, else nothing: behind a ring_wait, the tighter wait of a chunk that stops at a run-time k-step (conv_mfma.hip)
+__device__ __forceinline__ void ring_wait_if_le(int s, int most, int n) {
+  asm volatile(
+      "s_cmp_gt_u32 %0, %1\n\t"
+      "s_cbranch_scc1 .Lrwl_%=\n\t"
+      "s_waitcnt vmcnt(%2)\n"
+      ".Lrwl_%=:"
+      :
+      : "s"(s), "i"(most), "i"(vmcnt_clamp(n))
+      : "scc");
+}
+
+// weight_fetch of k-step i of the NEXT chunk unless that chunk has no such k-step: `ahead` = the k-steps it executes, 0 behind the last
+// chunk, which fetches nothing beyond its own k-steps.  (i = 0 with ahead = the chunks still to come: "unless this is the last chunk".)
+// i must fold to a constant, as ring_wait's n.
 template <int MW>
-__device__ __forceinline__ typename WVec<MW>::T weight_fetch_unless_last(int rest, const float* base, unsigned lane_bytes) {
+__device__ __forceinline__ typename WVec<MW>::T weight_fetch_unless_last(int ahead, int i, const float* base, unsigned lane_bytes) {
   typename WVec<MW>::T w;
 #define FN2_FETCH_UNLESS(INSN) \
-  asm volatile("s_cmp_eq_u32 %3, 0\n\ts_cbranch_scc1 .Lwfs_%=\n\t" INSN " %0, %1, %2\n.Lwfs_%=:" : "=v"(w) : "v"(lane_bytes), "s"(base), "s"(rest) : "scc")
+  asm volatile("s_cmp_le_u32 %3, %4\n\ts_cbranch_scc1 .Lwfs_%=\n\t" INSN " %0, %1, %2\n.Lwfs_%=:" \
+               : "=v"(w) : "v"(lane_bytes), "s"(base), "s"(ahead), "i"(i) : "scc")
   if constexpr (MW == 1) FN2_FETCH_UNLESS("global_load_dword");
   else if constexpr (MW == 2) FN2_FETCH_UNLESS("global_load_dwordx2");
   else FN2_FETCH_UNLESS("global_load_dwordx4");

@@ -638,6 +638,14 @@ def upsample_flow_deconv(x, weight, bias=None, out=None, out_c0=0):
     return run(x, weight, bias)
 
 
+def predict_upsample_flow(x, weight, bias, up_weight, up_bias, out, out_c0):
+    """predict_flow and the upsample_flow of it into out[:, out_c0:out_c0+2] with one launch less (no autograd): the flow, or None where
+    a gradient is needed or the kernel declines -- the caller then runs predict_flow_conv and upsample_flow_deconv."""
+    if _needs_grad(x, weight, bias) or _needs_grad(x, up_weight, up_bias):
+        return None
+    return ops.predict_upsample_flow_forward(x.contiguous(), weight.contiguous(), bias, up_weight.contiguous(), up_bias, out, out_c0)
+
+
 class _BiasLeakyReLU(torch.autograd.Function):
     """y -> leaky_relu(y + bias) in place on the convolution output (conv2d's backward does not need its output), with the
     fused backward: one pass for the activation gradient and the bias gradient."""

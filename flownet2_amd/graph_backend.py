@@ -56,6 +56,7 @@ class GraphBackend:
         self.own_conv, self.own_deconv = get("conv_mfma_relu") or _declines, get("deconv_relu") or _declines
         self.own_correlation_relu_into = get("correlation_relu_into") or _declines
         self._predict, self._upsample = get("predict_flow_conv"), get("upsample_flow_deconv")
+        self._predict_upsample = get("predict_upsample_flow")
         self._bias_act = get("conv_bias_leaky_relu")
         self._conv2d = get("lib_conv2d") or (lambda x, w, b, s, p: F.conv2d(x, w, b, stride=s, padding=p))
         self._deconv2d = get("lib_conv_transpose2d") or (lambda x, w, b, s, p: F.conv_transpose2d(x, w, b, stride=s, padding=p))
@@ -140,6 +141,17 @@ class GraphBackend:
         if out is not None:
             return self._upsample(x, P[name + ".w"], P[name + ".b"], out=out, out_c0=out_c0)
         return self._upsample(x, P[name + ".w"], P[name + ".b"])
+
+    def predict_upsample_flow(self, x, P, pname, uname, out, out_c0):
+        """predict_flow `pname` of x, and upsample_flow `uname` of it into channels [out_c0, out_c0 + 2) of `out`: (flow, written).  The
+        backend's one-launch form where it has one and takes the layer, else the two ops above; written is False when nothing wrote the
+        slice (no flow-head kernel that writes into a blob)."""
+        if self._predict_upsample is not None:
+            flow = self._predict_upsample(x, P[pname + ".w"], P[pname + ".b"], P[uname + ".w"], P[uname + ".b"], out, out_c0)
+            if flow is not None:
+                return flow, True
+        flow = self.predict_flow(x, P, pname)
+        return flow, self.upsample_flow(flow, P, uname, out=out, out_c0=out_c0) is not None
 
     def leaky_relu(self, x, name, slope=NEG_SLOPE):
         """A ReLU layer of the graph itself (the correlation's)."""

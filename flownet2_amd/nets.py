@@ -155,10 +155,11 @@ def _any_requires_grad(P) -> bool:
     return any(v.requires_grad for v in vals)
 
 
-def _refine_stage(P, skip, x, dname, flow, uname, be):
+def _refine_stage(P, skip, x, dname, flow, uname, be, upsampled=False):
     """One refinement Concat [skip | ReLU(deconv(x)) | upsampled flow].  `skip` is a tensor or a pair (concat blob, tensor) from
     _conv_into_concat: with a blob the Concat layer (concat_layer.cu:8-52) has nothing to copy -- the skip convolution already wrote its
-    channels there, and the deconvolution and the upsampled flow are written behind them by their own kernels."""
+    channels there, and the deconvolution and the upsampled flow are written behind them by their own kernels.  upsampled: _head_into_stage
+    has written the upsampled flow into the blob already."""
     blob, s = skip if isinstance(skip, tuple) else (None, skip)
     if blob is None:
         return torch.cat([s, be.deconv(x, P, dname), be.upsample_flow(flow, P, uname)], 1)
@@ -180,9 +181,20 @@ def _refine_stage(P, skip, x, dname, flow, uname, be):
         return _ConcatInPlace.apply(blob, s, part(d, cs, cd), part(u, cs + cd, 2))
     if d is None:
         blob[:, cs:cs + cd].copy_(be.deconv(x, P, dname))
-    if be.upsample_flow(flow, P, uname, out=blob, out_c0=cs + cd) is None:
+    if not upsampled and be.upsample_flow(flow, P, uname, out=blob, out_c0=cs + cd) is None:
         blob[:, cs + cd:].copy_(be.upsample_flow(flow, P, uname))
     return blob
+
+
+def _head_into_stage(P, x, pname, skip, dname, uname, be):
+    """predict_flow `pname` of x for the stage _refine_stage(P, skip, x, dname, flow, uname) that follows: (flow, upsampled).  Without
+    autograd and with a Concat blob, the flow is up-sampled into its slice of that blob on the way (be.predict_upsample_flow: one launch
+    less per stage), and the stage is told so."""
+    blob, s = skip if isinstance(skip, tuple) else (None, skip)
+    params = [P[n + k] for n in (pname, dname, uname) for k in (".w", ".b")]
+    if blob is None or (torch.is_grad_enabled() and (s.requires_grad or x.requires_grad or any(p.requires_grad for p in params))):
+        return be.predict_flow(x, P, pname), False
+    return be.predict_upsample_flow(x, P, pname, uname, blob, s.shape[1] + P[dname + ".w"].shape[1])
 
 
 def _decoder(P, conv6_1, conv5_1, conv4_1, conv3_1, conv2, be):
@@ -193,14 +205,14 @@ def _decoder(P, conv6_1, conv5_1, conv4_1, conv3_1, conv2, be):
     # 2.343 without -- the fork / join event pairs cost more than ~90 us of head kernels can hide behind GEMMs that fill every CU.  The branch was
     # removed in round 5; what a second stream pays for is LONG independent chains: FlowNet-SD beside the CSS stack, weight gradients beside data
     # gradients.)
-    flow6 = be.predict_flow(conv6_1, P, "Convolution1")
-    c5 = _refine_stage(P, conv5_1, conv6_1, "deconv5", flow6, "upsample_flow6to5", be)
-    flow5 = be.predict_flow(c5, P, "Convolution2")
-    c4 = _refine_stage(P, conv4_1, c5, "deconv4", flow5, "upsample_flow5to4", be)
-    flow4 = be.predict_flow(c4, P, "Convolution3")
-    c3 = _refine_stage(P, conv3_1, c4, "deconv3", flow4, "upsample_flow4to3", be)
-    flow3 = be.predict_flow(c3, P, "Convolution4")
-    c2 = _refine_stage(P, conv2, c3, "deconv2", flow3, "upsample_flow3to2", be)
+    flow6, up = _head_into_stage(P, conv6_1, "Convolution1", conv5_1, "deconv5", "upsample_flow6to5", be)
+    c5 = _refine_stage(P, conv5_1, conv6_1, "deconv5", flow6, "upsample_flow6to5", be, up)
+    flow5, up = _head_into_stage(P, c5, "Convolution2", conv4_1, "deconv4", "upsample_flow5to4", be)
+    c4 = _refine_stage(P, conv4_1, c5, "deconv4", flow5, "upsample_flow5to4", be, up)
+    flow4, up = _head_into_stage(P, c4, "Convolution3", conv3_1, "deconv3", "upsample_flow4to3", be)
+    c3 = _refine_stage(P, conv3_1, c4, "deconv3", flow4, "upsample_flow4to3", be, up)
+    flow3, up = _head_into_stage(P, c3, "Convolution4", conv2, "deconv2", "upsample_flow3to2", be)
+    c2 = _refine_stage(P, conv2, c3, "deconv2", flow3, "upsample_flow3to2", be, up)
     flow2 = be.predict_flow(c2, P, "Convolution5")
     return {2: flow2, 3: flow3, 4: flow4, 5: flow5, 6: flow6}
 

@@ -714,6 +714,28 @@ def upsample_flow_deconv_forward(x, weight, bias=None, out=None, out_c0=0):
     return out
 
 
+def predict_upsample_flow_forward(x, weight, bias, up_weight, up_bias, out, out_c0):
+    """predict_flow_conv_forward(x) and upsample_flow_deconv_forward of it into out[:, out_c0:out_c0+2], the gather and the up-sampling
+    in one launch (same bits).  Returns the flow [N,2,H,W], or None where the one-launch form declines the geometry."""
+    x, w, uw = _chk(x, "bottom[0]"), _chk(weight, "weight"), _chk(up_weight, "upsample weight")
+    N, Cc, H, W = x.shape
+    if tuple(w.shape) != (2, Cc, 3, 3) or tuple(uw.shape) != (2, 2, 4, 4):
+        raise ValueError(f"predict_upsample_flow: weights must be [2,{Cc},3,3] and [2,2,4,4], got {tuple(w.shape)} and {tuple(uw.shape)}")
+    _chk(out, "top[0]")
+    if out.shape[0] != N or tuple(out.shape[2:]) != (2 * H, 2 * W):
+        raise ValueError(f"predict_upsample_flow: top blob {tuple(out.shape)} does not match [{N},*,{2 * H},{2 * W}]")
+    if not _lib.lib().fn2_predict_upsample_flow_supported(N, Cc, H, W):
+        return None
+    b = _chk(bias, "bias", ndim=1) if bias is not None else None
+    ub = _chk(up_bias, "upsample bias", ndim=1) if up_bias is not None else None
+    flow = torch.empty((N, 2, H, W), device=x.device, dtype=torch.float32)
+    nbytes = _lib.lib().fn2_predict_flow_conv_workspace_bytes(N, Cc, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    check(_lib.lib().fn2_predict_upsample_flow_forward_into(_ptr(x), _ptr(w), _ptr(b), _ptr(flow), _ptr(uw), _ptr(ub), _ptr(out), N, Cc, H, W,
+                                                            out.shape[1], int(out_c0), _ptr(ws), nbytes, _stream()))
+    return flow
+
+
 def bias_leaky_relu_(x, bias=None, negative_slope=0.1):
     """In place: x[n,c] = leaky_relu(x[n,c] + bias[c]) -- the bias term + ReLU layer that follow every FlowNet conv/deconv."""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):

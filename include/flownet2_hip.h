@@ -294,6 +294,7 @@ int fn2_upsample_flow_deconv_backward(const float* bottom, const float* weight, 
  * the last input of the refinement stages' Concat layers (concat_layer.cu:8-52), which then has nothing left to copy. */
 int fn2_upsample_flow_deconv_forward_into(const float* in, const float* weight, const float* bias, float* top,
                                           int N, int H, int W, int top_channels, int top_c0, void* stream);
+/* (The gather and this layer in one launch: include/flownet2_hip_flow_head.h.) */
 
 /* ------------------------------------------------------------------------------------------------
  * Convolution bias + leaky ReLU, in place (one pass): top[n,c,:,:] = f(top[n,c,:,:] + bias[c]), f(t) = t > 0 ? t : t * negative_slope.
