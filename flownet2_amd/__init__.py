@@ -9,6 +9,8 @@ LpqSchedule  the p / q episodes of LpqLoss (lpq_schedule.py)
 evaluate   FlowMetrics (the rows of the metrics kernel, summary()), ground-truth readers incl. the KITTI flow PNG, the data-set loop
 flow_consistency  forward-backward consistency of two flows -> FlowConsistency (occlusion masks, rows, summary()) in one launch
 visualize  flow_to_color (Middlebury colour coding) and flow_error_map (KITTI-style error image) on fused kernels, color_wheel, write_png
+unsupervised_loss  photometric + smoothness training loss without ground truth, one fused pass per direction of differentiation;
+            unsupervised_loss_report -> UnsupLoss (rows, summary())
 flow_track  points carried through a flow sequence in one launch -> FlowTracks (trajectories, long_range_flow()); flow_track_reseed, flow_track_grid
 """
 from . import _lib  # noqa: F401
@@ -16,7 +18,7 @@ from ._lib import Fn2Error, version  # noqa: F401
 
 _SOLVER_EXPORTS = ("SolverParameter", "Solver", "SGDSolver", "AdamSolver", "get_solver", "CaffeOptimizer")
 __all__ = ["Fn2Error", "version", "LpqSchedule", "flow_consistency", "FlowConsistency", "flow_to_color", "flow_error_map", "flow_track",
-           "flow_track_reseed", "flow_track_grid", "FlowTracks", *_SOLVER_EXPORTS]
+           "flow_track_reseed", "flow_track_grid", "FlowTracks", "unsupervised_loss", "unsupervised_loss_report", "UnsupLoss", *_SOLVER_EXPORTS]
 
 
 def __getattr__(name):
@@ -30,7 +32,8 @@ def __getattr__(name):
     if name == "flow_consistency":
         from .functional import flow_consistency
         return flow_consistency
-    if name in ("flow_to_color", "flow_error_map", "flow_track", "flow_track_reseed", "flow_track_grid"):
+    if name in ("flow_to_color", "flow_error_map", "flow_track", "flow_track_reseed", "flow_track_grid", "unsupervised_loss",
+                "unsupervised_loss_report"):
         from . import functional
         return getattr(functional, name)
     if name == "FlowConsistency":
@@ -39,4 +42,7 @@ def __getattr__(name):
     if name == "FlowTracks":
         from .evaluate import FlowTracks
         return FlowTracks
+    if name == "UnsupLoss":
+        from .evaluate import UnsupLoss
+        return UnsupLoss
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -182,6 +182,56 @@ class FlowConsistency:
                           allow_nan=False) + "\n"
 
 
+# ---- unsupervised loss ---------------------------------------------------------------------------------------------------------------
+_U_PREFIX = "FN2_UNSUP_LOSS_"
+_U_ENUM = _lib.UNSUP_LOSS_CONSTANTS                                        # include/flownet2_hip_unsup_loss.h: the columns of a row
+UNSUP_LOSS_K = _U_ENUM[_U_PREFIX + "K"]
+UNSUP_LOSS_COLUMNS = tuple(sorted((n[len(_U_PREFIX):] for n in _U_ENUM if n != _U_PREFIX + "K"), key=lambda n: _U_ENUM[_U_PREFIX + n]))
+UNSUP_LOSS_COL = {name: i for i, name in enumerate(UNSUP_LOSS_COLUMNS)}
+
+
+class UnsupLoss:
+    """The [n, K] float64 rows (columns UNSUP_LOSS_COLUMNS) of n samples per direction of functional.unsupervised_loss_report, and the
+    loss of the call (None for rows put together by hand).  rows_bw is all zeros where no backward flow was given."""
+
+    def __init__(self, rows_fw=None, rows_bw=None, loss=None, data_weight=1.0, smooth_weight=1.0):
+        def rows(r, what):
+            r = np.zeros((0, UNSUP_LOSS_K), np.float64) if r is None else np.array(r, dtype=np.float64)
+            if r.ndim != 2 or r.shape[1] != UNSUP_LOSS_K:
+                raise ValueError(f"UnsupLoss: {what} must be [n, {UNSUP_LOSS_K}], got {r.shape}")
+            return r
+        self.rows_fw = rows(rows_fw, "rows_fw")
+        self.rows_bw = rows(rows_bw if rows_bw is not None else np.zeros_like(self.rows_fw), "rows_bw")
+        if self.rows_fw.shape != self.rows_bw.shape:
+            raise ValueError(f"UnsupLoss: {self.rows_fw.shape[0]} forward rows, {self.rows_bw.shape[0]} backward rows")
+        self.loss = None if loss is None else float(loss)
+        self.data_weight, self.smooth_weight = float(data_weight), float(smooth_weight)
+
+    def __len__(self):
+        return self.rows_fw.shape[0]
+
+    @staticmethod
+    def _direction(rows):
+        tot = lambda name: float(np.sum(rows[:, UNSUP_LOSS_COL[name]]))
+        pixels = tot("PIXELS")
+        return {
+            "data_mean": _ratio(tot("DATA_SUM"), tot("COUNTED")),
+            "smooth_mean": _ratio(tot("SMOOTH_SUM"), tot("SMOOTH_TERMS")),
+            "counted": _ratio(tot("COUNTED"), pixels),
+            "occluded": _ratio(tot("OCCLUDED"), pixels),
+            "outside": _ratio(tot("OUTSIDE"), pixels),
+            "nonfinite": _ratio(tot("NONFINITE"), pixels),
+            "pixels": int(pixels),
+        }
+
+    def summary(self):
+        """Per direction the mean data term over the counted pixels, the mean smoothness term, the shares of all pixels that were
+        counted, occluded, outside and non-finite, and the pixel count; then the sample count, the weights and the loss.  A quotient with
+        a zero denominator is nan."""
+        return {"fw": self._direction(self.rows_fw), "bw": self._direction(self.rows_bw), "samples": len(self),
+                "data_weight": self.data_weight, "smooth_weight": self.smooth_weight, "loss": self.loss}
+
+
 def write_pgm(path, plane):
     """A [H,W] (or [1,H,W]) plane -> 8-bit binary PGM (P5, maxval 255): 255 where the plane is non-zero, else 0."""
     a = np.asarray(plane)

@@ -472,6 +472,61 @@ def flow_consistency(fw, bw, *, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=Fal
     return FlowConsistency(rows[0], rows[1], occ=occ, flags=fl, err=er, warped=wa, alpha=alpha, beta=beta)
 
 
+class _UnsupLoss(torch.autograd.Function):
+    """Forward two launches, backward one; the normalisers and the upstream gradient stay on the device (as _LpqLossMulti)."""
+
+    @staticmethod
+    def forward(ctx, img0, img1, fw, bw, occ_fw, occ_bw, params):
+        results, loss = ops.unsup_loss_forward(img0, img1, fw, bw, occ_fw, occ_bw, params)
+        ctx.params, ctx.results = params, results
+        ctx.save_for_backward(img0, img1, fw, bw, occ_fw, occ_bw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        img0, img1, fw, bw, occ_fw, occ_bw = ctx.saved_tensors
+        need_bw = bw is not None and ctx.needs_input_grad[3]
+        fd, bd = ops.unsup_loss_backward(img0, img1, fw, bw, occ_fw, occ_bw, ctx.params, ctx.results, g.contiguous(), need_bw=need_bw)
+        return None, None, (fd if ctx.needs_input_grad[2] else None), (bd if need_bw else None), None, None, None
+
+
+def _unsup_loss_args(what, img0, img1, fw, bw, occ_fw, occ_bw, kw):
+    for name, t in (("img0", img0), ("img1", img1), ("occ_fw", occ_fw), ("occ_bw", occ_bw)):
+        if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{what}: {name} gets no gradient (the flows alone do): detach it")
+    blobs = tuple(t.contiguous() if t is not None else None for t in (img0, img1, fw, bw, occ_fw, occ_bw))
+    return blobs, ops.unsup_loss_params(**kw)
+
+
+def unsupervised_loss(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, *, data_weight=1.0, smooth_weight=1.0, charbonnier=(1e-3, 0.45),
+                      smooth_charbonnier=(1e-3, 0.45), edge_weight=10.0, smooth_order=2, flow_mult=1.0):
+    """The unsupervised training loss (csrc/unsup_loss.hip; the arithmetic is stated in include/flownet2_hip_unsup_loss.h) of a forward
+    flow fw [N,2,H,W] (frame 0 to frame 1) and, where given, a backward flow bw on the images img0, img1 [N,C,H,W], C up to 4: per
+    direction data_weight times the mean over the counted pixels of sum_c psi(I_own - I_other warped by the flow) plus smooth_weight times
+    the mean of the smoothness terms exp(-edge_weight mean_c |dI|) (psi(d u) + psi(d v)) of first or second order, psi(t) =
+    (t^2 + eps^2)^gamma with (eps, gamma) = charbonnier for the data and smooth_charbonnier for the smoothness term.  occ_fw / occ_bw
+    [N,1,H,W]: non-zero leaves the pixel out of the data term (flow_consistency's .occ_fw / .occ_bw go in as they are).  The flows are
+    multiplied by flow_mult first.  Returns the 0-axis device loss; gradients for fw and bw only."""
+    blobs, params = _unsup_loss_args("unsupervised_loss", img0, img1, fw, bw, occ_fw, occ_bw, dict(
+        data_weight=data_weight, smooth_weight=smooth_weight, charbonnier=charbonnier, smooth_charbonnier=smooth_charbonnier,
+        edge_weight=edge_weight, smooth_order=smooth_order, flow_mult=flow_mult))
+    return _UnsupLoss.apply(*blobs, params)
+
+
+def unsupervised_loss_report(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, *, data_weight=1.0, smooth_weight=1.0,
+                             charbonnier=(1e-3, 0.45), smooth_charbonnier=(1e-3, 0.45), edge_weight=10.0, smooth_order=2, flow_mult=1.0):
+    """unsupervised_loss's forward without autograd, as an evaluate.UnsupLoss: the rows per direction and sample (counted, occluded,
+    outside and non-finite pixels, the data and smoothness sums) and the loss; summary() gives the means and shares."""
+    from .evaluate import UnsupLoss
+    with torch.no_grad():
+        blobs, params = _unsup_loss_args("unsupervised_loss_report", img0, img1, fw, bw, occ_fw, occ_bw, dict(
+            data_weight=data_weight, smooth_weight=smooth_weight, charbonnier=charbonnier, smooth_charbonnier=smooth_charbonnier,
+            edge_weight=edge_weight, smooth_order=smooth_order, flow_mult=flow_mult))
+        results, loss = ops.unsup_loss_forward(*blobs, params)
+    rows = results[:, :-1].cpu().numpy()
+    return UnsupLoss(rows[0], rows[1], loss=float(loss), data_weight=data_weight, smooth_weight=smooth_weight)
+
+
 def _no_grad_inputs(what, tensors):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
         raise RuntimeError(f"{what} is not differentiable: detach the inputs or call it under torch.no_grad()")

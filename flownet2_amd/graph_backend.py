@@ -45,7 +45,8 @@ class GraphBackend:
     # the custom-layer ops (and their *_slices / one-launch forms) the graphs call by name: bound when the object has them; one it lacks
     # fails when it is called, with the object's own AttributeError that names it.  Nothing else of the object is reachable through the adapter.
     FORWARDED = ("correlation", "resample", "flow_warp", "channel_norm", "downsample", "l1_loss", "scale_shift", "resample_slices",
-                 "flow_warp_slices", "channel_norm_slices", "l1_loss_multi", "downsample_ahead", "wait_ahead", "lpq_loss", "lpq_loss_multi")
+                 "flow_warp_slices", "channel_norm_slices", "l1_loss_multi", "downsample_ahead", "wait_ahead", "lpq_loss", "lpq_loss_multi",
+                 "unsupervised_loss", "flow_consistency")
 
     def __init__(self, obj):
         get = lambda name: getattr(obj, name, None)
@@ -72,6 +73,7 @@ class GraphBackend:
         self.has_stem_chain = self.trains_in_place and self.conv_route_name is not None and self.relu_chain_supported is not None
         self.has_multi_loss = get("l1_loss_multi") is not None          # the five loss layers in one launch
         self.has_multi_lpq_loss = get("lpq_loss_multi") is not None     # the same for loss=("lpq", ...)
+        self.has_unsupervised_loss = get("unsupervised_loss") is not None      # the fused photometric + smoothness loss (nets.unsupervised_loss)
         self.targets_ahead = get("downsample_ahead") is not None        # the loss's target pyramid on a second stream
 
     def __getattr__(self, name):

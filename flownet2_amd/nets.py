@@ -504,6 +504,40 @@ def multiscale_loss(flows, gt_flow, backend, targets=None, loss=None):
     return total
 
 
+def unsupervised_loss(flows_fw, flows_bw, img0, img1, backend, occ="consistency", **kw):
+    """Training loss without ground truth: per scale s of LOSS_WEIGHTS that flows_fw holds, LOSS_WEIGHTS[s] times the backend's
+    unsupervised_loss (photometric + smoothness, both directions) of flows_fw[s] and flows_bw[s] on the images brought to that scale with
+    Downsample; the weighted sum in list order.  The predictions are in FlowNet's 1/20 units of full-resolution pixels, so flow_mult =
+    FLOW_SCALE * w_s / W makes them pixels of the scale.  occ="consistency": the occlusion planes of the data term come from the
+    backend's flow_consistency on the detached, rescaled flows of the scale; None: no pixel is masked.  kw: the keyword arguments of
+    functional.unsupervised_loss (weights, Charbonnier constants, edge_weight, smooth_order)."""
+    backend = backend_of(backend)
+    if not backend.has_unsupervised_loss:
+        raise RuntimeError("unsupervised_loss: the backend has no unsupervised_loss op (there is no composed fallback)")
+    if occ not in ("consistency", None):
+        raise ValueError('unsupervised_loss: occ must be "consistency" or None, got %r' % (occ,))
+    if "flow_mult" in kw:
+        raise ValueError("unsupervised_loss: flow_mult is set per scale (FLOW_SCALE * w_s / W)")
+    W = img0.shape[3]
+    total = None
+    for s, weight in LOSS_WEIGHTS.items():
+        if s not in flows_fw:
+            continue
+        fw, bw = flows_fw[s], flows_bw[s]
+        h, w = fw.shape[2], fw.shape[3]
+        mult = FLOW_SCALE * w / W
+        i0, i1 = backend.downsample(img0, h, w), backend.downsample(img1, h, w)
+        occ_fw = occ_bw = None
+        if occ is not None:
+            c = backend.flow_consistency(fw.detach() * mult, bw.detach() * mult)
+            occ_fw, occ_bw = c.occ_fw, c.occ_bw
+        term = backend.unsupervised_loss(i0, i1, fw, bw, occ_fw, occ_bw, flow_mult=mult, **kw) * weight
+        total = term if total is None else total + term
+    if total is None:
+        raise ValueError("unsupervised_loss: flows_fw holds no scale of LOSS_WEIGHTS")
+    return total
+
+
 # FLOP model (multiply-add = 2 flops) used by bench.py
 def conv_flops(kind: str, h: int, w: int, in_channels: int = 6) -> float:
     fl = 0.0

@@ -500,6 +500,76 @@ def flow_consistency(fw, bw, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=False,
     return results, occ, fl, er, wa
 
 
+_UNSUP_LOSS_K = _lib.UNSUP_LOSS_CONSTANTS["FN2_UNSUP_LOSS_K"]      # columns of a results row (evaluate.UNSUP_LOSS_COLUMNS)
+
+
+def unsup_loss_sizes(N: int, H: int, W: int):
+    """(workspace bytes for [N,*,H,W], K) of fn2_unsup_loss_forward (include/flownet2_hip_unsup_loss.h)."""
+    nbytes, k = C.c_size_t(), C.c_int()
+    check(_lib.lib().fn2_unsup_loss_sizes(int(N), int(H), int(W), C.byref(nbytes), C.byref(k)))
+    return nbytes.value, k.value
+
+
+def unsup_loss_params(data_weight=1.0, smooth_weight=1.0, charbonnier=(1e-3, 0.45), smooth_charbonnier=(1e-3, 0.45), edge_weight=10.0,
+                      smooth_order=2, flow_mult=1.0):
+    """The scalar arguments of fn2_unsup_loss_forward / _backward, in their order, as ctypes values."""
+    (eps_d, gamma_d), (eps_s, gamma_s) = charbonnier, smooth_charbonnier
+    return (*(C.c_float(float(v)) for v in (data_weight, smooth_weight, eps_d, gamma_d, eps_s, gamma_s, edge_weight)), int(smooth_order),
+            C.c_float(float(flow_mult)))
+
+
+def _unsup_loss_blobs(what, img0, img1, fw, bw, occ_fw, occ_bw):
+    i0, i1, f = _chk(img0, "img0"), _chk(img1, "img1"), _chk(fw, "fw")
+    b, of, ob = _chk_opt(bw, "bw"), _chk_opt(occ_fw, "occ_fw"), _chk_opt(occ_bw, "occ_bw")
+    N, Cc, H, W = i0.shape
+    if i1.shape != i0.shape:
+        raise ValueError(f"{what}: img0 {tuple(i0.shape)} and img1 {tuple(i1.shape)} must have one shape")
+    for name, t, ch in (("fw", f, 2), ("bw", b, 2), ("occ_fw", of, 1), ("occ_bw", ob, 1)):
+        if t is not None and tuple(t.shape) != (N, ch, H, W):
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} must be [{N},{ch},{H},{W}]")
+        if t is not None and t.device != i0.device:
+            raise ValueError(f"{what}: {name} on {t.device}, img0 on {i0.device}")
+    if i1.device != i0.device:
+        raise ValueError(f"{what}: img1 on {i1.device}, img0 on {i0.device}")
+    if ob is not None and b is None:
+        raise ValueError(f"{what}: occ_bw without a bw")
+    return (i0, i1, f, b, of, ob), (N, Cc, H, W)
+
+
+def unsup_loss_forward(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, params=None, loss=True):
+    """The unsupervised loss (csrc/unsup_loss.hip) of fw (frame 0 -> 1) and, where given, bw (frame 1 -> 0) [N,2,H,W] on the images
+    [N,C,H,W]; occ_* [N,1,H,W] or None; params: unsup_loss_params(...).  Returns (results [2, N + 1, K] float64 on the device: per
+    direction one row per sample and the totals row, columns evaluate.UNSUP_LOSS_COLUMNS; the loss, a 0-axis device tensor, or None)."""
+    blobs, (N, Cc, H, W) = _unsup_loss_blobs("unsup_loss_forward", img0, img1, fw, bw, occ_fw, occ_bw)
+    dev = blobs[0].device
+    ws = torch.empty(unsup_loss_sizes(N, H, W)[0], dtype=torch.uint8, device=dev)
+    results = torch.empty((2, N + 1, _UNSUP_LOSS_K), dtype=torch.float64, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev) if loss else None
+    check(_lib.lib().fn2_unsup_loss_forward(*(_ptr(t) for t in blobs), N, Cc, H, W, *(params or unsup_loss_params()), _ptr(results), _ptr(out),
+                                            _ptr(ws), ws.numel(), _stream()))
+    return results, out
+
+
+def unsup_loss_backward(img0, img1, fw, bw, occ_fw, occ_bw, params, results, total_diff=None, need_bw=True):
+    """The gradient of unsup_loss_forward's loss for fw and (need_bw, with a bw) bw, times total_diff (a device scalar; None: 1);
+    results: what the forward returned for the same inputs.  Returns (fw_diff, bw_diff or None), each [N,2,H,W]."""
+    blobs, (N, Cc, H, W) = _unsup_loss_blobs("unsup_loss_backward", img0, img1, fw, bw, occ_fw, occ_bw)
+    dev = blobs[0].device
+    if not isinstance(results, torch.Tensor) or results.dtype != torch.float64 or tuple(results.shape) != (2, N + 1, _UNSUP_LOSS_K) or \
+            results.device != dev or not results.is_contiguous():
+        raise ValueError(f"unsup_loss_backward: results must be the forward's float64 [2,{N + 1},{_UNSUP_LOSS_K}] on {dev}")
+    g = None
+    if total_diff is not None:
+        g = _chk(total_diff, "total_diff", None)
+        if g.numel() != 1 or g.device != dev:
+            raise ValueError(f"unsup_loss_backward: total_diff must be one float on {dev}")
+    fd = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev)
+    bd = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev) if need_bw and blobs[3] is not None else None
+    check(_lib.lib().fn2_unsup_loss_backward(*(_ptr(t) for t in blobs), N, Cc, H, W, *params, _ptr(results), _ptr(g), _ptr(fd), _ptr(bd),
+                                             _stream()))
+    return fd, bd
+
+
 _FLOW_TRACK_K = _lib.FLOW_TRACK_CONSTANTS["FN2_FLOW_TRACK_K"]      # columns of a results row (evaluate.TRACK_COLUMNS)
 
 

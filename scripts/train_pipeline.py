@@ -13,7 +13,10 @@ of iteration i are a function of (seed, i), so a worker PROCESS (augment.Coeffic
 step and the "draw" stages below are what the step WAITS for them; --prefetch-thread uses a background thread instead (no gain: it competes
 with the step's own Python for the interpreter lock), --no-prefetch draws inline (the r02 behaviour).  Everything downstream of
 the coefficient blobs is pinned against the reference's layers.
-Usage: python scripts/train_pipeline.py [--batch 8] [--iters 10] [--no-train] [--no-prefetch]"""
+--unsupervised trains without the ground truth: FlowNetC on (img0, img1) and on (img1, img0), nets.unsupervised_loss (photometric +
+smoothness, csrc/unsup_loss.hip) on the two pyramids; the ground truth the records carry is used only to print the EPE (flow_metrics).
+Usage: python scripts/train_pipeline.py [--batch 8] [--iters 10] [--no-train] [--no-prefetch]
+       [--unsupervised [--unsup-smooth W] [--unsup-order 1|2] [--unsup-no-occlusion]]"""
 import argparse
 import os
 import statistics
@@ -59,7 +62,7 @@ def draw_pair(it, B, W, H, cw, ch):
     return p0, p1
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=10)
@@ -76,7 +79,16 @@ def main():
     Fn.add_arithmetic_flags(ap, ARITH, notes={"wino": " (forward only: every gradient stays exact fp32)"})
     Fn.add_general_convolution_flag(ap)
     Fn.add_loss_flags(ap)
-    a = ap.parse_args()
+    ap.add_argument("--unsupervised", action="store_true",
+                    help="train on nets.unsupervised_loss (photometric + smoothness, both directions) instead of the ground-truth loss")
+    ap.add_argument("--unsup-smooth", type=float, default=1.0, metavar="W", help="smooth_weight of the unsupervised loss")
+    ap.add_argument("--unsup-order", type=int, default=2, choices=(1, 2), help="order of its smoothness term")
+    ap.add_argument("--unsup-no-occlusion", action="store_true", help="do not mask its data term with flow_consistency's occlusion planes")
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     schedule = Fn.loss_schedule(a)
     Fn.apply_arithmetic_flags(a, ARITH)
     Fn.apply_general_convolution_flag(a)
@@ -146,7 +158,13 @@ def main():
             opt.zero_grad(set_to_none=not a.solver)
             # --loss lpq: the episode of this iteration (the solver's, with --solver), as Solver::Step hands it to the net
             spec = None if schedule is None else ("lpq",) + schedule.at(opt.iter_ if a.solver else it) + (a.lpq_p_epsilon, a.lpq_q_epsilon)
-            loss = nets.multiscale_loss(nets.flownet_c_core(P, t_img0[0].data, t_img1[0].data, Fn), t_flow[0].data, Fn, loss=spec)
+            if a.unsupervised:
+                i0, i1 = t_img0[0].data, t_img1[0].data
+                flows_fw, flows_bw = nets.flownet_c_core(P, i0, i1, Fn), nets.flownet_c_core(P, i1, i0, Fn)
+                loss = nets.unsupervised_loss(flows_fw, flows_bw, i0, i1, Fn, occ=None if a.unsup_no_occlusion else "consistency",
+                                              smooth_weight=a.unsup_smooth, smooth_order=a.unsup_order)
+            else:
+                loss = nets.multiscale_loss(nets.flownet_c_core(P, t_img0[0].data, t_img1[0].data, Fn), t_flow[0].data, Fn, loss=spec)
             loss.backward()
             opt.step()
         marks[8].record()
@@ -164,7 +182,15 @@ def main():
     print("iteration (sum of the stages): %.3f ms" % sum(statistics.median(times[s_]) for s_ in stages))
     if not a.no_train:
         Fn.print_arithmetics(ARITH)
-        print("loss %.4f, NaN ground truth kept: %s" % (float(loss), bool(torch.isnan(t_flow[0].data).any())))
+        if a.unsupervised:
+            # the last batch's forward prediction at full resolution (deploy's x20 and Resample) against the ground truth of its records
+            with torch.no_grad():
+                pred = Fn.resample(flows_fw[2].detach() * nets.FLOW_SCALE, ch, cw)
+                epe = Fn.flow_metrics(pred, t_flow[0].data).summary()["epe"]
+            print("unsupervised loss %.4f (smooth weight %g, order %d, occlusion masks %s), EPE against the ground truth %.4f" % (
+                float(loss), a.unsup_smooth, a.unsup_order, "off" if a.unsup_no_occlusion else "on", epe))
+        else:
+            print("loss %.4f, NaN ground truth kept: %s" % (float(loss), bool(torch.isnan(t_flow[0].data).any())))
 
 
 if __name__ == "__main__":
