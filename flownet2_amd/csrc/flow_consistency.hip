@@ -14,18 +14,17 @@
 //
 // Reads stay inside the sample: the own-flow neighbours are clamped to the plane, and the tap indices are formed only after the finite
 // test and the inside test, from a coordinate in [0, W) x [0, H), and clamped to W - 1 and H - 1.
-#include "fn2_common.hpp"
+#include "stream_reduce.hpp"
 #include "../../include/flownet2_hip_flow_consistency.h"
 
 #pragma clang fp contract(off)
 
 namespace fn2 {
 
-constexpr int kFcThreads = 256;
+using namespace stream;
+
 constexpr int kFcK = FN2_FLOW_CONSISTENCY_K;
-constexpr int kFcPixelsPerBlock = 4 * kFcThreads;      // B = ceil(H W / this), at most kFcMaxChunks
-constexpr int kFcMaxChunks = 128;
-constexpr int kFcMaxGrid = 1 << 16;                    // work items beyond this are taken in a workgroup-stride loop
+constexpr unsigned kFcMaxMask = 1u << FN2_FLOW_CONSISTENCY_ERR_MAX;      // the column reduced by max
 constexpr unsigned kFcNonfinite = FN2_FLOW_CONSISTENCY_FLAG_NONFINITE, kFcOutside = FN2_FLOW_CONSISTENCY_FLAG_OUTSIDE,
                    kFcInconsistent = FN2_FLOW_CONSISTENCY_FLAG_INCONSISTENT, kFcBoundary = FN2_FLOW_CONSISTENCY_FLAG_BOUNDARY;
 constexpr unsigned kFcOccluded = kFcNonfinite | kFcOutside | kFcInconsistent;
@@ -52,29 +51,6 @@ struct FcAcc {
   float emax;
 };
 
-template <int V, bool VEC>
-__device__ __forceinline__ void fc_load(const float* __restrict__ p, float (&v)[V]) {
-  if constexpr (VEC) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = p[k];
-  }
-}
-
-template <int V, bool VEC>
-__device__ __forceinline__ void fc_store(float* __restrict__ p, const float (&v)[V]) {
-  if constexpr (VEC) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) p[k] = v[k];
-  }
-}
-
-__device__ __forceinline__ bool fc_ok(float x) { return fabsf(x) <= 1e9f; }      // false for NaN and +-Inf
-
 struct FcPixel {
   float err, bu, bv;
   unsigned flags;
@@ -86,14 +62,14 @@ __device__ __forceinline__ FcPixel fc_pixel(const FcArgs& a, const float* __rest
                                             float au, float av, const float (&n)[8]) {
   const float nan = __builtin_nanf("");
   FcPixel p = {nan, nan, nan, 0u};
-  if (!fc_ok(au) || !fc_ok(av)) {
+  if (!finite_1e9(au) || !finite_1e9(av)) {
     p.flags = kFcNonfinite;
     return p;
   }
   const float mag = au * au + av * av;
   bool nb = true;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) nb = nb && fc_ok(n[k]);
+  for (int k = 0; k < 8; ++k) nb = nb && finite_1e9(n[k]);
   if (nb) {
     const float ux = 0.5f * (n[1] - n[0]), uy = 0.5f * (n[3] - n[2]);
     const float vx = 0.5f * (n[5] - n[4]), vy = 0.5f * (n[7] - n[6]);
@@ -105,17 +81,12 @@ __device__ __forceinline__ FcPixel fc_pixel(const FcArgs& a, const float* __rest
     p.flags |= kFcOutside;
     return p;
   }
-  // 0 <= x2 < W here, so the conversion is defined; the min keeps the index inside where float(W) rounds up (W above 2^24)
-  const int ixL = min((int)x2, a.W - 1), iyT = min((int)y2, a.H - 1);
-  const int ixR = min(ixL + 1, a.W - 1), iyB = min(iyT + 1, a.H - 1);
-  const float al = x2 - (float)ixL, be = y2 - (float)iyT;
-  const float wTL = (1.f - al) * (1.f - be), wTR = al * (1.f - be), wBL = (1.f - al) * be, wBR = al * be;
-  const int oTL = iyT * a.W + ixL, oTR = iyT * a.W + ixR, oBL = iyB * a.W + ixL, oBR = iyB * a.W + ixR;
-  const float bu = ((wTL * ou[oTL] + wTR * ou[oTR]) + wBL * ou[oBL]) + wBR * ou[oBR];
-  const float bv = ((wTL * ov[oTL] + wTR * ov[oTR]) + wBL * ov[oBL]) + wBR * ov[oBR];
+  const BilinearTaps t = bilinear_taps(x2, y2, a.W, a.H);
+  const float bu = ((t.wTL * ou[t.oTL] + t.wTR * ou[t.oTR]) + t.wBL * ou[t.oBL]) + t.wBR * ou[t.oBR];
+  const float bv = ((t.wTL * ov[t.oTL] + t.wTR * ov[t.oTR]) + t.wBL * ov[t.oBL]) + t.wBR * ov[t.oBR];
   p.bu = bu;
   p.bv = bv;
-  if (!fc_ok(bu) || !fc_ok(bv)) {
+  if (!finite_1e9(bu) || !finite_1e9(bv)) {
     p.flags |= kFcNonfinite;
     return p;
   }
@@ -125,18 +96,6 @@ __device__ __forceinline__ FcPixel fc_pixel(const FcArgs& a, const float* __rest
   if (s > a.alpha1 * m + a.alpha2) p.flags |= kFcInconsistent;
   p.err = sqrtf(s);
   return p;
-}
-
-__device__ __forceinline__ double fc_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double fc_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  return v;
 }
 
 // Chunk `chunk` of (direction d, sample n): units chunk * 256 + thread, then every B * 256 further on; a unit is V pixels of one row.
@@ -151,18 +110,18 @@ __device__ __forceinline__ void fc_chunk(const FcArgs& a, int d, long long n, in
   const float* __restrict__ ou_ = a.flow[1 - d] + (size_t)n * 2 * hw;
   const float* __restrict__ ov_ = ou_ + hw;
   FcAcc t = {};
-  for (long long u = (long long)chunk * kFcThreads + threadIdx.x; u < units; u += (long long)a.chunks * kFcThreads) {
+  for (long long u = (long long)chunk * kThreads + threadIdx.x; u < units; u += (long long)a.chunks * kThreads) {
     const unsigned r = (unsigned)u * V;                                    // H W < 2^30
     const int y = (int)(r / (unsigned)W), x = (int)(r - (unsigned)y * W);  // V == 4: W % 4 == 0, so x % 4 == 0 and x + 3 < W
     const size_t rT = (size_t)max(y - 1, 0) * W + x, rB = (size_t)min(y + 1, H - 1) * W + x;
     const size_t rL = (size_t)y * W + max(x - 1, 0), rR = (size_t)y * W + min(x + V, W - 1);
     float cu[V], cv[V], tu[V], tv[V], bu[V], bv[V];
-    fc_load<V, VEC>(pu_ + r, cu);
-    fc_load<V, VEC>(pv_ + r, cv);
-    fc_load<V, VEC>(pu_ + rT, tu);
-    fc_load<V, VEC>(pv_ + rT, tv);
-    fc_load<V, VEC>(pu_ + rB, bu);
-    fc_load<V, VEC>(pv_ + rB, bv);
+    load<V, VEC>(pu_ + r, cu);
+    load<V, VEC>(pv_ + r, cv);
+    load<V, VEC>(pu_ + rT, tu);
+    load<V, VEC>(pv_ + rT, tv);
+    load<V, VEC>(pu_ + rB, bu);
+    load<V, VEC>(pv_ + rB, bv);
     const float lu = pu_[rL], lv = pv_[rL], ru = pu_[rR], rv = pv_[rR];
     float e[V], oc[V], wu[V], wv[V];
     unsigned fl[V];
@@ -194,11 +153,11 @@ __device__ __forceinline__ void fc_chunk(const FcArgs& a, int d, long long n, in
         for (int k = 0; k < V; ++k) a.flags[d][plane + k] = (unsigned char)fl[k];
       }
     }
-    if (a.occ[d]) fc_store<V, VEC>(a.occ[d] + plane, oc);
-    if (a.err[d]) fc_store<V, VEC>(a.err[d] + plane, e);
+    if (a.occ[d]) store<V, VEC>(a.occ[d] + plane, oc);
+    if (a.err[d]) store<V, VEC>(a.err[d] + plane, e);
     if (a.warped[d]) {
-      fc_store<V, VEC>(a.warped[d] + (size_t)n * 2 * hw + r, wu);
-      fc_store<V, VEC>(a.warped[d] + (size_t)n * 2 * hw + hw + r, wv);
+      store<V, VEC>(a.warped[d] + (size_t)n * 2 * hw + r, wu);
+      store<V, VEC>(a.warped[d] + (size_t)n * 2 * hw + hw + r, wv);
     }
   }
   double row[kFcK];
@@ -210,23 +169,10 @@ __device__ __forceinline__ void fc_chunk(const FcArgs& a, int d, long long n, in
   row[FN2_FLOW_CONSISTENCY_BOUNDARY] = (double)t.boundary;
   row[FN2_FLOW_CONSISTENCY_ERR_SUM] = t.err;
   row[FN2_FLOW_CONSISTENCY_ERR_MAX] = (double)t.emax;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kFcK; ++k) {
-    const double v = k == FN2_FLOW_CONSISTENCY_ERR_MAX ? fc_wave_max(row[k]) : fc_wave_sum(row[k]);
-    if (lane == 0) lds[wid][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kFcK) {
-    const int k = threadIdx.x;
-    const double v = k == FN2_FLOW_CONSISTENCY_ERR_MAX ? fmax(fmax(lds[0][k], lds[1][k]), fmax(lds[2][k], lds[3][k]))
-                                                       : ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
-    a.partial[(((size_t)d * a.N + n) * a.chunks + chunk) * kFcK + k] = v;
-  }
-  __syncthreads();                                           // the next work item of this workgroup writes lds again
+  reduce_row<kFcK, kFcMaxMask>(row, lds, a.partial + (((size_t)d * a.N + n) * a.chunks + chunk) * kFcK);
 }
 
-__global__ void __launch_bounds__(kFcThreads) flow_consistency_partial(FcArgs a) {
+__global__ void __launch_bounds__(kThreads) flow_consistency_partial(FcArgs a) {
   __shared__ double lds[4][kFcK];
   const long long per_dir = (long long)a.N * a.chunks;
   for (long long w = blockIdx.x; w < 2 * per_dir; w += gridDim.x) {
@@ -240,50 +186,17 @@ __global__ void __launch_bounds__(kFcThreads) flow_consistency_partial(FcArgs a)
   }
 }
 
-// One workgroup.  A thread per (direction, sample, column) adds that sample's B partial rows in index order (eight loads in flight at a
-// time); then a thread per (direction, column) adds the sample rows in sample order.
-__global__ void __launch_bounds__(kFcThreads) flow_consistency_final(FcArgs a) {
-  const int B = a.chunks;
-  const long long cells = 2LL * a.N * kFcK;
-  for (long long c = threadIdx.x; c < cells; c += kFcThreads) {
-    const long long dn = c / kFcK;                           // d * N + n
-    const int k = (int)(c % kFcK);
-    const double* __restrict__ p = a.partial + (size_t)dn * B * kFcK + k;
-    double v = 0.0;
-#pragma unroll 8
-    for (int b = 0; b < B; ++b) v = k == FN2_FLOW_CONSISTENCY_ERR_MAX ? fmax(v, p[(size_t)b * kFcK]) : v + p[(size_t)b * kFcK];
-    const long long d = dn / a.N, n = dn - d * a.N;
-    a.results[((size_t)d * (a.N + 1) + n) * kFcK + k] = v;
-  }
-  __threadfence_block();                                     // the sample rows, written by other threads of this workgroup, are read below
-  __syncthreads();
-  if (threadIdx.x < 2 * kFcK) {
-    const int d = threadIdx.x / kFcK, k = threadIdx.x % kFcK;
-    const double* p = a.results + (size_t)d * (a.N + 1) * kFcK + k;
-    double total = 0.0;
-#pragma unroll 8
-    for (long long n = 0; n < a.N; ++n) total = k == FN2_FLOW_CONSISTENCY_ERR_MAX ? fmax(total, p[(size_t)n * kFcK]) : total + p[(size_t)n * kFcK];
-    a.results[((size_t)d * (a.N + 1) + a.N) * kFcK + k] = total;
-  }
-}
-
-static int fc_chunks(long long hw) {
-  const long long b = (hw + kFcPixelsPerBlock - 1) / kFcPixelsPerBlock;
-  return (int)(b < 1 ? 1 : b > kFcMaxChunks ? kFcMaxChunks : b);
+// One workgroup; the two directions are the groups of the plain finalise.
+__global__ void __launch_bounds__(kThreads) flow_consistency_final(FcArgs a) {
+  finalize_rows<kFcK, kFcMaxMask>(a.partial, a.results, 2, a.N, a.chunks, 2);
 }
 
 static int fc_shape(const char* what, int N, int H, int W) {
   if (N < 1 || H < 1 || W < 1) return fail(FN2_ERR_INVALID_ARG, "%s: bad shape [%d,2,%d,%d]", what, N, H, W);
-  // in steps, so that no product of three ints wraps: H W < 2^62; then 2 H W < 2^31 and N < 2^31 give N 2 H W < 2^62
-  const long long hw = (long long)H * W;
-  if (hw >= (1LL << 30) || (long long)N * (2 * hw) >= (1LL << 31))
-    return fail(FN2_ERR_INVALID_ARG, "%s: blob [%d,2,%d,%d] of 2^31 elements or more", what, N, H, W);
-  return FN2_OK;
+  return check_planes(what, N, 2, H, W);
 }
 
-static size_t fc_ws_bytes(int N, int H, int W) { return sizeof(double) * kFcK * 2 * (size_t)N * fc_chunks((long long)H * W); }
-
-static bool fc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }      // NULL (absent) counts as aligned
+static size_t fc_ws_bytes(int N, int H, int W) { return sizeof(double) * kFcK * 2 * (size_t)N * chunks((long long)H * W); }
 
 }  // namespace fn2
 
@@ -322,16 +235,16 @@ FN2_API int fn2_flow_consistency(const float* fw, const float* bw, int N, int H,
   a.partial = reinterpret_cast<double*>(workspace);
   a.results = results;
   a.N = N; a.H = H; a.W = W;
-  a.chunks = fc_chunks((long long)H * W);
+  a.chunks = chunks((long long)H * W);
   a.quad = (W % 4) == 0;
   a.vec = a.quad;
   for (int d = 0; d < 2; ++d)
-    a.vec = a.vec && fc_aligned16(a.flow[d]) && fc_aligned16(a.flags[d]) && fc_aligned16(a.occ[d]) && fc_aligned16(a.err[d]) &&
-            fc_aligned16(a.warped[d]);
+    a.vec = a.vec && aligned16(a.flow[d]) && aligned16(a.flags[d]) && aligned16(a.occ[d]) && aligned16(a.err[d]) &&
+            aligned16(a.warped[d]);
   a.alpha1 = alpha1; a.alpha2 = alpha2; a.beta1 = beta1; a.beta2 = beta2;
   const long long items = 2LL * N * a.chunks;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(flow_consistency_partial, dim3((unsigned)(items < kFcMaxGrid ? items : kFcMaxGrid)), dim3(kFcThreads), 0, st, a);
-  hipLaunchKernelGGL(flow_consistency_final, dim3(1), dim3(kFcThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_consistency_partial, grid_for(items), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_consistency_final, dim3(1), dim3(kThreads), 0, st, a);
   return check_launch(what);
 }

@@ -13,20 +13,19 @@
 // off): include/flownet2_hip_flow_metrics.h states the arithmetic.
 //
 // -Rpass-analysis=kernel-resource-usage (gfx950, -O3; the kernel holds the three load forms):
-//   flow_metrics_partial  VGPRs 83  SGPRs 106  LDS 480 B  occupancy 5     flow_metrics_final  VGPRs 56  SGPRs 44  LDS 61440 B  occupancy 2
+//   flow_metrics_partial  VGPRs 83  SGPRs 106  LDS 480 B  occupancy 5     flow_metrics_final  VGPRs 56  SGPRs 72  LDS 61440 B  occupancy 2
 // no scratch in either.
-#include "fn2_common.hpp"
+#include "stream_reduce.hpp"
 #include "../../include/flownet2_hip_flow_metrics.h"
 
 #pragma clang fp contract(off)
 
 namespace fn2 {
 
-constexpr int kFmThreads = 256;
+using namespace stream;
+
 constexpr int kFmK = FN2_FLOW_METRICS_K;
-constexpr int kFmPixelsPerBlock = 4 * kFmThreads;      // B = ceil(H W / this), at most kFmMaxChunks
-constexpr int kFmMaxChunks = 128;
-constexpr int kFmMaxGrid = 1 << 16;                    // work items beyond this are taken in a workgroup-stride loop
+constexpr unsigned kFmMaxMask = 1u << FN2_FLOW_METRICS_EPE_MAX;      // the column reduced by max
 
 struct FmArgs {
   const float* pred; const float* gt; const float* valid; const float* occ;
@@ -46,27 +45,6 @@ struct FmAcc {
   int valid, nonfinite, outliers, band[3], occ;
   float emax;
 };
-
-template <int V, bool VEC>
-__device__ __forceinline__ void fm_load(const float* __restrict__ p, float (&v)[V]) {
-  if constexpr (VEC) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = p[k];
-  }
-}
-
-template <int V, bool VEC>
-__device__ __forceinline__ void fm_store(float* __restrict__ p, const float (&v)[V]) {
-  if constexpr (VEC) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) p[k] = v[k];
-  }
-}
 
 __device__ __forceinline__ bool fm_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }      // false for NaN and +-Inf
 
@@ -101,18 +79,6 @@ __device__ __forceinline__ float fm_pixel(const FmArgs& a, float pu, float pv, f
   return epe;
 }
 
-__device__ __forceinline__ double fm_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double fm_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  return v;
-}
-
 // Chunk `chunk` of sample n: units chunk * 256 + thread, then every B * 256 further on; row -> partial[(n * B + chunk) * K].
 template <int V, bool VEC>
 __device__ __forceinline__ void fm_chunk(const FmArgs& a, long long n, int chunk, double (*lds)[kFmK]) {
@@ -121,19 +87,19 @@ __device__ __forceinline__ void fm_chunk(const FmArgs& a, long long n, int chunk
   const float* __restrict__ pu_ = a.pred + (size_t)n * 2 * hw;
   const float* __restrict__ gu_ = a.gt + (size_t)n * 2 * hw;
   FmAcc t = {};
-  for (long long u = (long long)chunk * kFmThreads + threadIdx.x; u < units; u += (long long)a.chunks * kFmThreads) {
+  for (long long u = (long long)chunk * kThreads + threadIdx.x; u < units; u += (long long)a.chunks * kThreads) {
     const size_t r = (size_t)u * V;
     float pu[V], pv[V], gu[V], gv[V], use[V], oc[V], e[V];
-    fm_load<V, VEC>(pu_ + r, pu);
-    fm_load<V, VEC>(pu_ + hw + r, pv);
-    fm_load<V, VEC>(gu_ + r, gu);
-    fm_load<V, VEC>(gu_ + hw + r, gv);
-    if (a.valid) fm_load<V, VEC>(a.valid + (size_t)n * hw + r, use);
-    if (a.occ) fm_load<V, VEC>(a.occ + (size_t)n * hw + r, oc);
+    load<V, VEC>(pu_ + r, pu);
+    load<V, VEC>(pu_ + hw + r, pv);
+    load<V, VEC>(gu_ + r, gu);
+    load<V, VEC>(gu_ + hw + r, gv);
+    if (a.valid) load<V, VEC>(a.valid + (size_t)n * hw + r, use);
+    if (a.occ) load<V, VEC>(a.occ + (size_t)n * hw + r, oc);
 #pragma unroll
     for (int k = 0; k < V; ++k)
       e[k] = fm_pixel(a, pu[k], pv[k], gu[k], gv[k], a.valid ? use[k] != 0.f : true, a.occ ? oc[k] != 0.f : false, t);
-    if (a.epe_map) fm_store<V, VEC>(a.epe_map + (size_t)n * hw + r, e);
+    if (a.epe_map) store<V, VEC>(a.epe_map + (size_t)n * hw + r, e);
   }
   double row[kFmK];
   row[FN2_FLOW_METRICS_VALID] = (double)t.valid;
@@ -150,23 +116,10 @@ __device__ __forceinline__ void fm_chunk(const FmArgs& a, long long n, int chunk
   }
   row[FN2_FLOW_METRICS_OCC_COUNT] = (double)t.occ;
   row[FN2_FLOW_METRICS_OCC_EPE_SUM] = t.occ_epe;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kFmK; ++k) {
-    const double v = k == FN2_FLOW_METRICS_EPE_MAX ? fm_wave_max(row[k]) : fm_wave_sum(row[k]);
-    if (lane == 0) lds[wid][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kFmK) {
-    const int k = threadIdx.x;
-    const double v = k == FN2_FLOW_METRICS_EPE_MAX ? fmax(fmax(lds[0][k], lds[1][k]), fmax(lds[2][k], lds[3][k]))
-                                                   : ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
-    a.partial[((size_t)n * a.chunks + chunk) * kFmK + k] = v;
-  }
-  __syncthreads();                                           // the next work item of this workgroup writes lds again
+  reduce_row<kFmK, kFmMaxMask>(row, lds, a.partial + ((size_t)n * a.chunks + chunk) * kFmK);
 }
 
-__global__ void __launch_bounds__(kFmThreads) flow_metrics_partial(FmArgs a) {
+__global__ void __launch_bounds__(kThreads) flow_metrics_partial(FmArgs a) {
   __shared__ double lds[4][kFmK];
   const long long items = (long long)a.N * a.chunks;
   for (long long w = blockIdx.x; w < items; w += gridDim.x) {
@@ -196,11 +149,11 @@ __device__ __forceinline__ void fm_stage(double* dst, const double* __restrict__
 // rows of S = 128 / B consecutive samples (one contiguous piece of the workspace) into its quarter of the LDS buffer with all its loads
 // in flight at once, then a lane per (sample, column) adds that sample's B partials from LDS in index order.  The totals row likewise:
 // 512 sample rows at a time into LDS, then a thread per column adds them in sample order.
-__global__ void __launch_bounds__(kFmThreads) flow_metrics_final(FmArgs a) {
-  constexpr int kStage = kFmMaxChunks * kFmK;              // doubles per wave
+__global__ void __launch_bounds__(kThreads) flow_metrics_final(FmArgs a) {
+  constexpr int kStage = kMaxChunks * kFmK;              // doubles per wave
   __shared__ double lds[4 * kStage];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int B = a.chunks, S = kFmMaxChunks / B;
+  const int B = a.chunks, S = kMaxChunks / B;
   double* stage = lds + wid * kStage;
   for (long long base = 0; base < a.N; base += 4 * S) {    // the same trip count in every wave: the barriers are uniform
     const long long n0 = base + (long long)wid * S;
@@ -230,7 +183,7 @@ __global__ void __launch_bounds__(kFmThreads) flow_metrics_final(FmArgs a) {
     const long long left = a.N - base;
     const int rows = (int)(left < kRows ? left : kRows);
     const double* src = a.results + (size_t)base * kFmK;
-    fm_stage<kFmThreads>(lds, src, rows * kFmK, threadIdx.x);
+    fm_stage<kThreads>(lds, src, rows * kFmK, threadIdx.x);
     __syncthreads();
     if (threadIdx.x < kFmK) {
       const int k = threadIdx.x;
@@ -242,23 +195,12 @@ __global__ void __launch_bounds__(kFmThreads) flow_metrics_final(FmArgs a) {
   if (threadIdx.x < kFmK) a.results[(size_t)a.N * kFmK + threadIdx.x] = total;
 }
 
-static int fm_chunks(long long hw) {
-  const long long b = (hw + kFmPixelsPerBlock - 1) / kFmPixelsPerBlock;
-  return (int)(b < 1 ? 1 : b > kFmMaxChunks ? kFmMaxChunks : b);
-}
-
 static int fm_shape(const char* what, int N, int H, int W) {
   if (N < 1 || H < 1 || W < 1) return fail(FN2_ERR_INVALID_ARG, "%s: bad shape [%d,2,%d,%d]", what, N, H, W);
-  // in steps, so that no product of three ints wraps: H W < 2^62; then 2 H W < 2^31 and N < 2^31 give N 2 H W < 2^62
-  const long long hw = (long long)H * W;
-  if (hw >= (1LL << 30) || (long long)N * (2 * hw) >= (1LL << 31))
-    return fail(FN2_ERR_INVALID_ARG, "%s: blob [%d,2,%d,%d] of 2^31 elements or more", what, N, H, W);
-  return FN2_OK;
+  return check_planes(what, N, 2, H, W);
 }
 
-static size_t fm_ws_bytes(int N, int H, int W) { return sizeof(double) * kFmK * (size_t)N * fm_chunks((long long)H * W); }
-
-static bool fm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }      // NULL (absent) counts as aligned
+static size_t fm_ws_bytes(int N, int H, int W) { return sizeof(double) * kFmK * (size_t)N * chunks((long long)H * W); }
 
 }  // namespace fn2
 
@@ -291,13 +233,13 @@ FN2_API int fn2_flow_metrics(const float* pred, const float* gt, const float* va
   a.results = results;
   a.N = N; a.H = H; a.W = W;
   const long long hw = (long long)H * W;
-  a.chunks = fm_chunks(hw);
+  a.chunks = chunks(hw);
   a.quad = (hw % 4) == 0;
-  a.vec = a.quad && fm_aligned16(pred) && fm_aligned16(gt) && fm_aligned16(valid) && fm_aligned16(occ) && fm_aligned16(epe_map);
+  a.vec = a.quad && aligned16(pred) && aligned16(gt) && aligned16(valid) && aligned16(occ) && aligned16(epe_map);
   a.outlier_abs = outlier_abs; a.outlier_rel = outlier_rel; a.band0 = band0; a.band1 = band1;
   const long long items = (long long)N * a.chunks;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(flow_metrics_partial, dim3((unsigned)(items < kFmMaxGrid ? items : kFmMaxGrid)), dim3(kFmThreads), 0, st, a);
-  hipLaunchKernelGGL(flow_metrics_final, dim3(1), dim3(kFmThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_metrics_partial, grid_for(items), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_metrics_final, dim3(1), dim3(kThreads), 0, st, a);
   return check_launch(what);
 }

@@ -14,18 +14,17 @@
 //
 // Reads stay inside the sample: tap and stop indices are formed only from a position that has passed the finite test and the inside test,
 // so from a coordinate in [0, W) x [0, H), and are clamped to W - 1 and H - 1.
-#include "fn2_common.hpp"
+#include "stream_reduce.hpp"
 #include "../../include/flownet2_hip_flow_track.h"
 
 #pragma clang fp contract(off)
 
 namespace fn2 {
 
-constexpr int kFtThreads = 256;
+using namespace stream;
+
 constexpr int kFtK = FN2_FLOW_TRACK_K;
-constexpr int kFtPointsPerBlock = 4 * kFtThreads;      // B = ceil(P / this), at most kFtMaxChunks
-constexpr int kFtMaxChunks = 128;
-constexpr int kFtMaxGrid = 1 << 16;                    // work items beyond this are taken in a workgroup-stride loop
+constexpr unsigned kFtMaxMask = 1u << FN2_FLOW_TRACK_STEPS_MAX | 1u << FN2_FLOW_TRACK_DISP_MAX;      // the columns reduced by max
 constexpr unsigned kFtNonfinite = FN2_FLOW_TRACK_STOP_NONFINITE, kFtOutside = FN2_FLOW_TRACK_STOP_OUTSIDE,
                    kFtInconsistent = FN2_FLOW_TRACK_STOP_INCONSISTENT, kFtMarked = FN2_FLOW_TRACK_STOP_MARKED;
 
@@ -47,21 +46,15 @@ struct FtArgs {
   float alpha1, alpha2;
 };
 
-__device__ __forceinline__ bool ft_ok(float x) { return fabsf(x) <= 1e9f; }      // false for NaN and +-Inf
-
 __device__ __forceinline__ bool ft_inside(float x, float y, int W, int H) { return x >= 0.f && y >= 0.f && x < (float)W && y < (float)H; }
 
 // The bilinear value of the planes pu / pv at (x, y), which has passed ft_inside: FlowWarp's taps in the association of
-// flow_consistency.hip.  0 <= x < W, so the conversion is defined; the min keeps the index inside where float(W) rounds up.
+// flow_consistency.hip.
 __device__ __forceinline__ void ft_sample(const float* __restrict__ pu, const float* __restrict__ pv, int W, int H, float x, float y, float& u,
                                           float& v) {
-  const int ixL = min((int)x, W - 1), iyT = min((int)y, H - 1);
-  const int ixR = min(ixL + 1, W - 1), iyB = min(iyT + 1, H - 1);
-  const float al = x - (float)ixL, be = y - (float)iyT;
-  const float wTL = (1.f - al) * (1.f - be), wTR = al * (1.f - be), wBL = (1.f - al) * be, wBR = al * be;
-  const size_t oTL = (size_t)iyT * W + ixL, oTR = (size_t)iyT * W + ixR, oBL = (size_t)iyB * W + ixL, oBR = (size_t)iyB * W + ixR;
-  u = ((wTL * pu[oTL] + wTR * pu[oTR]) + wBL * pu[oBL]) + wBR * pu[oBR];
-  v = ((wTL * pv[oTL] + wTR * pv[oTR]) + wBL * pv[oBL]) + wBR * pv[oBR];
+  const BilinearTaps t = bilinear_taps(x, y, W, H);
+  u = ((t.wTL * pu[t.oTL] + t.wTR * pu[t.oTR]) + t.wBL * pu[t.oBL]) + t.wBR * pu[t.oBR];
+  v = ((t.wTL * pv[t.oTL] + t.wTR * pv[t.oTR]) + t.wBL * pv[t.oBL]) + t.wBR * pv[t.oBR];
 }
 
 // One frame step of an alive point at (x, y) inside the plane: 0 and the new position, or the reason it stops (x, y unchanged).
@@ -71,7 +64,7 @@ __device__ __forceinline__ unsigned ft_step(const FtArgs& a, const float* __rest
   const size_t hw = (size_t)H * W;
   float au, av;
   ft_sample(f, f + hw, W, H, x, y, au, av);
-  if (!ft_ok(au) || !ft_ok(av)) return kFtNonfinite;
+  if (!finite_1e9(au) || !finite_1e9(av)) return kFtNonfinite;
   if (s) {
     const int jx = min((int)(x + 0.5f), W - 1), jy = min((int)(y + 0.5f), H - 1);      // x + 0.5f <= W, as x < W
     if ((unsigned)s[(size_t)jy * W + jx] & a.stop_mask) return kFtMarked;
@@ -80,7 +73,7 @@ __device__ __forceinline__ unsigned ft_step(const FtArgs& a, const float* __rest
   if (!ft_inside(x2, y2, W, H)) return kFtOutside;
   float bu, bv;
   ft_sample(b, b + hw, W, H, x2, y2, bu, bv);
-  if (!ft_ok(bu) || !ft_ok(bv)) return kFtNonfinite;
+  if (!finite_1e9(bu) || !finite_1e9(bv)) return kFtNonfinite;
   const float su = au + bu, sv = av + bv;
   const float sq = su * su + sv * sv;
   const float m = (au * au + av * av) + (bu * bu + bv * bv);
@@ -89,20 +82,6 @@ __device__ __forceinline__ unsigned ft_step(const FtArgs& a, const float* __rest
   y = y2;
   return 0u;
 }
-
-__device__ __forceinline__ double ft_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double ft_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  return v;
-}
-
-__device__ __forceinline__ bool ft_is_max(int k) { return k == FN2_FLOW_TRACK_STEPS_MAX || k == FN2_FLOW_TRACK_DISP_MAX; }
 
 // what one thread has seen; counts stay integers until the reduction (a thread sees fewer than 2^31 points, and steps sum below 2^31:
 // a thread's points times T is at most N (T + 1) 2 P)
@@ -123,7 +102,7 @@ __device__ __forceinline__ void ft_chunk(const FtArgs& a, long long n, int chunk
   float* tr = a.tracks ? a.tracks + (size_t)n * (T + 1) * 2 * P : nullptr;
   const float nan = __builtin_nanf("");
   FtAcc t = {};
-  for (long long q = (long long)chunk * kFtThreads + threadIdx.x; q < P; q += (long long)a.chunks * kFtThreads) {
+  for (long long q = (long long)chunk * kThreads + threadIdx.x; q < P; q += (long long)a.chunks * kThreads) {
     const size_t p = (size_t)q;
     const float x0 = px[p], y0 = px[P + p];
     const unsigned given = a.state_in ? (unsigned)a.state_in[(size_t)n * P + p] : 0u;
@@ -131,7 +110,7 @@ __device__ __forceinline__ void ft_chunk(const FtArgs& a, long long n, int chunk
     float x = x0, y = y0;
     int steps = 0;
     if (st == 0u) {
-      if (!ft_ok(x) || !ft_ok(y)) st = kFtNonfinite;
+      if (!finite_1e9(x) || !finite_1e9(y)) st = kFtNonfinite;
       else if (!ft_inside(x, y, a.W, a.H)) st = kFtOutside;
     }
     if (tr) {
@@ -182,52 +161,18 @@ __device__ __forceinline__ void ft_chunk(const FtArgs& a, long long n, int chunk
   row[FN2_FLOW_TRACK_STEPS_MAX] = (double)t.smax;
   row[FN2_FLOW_TRACK_DISP_SUM] = t.disp;
   row[FN2_FLOW_TRACK_DISP_MAX] = (double)t.dmax;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kFtK; ++k) {
-    const double v = ft_is_max(k) ? ft_wave_max(row[k]) : ft_wave_sum(row[k]);
-    if (lane == 0) lds[wid][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kFtK) {
-    const int k = threadIdx.x;
-    const double v = ft_is_max(k) ? fmax(fmax(lds[0][k], lds[1][k]), fmax(lds[2][k], lds[3][k]))
-                                  : ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
-    a.partial[((size_t)n * a.chunks + chunk) * kFtK + k] = v;
-  }
-  __syncthreads();                                           // the next work item of this workgroup writes lds again
+  reduce_row<kFtK, kFtMaxMask>(row, lds, a.partial + ((size_t)n * a.chunks + chunk) * kFtK);
 }
 
-__global__ void __launch_bounds__(kFtThreads) flow_track_gather(FtArgs a) {
+__global__ void __launch_bounds__(kThreads) flow_track_gather(FtArgs a) {
   __shared__ double lds[4][kFtK];
   const long long items = (long long)a.N * a.chunks;
   for (long long w = blockIdx.x; w < items; w += gridDim.x) ft_chunk(a, w / a.chunks, (int)(w % a.chunks), lds);
 }
 
-// One workgroup.  A thread per (sample, column) adds that sample's B partial rows in index order; then a thread per column adds the
-// sample rows in sample order.
-__global__ void __launch_bounds__(kFtThreads) flow_track_final(FtArgs a) {
-  const int B = a.chunks;
-  const long long cells = (long long)a.N * kFtK;
-  for (long long c = threadIdx.x; c < cells; c += kFtThreads) {
-    const long long n = c / kFtK;
-    const int k = (int)(c % kFtK);
-    const double* __restrict__ p = a.partial + (size_t)n * B * kFtK + k;
-    double v = 0.0;
-#pragma unroll 8
-    for (int b = 0; b < B; ++b) v = ft_is_max(k) ? fmax(v, p[(size_t)b * kFtK]) : v + p[(size_t)b * kFtK];
-    a.results[(size_t)n * kFtK + k] = v;
-  }
-  __threadfence_block();                                     // the sample rows, written by other threads of this workgroup, are read below
-  __syncthreads();
-  if (threadIdx.x < kFtK) {
-    const int k = threadIdx.x;
-    const double* p = a.results + k;
-    double total = 0.0;
-#pragma unroll 8
-    for (long long n = 0; n < a.N; ++n) total = ft_is_max(k) ? fmax(total, p[(size_t)n * kFtK]) : total + p[(size_t)n * kFtK];
-    a.results[(size_t)a.N * kFtK + k] = total;
-  }
+// One workgroup; the plain finalise with one group.
+__global__ void __launch_bounds__(kThreads) flow_track_final(FtArgs a) {
+  finalize_rows<kFtK, kFtMaxMask>(a.partial, a.results, 1, a.N, a.chunks, 1);
 }
 
 // ---- reseeding ------------------------------------------------------------------------------------------------------------------------
@@ -240,25 +185,25 @@ struct FrArgs {
   long long P, total;          // total = N P < 2^30
 };
 
-__global__ void __launch_bounds__(kFtThreads) flow_track_reseed_clear(FrArgs a) {
-  for (long long i = (long long)blockIdx.x * kFtThreads + threadIdx.x; i < a.total; i += (long long)gridDim.x * kFtThreads) a.covered[i] = 0;
+__global__ void __launch_bounds__(kThreads) flow_track_reseed_clear(FrArgs a) {
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < a.total; i += (long long)gridDim.x * kThreads) a.covered[i] = 0;
 }
 
 // every alive point inside the plane marks its cell: the same byte from every writer
-__global__ void __launch_bounds__(kFtThreads) flow_track_reseed_cover(FrArgs a) {
-  for (long long i = (long long)blockIdx.x * kFtThreads + threadIdx.x; i < a.total; i += (long long)gridDim.x * kFtThreads) {
+__global__ void __launch_bounds__(kThreads) flow_track_reseed_cover(FrArgs a) {
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < a.total; i += (long long)gridDim.x * kThreads) {
     if (a.state[i] != 0) continue;
     const long long n = i / a.P, p = i - n * a.P;
     const float x = a.points[(size_t)n * 2 * a.P + p], y = a.points[(size_t)n * 2 * a.P + a.P + p];
-    if (!ft_ok(x) || !ft_ok(y) || !ft_inside(x, y, a.W, a.H)) continue;
+    if (!finite_1e9(x) || !finite_1e9(y) || !ft_inside(x, y, a.W, a.H)) continue;
     const int cx = min((int)x, a.W - 1) / a.cell, cy = min((int)y, a.H - 1) / a.cell;
     a.covered[(size_t)n * a.P + (size_t)cy * a.cw + cx] = 1;
   }
 }
 
 // every slot that is not alive and whose home cell nobody covers starts anew at the cell's centre
-__global__ void __launch_bounds__(kFtThreads) flow_track_reseed_fill(FrArgs a) {
-  for (long long i = (long long)blockIdx.x * kFtThreads + threadIdx.x; i < a.total; i += (long long)gridDim.x * kFtThreads) {
+__global__ void __launch_bounds__(kThreads) flow_track_reseed_fill(FrArgs a) {
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < a.total; i += (long long)gridDim.x * kThreads) {
     const bool fill = a.state[i] != 0 && a.covered[i] == 0;
     if (fill) {
       const long long n = i / a.P, p = i - n * a.P;
@@ -270,11 +215,6 @@ __global__ void __launch_bounds__(kFtThreads) flow_track_reseed_fill(FrArgs a) {
     }
     if (a.born) a.born[i] = fill ? 1 : 0;
   }
-}
-
-static int ft_chunks(long long P) {
-  const long long b = (P + kFtPointsPerBlock - 1) / kFtPointsPerBlock;
-  return (int)(b < 1 ? 1 : b > kFtMaxChunks ? kFtMaxChunks : b);
 }
 
 static int ft_shape(const char* what, int N, int T, int H, int W, int P) {
@@ -289,7 +229,7 @@ static int ft_shape(const char* what, int N, int T, int H, int W, int P) {
   return FN2_OK;
 }
 
-static size_t ft_partial_bytes(int N, int P) { return sizeof(double) * kFtK * (size_t)N * ft_chunks(P); }
+static size_t ft_partial_bytes(int N, int P) { return sizeof(double) * kFtK * (size_t)N * chunks(P); }
 
 static size_t ft_ws_bytes(int N, int P) {
   const size_t a = ft_partial_bytes(N, P), b = (size_t)N * P;
@@ -330,13 +270,13 @@ FN2_API int fn2_flow_track(const float* fw, const float* bw, const unsigned char
   a.partial = reinterpret_cast<double*>(workspace);
   a.results = results;
   a.N = N; a.T = T; a.H = H; a.W = W; a.P = P;
-  a.chunks = ft_chunks(P);
+  a.chunks = chunks(P);
   a.stop_mask = stop_mask;
   a.alpha1 = alpha1; a.alpha2 = alpha2;
   const long long items = (long long)N * a.chunks;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(flow_track_gather, dim3((unsigned)(items < kFtMaxGrid ? items : kFtMaxGrid)), dim3(kFtThreads), 0, st, a);
-  hipLaunchKernelGGL(flow_track_final, dim3(1), dim3(kFtThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_track_gather, grid_for(items), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_track_final, dim3(1), dim3(kThreads), 0, st, a);
   return check_launch(what);
 }
 
@@ -357,11 +297,11 @@ FN2_API int fn2_flow_track_reseed(float* points, unsigned char* state, unsigned 
   a.covered = reinterpret_cast<unsigned char*>(workspace);
   a.N = N; a.H = H; a.W = W; a.cell = cell; a.cw = (int)cw;
   a.P = P; a.total = (long long)N * P;
-  const long long blocks = (a.total + kFtThreads - 1) / kFtThreads;
-  const dim3 grid((unsigned)(blocks < kFtMaxGrid ? blocks : kFtMaxGrid));
+  const long long blocks = (a.total + kThreads - 1) / kThreads;
+  const dim3 grid = grid_for(blocks);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(flow_track_reseed_clear, grid, dim3(kFtThreads), 0, st, a);
-  hipLaunchKernelGGL(flow_track_reseed_cover, grid, dim3(kFtThreads), 0, st, a);
-  hipLaunchKernelGGL(flow_track_reseed_fill, grid, dim3(kFtThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_track_reseed_clear, grid, dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_track_reseed_cover, grid, dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_track_reseed_fill, grid, dim3(kThreads), 0, st, a);
   return check_launch(what);
 }

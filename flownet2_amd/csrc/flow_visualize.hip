@@ -17,17 +17,15 @@
 // Writes stay inside [N,H,W,3]: a unit is V pixels at r = u * V < H W with r + V <= H W (V == 4 only where 4 divides W, hence H W), and its
 // bytes are 3 (n H W + r) .. 3 (n H W + r + V) - 1.  The wheel index is formed only for a known pixel (ok(u) && ok(v), so atan2f is a
 // number) and is clamped to 0 .. 54.
-#include "fn2_common.hpp"
+#include "stream_reduce.hpp"
 #include "../../include/flownet2_hip_flow_visualize.h"
 
 #pragma clang fp contract(off)
 
 namespace fn2 {
 
-constexpr int kFvThreads = 256;
-constexpr int kFvPixelsPerBlock = 4 * kFvThreads;      // B = ceil(H W / this), at most kFvMaxChunks
-constexpr int kFvMaxChunks = 128;
-constexpr int kFvMaxGrid = 1 << 16;                    // work items beyond this are taken in a workgroup-stride loop
+using namespace stream;
+
 constexpr int kFvWheelSize = 55;
 constexpr int kFvBins = 10;
 
@@ -83,17 +81,6 @@ struct FvErrorArgs {
   float abs_thresh, rel_thresh;
 };
 
-template <int V, bool VEC>
-__device__ __forceinline__ void fv_load(const float* __restrict__ p, float (&v)[V]) {
-  if constexpr (VEC) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = p[k];
-  }
-}
-
 // V pixels' colours (R | G << 8 | B << 16 each) -> the 3 V bytes at p; `words`: p is 4-byte aligned and V == 4
 template <int V>
 __device__ __forceinline__ void fv_store(unsigned char* __restrict__ p, const unsigned (&c)[V], bool words) {
@@ -114,20 +101,7 @@ __device__ __forceinline__ void fv_store(unsigned char* __restrict__ p, const un
   }
 }
 
-__device__ __forceinline__ bool fv_ok(float x) { return fabsf(x) <= 1e9f; }      // false for NaN and +-Inf
-
 __device__ __forceinline__ float fv_rad(float u, float v) { return sqrtf(u * u + v * v); }      // the one radius of both launches
-
-// the largest v of the workgroup's 256 threads, to every thread; lds[4].  0 is the identity here: a radius is never negative.
-__device__ __forceinline__ float fv_block_max(float v, float* lds) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 64));
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float m = fmaxf(fmaxf(lds[0], lds[1]), fmaxf(lds[2], lds[3]));
-  __syncthreads();                                           // the next reduction of this workgroup writes lds again
-  return m;
-}
 
 // ---- the maximum -----------------------------------------------------------------------------------------------------------------------
 template <int V, bool VEC>
@@ -137,19 +111,19 @@ __device__ __forceinline__ float fv_max_chunk(const FvColorArgs& a, long long n,
   const float* __restrict__ pu_ = a.flow + (size_t)n * 2 * hw;
   const float* __restrict__ pv_ = pu_ + hw;
   float m = 0.f;
-  for (long long u = (long long)chunk * kFvThreads + threadIdx.x; u < units; u += (long long)a.chunks * kFvThreads) {
+  for (long long u = (long long)chunk * kThreads + threadIdx.x; u < units; u += (long long)a.chunks * kThreads) {
     const size_t r = (size_t)u * V;
     float cu[V], cv[V];
-    fv_load<V, VEC>(pu_ + r, cu);
-    fv_load<V, VEC>(pv_ + r, cv);
+    load<V, VEC>(pu_ + r, cu);
+    load<V, VEC>(pv_ + r, cv);
 #pragma unroll
     for (int k = 0; k < V; ++k)
-      if (fv_ok(cu[k]) && fv_ok(cv[k])) m = fmaxf(m, fv_rad(cu[k], cv[k]));
+      if (finite_1e9(cu[k]) && finite_1e9(cv[k])) m = fmaxf(m, fv_rad(cu[k], cv[k]));
   }
   return m;
 }
 
-__global__ void __launch_bounds__(kFvThreads) flow_color_max(FvColorArgs a) {
+__global__ void __launch_bounds__(kThreads) flow_color_max(FvColorArgs a) {
   __shared__ float lds[4];
   const long long items = (long long)a.N * a.chunks;
   for (long long w = blockIdx.x; w < items; w += gridDim.x) {
@@ -159,14 +133,14 @@ __global__ void __launch_bounds__(kFvThreads) flow_color_max(FvColorArgs a) {
     if (!a.quad) m = fv_max_chunk<1, false>(a, n, chunk);
     else if (a.vec) m = fv_max_chunk<4, true>(a, n, chunk);
     else m = fv_max_chunk<4, false>(a, n, chunk);
-    m = fv_block_max(m, lds);
+    m = block_max(m, lds);
     if (threadIdx.x == 0) a.partial[w] = m;
   }
 }
 
 // ---- the colour coding -----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned fv_color_pixel(float u, float v, float maxrad) {
-  if (!fv_ok(u) || !fv_ok(v)) return 0u;
+  if (!finite_1e9(u) || !finite_1e9(v)) return 0u;
   const float rn = fv_rad(u, v) / maxrad;
   const float ang = atan2f(-v, -u) / 3.14159265358979323846f;
   const float fk = ((ang + 1.0f) * 0.5f) * 54.0f;
@@ -192,19 +166,19 @@ __device__ __forceinline__ void fv_color_chunk(const FvColorArgs& a, long long n
   const float* __restrict__ pu_ = a.flow + (size_t)n * 2 * hw;
   const float* __restrict__ pv_ = pu_ + hw;
   unsigned char* __restrict__ out = a.rgb + 3 * (size_t)n * hw;
-  for (long long u = (long long)chunk * kFvThreads + threadIdx.x; u < units; u += (long long)a.chunks * kFvThreads) {
+  for (long long u = (long long)chunk * kThreads + threadIdx.x; u < units; u += (long long)a.chunks * kThreads) {
     const size_t r = (size_t)u * V;
     float cu[V], cv[V];
     unsigned c[V];
-    fv_load<V, VEC>(pu_ + r, cu);
-    fv_load<V, VEC>(pv_ + r, cv);
+    load<V, VEC>(pu_ + r, cu);
+    load<V, VEC>(pv_ + r, cv);
 #pragma unroll
     for (int k = 0; k < V; ++k) c[k] = fv_color_pixel(cu[k], cv[k], maxrad);
     fv_store<V>(out + 3 * r, c, a.words != 0);
   }
 }
 
-__global__ void __launch_bounds__(kFvThreads) flow_color(FvColorArgs a) {
+__global__ void __launch_bounds__(kThreads) flow_color(FvColorArgs a) {
   __shared__ float lds[4];
   const long long items = (long long)a.N * a.chunks;
   for (long long w = blockIdx.x; w < items; w += gridDim.x) {
@@ -216,8 +190,8 @@ __global__ void __launch_bounds__(kFvThreads) flow_color(FvColorArgs a) {
       const long long first = a.norm == FN2_FLOW_COLOR_NORM_BATCH ? 0 : n * a.chunks;
       const long long count = a.norm == FN2_FLOW_COLOR_NORM_BATCH ? items : a.chunks;
       float m = 0.f;
-      for (long long i = threadIdx.x; i < count; i += kFvThreads) m = fmaxf(m, a.partial[first + i]);
-      m = fv_block_max(m, lds);
+      for (long long i = threadIdx.x; i < count; i += kThreads) m = fmaxf(m, a.partial[first + i]);
+      m = block_max(m, lds);
       maxrad = m > 0.f ? m : 1.0f;
     }
     if (chunk == 0 && threadIdx.x == 0 && a.maxrad_out) a.maxrad_out[n] = maxrad;
@@ -237,9 +211,9 @@ __device__ __forceinline__ unsigned fv_half(unsigned c) {
 
 __device__ __forceinline__ unsigned fv_error_pixel(const FvErrorArgs& a, float pu, float pv, float gu, float gv, bool use, bool occluded) {
   unsigned c = 0u;
-  if (use && fv_ok(gu) && fv_ok(gv)) {
+  if (use && finite_1e9(gu) && finite_1e9(gv)) {
     int bin = kFvBins - 1;
-    if (fv_ok(pu) && fv_ok(pv)) {
+    if (finite_1e9(pu) && finite_1e9(pv)) {
       const float du = pu - gu, dv = pv - gv;
       const float epe = sqrtf(du * du + dv * dv);
       const float mag = sqrtf(gu * gu + gv * gv);
@@ -261,16 +235,16 @@ __device__ __forceinline__ void fv_error_chunk(const FvErrorArgs& a, long long n
   const float* __restrict__ pu_ = a.pred + (size_t)n * 2 * hw;
   const float* __restrict__ gu_ = a.gt + (size_t)n * 2 * hw;
   unsigned char* __restrict__ out = a.rgb + 3 * (size_t)n * hw;
-  for (long long u = (long long)chunk * kFvThreads + threadIdx.x; u < units; u += (long long)a.chunks * kFvThreads) {
+  for (long long u = (long long)chunk * kThreads + threadIdx.x; u < units; u += (long long)a.chunks * kThreads) {
     const size_t r = (size_t)u * V;
     float pu[V], pv[V], gu[V], gv[V], use[V], oc[V];
     unsigned c[V];
-    fv_load<V, VEC>(pu_ + r, pu);
-    fv_load<V, VEC>(pu_ + hw + r, pv);
-    fv_load<V, VEC>(gu_ + r, gu);
-    fv_load<V, VEC>(gu_ + hw + r, gv);
-    if (a.valid) fv_load<V, VEC>(a.valid + (size_t)n * hw + r, use);
-    if (a.occ) fv_load<V, VEC>(a.occ + (size_t)n * hw + r, oc);
+    load<V, VEC>(pu_ + r, pu);
+    load<V, VEC>(pu_ + hw + r, pv);
+    load<V, VEC>(gu_ + r, gu);
+    load<V, VEC>(gu_ + hw + r, gv);
+    if (a.valid) load<V, VEC>(a.valid + (size_t)n * hw + r, use);
+    if (a.occ) load<V, VEC>(a.occ + (size_t)n * hw + r, oc);
 #pragma unroll
     for (int k = 0; k < V; ++k)
       c[k] = fv_error_pixel(a, pu[k], pv[k], gu[k], gv[k], a.valid ? use[k] != 0.f : true, a.occ ? oc[k] != 0.f : false);
@@ -278,7 +252,7 @@ __device__ __forceinline__ void fv_error_chunk(const FvErrorArgs& a, long long n
   }
 }
 
-__global__ void __launch_bounds__(kFvThreads) flow_error_map(FvErrorArgs a) {
+__global__ void __launch_bounds__(kThreads) flow_error_map(FvErrorArgs a) {
   const long long items = (long long)a.N * a.chunks;
   for (long long w = blockIdx.x; w < items; w += gridDim.x) {
     const long long n = w / a.chunks;
@@ -289,23 +263,14 @@ __global__ void __launch_bounds__(kFvThreads) flow_error_map(FvErrorArgs a) {
   }
 }
 
-static int fv_chunks(long long hw) {
-  const long long b = (hw + kFvPixelsPerBlock - 1) / kFvPixelsPerBlock;
-  return (int)(b < 1 ? 1 : b > kFvMaxChunks ? kFvMaxChunks : b);
-}
-
 static int fv_shape(const char* what, int N, int H, int W) {
   if (N < 1 || H < 1 || W < 1) return fail(FN2_ERR_INVALID_ARG, "%s: bad shape [%d,2,%d,%d]", what, N, H, W);
-  // in steps, so that no product of three ints wraps: H W < 2^62; then 2 H W < 2^31 and N < 2^31 give N 2 H W < 2^62
-  const long long hw = (long long)H * W;
-  if (hw >= (1LL << 30) || (long long)N * (2 * hw) >= (1LL << 31))
-    return fail(FN2_ERR_INVALID_ARG, "%s: blob [%d,2,%d,%d] of 2^31 elements or more", what, N, H, W);
-  return FN2_OK;
+  return check_planes(what, N, 2, H, W);
 }
 
-static size_t fv_ws_bytes(int N, int H, int W) { return sizeof(float) * (size_t)N * fv_chunks((long long)H * W); }
+static size_t fv_ws_bytes(int N, int H, int W) { return sizeof(float) * (size_t)N * chunks((long long)H * W); }
 
-static bool fv_aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) == 0; }      // NULL (absent) counts as aligned
+static bool fv_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 }  // namespace fn2
 
@@ -337,17 +302,17 @@ FN2_API int fn2_flow_color(const float* flow, int N, int H, int W, int norm, flo
   a.maxrad_out = maxrad_out;
   a.partial = fixed ? nullptr : reinterpret_cast<float*>(workspace);
   a.N = N; a.H = H; a.W = W;
-  a.chunks = fv_chunks((long long)H * W);
+  a.chunks = chunks((long long)H * W);
   a.quad = (W % 4) == 0;
-  a.vec = a.quad && fv_aligned(flow, 16);
-  a.words = a.quad && fv_aligned(rgb, 4);
+  a.vec = a.quad && aligned16(flow);
+  a.words = a.quad && fv_aligned4(rgb);
   a.norm = norm;
   a.max_flow = fixed ? max_flow : 0.f;
   const long long items = (long long)N * a.chunks;
-  const dim3 grid((unsigned)(items < kFvMaxGrid ? items : kFvMaxGrid));
+  const dim3 grid = grid_for(items);
   hipStream_t st = as_stream(stream);
-  if (!fixed) hipLaunchKernelGGL(flow_color_max, grid, dim3(kFvThreads), 0, st, a);
-  hipLaunchKernelGGL(flow_color, grid, dim3(kFvThreads), 0, st, a);
+  if (!fixed) hipLaunchKernelGGL(flow_color_max, grid, dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_color, grid, dim3(kThreads), 0, st, a);
   return check_launch(what);
 }
 
@@ -365,13 +330,13 @@ FN2_API int fn2_flow_error_map(const float* pred, const float* gt, const float* 
   a.pred = pred; a.gt = gt; a.valid = valid; a.occ = occ;
   a.rgb = rgb;
   a.N = N; a.H = H; a.W = W;
-  a.chunks = fv_chunks((long long)H * W);
+  a.chunks = chunks((long long)H * W);
   a.quad = (W % 4) == 0;
-  a.vec = a.quad && fv_aligned(pred, 16) && fv_aligned(gt, 16) && fv_aligned(valid, 16) && fv_aligned(occ, 16);
-  a.words = a.quad && fv_aligned(rgb, 4);
+  a.vec = a.quad && aligned16(pred) && aligned16(gt) && aligned16(valid) && aligned16(occ);
+  a.words = a.quad && fv_aligned4(rgb);
   a.abs_thresh = abs_thresh; a.rel_thresh = rel_thresh;
   const long long items = (long long)N * a.chunks;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(flow_error_map, dim3((unsigned)(items < kFvMaxGrid ? items : kFvMaxGrid)), dim3(kFvThreads), 0, st, a);
+  hipLaunchKernelGGL(flow_error_map, grid_for(items), dim3(kThreads), 0, st, a);
   return check_launch(what);
 }

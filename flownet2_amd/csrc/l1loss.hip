@@ -7,11 +7,12 @@
 // norm, wave64 DPP reduction -> LDS -> one partial per block) plus a 1-block finalise kernel; the
 // loss and the normalisation coefficient stay on the device.  Reduction order is fixed (no
 // atomics), so the loss is bit-reproducible run to run.
-#include "fn2_common.hpp"
+#include "stream_reduce.hpp"
 
 namespace fn2 {
 
-constexpr int kL1Threads = 256;
+using namespace stream;
+
 constexpr int kL1MaxBlocks = 1024;
 
 struct L1Args {
@@ -19,25 +20,6 @@ struct L1Args {
   int l2_per_location, prescale, normalize;
   float epsilon, plateau;
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// One block-level reduction of two doubles; result valid in thread 0.
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* lds /* [2*4] */) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { lds[wid] = a; lds[4 + wid] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = lds[0] + lds[1] + lds[2] + lds[3];
-    b = lds[4] + lds[5] + lds[6] + lds[7];
-  }
-}
 
 // partial[2*b] = sum of per-location loss terms, partial[2*b+1] = number of non-NaN entries.
 // (bid, nblk): this workgroup's index and the number of workgroups of ITS blob pair -- the grid-stride loop and with it the summation
@@ -86,8 +68,8 @@ __device__ __forceinline__ void l1_partial_body(const float* __restrict__ b0, co
   }
 }
 
-__global__ void __launch_bounds__(kL1Threads) l1loss_fwd_partial(const float* __restrict__ b0, const float* __restrict__ b1,
-                                                                 double* __restrict__ partial, L1Args a) {
+__global__ void __launch_bounds__(kThreads) l1loss_fwd_partial(const float* __restrict__ b0, const float* __restrict__ b1,
+                                                               double* __restrict__ partial, L1Args a) {
   __shared__ double lds[8];
   l1_partial_body(b0, b1, partial, a, blockIdx.x, gridDim.x, lds);
 }
@@ -110,8 +92,8 @@ __device__ __forceinline__ void l1_final_body(const double* __restrict__ partial
   }
 }
 
-__global__ void __launch_bounds__(kL1Threads) l1loss_fwd_final(const double* __restrict__ partial, int nblocks,
-                                                               float* __restrict__ ws, float* __restrict__ loss_out, L1Args a) {
+__global__ void __launch_bounds__(kThreads) l1loss_fwd_final(const double* __restrict__ partial, int nblocks,
+                                                             float* __restrict__ ws, float* __restrict__ loss_out, L1Args a) {
   __shared__ double lds[8];
   l1_final_body(partial, nblocks, ws, loss_out, a, lds);
 }
@@ -166,9 +148,9 @@ __device__ __forceinline__ void l1_bwd_body(const float* __restrict__ b0, const 
   }
 }
 
-__global__ void __launch_bounds__(kL1Threads) l1loss_bwd(const float* __restrict__ b0, const float* __restrict__ b1,
-                                                         const float* __restrict__ ws, float top_diff,
-                                                         float* __restrict__ d0, float* __restrict__ d1, L1Args a) {
+__global__ void __launch_bounds__(kThreads) l1loss_bwd(const float* __restrict__ b0, const float* __restrict__ b1,
+                                                       const float* __restrict__ ws, float top_diff,
+                                                       float* __restrict__ d0, float* __restrict__ d1, L1Args a) {
   l1_bwd_body(b0, b1, ws, top_diff, d0, d1, a, blockIdx.x, gridDim.x);
 }
 
@@ -203,7 +185,7 @@ __device__ __forceinline__ int l1_scale_of(const L1Multi& m) {
   return s;
 }
 
-__global__ void __launch_bounds__(kL1Threads) l1loss_fwd_multi(L1Multi m) {
+__global__ void __launch_bounds__(kThreads) l1loss_fwd_multi(L1Multi m) {
 #pragma clang fp contract(off)
   __shared__ double lds[8];
   __shared__ int s_last;
@@ -234,7 +216,7 @@ __global__ void __launch_bounds__(kL1Threads) l1loss_fwd_multi(L1Multi m) {
   }
 }
 
-__global__ void __launch_bounds__(kL1Threads) l1loss_bwd_multi(L1Multi m) {
+__global__ void __launch_bounds__(kThreads) l1loss_bwd_multi(L1Multi m) {
 #pragma clang fp contract(off)
   const int si = l1_scale_of(m);
   const L1Scale& sc = m.s[si];
@@ -256,7 +238,7 @@ static int l1_args(const fn2_l1loss_params* p, int N, int C, int H, int W, L1Arg
 
 static int l1_blocks(const L1Args& a) {
   const long long work = a.l2_per_location ? (long long)a.N * a.H * a.W : (long long)a.N * a.C * a.H * a.W;
-  return (int)blocks_for(work, kL1Threads, kL1MaxBlocks);
+  return (int)blocks_for(work, kThreads, kL1MaxBlocks);
 }
 
 }  // namespace fn2
@@ -278,8 +260,8 @@ FN2_API int fn2_l1loss_forward(const fn2_l1loss_params* p, const float* bottom0,
   float* wsf = reinterpret_cast<float*>(workspace);
   double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + 64);
   const int nb = l1_blocks(a);
-  hipLaunchKernelGGL(l1loss_fwd_partial, dim3(nb), dim3(kL1Threads), 0, st, bottom0, bottom1, partial, a);
-  hipLaunchKernelGGL(l1loss_fwd_final, dim3(1), dim3(kL1Threads), 0, st, partial, nb, wsf, loss_out, a);
+  hipLaunchKernelGGL(l1loss_fwd_partial, dim3(nb), dim3(kThreads), 0, st, bottom0, bottom1, partial, a);
+  hipLaunchKernelGGL(l1loss_fwd_final, dim3(1), dim3(kThreads), 0, st, partial, nb, wsf, loss_out, a);
   return check_launch("l1loss_forward");
 }
 
@@ -293,7 +275,7 @@ FN2_API int fn2_l1loss_backward(const fn2_l1loss_params* p, const float* bottom0
   if (!workspace || workspace_bytes < fn2_l1loss_workspace_bytes(N, C, H, W))
     return fail(FN2_ERR_WORKSPACE, "l1loss_backward: workspace too small");
   const int nb = l1_blocks(a);
-  hipLaunchKernelGGL(l1loss_bwd, dim3(nb), dim3(kL1Threads), 0, as_stream(stream), bottom0, bottom1,
+  hipLaunchKernelGGL(l1loss_bwd, dim3(nb), dim3(kThreads), 0, as_stream(stream), bottom0, bottom1,
                      reinterpret_cast<const float*>(workspace), top_diff, bottom0_diff, bottom1 ? bottom1_diff : nullptr, a);
   return check_launch("l1loss_backward");
 }
@@ -340,7 +322,7 @@ FN2_API int fn2_l1loss_forward_multi(const fn2_l1loss_params* p, int nscales, co
   if (!sync) return fail(FN2_ERR_INVALID_ARG, "l1loss_forward_multi: sync == NULL (fn2_l1loss_multi_sync_bytes zero bytes, left zero by every call)");
   m.sync = reinterpret_cast<unsigned*>(sync);
   m.losses = losses; m.total = total; m.total_diff = nullptr;
-  hipLaunchKernelGGL(l1loss_fwd_multi, dim3(blocks), dim3(kL1Threads), 0, as_stream(stream), m);
+  hipLaunchKernelGGL(l1loss_fwd_multi, dim3(blocks), dim3(kThreads), 0, as_stream(stream), m);
   return check_launch("l1loss_forward_multi");
 }
 
@@ -351,6 +333,6 @@ FN2_API int fn2_l1loss_backward_multi(const fn2_l1loss_params* p, int nscales, c
   int rc = l1_multi_fill("l1loss_backward_multi", p, nscales, scales, workspace, workspace_bytes, true, &m, &blocks);
   if (rc) return rc;
   m.sync = nullptr; m.losses = nullptr; m.total = nullptr; m.total_diff = total_diff;
-  hipLaunchKernelGGL(l1loss_bwd_multi, dim3(blocks), dim3(kL1Threads), 0, as_stream(stream), m);
+  hipLaunchKernelGGL(l1loss_bwd_multi, dim3(blocks), dim3(kThreads), 0, as_stream(stream), m);
   return check_launch("l1loss_backward_multi");
 }

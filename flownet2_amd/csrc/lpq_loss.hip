@@ -17,14 +17,15 @@
 //   lpq_bwd          VGPRs 46   SGPRs 79  LDS 0 B    occupancy 8
 //   lpq_fwd_multi    VGPRs 44   SGPRs 71  LDS 72 B   occupancy 8     lpq_bwd_multi  VGPRs 47  SGPRs 75  LDS 0 B   occupancy 8
 // no scratch in any of them.
-#include "fn2_common.hpp"
+#include "stream_reduce.hpp"
 #include "../../include/flownet2_hip_lpq_loss.h"
 
 #pragma clang fp contract(off)
 
 namespace fn2 {
 
-constexpr int kLpqThreads = 256;
+using namespace stream;
+
 constexpr int kLpqMaxBlocks = 1024;
 constexpr int kLpqMaxScales = 8;
 
@@ -57,25 +58,6 @@ struct LpqMulti {
   const float* total_diff;  // backward: d(objective) / d(total), a device scalar (null: 1)
 };
 
-__device__ __forceinline__ double lpq_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// One block-level reduction of two doubles; result valid in thread 0.
-__device__ __forceinline__ void lpq_block_sum2(double& a, double& b, double* lds /* [2*4] */) {
-  a = lpq_wave_sum(a);
-  b = lpq_wave_sum(b);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { lds[wid] = a; lds[4 + wid] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = lds[0] + lds[1] + lds[2] + lds[3];
-    b = lds[4] + lds[5] + lds[6] + lds[7];
-  }
-}
-
 __device__ __forceinline__ float lpq_pow(float t, float power, int mode) {
   if (mode == kPowIdentity) return t;
   if (mode == kPowOne) return 1.f;
@@ -90,34 +72,13 @@ __device__ __forceinline__ float lpq_dpow(float t, float power, int mode) {
   return power * (powf(t, power) / t);                         // :55-76 (shift == 0: t is x itself)
 }
 
-template <int V, bool VEC>
-__device__ __forceinline__ void lpq_load(const float* __restrict__ p, float (&v)[V]) {
-  if constexpr (VEC) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = p[k];
-  }
-}
-
-template <int V, bool VEC>
-__device__ __forceinline__ void lpq_store(float* __restrict__ p, const float (&v)[V]) {
-  if constexpr (VEC) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) p[k] = v[k];
-  }
-}
-
 // d = b0 - b1 of V neighbouring pixels of one channel (Eltwise coeff +1, -1: lpq_loss_layer.cpp:87-97)
 template <int V, bool VEC>
 __device__ __forceinline__ void lpq_diff(const LpqBlob& s, size_t i, float (&d)[V]) {
-  lpq_load<V, VEC>(s.b0 + i, d);
+  load<V, VEC>(s.b0 + i, d);
   if (s.b1) {
     float e[V];
-    lpq_load<V, VEC>(s.b1 + i, e);
+    load<V, VEC>(s.b1 + i, e);
 #pragma unroll
     for (int k = 0; k < V; ++k) d[k] = d[k] - e[k];
   }
@@ -160,7 +121,7 @@ __device__ __forceinline__ void lpq_partial_body(const LpqBlob& s, const LpqArgs
     for (int k = 0; k < V; ++k) dot += (double)lpq_pow(acc[k] + a.q_eps, a.q, a.qmode);     // Power q cu:191, dot with ones cu:194
     nvalid += (double)cnt;
   }
-  lpq_block_sum2(dot, nvalid, lds);
+  block_sum2(dot, nvalid, lds);
   if (threadIdx.x == 0) {
     s.partial[2 * bid] = dot;
     s.partial[2 * bid + 1] = nvalid;
@@ -180,7 +141,7 @@ __device__ __forceinline__ void lpq_final_body(const LpqBlob& s, const LpqArgs& 
     dot += s.partial[2 * b];
     nvalid += s.partial[2 * b + 1];
   }
-  lpq_block_sum2(dot, nvalid, lds);
+  block_sum2(dot, nvalid, lds);
   if (threadIdx.x == 0) {
     const float norm = a.normalize ? (float)nvalid / (float)s.C : (float)s.N;      // cu:157-162
     const float loss = (float)(dot / (double)norm);                                // cu:196
@@ -219,11 +180,11 @@ __device__ __forceinline__ void lpq_bwd_body(const LpqBlob& s, const LpqArgs& a,
         const float gk = (coef[k] * lpq_dpow(t, a.p, a.pmode)) * sign;     // Power p backward; EltwiseMult cu:225-231
         g[k] = ok ? gk : 0.f;                                  // KillMasked cu:233-237
       }
-      if (s.d0) lpq_store<V, VEC>(s.d0 + i, g);                // Eltwise backward, coeff +1
+      if (s.d0) store<V, VEC>(s.d0 + i, g);                // Eltwise backward, coeff +1
       if (s.d1) {
 #pragma unroll
         for (int k = 0; k < V; ++k) g[k] = -g[k];              // coeff -1
-        lpq_store<V, VEC>(s.d1 + i, g);
+        store<V, VEC>(s.d1 + i, g);
       }
     }
   }
@@ -235,17 +196,17 @@ __device__ __forceinline__ void lpq_bwd_dispatch(const LpqBlob& s, const LpqArgs
   else lpq_bwd_body<4, false>(s, a, top_diff, bid, nblk);
 }
 
-__global__ void __launch_bounds__(kLpqThreads) lpq_fwd_partial(LpqBlob s, LpqArgs a) {
+__global__ void __launch_bounds__(kThreads) lpq_fwd_partial(LpqBlob s, LpqArgs a) {
   __shared__ double lds[8];
   lpq_partial(s, a, blockIdx.x, gridDim.x, lds);
 }
 
-__global__ void __launch_bounds__(kLpqThreads) lpq_fwd_final(LpqBlob s, LpqArgs a, float* __restrict__ loss_out) {
+__global__ void __launch_bounds__(kThreads) lpq_fwd_final(LpqBlob s, LpqArgs a, float* __restrict__ loss_out) {
   __shared__ double lds[8];
   lpq_final_body(s, a, loss_out, lds);
 }
 
-__global__ void __launch_bounds__(kLpqThreads) lpq_bwd(LpqBlob s, LpqArgs a, float top_diff) {
+__global__ void __launch_bounds__(kThreads) lpq_bwd(LpqBlob s, LpqArgs a, float top_diff) {
   lpq_bwd_dispatch(s, a, top_diff, blockIdx.x, gridDim.x);
 }
 
@@ -260,7 +221,7 @@ __device__ __forceinline__ int lpq_scale_of(const LpqMulti& m) {
 // the workgroup that arrives LAST at its scale's counter (release / acquire around an integer atomic) runs the finalise body; the scale
 // that finishes last adds up total = sum_s loss_weight[s] * loss[s] in scale order, each product and sum rounded to float.  The
 // counters are left at zero for the next call.
-__global__ void __launch_bounds__(kLpqThreads) lpq_fwd_multi(LpqMulti m) {
+__global__ void __launch_bounds__(kThreads) lpq_fwd_multi(LpqMulti m) {
   __shared__ double lds[8];
   __shared__ int s_last;
   const int si = lpq_scale_of(m);
@@ -290,7 +251,7 @@ __global__ void __launch_bounds__(kLpqThreads) lpq_fwd_multi(LpqMulti m) {
   }
 }
 
-__global__ void __launch_bounds__(kLpqThreads) lpq_bwd_multi(LpqMulti m) {
+__global__ void __launch_bounds__(kThreads) lpq_bwd_multi(LpqMulti m) {
   const int si = lpq_scale_of(m);
   const LpqBlob& sc = m.s[si];
   const float g = m.total_diff ? m.total_diff[0] : 1.f;
@@ -310,8 +271,6 @@ static int lpq_args(const char* what, float p, float q, float p_eps, float q_eps
 
 static size_t lpq_ws_bytes() { return 64 + sizeof(double) * 2 * kLpqMaxBlocks; }   // float[0] = loss, float[1] = normalize_coeff, pad to 64 B, partial[2 * kLpqMaxBlocks]
 
-static bool lpq_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // One blob pair: shape and pointer checks, the launch geometry (by the shape alone) and the load form.
 static int lpq_blob(const char* what, int scale, const float* b0, const float* b1, float* d0, float* d1, bool backward, int N, int C, int H,
                     int W, void* ws, LpqBlob* s) {
@@ -327,8 +286,8 @@ static int lpq_blob(const char* what, int scale, const float* b0, const float* b
   s->N = N; s->C = C; s->H = H; s->W = W;
   const long long hw = (long long)H * W;
   s->quad = (hw % 4) == 0;
-  s->vec = s->quad && lpq_aligned16(b0) && lpq_aligned16(b1) && lpq_aligned16(d0) && lpq_aligned16(d1);
-  s->nb = (int)blocks_for((long long)N * (hw / (s->quad ? 4 : 1)), kLpqThreads, kLpqMaxBlocks);
+  s->vec = s->quad && aligned16(b0) && aligned16(b1) && aligned16(d0) && aligned16(d1);
+  s->nb = (int)blocks_for((long long)N * (hw / (s->quad ? 4 : 1)), kThreads, kLpqMaxBlocks);
   s->blk0 = 0;
   s->loss_weight = 1.f;
   return FN2_OK;
@@ -388,8 +347,8 @@ FN2_API int fn2_lpq_loss_forward(const float* bottom0, const float* bottom1, flo
   if (!workspace || workspace_bytes < lpq_ws_bytes())
     return fail(FN2_ERR_WORKSPACE, "lpq_loss_forward: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, lpq_ws_bytes());
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(lpq_fwd_partial, dim3(s.nb), dim3(kLpqThreads), 0, st, s, a);
-  hipLaunchKernelGGL(lpq_fwd_final, dim3(1), dim3(kLpqThreads), 0, st, s, a, loss_out);
+  hipLaunchKernelGGL(lpq_fwd_partial, dim3(s.nb), dim3(kThreads), 0, st, s, a);
+  hipLaunchKernelGGL(lpq_fwd_final, dim3(1), dim3(kThreads), 0, st, s, a, loss_out);
   return check_launch("lpq_loss_forward");
 }
 
@@ -404,7 +363,7 @@ FN2_API int fn2_lpq_loss_backward(const float* bottom0, const float* bottom1, fl
   if (rc) return rc;
   if (!workspace || workspace_bytes < lpq_ws_bytes())
     return fail(FN2_ERR_WORKSPACE, "lpq_loss_backward: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, lpq_ws_bytes());
-  hipLaunchKernelGGL(lpq_bwd, dim3(s.nb), dim3(kLpqThreads), 0, as_stream(stream), s, a, top_diff);
+  hipLaunchKernelGGL(lpq_bwd, dim3(s.nb), dim3(kThreads), 0, as_stream(stream), s, a, top_diff);
   return check_launch("lpq_loss_backward");
 }
 
@@ -422,7 +381,7 @@ FN2_API int fn2_lpq_loss_forward_multi(int nscales, const void* const* bottoms0,
   if (!sync) return fail(FN2_ERR_INVALID_ARG, "lpq_loss_forward_multi: sync == NULL (fn2_lpq_loss_sizes' sync bytes, zero, left zero by every call)");
   m.sync = reinterpret_cast<unsigned*>(sync);
   m.losses = losses; m.total = total; m.total_diff = nullptr;
-  hipLaunchKernelGGL(lpq_fwd_multi, dim3(blocks), dim3(kLpqThreads), 0, as_stream(stream), m);
+  hipLaunchKernelGGL(lpq_fwd_multi, dim3(blocks), dim3(kThreads), 0, as_stream(stream), m);
   return check_launch("lpq_loss_forward_multi");
 }
 
@@ -438,6 +397,6 @@ FN2_API int fn2_lpq_loss_backward_multi(int nscales, const void* const* bottoms0
                       workspace, workspace_bytes, &m, &blocks);
   if (rc) return rc;
   m.sync = nullptr; m.losses = nullptr; m.total = nullptr; m.total_diff = total_diff;
-  hipLaunchKernelGGL(lpq_bwd_multi, dim3(blocks), dim3(kLpqThreads), 0, as_stream(stream), m);
+  hipLaunchKernelGGL(lpq_bwd_multi, dim3(blocks), dim3(kThreads), 0, as_stream(stream), m);
   return check_launch("lpq_loss_backward_multi");
 }

@@ -22,18 +22,16 @@
 // Reads stay inside the sample: a row or a four-pixel group of the neighbourhood is loaded only where it lies inside the plane, a
 // smoothness term is formed only where its pixels are, and the tap indices are formed only after the finite, occlusion and inside tests,
 // from a coordinate in [0, W) x [0, H), and clamped to W - 1 and H - 1.
-#include "fn2_common.hpp"
+#include "stream_reduce.hpp"
 #include "../../include/flownet2_hip_unsup_loss.h"
 
 #pragma clang fp contract(off)
 
 namespace fn2 {
 
-constexpr int kUlThreads = 256;
-constexpr int kUlK = FN2_UNSUP_LOSS_K;
-constexpr int kUlPixelsPerBlock = 4 * kUlThreads;      // B = ceil(H W / this), at most kUlMaxChunks
-constexpr int kUlMaxChunks = 128;
-constexpr int kUlMaxGrid = 1 << 16;                    // work items beyond this are taken in a workgroup-stride loop
+using namespace stream;
+
+constexpr int kUlK = FN2_UNSUP_LOSS_K;                 // every column is a sum
 constexpr int kUlMaxC = 4;
 enum { kUlCounted = 0, kUlOccluded, kUlOutside, kUlNonfinite };
 
@@ -65,29 +63,6 @@ struct UlSample {
   const float* __restrict__ occ;
 };
 
-template <int V, bool VEC>
-__device__ __forceinline__ void ul_load(const float* __restrict__ p, float (&v)[V]) {
-  if constexpr (VEC) {
-    const float4 f = *reinterpret_cast<const float4*>(p);
-    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = p[k];
-  }
-}
-
-template <int V, bool VEC>
-__device__ __forceinline__ void ul_store(float* __restrict__ p, const float (&v)[V]) {
-  if constexpr (VEC) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) p[k] = v[k];
-  }
-}
-
-__device__ __forceinline__ bool ul_ok(float x) { return fabsf(x) <= 1e9f; }      // false for NaN and +-Inf
-
 __device__ __forceinline__ float ul_psi(float t, float eps, float gam) {
   const float r = t * t + eps * eps;
   return gam == 0.5f ? sqrtf(r) : powf(r, gam);
@@ -109,7 +84,7 @@ __device__ __forceinline__ UlData ul_data(const UlArgs& a, const UlSample& s, in
                                           const float (&ic)[kUlMaxC]) {
   UlData r = {kUlNonfinite, 0.f, 0.f, 0.f};
   const float au = a.mult * fu, av = a.mult * fv;
-  if (!ul_ok(au) || !ul_ok(av)) return r;
+  if (!finite_1e9(au) || !finite_1e9(av)) return r;
   if (!(oc == 0.0f)) {
     r.cls = kUlOccluded;
     return r;
@@ -119,21 +94,16 @@ __device__ __forceinline__ UlData ul_data(const UlArgs& a, const UlSample& s, in
     r.cls = kUlOutside;
     return r;
   }
-  // 0 <= x2 < W here, so the conversion is defined; the min keeps the index inside where float(W) rounds up (W above 2^24)
-  const int ixL = min((int)x2, a.W - 1), iyT = min((int)y2, a.H - 1);
-  const int ixR = min(ixL + 1, a.W - 1), iyB = min(iyT + 1, a.H - 1);
-  const float al = x2 - (float)ixL, be = y2 - (float)iyT;
-  const float cTL = (1.f - al) * (1.f - be), cTR = al * (1.f - be), cBL = (1.f - al) * be, cBR = al * be;
-  const int oTL = iyT * a.W + ixL, oTR = iyT * a.W + ixR, oBL = iyB * a.W + ixL, oBR = iyB * a.W + ixR;
-  const float gy = (float)iyB - y2, gx = (float)ixR - x2;
+  const BilinearTaps t = bilinear_taps(x2, y2, a.W, a.H);
+  const float gy = (float)t.iyB - y2, gx = (float)t.ixR - x2;
   const size_t hw = (size_t)a.H * a.W;
   float e = 0.f, su = 0.f, sv = 0.f;
   bool fin = true;
   for (int c = 0; c < a.C; ++c) {
     const float* __restrict__ p = s.Io + (size_t)c * hw;
-    const float TL = p[oTL], TR = p[oTR], BL = p[oBL], BR = p[oBR], I = ic[c];
-    fin = fin && ul_ok(TL) && ul_ok(TR) && ul_ok(BL) && ul_ok(BR) && ul_ok(I);
-    const float warped = ((cTL * TL + cTR * TR) + cBL * BL) + cBR * BR;
+    const float TL = p[t.oTL], TR = p[t.oTR], BL = p[t.oBL], BR = p[t.oBR], I = ic[c];
+    fin = fin && finite_1e9(TL) && finite_1e9(TR) && finite_1e9(BL) && finite_1e9(BR) && finite_1e9(I);
+    const float warped = ((t.wTL * TL + t.wTR * TR) + t.wBL * BL) + t.wBR * BR;
     const float d = I - warped;
     if constexpr (GRAD) {
       const float dp = ul_dpsi(d, a.eps_d, a.gam_d);
@@ -168,10 +138,10 @@ __device__ __forceinline__ UlTerm ul_term(const UlArgs& a, const UlSample& s, in
   }
   const int o0 = y * a.W + x, op = yp * a.W + xp, oq = yq * a.W + xq;
   const float u0 = a.mult * s.u[o0], v0 = a.mult * s.v[o0], up = a.mult * s.u[op], vp = a.mult * s.v[op];
-  if (!ul_ok(u0) || !ul_ok(v0) || !ul_ok(up) || !ul_ok(vp)) return t;
+  if (!finite_1e9(u0) || !finite_1e9(v0) || !finite_1e9(up) || !finite_1e9(vp)) return t;
   if (a.order == 2) {
     const float um = a.mult * s.u[oq], vm = a.mult * s.v[oq];
-    if (!ul_ok(um) || !ul_ok(vm)) return t;
+    if (!finite_1e9(um) || !finite_1e9(vm)) return t;
     t.su = (um - 2.0f * u0) + up;
     t.sv = (vm - 2.0f * v0) + vp;
   } else {
@@ -183,7 +153,7 @@ __device__ __forceinline__ UlTerm ul_term(const UlArgs& a, const UlSample& s, in
     float g = 0.f;
     for (int c = 0; c < a.C; ++c) {
       const float ip = s.Ia[(size_t)c * hw + op], iq = s.Ia[(size_t)c * hw + oq];
-      if (!ul_ok(ip) || !ul_ok(iq)) return t;
+      if (!finite_1e9(ip) || !finite_1e9(iq)) return t;
       g += fabsf(ip - iq);
     }
     t.wgt = expf((-a.edge) * (g / (float)a.C));
@@ -215,12 +185,6 @@ __device__ __forceinline__ void ul_g(const UlArgs& a, const UlSample& s, int x, 
     gu = mu - cu;
     gv = mv - cv;
   }
-}
-
-__device__ __forceinline__ double ul_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
 }
 
 __device__ __forceinline__ UlSample ul_sample(const UlArgs& a, int d, long long n) {
@@ -257,18 +221,7 @@ __device__ __forceinline__ void ul_reduce(const UlArgs& a, int d, long long n, i
   row[FN2_UNSUP_LOSS_DATA_SUM] = t.data;
   row[FN2_UNSUP_LOSS_SMOOTH_TERMS] = (double)t.terms;
   row[FN2_UNSUP_LOSS_SMOOTH_SUM] = t.smooth;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kUlK; ++k) {
-    const double v = ul_wave_sum(row[k]);
-    if (lane == 0) lds[wid][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kUlK) {
-    const int k = threadIdx.x;
-    a.partial[(((size_t)d * a.N + n) * a.chunks + chunk) * kUlK + k] = ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
-  }
-  __syncthreads();                                           // the next work item of this workgroup writes lds again
+  reduce_row<kUlK, 0u>(row, lds, a.partial + (((size_t)d * a.N + n) * a.chunks + chunk) * kUlK);
 }
 
 // Chunk `chunk` of (direction d, sample n) on the one-pixel path: pixels chunk * 256 + thread, then every B * 256 further on; every term
@@ -279,7 +232,7 @@ __device__ __forceinline__ void ul_chunk1(const UlArgs& a, int d, long long n, i
   const size_t hw = (size_t)H * W;
   const UlSample s = ul_sample(a, d, n);
   UlSums t = {};
-  for (long long un = (long long)chunk * kUlThreads + threadIdx.x; un < (long long)hw; un += (long long)a.chunks * kUlThreads) {
+  for (long long un = (long long)chunk * kThreads + threadIdx.x; un < (long long)hw; un += (long long)a.chunks * kThreads) {
     const unsigned r = (unsigned)un;                                       // H W < 2^30
     const int y = (int)(r / (unsigned)W), x = (int)(r - (unsigned)y * W);
     float ic[kUlMaxC];
@@ -352,14 +305,14 @@ template <int N>
 __device__ __forceinline__ bool ul_line_edge(const UlArgs& a, const float (&I)[N], int i, float& g) {
   const float ip = I[i + 1], iq = a.order == 2 ? I[i - 1] : I[i];
   g += fabsf(ip - iq);
-  return ul_ok(ip) && ul_ok(iq);
+  return finite_1e9(ip) && finite_1e9(iq);
 }
 
 // four values at p where `there`, else zeros
 template <bool VEC>
 __device__ __forceinline__ void ul_load4_if(bool there, const float* __restrict__ p, float* o) {
   float t[4] = {0.f, 0.f, 0.f, 0.f};
-  if (there) ul_load<4, VEC>(p, t);
+  if (there) load<4, VEC>(p, t);
   o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = t[3];
 }
 
@@ -396,7 +349,7 @@ __device__ __forceinline__ void ul_unit4(const UlArgs& a, const UlSample& s, int
     for (int j = 0; j < 12; ++j) {
       row.u[j] = a.mult * ru[j];
       row.v[j] = a.mult * rv[j];
-      if (((in >> j) & 1u) && ul_ok(row.u[j]) && ul_ok(row.v[j])) row.ok |= 1u << j;
+      if (((in >> j) & 1u) && finite_1e9(row.u[j]) && finite_1e9(row.v[j])) row.ok |= 1u << j;
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -415,13 +368,13 @@ __device__ __forceinline__ void ul_unit4(const UlArgs& a, const UlSample& s, int
       for (int k = 0; k < 4; ++k) {
         col[k].u[e] = a.mult * cu[k];
         col[k].v[e] = a.mult * cv[k];
-        if (there[q] && ul_ok(col[k].u[e]) && ul_ok(col[k].v[e])) col[k].ok |= 1u << e;
+        if (there[q] && finite_1e9(col[k].u[e]) && finite_1e9(col[k].v[e])) col[k].ok |= 1u << e;
       }
     }
   }
   float oc[4];
   if (s.occ) {
-    ul_load<4, VEC>(s.occ + r, oc);
+    load<4, VEC>(s.occ + r, oc);
   } else {
 #pragma unroll
     for (int k = 0; k < 4; ++k) oc[k] = 0.f;
@@ -441,7 +394,7 @@ __device__ __forceinline__ void ul_unit4(const UlArgs& a, const UlSample& s, int
     if (c < a.C) {
       const float* __restrict__ p = s.Ia + (size_t)c * hw + r;
       if (!edge) {
-        ul_load<4, VEC>(p, ic[c]);
+        load<4, VEC>(p, ic[c]);
       } else {
         float ir[12], icol[5];
         ul_load4_if<VEC>(left, p - 4, ir);
@@ -547,8 +500,8 @@ __device__ __forceinline__ void ul_unit4(const UlArgs& a, const UlSample& s, int
   }
   if constexpr (!FWD) {
     float* __restrict__ o = a.diff[d] + (size_t)n * 2 * hw + r;
-    ul_store<4, VEC>(o, ou);
-    ul_store<4, VEC>(o + hw, ov);
+    store<4, VEC>(o, ou);
+    store<4, VEC>(o + hw, ov);
   }
 }
 
@@ -558,7 +511,7 @@ __device__ __forceinline__ void ul_chunk4(const UlArgs& a, int d, long long n, i
   const long long units = (long long)(((size_t)a.H * a.W) / 4);
   const UlSample s = ul_sample(a, d, n);
   UlSums t = {};
-  for (long long un = (long long)chunk * kUlThreads + threadIdx.x; un < units; un += (long long)a.chunks * kUlThreads)
+  for (long long un = (long long)chunk * kThreads + threadIdx.x; un < units; un += (long long)a.chunks * kThreads)
     ul_unit4<VEC, FWD>(a, s, d, n, (unsigned)un * 4u, t, kd, ks);                // H W < 2^30
   if constexpr (FWD) ul_reduce(a, d, n, chunk, lds, t);
 }
@@ -584,42 +537,19 @@ __device__ __forceinline__ void ul_items(const UlArgs& a, double (*lds)[kUlK]) {
   }
 }
 
-__global__ void __launch_bounds__(kUlThreads) unsup_loss_partial(UlArgs a) {
+__global__ void __launch_bounds__(kThreads) unsup_loss_partial(UlArgs a) {
   __shared__ double lds[4][kUlK];
   ul_items<true>(a, lds);
 }
 
-__global__ void __launch_bounds__(kUlThreads) unsup_loss_grad(UlArgs a) {
+__global__ void __launch_bounds__(kThreads) unsup_loss_grad(UlArgs a) {
   ul_items<false>(a, nullptr);
 }
 
-// One workgroup.  A thread per (direction, sample, column) adds that sample's B partial rows in index order; then a thread per
-// (direction, column) adds the sample rows in sample order; then one thread forms the loss.  A direction that was not run gets zeros.
-__global__ void __launch_bounds__(kUlThreads) unsup_loss_final(UlArgs a) {
-  const int B = a.chunks;
-  const long long cells = 2LL * a.N * kUlK;
-  for (long long c = threadIdx.x; c < cells; c += kUlThreads) {
-    const long long dn = c / kUlK;                           // d * N + n
-    const int k = (int)(c % kUlK);
-    const long long d = dn / a.N, n = dn - d * a.N;
-    double v = 0.0;
-    if (d < a.dirs) {
-      const double* __restrict__ p = a.partial + (size_t)dn * B * kUlK + k;
-#pragma unroll 8
-      for (int b = 0; b < B; ++b) v = v + p[(size_t)b * kUlK];
-    }
-    a.results[((size_t)d * (a.N + 1) + n) * kUlK + k] = v;
-  }
-  __threadfence_block();                                     // the sample rows, written by other threads of this workgroup, are read below
-  __syncthreads();
-  if (threadIdx.x < 2 * kUlK) {
-    const int d = threadIdx.x / kUlK, k = threadIdx.x % kUlK;
-    const double* p = a.results + (size_t)d * (a.N + 1) * kUlK + k;
-    double total = 0.0;
-#pragma unroll 8
-    for (long long n = 0; n < a.N; ++n) total = total + p[(size_t)n * kUlK];
-    a.results[((size_t)d * (a.N + 1) + a.N) * kUlK + k] = total;
-  }
+// One workgroup.  The two directions are the groups of the plain finalise, a direction that was not run gets zeros; then one thread
+// forms the loss.
+__global__ void __launch_bounds__(kThreads) unsup_loss_final(UlArgs a) {
+  finalize_rows<kUlK, 0u>(a.partial, a.results, 2, a.N, a.chunks, a.dirs);
   __threadfence_block();
   __syncthreads();
   if (threadIdx.x == 0 && a.loss) {
@@ -634,25 +564,13 @@ __global__ void __launch_bounds__(kUlThreads) unsup_loss_final(UlArgs a) {
   }
 }
 
-static int ul_chunks(long long hw) {
-  const long long b = (hw + kUlPixelsPerBlock - 1) / kUlPixelsPerBlock;
-  return (int)(b < 1 ? 1 : b > kUlMaxChunks ? kUlMaxChunks : b);
-}
-
 static int ul_shape(const char* what, int N, int C, int H, int W) {
   if (N < 1 || H < 1 || W < 1) return fail(FN2_ERR_INVALID_ARG, "%s: bad shape [%d,%d,%d,%d]", what, N, C, H, W);
   if (C < 1 || C > kUlMaxC) return fail(FN2_ERR_INVALID_ARG, "%s: C = %d channels (need 1 .. %d)", what, C, kUlMaxC);
-  // in steps, so that no product of three ints wraps: H W < 2^62; then 4 H W < 2^32 and N < 2^31 give N 4 H W < 2^63
-  const long long hw = (long long)H * W;
-  const int planes = C > 2 ? C : 2;
-  if (hw >= (1LL << 30) || (long long)N * (planes * hw) >= (1LL << 31))
-    return fail(FN2_ERR_INVALID_ARG, "%s: blob [%d,%d,%d,%d] of 2^31 elements or more", what, N, planes, H, W);
-  return FN2_OK;
+  return check_planes(what, N, C > 2 ? C : 2, H, W);      // the larger of an image [N,C,H,W] and a flow [N,2,H,W]
 }
 
-static size_t ul_ws_bytes(int N, int H, int W) { return sizeof(double) * kUlK * 2 * (size_t)N * ul_chunks((long long)H * W); }
-
-static bool ul_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }      // NULL (absent) counts as aligned
+static size_t ul_ws_bytes(int N, int H, int W) { return sizeof(double) * kUlK * 2 * (size_t)N * chunks((long long)H * W); }
 
 // the checks both directions of differentiation share; fills what they share of `a`
 static int ul_setup(const char* what, UlArgs& a, const float* img0, const float* img1, const float* fw, const float* bw, const float* occ_fw,
@@ -676,11 +594,11 @@ static int ul_setup(const char* what, UlArgs& a, const float* img0, const float*
   a.flow[0] = fw; a.flow[1] = bw;
   a.occ[0] = occ_fw; a.occ[1] = occ_bw;
   a.N = N; a.C = C; a.H = H; a.W = W;
-  a.chunks = ul_chunks((long long)H * W);
+  a.chunks = chunks((long long)H * W);
   a.dirs = bw ? 2 : 1;
   a.quad = (W % 4) == 0;
-  a.vec = a.quad && ul_aligned16(img0) && ul_aligned16(img1) && ul_aligned16(fw) && ul_aligned16(bw) && ul_aligned16(occ_fw) &&
-          ul_aligned16(occ_bw);
+  a.vec = a.quad && aligned16(img0) && aligned16(img1) && aligned16(fw) && aligned16(bw) && aligned16(occ_fw) &&
+          aligned16(occ_bw);
   a.order = smooth_order;
   a.dw = data_weight; a.sw = smooth_weight; a.eps_d = eps_d; a.gam_d = gamma_d; a.eps_s = eps_s; a.gam_s = gamma_s;
   a.edge = edge_weight; a.mult = flow_mult;
@@ -716,8 +634,8 @@ FN2_API int fn2_unsup_loss_forward(const float* img0, const float* img1, const f
   a.loss = loss;
   const long long items = (long long)a.dirs * N * a.chunks;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(unsup_loss_partial, dim3((unsigned)(items < kUlMaxGrid ? items : kUlMaxGrid)), dim3(kUlThreads), 0, st, a);
-  hipLaunchKernelGGL(unsup_loss_final, dim3(1), dim3(kUlThreads), 0, st, a);
+  hipLaunchKernelGGL(unsup_loss_partial, grid_for(items), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(unsup_loss_final, dim3(1), dim3(kThreads), 0, st, a);
   return check_launch(what);
 }
 
@@ -737,8 +655,8 @@ FN2_API int fn2_unsup_loss_backward(const float* img0, const float* img1, const 
   a.total_diff = total_diff;
   a.diff[0] = fw_diff; a.diff[1] = bw_diff;
   a.dirs = bw_diff ? 2 : 1;
-  a.vec = a.vec && ul_aligned16(fw_diff) && ul_aligned16(bw_diff);
+  a.vec = a.vec && aligned16(fw_diff) && aligned16(bw_diff);
   const long long items = (long long)a.dirs * N * a.chunks;
-  hipLaunchKernelGGL(unsup_loss_grad, dim3((unsigned)(items < kUlMaxGrid ? items : kUlMaxGrid)), dim3(kUlThreads), 0, as_stream(stream), a);
+  hipLaunchKernelGGL(unsup_loss_grad, grid_for(items), dim3(kThreads), 0, as_stream(stream), a);
   return check_launch(what);
 }
