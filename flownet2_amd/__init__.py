@@ -11,6 +11,8 @@ flow_consistency  forward-backward consistency of two flows -> FlowConsistency (
 visualize  flow_to_color (Middlebury colour coding) and flow_error_map (KITTI-style error image) on fused kernels, color_wheel, write_png
 unsupervised_loss  photometric + smoothness training loss without ground truth, one fused pass per direction of differentiation;
             unsupervised_loss_report -> UnsupLoss (rows, summary())
+census_loss  the census data term of UnFlow (soft Hamming distance of ternary census signatures over a patch) on fused kernels: unchanged
+            by an additive change of brightness; unsupervised_loss(data_term="census") uses it; census_loss_report -> CensusLoss
 flow_track  points carried through a flow sequence in one launch -> FlowTracks (trajectories, long_range_flow()); flow_track_reseed, flow_track_grid
 """
 from . import _lib  # noqa: F401
@@ -18,7 +20,8 @@ from ._lib import Fn2Error, version  # noqa: F401
 
 _SOLVER_EXPORTS = ("SolverParameter", "Solver", "SGDSolver", "AdamSolver", "get_solver", "CaffeOptimizer")
 __all__ = ["Fn2Error", "version", "LpqSchedule", "flow_consistency", "FlowConsistency", "flow_to_color", "flow_error_map", "flow_track",
-           "flow_track_reseed", "flow_track_grid", "FlowTracks", "unsupervised_loss", "unsupervised_loss_report", "UnsupLoss", *_SOLVER_EXPORTS]
+           "flow_track_reseed", "flow_track_grid", "FlowTracks", "unsupervised_loss", "unsupervised_loss_report", "UnsupLoss", "census_loss",
+           "census_loss_report", "CensusLoss", *_SOLVER_EXPORTS]
 
 
 def __getattr__(name):
@@ -33,7 +36,7 @@ def __getattr__(name):
         from .functional import flow_consistency
         return flow_consistency
     if name in ("flow_to_color", "flow_error_map", "flow_track", "flow_track_reseed", "flow_track_grid", "unsupervised_loss",
-                "unsupervised_loss_report"):
+                "unsupervised_loss_report", "census_loss", "census_loss_report"):
         from . import functional
         return getattr(functional, name)
     if name == "FlowConsistency":
@@ -45,4 +48,7 @@ def __getattr__(name):
     if name == "UnsupLoss":
         from .evaluate import UnsupLoss
         return UnsupLoss
+    if name == "CensusLoss":
+        from .evaluate import CensusLoss
+        return CensusLoss
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -194,7 +194,7 @@ class UnsupLoss:
     """The [n, K] float64 rows (columns UNSUP_LOSS_COLUMNS) of n samples per direction of functional.unsupervised_loss_report, and the
     loss of the call (None for rows put together by hand).  rows_bw is all zeros where no backward flow was given."""
 
-    def __init__(self, rows_fw=None, rows_bw=None, loss=None, data_weight=1.0, smooth_weight=1.0):
+    def __init__(self, rows_fw=None, rows_bw=None, loss=None, data_weight=1.0, smooth_weight=1.0, census=None):
         def rows(r, what):
             r = np.zeros((0, UNSUP_LOSS_K), np.float64) if r is None else np.array(r, dtype=np.float64)
             if r.ndim != 2 or r.shape[1] != UNSUP_LOSS_K:
@@ -206,6 +206,7 @@ class UnsupLoss:
             raise ValueError(f"UnsupLoss: {self.rows_fw.shape[0]} forward rows, {self.rows_bw.shape[0]} backward rows")
         self.loss = None if loss is None else float(loss)
         self.data_weight, self.smooth_weight = float(data_weight), float(smooth_weight)
+        self.census = census                                                        # a CensusLoss where the census term is the data term
 
     def __len__(self):
         return self.rows_fw.shape[0]
@@ -227,9 +228,63 @@ class UnsupLoss:
     def summary(self):
         """Per direction the mean data term over the counted pixels, the mean smoothness term, the shares of all pixels that were
         counted, occluded, outside and non-finite, and the pixel count; then the sample count, the weights and the loss.  A quotient with
-        a zero denominator is nan."""
+        a zero denominator is nan.  Where the census term is the data term, its summary under "census"."""
+        out = {"fw": self._direction(self.rows_fw), "bw": self._direction(self.rows_bw), "samples": len(self),
+               "data_weight": self.data_weight, "smooth_weight": self.smooth_weight, "loss": self.loss}
+        if self.census is not None:
+            out["census"] = self.census.summary()
+        return out
+
+
+# ---- census data term ----------------------------------------------------------------------------------------------------------------
+_C_PREFIX = "FN2_CENSUS_LOSS_"
+_C_ENUM = _lib.CENSUS_LOSS_CONSTANTS                                      # include/flownet2_hip_census_loss.h: the columns of a row
+CENSUS_LOSS_K = _C_ENUM[_C_PREFIX + "K"]
+CENSUS_LOSS_COLUMNS = tuple(sorted((n[len(_C_PREFIX):] for n in _C_ENUM if n != _C_PREFIX + "K"), key=lambda n: _C_ENUM[_C_PREFIX + n]))
+CENSUS_LOSS_COL = {name: i for i, name in enumerate(CENSUS_LOSS_COLUMNS)}
+
+
+class CensusLoss:
+    """The [n, K] float64 rows (columns CENSUS_LOSS_COLUMNS) of n samples per direction of functional.census_loss_report, and the loss of
+    the call (None for rows put together by hand).  rows_bw is all zeros where no backward flow was given."""
+
+    def __init__(self, rows_fw=None, rows_bw=None, loss=None, data_weight=1.0, radius=3):
+        def rows(r, what):
+            r = np.zeros((0, CENSUS_LOSS_K), np.float64) if r is None else np.array(r, dtype=np.float64)
+            if r.ndim != 2 or r.shape[1] != CENSUS_LOSS_K:
+                raise ValueError(f"CensusLoss: {what} must be [n, {CENSUS_LOSS_K}], got {r.shape}")
+            return r
+        self.rows_fw = rows(rows_fw, "rows_fw")
+        self.rows_bw = rows(rows_bw if rows_bw is not None else np.zeros_like(self.rows_fw), "rows_bw")
+        if self.rows_fw.shape != self.rows_bw.shape:
+            raise ValueError(f"CensusLoss: {self.rows_fw.shape[0]} forward rows, {self.rows_bw.shape[0]} backward rows")
+        self.loss = None if loss is None else float(loss)
+        self.data_weight, self.radius = float(data_weight), int(radius)
+
+    def __len__(self):
+        return self.rows_fw.shape[0]
+
+    @staticmethod
+    def _direction(rows):
+        tot = lambda name: float(np.sum(rows[:, CENSUS_LOSS_COL[name]]))
+        pixels, counted = tot("PIXELS"), tot("COUNTED")
+        return {
+            "data_mean": _ratio(tot("DATA_SUM"), counted),
+            "dist_mean": _ratio(tot("DIST_SUM"), counted),
+            "pairs_mean": _ratio(tot("PAIRS"), counted),
+            "counted": _ratio(counted, pixels),
+            "occluded": _ratio(tot("OCCLUDED"), pixels),
+            "outside": _ratio(tot("OUTSIDE"), pixels),
+            "nonfinite": _ratio(tot("NONFINITE"), pixels),
+            "pixels": int(pixels),
+        }
+
+    def summary(self):
+        """Per direction the mean data term, the mean soft Hamming distance and the mean number of pairs over the counted pixels, the
+        shares of all pixels that were counted, occluded, outside and non-finite, and the pixel count; then the sample count, the weight,
+        the radius and the loss.  A quotient with a zero denominator is nan."""
         return {"fw": self._direction(self.rows_fw), "bw": self._direction(self.rows_bw), "samples": len(self),
-                "data_weight": self.data_weight, "smooth_weight": self.smooth_weight, "loss": self.loss}
+                "data_weight": self.data_weight, "radius": self.radius, "loss": self.loss}
 
 
 def write_pgm(path, plane):

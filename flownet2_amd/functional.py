@@ -498,15 +498,93 @@ def _unsup_loss_args(what, img0, img1, fw, bw, occ_fw, occ_bw, kw):
     return blobs, ops.unsup_loss_params(**kw)
 
 
+class _CensusLoss(torch.autograd.Function):
+    """Forward three launches, backward one; the planes G, Wg, pd, the normalisers and the upstream gradient stay on the device."""
+
+    @staticmethod
+    def forward(ctx, img0, img1, fw, bw, occ_fw, occ_bw, params):
+        results, loss, saved = ops.census_loss_forward(img0, img1, fw, bw, occ_fw, occ_bw, params)
+        ctx.params, ctx.results, ctx.planes = params, results, saved
+        ctx.save_for_backward(img0, img1, fw, bw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        img0, img1, fw, bw = ctx.saved_tensors
+        need_bw = bw is not None and ctx.needs_input_grad[3]
+        fd, bd = ops.census_loss_backward(img0, img1, fw, bw, ctx.params, ctx.results, ctx.planes, g.contiguous(), need_bw=need_bw)
+        return None, None, (fd if ctx.needs_input_grad[2] else None), (bd if need_bw else None), None, None, None
+
+
+def _census_loss_args(what, img0, img1, fw, bw, occ_fw, occ_bw, kw):
+    for name, t in (("img0", img0), ("img1", img1), ("occ_fw", occ_fw), ("occ_bw", occ_bw)):
+        if isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{what}: {name} gets no gradient (the flows alone do): detach it")
+    blobs = tuple(t.contiguous() if t is not None else None for t in (img0, img1, fw, bw, occ_fw, occ_bw))
+    return blobs, ops.census_loss_params(**kw)
+
+
+def census_loss(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, *, data_weight=1.0, charbonnier=(1e-3, 0.45), radius=3,
+                census_eps=(0.81, 0.1), intensity_scale=255.0, flow_mult=1.0):
+    """The census data term of UnFlow (csrc/census_loss.hip; the arithmetic is stated in include/flownet2_hip_census_loss.h) of a forward
+    flow fw [N,2,H,W] (frame 0 to frame 1) and, where given, a backward flow bw on the images img0, img1 [N,C,H,W], C up to 4: per
+    direction data_weight times the mean over the counted pixels of psi(dist), dist the soft Hamming distance between the ternary census
+    signatures, over a (2 radius + 1)^2 patch, of the own image and of the other image warped by the flow (grey values: the channel mean
+    times intensity_scale; census_eps = (c_t, c_h)), psi(t) = (t^2 + eps^2)^gamma with (eps, gamma) = charbonnier.  An additive change of
+    brightness between the frames leaves it unchanged.  occ_fw / occ_bw [N,1,H,W]: non-zero leaves the pixel's own term out
+    (flow_consistency's .occ_fw / .occ_bw go in as they are).  The flows are multiplied by flow_mult first.  Returns the 0-axis device
+    loss; gradients for fw and bw only."""
+    blobs, params = _census_loss_args("census_loss", img0, img1, fw, bw, occ_fw, occ_bw, dict(
+        data_weight=data_weight, charbonnier=charbonnier, radius=radius, census_eps=census_eps, intensity_scale=intensity_scale,
+        flow_mult=flow_mult))
+    return _CensusLoss.apply(*blobs, params)
+
+
+def census_loss_report(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, *, data_weight=1.0, charbonnier=(1e-3, 0.45), radius=3,
+                       census_eps=(0.81, 0.1), intensity_scale=255.0, flow_mult=1.0):
+    """census_loss's forward without autograd, as an evaluate.CensusLoss: the rows per direction and sample (counted, occluded, outside and
+    non-finite pixels, the data sum, the pairs and the sum of the distances) and the loss; summary() gives the means and shares."""
+    from .evaluate import CensusLoss
+    with torch.no_grad():
+        blobs, params = _census_loss_args("census_loss_report", img0, img1, fw, bw, occ_fw, occ_bw, dict(
+            data_weight=data_weight, charbonnier=charbonnier, radius=radius, census_eps=census_eps, intensity_scale=intensity_scale,
+            flow_mult=flow_mult))
+        results, loss, _ = ops.census_loss_forward(*blobs, params, save=False)
+    rows = results[:, :-1].cpu().numpy()
+    return CensusLoss(rows[0], rows[1], loss=float(loss), data_weight=data_weight, radius=radius)
+
+
+def _data_term(what, data_term, census):
+    if data_term not in ("brightness", "census"):
+        raise ValueError('%s: data_term must be "brightness" or "census", got %r' % (what, data_term))
+    if census is not None and data_term != "census":
+        raise ValueError(f'{what}: census= is given but data_term is "brightness"')
+    census = dict(census or {})
+    unknown = set(census) - {"radius", "census_eps", "intensity_scale"}
+    if unknown:
+        raise ValueError(f"{what}: census= takes radius, census_eps and intensity_scale, not {sorted(unknown)}")
+    return census
+
+
 def unsupervised_loss(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, *, data_weight=1.0, smooth_weight=1.0, charbonnier=(1e-3, 0.45),
-                      smooth_charbonnier=(1e-3, 0.45), edge_weight=10.0, smooth_order=2, flow_mult=1.0):
+                      smooth_charbonnier=(1e-3, 0.45), edge_weight=10.0, smooth_order=2, flow_mult=1.0, data_term="brightness", census=None):
     """The unsupervised training loss (csrc/unsup_loss.hip; the arithmetic is stated in include/flownet2_hip_unsup_loss.h) of a forward
     flow fw [N,2,H,W] (frame 0 to frame 1) and, where given, a backward flow bw on the images img0, img1 [N,C,H,W], C up to 4: per
     direction data_weight times the mean over the counted pixels of sum_c psi(I_own - I_other warped by the flow) plus smooth_weight times
     the mean of the smoothness terms exp(-edge_weight mean_c |dI|) (psi(d u) + psi(d v)) of first or second order, psi(t) =
     (t^2 + eps^2)^gamma with (eps, gamma) = charbonnier for the data and smooth_charbonnier for the smoothness term.  occ_fw / occ_bw
     [N,1,H,W]: non-zero leaves the pixel out of the data term (flow_consistency's .occ_fw / .occ_bw go in as they are).  The flows are
-    multiplied by flow_mult first.  Returns the 0-axis device loss; gradients for fw and bw only."""
+    multiplied by flow_mult first.  Returns the 0-axis device loss; gradients for fw and bw only.
+
+    data_term="census" replaces the brightness-constancy data term by census_loss (census=dict(radius=, census_eps=, intensity_scale=)
+    where its defaults are not wanted; data_weight and charbonnier go to it): the sum of census_loss(...) and of this call with
+    data_weight=0.0, which is the smoothness term.  The default leaves everything as it was."""
+    census = _data_term("unsupervised_loss", data_term, census)
+    if data_term == "census":
+        data = census_loss(img0, img1, fw, bw, occ_fw, occ_bw, data_weight=data_weight, charbonnier=charbonnier, flow_mult=flow_mult, **census)
+        return data + unsupervised_loss(img0, img1, fw, bw, occ_fw, occ_bw, data_weight=0.0, smooth_weight=smooth_weight, charbonnier=charbonnier,
+                                        smooth_charbonnier=smooth_charbonnier, edge_weight=edge_weight, smooth_order=smooth_order,
+                                        flow_mult=flow_mult)
     blobs, params = _unsup_loss_args("unsupervised_loss", img0, img1, fw, bw, occ_fw, occ_bw, dict(
         data_weight=data_weight, smooth_weight=smooth_weight, charbonnier=charbonnier, smooth_charbonnier=smooth_charbonnier,
         edge_weight=edge_weight, smooth_order=smooth_order, flow_mult=flow_mult))
@@ -514,10 +592,21 @@ def unsupervised_loss(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, *, data
 
 
 def unsupervised_loss_report(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, *, data_weight=1.0, smooth_weight=1.0,
-                             charbonnier=(1e-3, 0.45), smooth_charbonnier=(1e-3, 0.45), edge_weight=10.0, smooth_order=2, flow_mult=1.0):
+                             charbonnier=(1e-3, 0.45), smooth_charbonnier=(1e-3, 0.45), edge_weight=10.0, smooth_order=2, flow_mult=1.0,
+                             data_term="brightness", census=None):
     """unsupervised_loss's forward without autograd, as an evaluate.UnsupLoss: the rows per direction and sample (counted, occluded,
-    outside and non-finite pixels, the data and smoothness sums) and the loss; summary() gives the means and shares."""
+    outside and non-finite pixels, the data and smoothness sums) and the loss; summary() gives the means and shares.  With
+    data_term="census" the rows are those of the smoothness call (data_weight 0), .census holds census_loss_report's CensusLoss and .loss
+    the sum of the two losses."""
     from .evaluate import UnsupLoss
+    census = _data_term("unsupervised_loss_report", data_term, census)
+    if data_term == "census":
+        data = census_loss_report(img0, img1, fw, bw, occ_fw, occ_bw, data_weight=data_weight, charbonnier=charbonnier, flow_mult=flow_mult,
+                                  **census)
+        u = unsupervised_loss_report(img0, img1, fw, bw, occ_fw, occ_bw, data_weight=0.0, smooth_weight=smooth_weight, charbonnier=charbonnier,
+                                     smooth_charbonnier=smooth_charbonnier, edge_weight=edge_weight, smooth_order=smooth_order,
+                                     flow_mult=flow_mult)
+        return UnsupLoss(u.rows_fw, u.rows_bw, loss=data.loss + u.loss, data_weight=0.0, smooth_weight=smooth_weight, census=data)
     with torch.no_grad():
         blobs, params = _unsup_loss_args("unsupervised_loss_report", img0, img1, fw, bw, occ_fw, occ_bw, dict(
             data_weight=data_weight, smooth_weight=smooth_weight, charbonnier=charbonnier, smooth_charbonnier=smooth_charbonnier,

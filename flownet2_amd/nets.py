@@ -510,10 +510,13 @@ def unsupervised_loss(flows_fw, flows_bw, img0, img1, backend, occ="consistency"
     Downsample; the weighted sum in list order.  The predictions are in FlowNet's 1/20 units of full-resolution pixels, so flow_mult =
     FLOW_SCALE * w_s / W makes them pixels of the scale.  occ="consistency": the occlusion planes of the data term come from the
     backend's flow_consistency on the detached, rescaled flows of the scale; None: no pixel is masked.  kw: the keyword arguments of
-    functional.unsupervised_loss (weights, Charbonnier constants, edge_weight, smooth_order)."""
+    functional.unsupervised_loss (weights, Charbonnier constants, edge_weight, smooth_order, data_term and census: data_term="census"
+    takes the census data term of csrc/census_loss.hip at every scale)."""
     backend = backend_of(backend)
     if not backend.has_unsupervised_loss:
         raise RuntimeError("unsupervised_loss: the backend has no unsupervised_loss op (there is no composed fallback)")
+    if kw.get("data_term", "brightness") == "census" and not backend.has_census_loss:
+        raise RuntimeError("unsupervised_loss: the backend has no census_loss op (there is no composed fallback)")
     if occ not in ("consistency", None):
         raise ValueError('unsupervised_loss: occ must be "consistency" or None, got %r' % (occ,))
     if "flow_mult" in kw:

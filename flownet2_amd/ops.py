@@ -570,7 +570,64 @@ def unsup_loss_backward(img0, img1, fw, bw, occ_fw, occ_bw, params, results, tot
     return fd, bd
 
 
-_FLOW_TRACK_K = _lib.FLOW_TRACK_CONSTANTS["FN2_FLOW_TRACK_K"]      # columns of a results row (evaluate.TRACK_COLUMNS)
+_CENSUS_LOSS_K = _lib.CENSUS_LOSS_CONSTANTS["FN2_CENSUS_LOSS_K"]      # columns of a results row (evaluate.CENSUS_LOSS_COLUMNS)
+
+
+def census_loss_sizes(N: int, H: int, W: int, radius: int = 3):
+    """(workspace bytes, floats of `saved`, K) of fn2_census_loss_forward for [N,*,H,W] (include/flownet2_hip_census_loss.h)."""
+    nbytes, nsaved, k = C.c_size_t(), C.c_size_t(), C.c_int()
+    check(_lib.lib().fn2_census_loss_sizes(int(N), int(H), int(W), int(radius), C.byref(nbytes), C.byref(nsaved), C.byref(k)))
+    return nbytes.value, nsaved.value, k.value
+
+
+def census_loss_params(data_weight=1.0, charbonnier=(1e-3, 0.45), radius=3, census_eps=(0.81, 0.1), intensity_scale=255.0, flow_mult=1.0):
+    """The scalar arguments of fn2_census_loss_forward / _backward, in their order, as ctypes values."""
+    (eps_d, gamma_d), (c_t, c_h) = charbonnier, census_eps
+    f = lambda v: C.c_float(float(v))
+    return (f(data_weight), f(eps_d), f(gamma_d), int(radius), f(c_t), f(c_h), f(intensity_scale), f(flow_mult))
+
+
+def census_loss_forward(img0, img1, fw, bw=None, occ_fw=None, occ_bw=None, params=None, loss=True, save=True):
+    """The census data term (csrc/census_loss.hip) of fw (frame 0 -> 1) and, where given, bw (frame 1 -> 0) [N,2,H,W] on the images
+    [N,C,H,W]; occ_* [N,1,H,W] or None; params: census_loss_params(...).  Returns (results [2, N + 1, K] float64 on the device: per
+    direction one row per sample and the totals row, columns evaluate.CENSUS_LOSS_COLUMNS; the loss, a 0-axis device tensor, or None;
+    saved [2,N,3,H,W], the planes G, Wg and pd the backward reads, or None)."""
+    blobs, (N, Cc, H, W) = _unsup_loss_blobs("census_loss_forward", img0, img1, fw, bw, occ_fw, occ_bw)
+    dev = blobs[0].device
+    params = params or census_loss_params()
+    ws = torch.empty(census_loss_sizes(N, H, W, params[3])[0], dtype=torch.uint8, device=dev)
+    results = torch.empty((2, N + 1, _CENSUS_LOSS_K), dtype=torch.float64, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev) if loss else None
+    saved = torch.empty((2, N, 3, H, W), dtype=torch.float32, device=dev) if save else None
+    check(_lib.lib().fn2_census_loss_forward(*(_ptr(t) for t in blobs), N, Cc, H, W, *params, _ptr(results), _ptr(out), _ptr(saved), _ptr(ws),
+                                             ws.numel(), _stream()))
+    return results, out, saved
+
+
+def census_loss_backward(img0, img1, fw, bw, params, results, saved, total_diff=None, need_bw=True):
+    """The gradient of census_loss_forward's loss for fw and (need_bw, with a bw) bw, times total_diff (a device scalar; None: 1);
+    results, saved: what the forward returned for the same inputs.  Returns (fw_diff, bw_diff or None), each [N,2,H,W]."""
+    blobs, (N, Cc, H, W) = _unsup_loss_blobs("census_loss_backward", img0, img1, fw, bw, None, None)
+    dev = blobs[0].device
+    if not isinstance(results, torch.Tensor) or results.dtype != torch.float64 or tuple(results.shape) != (2, N + 1, _CENSUS_LOSS_K) or \
+            results.device != dev or not results.is_contiguous():
+        raise ValueError(f"census_loss_backward: results must be the forward's float64 [2,{N + 1},{_CENSUS_LOSS_K}] on {dev}")
+    if not isinstance(saved, torch.Tensor) or saved.dtype != torch.float32 or tuple(saved.shape) != (2, N, 3, H, W) or saved.device != dev or \
+            not saved.is_contiguous():
+        raise ValueError(f"census_loss_backward: saved must be the forward's float32 [2,{N},3,{H},{W}] on {dev}")
+    g = None
+    if total_diff is not None:
+        g = _chk(total_diff, "total_diff", None)
+        if g.numel() != 1 or g.device != dev:
+            raise ValueError(f"census_loss_backward: total_diff must be one float on {dev}")
+    fd = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev)
+    bd = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev) if need_bw and blobs[3] is not None else None
+    check(_lib.lib().fn2_census_loss_backward(*(_ptr(t) for t in blobs[:4]), N, Cc, H, W, *params, _ptr(results), _ptr(saved), _ptr(g), _ptr(fd),
+                                              _ptr(bd), _stream()))
+    return fd, bd
+
+
+_FLOW_TRACK_K =_lib.FLOW_TRACK_CONSTANTS["FN2_FLOW_TRACK_K"]      # columns of a results row (evaluate.TRACK_COLUMNS)
 
 
 def flow_track_sizes(N: int, T: int, H: int, W: int, P: int):
