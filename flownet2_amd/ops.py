@@ -1085,9 +1085,7 @@ def conv_backward_data_route(desc, transposed=False, bf16x3=False) -> int:
     the split-bf16 data-gradient kernel takes (csrc/tconv_bf16x3.hip: the 5x5 / 2 / 2 class of BWD_ROUTE_TCONV) come back as
     BWD_ROUTE_TCONV | CONV_ARITH_BF16X3, every other layer as without it (fn2_conv_backward_data_route_flags); the pack, run and masked
     wrappers below take that value."""
-    if not bf16x3:
-        return int(_lib.lib().fn2_conv_backward_data_route(C.byref(desc), int(bool(transposed))))
-    return int(_lib.lib().fn2_conv_backward_data_route_flags(C.byref(desc), int(bool(transposed)), ROUTE_BF16X3))
+    return int(_lib.lib().fn2_conv_backward_data_route_flags(C.byref(desc), int(bool(transposed)), ROUTE_BF16X3 if bf16x3 else 0))
 
 
 def _check_dgrad_operand(what, packed, desc, tr, route):
@@ -1155,17 +1153,11 @@ def conv_backward_weights(bottom, top_diff, desc, transposed=False, out=None, ac
         out = _chk(out, "weight diff")
         if tuple(out.shape) != shape:
             raise ValueError("conv_backward_weights: weight diff has the wrong shape")
-    arith = conv_backward_weights_arith(desc, transposed, True) if bf16x3 else 0
-    if arith:
-        need = int(L.fn2_conv_backward_weights_workspace_bytes_arith(C.byref(desc), tr, arith))
-        ws = _plane_workspace(x.device, need) if need else None
-        check(L.fn2_conv_backward_weights_arith_run(C.byref(desc), tr, arith, _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1], int(top_c0),
-                                                    _ptr(out), int(bool(accumulate)), _ptr(ws), need, _stream()))
-        return out
-    need = int(L.fn2_conv_backward_weights_workspace_bytes(C.byref(desc), tr))
+    arith = conv_backward_weights_arith(desc, transposed, bf16x3)         # 0: the exact kernel, as fn2_conv_backward_weights runs it
+    need = int(L.fn2_conv_backward_weights_workspace_bytes_arith(C.byref(desc), tr, arith))
     ws = _plane_workspace(x.device, need) if need else None
-    check(L.fn2_conv_backward_weights(C.byref(desc), tr, _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1], int(top_c0), _ptr(out),
-                                      int(bool(accumulate)), _ptr(ws), need, _stream()))
+    check(L.fn2_conv_backward_weights_arith_run(C.byref(desc), tr, arith, _ptr(x), x.shape[1], int(bottom_c0), _ptr(d), d.shape[1], int(top_c0),
+                                                _ptr(out), int(bool(accumulate)), _ptr(ws), need, _stream()))
     return out
 
 
