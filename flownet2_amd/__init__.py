@@ -13,6 +13,8 @@ unsupervised_loss  photometric + smoothness training loss without ground truth, 
             unsupervised_loss_report -> UnsupLoss (rows, summary())
 census_loss  the census data term of UnFlow (soft Hamming distance of ternary census signatures over a patch) on fused kernels: unchanged
             by an additive change of brightness; unsupervised_loss(data_term="census") uses it; census_loss_report -> CensusLoss
+flow_splat  forward warping (summation / average / linear / softmax splatting) with gradients, the same bits from run to run;
+            flow_splat_report -> FlowSplat; flow_range_occlusion (range-map occlusion planes); flow_interpolate (the frame between two frames)
 flow_track  points carried through a flow sequence in one launch -> FlowTracks (trajectories, long_range_flow()); flow_track_reseed, flow_track_grid
 """
 from . import _lib  # noqa: F401
@@ -21,7 +23,8 @@ from ._lib import Fn2Error, version  # noqa: F401
 _SOLVER_EXPORTS = ("SolverParameter", "Solver", "SGDSolver", "AdamSolver", "get_solver", "CaffeOptimizer")
 __all__ = ["Fn2Error", "version", "LpqSchedule", "flow_consistency", "FlowConsistency", "flow_to_color", "flow_error_map", "flow_track",
            "flow_track_reseed", "flow_track_grid", "FlowTracks", "unsupervised_loss", "unsupervised_loss_report", "UnsupLoss", "census_loss",
-           "census_loss_report", "CensusLoss", *_SOLVER_EXPORTS]
+           "census_loss_report", "CensusLoss", "flow_splat", "flow_splat_report", "flow_range_occlusion", "flow_interpolate", "FlowSplat",
+           *_SOLVER_EXPORTS]
 
 
 def __getattr__(name):
@@ -36,7 +39,8 @@ def __getattr__(name):
         from .functional import flow_consistency
         return flow_consistency
     if name in ("flow_to_color", "flow_error_map", "flow_track", "flow_track_reseed", "flow_track_grid", "unsupervised_loss",
-                "unsupervised_loss_report", "census_loss", "census_loss_report"):
+                "unsupervised_loss_report", "census_loss", "census_loss_report", "flow_splat", "flow_splat_report", "flow_range_occlusion",
+                "flow_interpolate"):
         from . import functional
         return getattr(functional, name)
     if name == "FlowConsistency":
@@ -51,4 +55,7 @@ def __getattr__(name):
     if name == "CensusLoss":
         from .evaluate import CensusLoss
         return CensusLoss
+    if name == "FlowSplat":
+        from .evaluate import FlowSplat
+        return FlowSplat
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

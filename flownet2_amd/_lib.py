@@ -1,11 +1,11 @@
 """ctypes binding of libflownet2_hip.so, derived from the C headers in include/ (they are its one source).
 
-Importing this module parses the fourteen headers: every `fn2_*` function declaration becomes argtypes / restype, every `typedef struct fn2_*`
+Importing this module parses the fifteen headers: every `fn2_*` function declaration becomes argtypes / restype, every `typedef struct fn2_*`
 a ctypes.Structure (CorrParams, ConvDesc, ...), every `enum { FN2_* }` and `#define FN2_* <integer>` an entry of CONSTANTS (of
 FLOW_METRICS_CONSTANTS for include/flownet2_hip_flow_metrics.h, of FLOW_CONSISTENCY_CONSTANTS for
 include/flownet2_hip_flow_consistency.h, of FLOW_VISUALIZE_CONSTANTS for include/flownet2_hip_flow_visualize.h, of FLOW_TRACK_CONSTANTS for
 include/flownet2_hip_flow_track.h, of UNSUP_LOSS_CONSTANTS for include/flownet2_hip_unsup_loss.h, of CENSUS_LOSS_CONSTANTS for
-include/flownet2_hip_census_loss.h).  lib() loads the library and applies the prototypes.  A new entry point is declared in a header;
+include/flownet2_hip_census_loss.h, of FLOW_SPLAT_CONSTANTS for include/flownet2_hip_flow_splat.h).  lib() loads the library and applies the prototypes.  A new entry point is declared in a header;
 nothing is added here.  What the parser does not understand is an error that names the declaration, never an `int` by default.
 
 There is NO fallback: if the shared library is missing or does not load, every operator raises.
@@ -105,37 +105,38 @@ def parse_header(text, structs=None):
 
 
 def _parse_headers():
-    """The fourteen headers, each read on its own (an #include is not followed: the per-header name lists stay apart); the main one first,
+    """The fifteen headers, each read on its own (an #include is not followed: the per-header name lists stay apart); the main one first,
     whose structures the others use.  The enumerators of the last four headers (the result columns of fn2_flow_metrics; the result columns
-    and flag bits of fn2_flow_consistency; the normalisations of fn2_flow_color; the result columns and stop reasons of fn2_flow_track) and of the last two (the result columns of fn2_unsup_loss_forward and of
-    fn2_census_loss_forward) are kept in tables of their own, as their functions are
+    and flag bits of fn2_flow_consistency; the normalisations of fn2_flow_color; the result columns and stop reasons of fn2_flow_track) and of the last three (the result columns of fn2_unsup_loss_forward and of
+    fn2_census_loss_forward; the result columns, importances and statuses of fn2_flow_splat_forward) are kept in tables of their own, as their functions are
     in lists of their own."""
     per_header, structs, constants = [], {}, {}
     own = {"flownet2_hip_flow_metrics.h": {}, "flownet2_hip_flow_consistency.h": {}, "flownet2_hip_flow_visualize.h": {},
-           "flownet2_hip_flow_track.h": {}, "flownet2_hip_unsup_loss.h": {}, "flownet2_hip_census_loss.h": {}}
+           "flownet2_hip_flow_track.h": {}, "flownet2_hip_unsup_loss.h": {}, "flownet2_hip_census_loss.h": {},
+           "flownet2_hip_flow_splat.h": {}}
     for h in ("flownet2_hip.h", "flownet2_hip_solver.h", "flownet2_hip_corr_route.h", "flownet2_hip_conv_general.h",
               "flownet2_hip_conv_geometry.h", "flownet2_hip_conv_volume.h", "flownet2_hip_lpq_loss.h", "flownet2_hip_flow_metrics.h",
               "flownet2_hip_flow_consistency.h", "flownet2_hip_flow_visualize.h", "flownet2_hip_flow_track.h", "flownet2_hip_flow_head.h",
-              "flownet2_hip_unsup_loss.h", "flownet2_hip_census_loss.h"):
+              "flownet2_hip_unsup_loss.h", "flownet2_hip_census_loss.h", "flownet2_hip_flow_splat.h"):
         with open(os.path.join(INCLUDE_DIR, h)) as f:
             functions, structs, c = parse_header(f.read(), structs)
         per_header.append(functions)
         own.get(h, constants).update(c)
     return (per_header, structs, constants, own["flownet2_hip_flow_metrics.h"], own["flownet2_hip_flow_consistency.h"],
             own["flownet2_hip_flow_visualize.h"], own["flownet2_hip_flow_track.h"], own["flownet2_hip_unsup_loss.h"],
-            own["flownet2_hip_census_loss.h"])
+            own["flownet2_hip_census_loss.h"], own["flownet2_hip_flow_splat.h"])
 
 
 # CONSTANTS: every FN2_* enumerator and integer #define of the first seven headers; FLOW_METRICS_CONSTANTS: the FN2_FLOW_METRICS_* enum;
 # FLOW_CONSISTENCY_CONSTANTS: the two FN2_FLOW_CONSISTENCY_* enums; FLOW_VISUALIZE_CONSTANTS: the FN2_FLOW_COLOR_NORM_* enum;
 # FLOW_TRACK_CONSTANTS: the two FN2_FLOW_TRACK_* enums; UNSUP_LOSS_CONSTANTS: the FN2_UNSUP_LOSS_* enum;
-# CENSUS_LOSS_CONSTANTS: the FN2_CENSUS_LOSS_* enum
+# CENSUS_LOSS_CONSTANTS: the FN2_CENSUS_LOSS_* enum; FLOW_SPLAT_CONSTANTS: the three FN2_FLOW_SPLAT_* enums
 (_PER_HEADER, _STRUCTS, CONSTANTS, FLOW_METRICS_CONSTANTS, FLOW_CONSISTENCY_CONSTANTS, FLOW_VISUALIZE_CONSTANTS,
- FLOW_TRACK_CONSTANTS, UNSUP_LOSS_CONSTANTS, CENSUS_LOSS_CONSTANTS) = _parse_headers()
+ FLOW_TRACK_CONSTANTS, UNSUP_LOSS_CONSTANTS, CENSUS_LOSS_CONSTANTS, FLOW_SPLAT_CONSTANTS) = _parse_headers()
 (EXPORTS, SOLVER_EXPORTS, CORR_ROUTE_EXPORTS, CONV_GENERAL_EXPORTS, CONV_GEOMETRY_EXPORTS, CONV_VOLUME_EXPORTS, LPQ_LOSS_EXPORTS,
  FLOW_METRICS_EXPORTS, FLOW_CONSISTENCY_EXPORTS, FLOW_VISUALIZE_EXPORTS, FLOW_TRACK_EXPORTS, FLOW_HEAD_EXPORTS,
- UNSUP_LOSS_EXPORTS, CENSUS_LOSS_EXPORTS) = (list(f) for f in _PER_HEADER)      # per header
-# PROTOTYPES: the functions of the first eight headers (tests/test_flow_metrics_host.py counts them); the ninth to fourteenth headers' are in
+ UNSUP_LOSS_EXPORTS, CENSUS_LOSS_EXPORTS, FLOW_SPLAT_EXPORTS) = (list(f) for f in _PER_HEADER)      # per header
+# PROTOTYPES: the functions of the first eight headers (tests/test_flow_metrics_host.py counts them); the ninth to fifteenth headers' are in
 # tables of their own, bound by lib() like the others
 PROTOTYPES = {name: proto for f in _PER_HEADER[:8] for name, proto in f.items()}
 FLOW_CONSISTENCY_PROTOTYPES = dict(_PER_HEADER[8])
@@ -144,6 +145,7 @@ FLOW_TRACK_PROTOTYPES = dict(_PER_HEADER[10])
 FLOW_HEAD_PROTOTYPES = dict(_PER_HEADER[11])          # include/flownet2_hip_flow_head.h: the one-launch gather + up-sampling of the flow heads
 UNSUP_LOSS_PROTOTYPES = dict(_PER_HEADER[12])         # include/flownet2_hip_unsup_loss.h: the unsupervised loss, forward and backward
 CENSUS_LOSS_PROTOTYPES = dict(_PER_HEADER[13])        # include/flownet2_hip_census_loss.h: its census data term, forward and backward
+FLOW_SPLAT_PROTOTYPES = dict(_PER_HEADER[14])         # include/flownet2_hip_flow_splat.h: forward warping (splatting), forward and backward
 globals().update({cls.__name__: cls for cls in _STRUCTS.values()})      # CaffemodelEntry, Hdf5Entry, ConvDesc, CorrParams, DatumView, ...
 # debug hooks the library may export without declaring them in a header (FN2_ABLATION builds have the trace)
 _HOOKS = parse_header("""
@@ -167,7 +169,7 @@ def lib():
     L = C.CDLL(SO_PATH)
     for table, required in ((PROTOTYPES, True), (FLOW_CONSISTENCY_PROTOTYPES, True), (FLOW_VISUALIZE_PROTOTYPES, True),
                             (FLOW_TRACK_PROTOTYPES, True), (FLOW_HEAD_PROTOTYPES, True), (UNSUP_LOSS_PROTOTYPES, True),
-                            (CENSUS_LOSS_PROTOTYPES, True), (_HOOKS, False)):
+                            (CENSUS_LOSS_PROTOTYPES, True), (FLOW_SPLAT_PROTOTYPES, True), (_HOOKS, False)):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 if required:

@@ -287,6 +287,51 @@ class CensusLoss:
                 "data_weight": self.data_weight, "radius": self.radius, "loss": self.loss}
 
 
+# ---- forward warping (splatting) -----------------------------------------------------------------------------------------------------
+_S_PREFIX = "FN2_FLOW_SPLAT_"
+_S_ENUM = _lib.FLOW_SPLAT_CONSTANTS                                        # include/flownet2_hip_flow_splat.h: columns, importances, statuses
+FLOW_SPLAT_K = _S_ENUM[_S_PREFIX + "K"]
+FLOW_SPLAT_STATUS = {n[len(_S_PREFIX + "STATUS_"):]: v for n, v in _S_ENUM.items() if n.startswith(_S_PREFIX + "STATUS_")}      # name -> byte
+FLOW_SPLAT_COLUMNS = tuple(sorted((n[len(_S_PREFIX):] for n in _S_ENUM if n != _S_PREFIX + "K" and not n.startswith(_S_PREFIX + "STATUS_")
+                                   and not n.startswith(_S_PREFIX + "IMPORTANCE_")), key=lambda n: _S_ENUM[_S_PREFIX + n]))
+FLOW_SPLAT_COL = {name: i for i, name in enumerate(FLOW_SPLAT_COLUMNS)}
+
+
+class FlowSplat:
+    """The [n, K] float64 rows (columns FLOW_SPLAT_COLUMNS) of n samples of functional.flow_splat_report, and the planes of the call that
+    made them (None for rows put together by hand): out, weight (the denominator), hole, status (uint8, FLOW_SPLAT_STATUS)."""
+
+    def __init__(self, rows=None, out=None, weight=None, hole=None, status=None, t=1.0, mode="sum"):
+        r = np.zeros((0, FLOW_SPLAT_K), np.float64) if rows is None else np.array(rows, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != FLOW_SPLAT_K:
+            raise ValueError(f"FlowSplat: rows must be [n, {FLOW_SPLAT_K}], got {r.shape}")
+        self.rows, self.out, self.weight, self.hole, self.status = r, out, weight, hole, status
+        self.t, self.mode = float(t), str(mode)
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def summary(self):
+        """The shares of all source pixels that were splatted, outside, masked and non-finite, the share of target cells that are holes,
+        the mean of the weight plane over all cells and its maximum, the pixel and sample counts, the time and the mode.  A quotient with
+        a zero denominator is nan."""
+        tot = lambda name: float(np.sum(self.rows[:, FLOW_SPLAT_COL[name]]))
+        pixels = tot("PIXELS")
+        return {
+            "splatted": _ratio(tot("SPLATTED"), pixels),
+            "outside": _ratio(tot("OUTSIDE"), pixels),
+            "masked": _ratio(tot("MASKED"), pixels),
+            "nonfinite": _ratio(tot("NONFINITE"), pixels),
+            "holes": _ratio(tot("HOLES"), pixels),
+            "weight_mean": _ratio(tot("WEIGHT_SUM"), pixels),
+            "weight_max": float(np.max(self.rows[:, FLOW_SPLAT_COL["WEIGHT_MAX"]])) if self.rows.shape[0] else math.nan,
+            "pixels": int(pixels),
+            "samples": len(self),
+            "t": self.t,
+            "mode": self.mode,
+        }
+
+
 def write_pgm(path, plane):
     """A [H,W] (or [1,H,W]) plane -> 8-bit binary PGM (P5, maxval 255): 255 where the plane is non-zero, else 0."""
     a = np.asarray(plane)

@@ -472,6 +472,127 @@ def flow_consistency(fw, bw, *, alpha=(0.01, 0.5), beta=(0.01, 0.002), flags=Fal
     return FlowConsistency(rows[0], rows[1], occ=occ, flags=fl, err=er, warped=wa, alpha=alpha, beta=beta)
 
 
+_SPLAT_MODES = {"sum": ("none", False), "average": ("none", True), "linear": ("linear", True), "softmax": ("softmax", True)}
+
+
+class _FlowSplat(torch.autograd.Function):
+    """Forward three launches, backward one gather launch; out and the denominator stay on the device for the backward."""
+
+    @staticmethod
+    def forward(ctx, values, flow, metric, src_valid, t, importance, normalize, fill_value, want_hole):
+        _, out, den, hole, _ = ops.flow_splat_forward(values, flow, metric, src_valid, t=t, importance=importance, normalize=normalize,
+                                                      fill_value=fill_value, hole=want_hole)
+        ctx.cfg = (t, importance, normalize)
+        ctx.save_for_backward(values, flow, metric, src_valid, out, den)
+        ctx.mark_non_differentiable(*([hole] if want_hole else []))
+        return (out, den, hole) if want_hole else (out, den)
+
+    @staticmethod
+    def backward(ctx, g, gw, *_):
+        values, flow, metric, src_valid, out, den = ctx.saved_tensors
+        t, importance, normalize = ctx.cfg
+        need = ctx.needs_input_grad
+        if g is None:
+            g = torch.zeros_like(out)
+        dv, df, dz = ops.flow_splat_backward(g.contiguous(), None if gw is None else gw.contiguous(), values, flow, metric, src_valid, out, den,
+                                             t=t, importance=importance, normalize=normalize, need_values=need[0], need_flow=need[1],
+                                             need_metric=need[2])
+        return (dv, df, dz if need[2] else None) + (None,) * 6
+
+
+def _flow_splat_mode(what, mode, normalize, fill, metric):
+    if mode not in _SPLAT_MODES:
+        raise ValueError(f'{what}: mode must be "sum", "average", "linear" or "softmax", got {mode!r}')
+    importance, norm = _SPLAT_MODES[mode]
+    if normalize is not None:
+        norm = bool(normalize)
+    if importance != "none" and metric is None:
+        raise ValueError(f'{what}: mode "{mode}" needs a metric')
+    if isinstance(fill, float) and fill != fill:
+        fill_value = ops.FILL_NAN
+    elif fill == 0:
+        fill_value = ops.FILL_ZERO
+    else:
+        raise ValueError(f"{what}: fill must be 0.0 or nan, got {fill!r}")
+    return importance, norm, fill_value
+
+
+def flow_splat(values, flow, metric=None, *, t=1.0, mode="sum", normalize=None, fill=0.0, src_valid=None, weight=False, hole=False):
+    """Forward warping (csrc/flow_splat.hip; the arithmetic is stated in include/flownet2_hip_flow_splat.h): every pixel of values [N,C,H,W]
+    is carried along t * flow [N,2,H,W] and spread bilinearly over the four cells around its landing point -- the push that flow_warp's
+    pull lacks.  mode (Niklaus and Liu, "Softmax Splatting", CVPR 2020): "sum" the plain sum; "average" the sum divided by the summed
+    bilinear weights; "linear" / "softmax" the mean weighted by metric [N,1,H,W] / by exp(metric).  normalize=False with "linear" /
+    "softmax" returns the raw numerator (the denominator is `weight`); normalize=True with "sum" is "average".  A cell that nothing reaches
+    holds `fill` (0.0 or nan) where the result is normalised.  src_valid [N,1,H,W]: zero leaves the source out.  The sum at a cell runs in
+    ascending source index whatever the batch and however many sources meet there: the same bits from run to run.  Returns out, or
+    (out, weight, hole) with those asked for: weight [N,1,H,W] the denominator (with "sum" / "average" the range map), hole 1.0 where it is
+    0.  Gradients for values, flow and metric (through out and weight); none for t."""
+    importance, norm, fill_value = _flow_splat_mode("flow_splat", mode, normalize, fill, metric)
+    if isinstance(src_valid, torch.Tensor) and src_valid.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("flow_splat: src_valid gets no gradient (values, flow and metric do): detach it")
+    if importance == "none":
+        metric = None
+    res = _FlowSplat.apply(values.contiguous(), flow.contiguous(), None if metric is None else metric.contiguous(),
+                           None if src_valid is None else src_valid.contiguous(), float(t), importance, norm, fill_value, bool(hole))
+    picked = (res[0],) + ((res[1],) if weight else ()) + ((res[2],) if hole else ())
+    return picked[0] if len(picked) == 1 else picked
+
+
+def flow_splat_report(values, flow, metric=None, *, t=1.0, mode="sum", normalize=None, fill=0.0, src_valid=None):
+    """flow_splat's forward without autograd, as an evaluate.FlowSplat: the rows per sample (masked, non-finite, outside and splatted
+    sources, holes, the sum and the maximum of the weight plane) with out / weight / hole / status attached; summary() gives the shares."""
+    from .evaluate import FlowSplat
+    importance, norm, fill_value = _flow_splat_mode("flow_splat_report", mode, normalize, fill, metric)
+    with torch.no_grad():
+        results, out, den, hole, status = ops.flow_splat_forward(values, flow, None if importance == "none" else metric, src_valid, t=t,
+                                                                 importance=importance, normalize=norm, fill_value=fill_value, hole=True,
+                                                                 status=True)
+    return FlowSplat(results[:-1].cpu().numpy(), out=out, weight=den, hole=hole, status=status, t=t, mode=mode)
+
+
+def flow_range_occlusion(fw, bw, *, threshold=0.5):
+    """The range-map occlusion of Wang et al., "Occlusion Aware Unsupervised Learning of Optical Flow" (CVPR 2018), of two flows
+    [N,2,H,W], fw from frame 0 to frame 1 and bw back: the range map of a flow is a plane of ones splatted along it (flow_splat, "sum",
+    t = 1), and a pixel of frame 0 is occluded where the range map of bw is below `threshold` -- nothing of frame 1 maps to it.  Returns
+    (occ_fw, occ_bw, range_fw, range_bw), each [N,1,H,W]: occ_fw = 1.0 where range_fw (the range map of bw, on frame 0's grid) <
+    threshold, occ_bw likewise from fw.  threshold is the caller's choice (0.5 here; the paper clips the map to [0, 1] instead).  The
+    occ planes go where flow_consistency's do: flow_metrics(occ=), unsupervised_loss, census_loss.  Not differentiable."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (fw, bw)):
+        raise RuntimeError("flow_range_occlusion is not differentiable: detach the inputs or call it under torch.no_grad()")
+    if not (isinstance(fw, torch.Tensor) and isinstance(bw, torch.Tensor)) or fw.shape != bw.shape or fw.dim() != 4 or fw.shape[1] != 2:
+        raise ValueError("flow_range_occlusion: fw and bw must both be [N,2,H,W]")
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise ValueError(f"flow_range_occlusion: threshold = {threshold} (need >= 0)")
+    with torch.no_grad():
+        ones = torch.ones((fw.shape[0], 1, fw.shape[2], fw.shape[3]), dtype=torch.float32, device=fw.device)
+        range_fw = ops.flow_splat_forward(ones, bw, out=False)[2]
+        range_bw = ops.flow_splat_forward(ones, fw, out=False)[2]
+    return (range_fw < threshold).float(), (range_bw < threshold).float(), range_fw, range_bw
+
+
+def flow_interpolate(img0, img1, fw, bw, t, *, alpha=20.0, intensity_scale=255.0):
+    """The frame at time t in (0, 1) between img0 and img1 [N,C,H,W] from the flows fw (frame 0 to 1) and bw (back), by softmax
+    splatting: a composition over flow_warp and flow_splat, no network and no refinement.  z0 = -alpha mean_c |img0 - flow_warp(img1, fw)|
+    / intensity_scale is the importance of a pixel of frame 0 (a pixel whose brightness the flow does not explain gives way where several
+    land on one cell), z1 likewise for img1 and bw; (N0, D0) is the raw softmax splat of img0 along fw at t, (N1, D1) that of img1 along bw
+    at 1 - t; the frame is ((1-t) N0 + t N1) / ((1-t) D0 + t D1) where that denominator is positive and (1-t) img0 + t img1 elsewhere.
+    alpha is the user's knob and its default is arbitrary: 0 weighs every pixel alike, larger values let the better explained pixel win.
+    Images in [0, 255] go with the default intensity_scale.  Not differentiable as it stands (call flow_splat for gradients)."""
+    t = float(t)
+    if not 0.0 <= t <= 1.0:
+        raise ValueError(f"flow_interpolate: t = {t} (need 0 <= t <= 1)")
+    with torch.no_grad():
+        z0 = -float(alpha) * (img0 - flow_warp(img1, fw)).abs().mean(dim=1, keepdim=True) / float(intensity_scale)
+        z1 = -float(alpha) * (img1 - flow_warp(img0, bw)).abs().mean(dim=1, keepdim=True) / float(intensity_scale)
+        _, n0, d0, _, _ = ops.flow_splat_forward(img0, fw, z0, t=t, importance="softmax")
+        _, n1, d1, _, _ = ops.flow_splat_forward(img1, bw, z1, t=1.0 - t, importance="softmax")
+        den = (1.0 - t) * d0 + t * d1
+        num = (1.0 - t) * n0 + t * n1
+        blend = (1.0 - t) * img0 + t * img1
+        return torch.where(den > 0, num / den, blend)
+
+
 class _UnsupLoss(torch.autograd.Function):
     """Forward two launches, backward one; the normalisers and the upstream gradient stay on the device (as _LpqLossMulti)."""
 

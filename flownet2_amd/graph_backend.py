@@ -46,7 +46,7 @@ class GraphBackend:
     # fails when it is called, with the object's own AttributeError that names it.  Nothing else of the object is reachable through the adapter.
     FORWARDED = ("correlation", "resample", "flow_warp", "channel_norm", "downsample", "l1_loss", "scale_shift", "resample_slices",
                  "flow_warp_slices", "channel_norm_slices", "l1_loss_multi", "downsample_ahead", "wait_ahead", "lpq_loss", "lpq_loss_multi",
-                 "unsupervised_loss", "flow_consistency", "census_loss")
+                 "unsupervised_loss", "flow_consistency", "census_loss", "flow_splat", "flow_range_occlusion")
 
     def __init__(self, obj):
         get = lambda name: getattr(obj, name, None)
@@ -75,6 +75,7 @@ class GraphBackend:
         self.has_multi_lpq_loss = get("lpq_loss_multi") is not None     # the same for loss=("lpq", ...)
         self.has_unsupervised_loss = get("unsupervised_loss") is not None      # the fused photometric + smoothness loss (nets.unsupervised_loss)
         self.has_census_loss = get("census_loss") is not None           # its census data term (data_term="census")
+        self.has_flow_splat = get("flow_splat") is not None and get("flow_range_occlusion") is not None      # forward warping; occ="range"
         self.targets_ahead = get("downsample_ahead") is not None        # the loss's target pyramid on a second stream
 
     def __getattr__(self, name):

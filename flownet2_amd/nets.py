@@ -509,7 +509,8 @@ def unsupervised_loss(flows_fw, flows_bw, img0, img1, backend, occ="consistency"
     unsupervised_loss (photometric + smoothness, both directions) of flows_fw[s] and flows_bw[s] on the images brought to that scale with
     Downsample; the weighted sum in list order.  The predictions are in FlowNet's 1/20 units of full-resolution pixels, so flow_mult =
     FLOW_SCALE * w_s / W makes them pixels of the scale.  occ="consistency": the occlusion planes of the data term come from the
-    backend's flow_consistency on the detached, rescaled flows of the scale; None: no pixel is masked.  kw: the keyword arguments of
+    backend's flow_consistency on the detached, rescaled flows of the scale; "range": from its flow_range_occlusion (the range maps of
+    csrc/flow_splat.hip: a pixel nothing of the other frame maps to); None: no pixel is masked.  kw: the keyword arguments of
     functional.unsupervised_loss (weights, Charbonnier constants, edge_weight, smooth_order, data_term and census: data_term="census"
     takes the census data term of csrc/census_loss.hip at every scale)."""
     backend = backend_of(backend)
@@ -517,8 +518,10 @@ def unsupervised_loss(flows_fw, flows_bw, img0, img1, backend, occ="consistency"
         raise RuntimeError("unsupervised_loss: the backend has no unsupervised_loss op (there is no composed fallback)")
     if kw.get("data_term", "brightness") == "census" and not backend.has_census_loss:
         raise RuntimeError("unsupervised_loss: the backend has no census_loss op (there is no composed fallback)")
-    if occ not in ("consistency", None):
-        raise ValueError('unsupervised_loss: occ must be "consistency" or None, got %r' % (occ,))
+    if occ not in ("consistency", "range", None):
+        raise ValueError('unsupervised_loss: occ must be "consistency", "range" or None, got %r' % (occ,))
+    if occ == "range" and not backend.has_flow_splat:
+        raise RuntimeError("unsupervised_loss: the backend has no flow_range_occlusion op (there is no composed fallback)")
     if "flow_mult" in kw:
         raise ValueError("unsupervised_loss: flow_mult is set per scale (FLOW_SCALE * w_s / W)")
     W = img0.shape[3]
@@ -531,7 +534,9 @@ def unsupervised_loss(flows_fw, flows_bw, img0, img1, backend, occ="consistency"
         mult = FLOW_SCALE * w / W
         i0, i1 = backend.downsample(img0, h, w), backend.downsample(img1, h, w)
         occ_fw = occ_bw = None
-        if occ is not None:
+        if occ == "range":
+            occ_fw, occ_bw = backend.flow_range_occlusion(fw.detach() * mult, bw.detach() * mult)[:2]
+        elif occ is not None:
             c = backend.flow_consistency(fw.detach() * mult, bw.detach() * mult)
             occ_fw, occ_bw = c.occ_fw, c.occ_bw
         term = backend.unsupervised_loss(i0, i1, fw, bw, occ_fw, occ_bw, flow_mult=mult, **kw) * weight

@@ -627,6 +627,74 @@ def census_loss_backward(img0, img1, fw, bw, params, results, saved, total_diff=
     return fd, bd
 
 
+_FLOW_SPLAT_K = _lib.FLOW_SPLAT_CONSTANTS["FN2_FLOW_SPLAT_K"]      # columns of a results row (evaluate.FLOW_SPLAT_COLUMNS)
+_FLOW_SPLAT_IMPORTANCES = {n[len("FN2_FLOW_SPLAT_IMPORTANCE_"):].lower(): v for n, v in _lib.FLOW_SPLAT_CONSTANTS.items()
+                           if n.startswith("FN2_FLOW_SPLAT_IMPORTANCE_")}      # none, linear, softmax
+
+
+def flow_splat_sizes(N: int, C_: int, H: int, W: int):
+    """(workspace bytes for [N,C,H,W], K) of fn2_flow_splat_forward (include/flownet2_hip_flow_splat.h)."""
+    nbytes, k = C.c_size_t(), C.c_int()
+    check(_lib.lib().fn2_flow_splat_sizes(int(N), int(C_), int(H), int(W), C.byref(nbytes), C.byref(k)))
+    return nbytes.value, k.value
+
+
+def _flow_splat_blobs(what, values, flow, metric, src_valid):
+    v, f = _chk(values, "values"), _chk(flow, "flow")
+    z, m = _chk_opt(metric, "metric"), _chk_opt(src_valid, "src_valid")
+    N, Cc, H, W = v.shape
+    for name, t, ch in (("flow", f, 2), ("metric", z, 1), ("src_valid", m, 1)):
+        if t is not None and tuple(t.shape) != (N, ch, H, W):
+            raise ValueError(f"{what}: {name} {tuple(t.shape)} must be [{N},{ch},{H},{W}]")
+        if t is not None and t.device != v.device:
+            raise ValueError(f"{what}: {name} on {t.device}, values on {v.device}")
+    return (v, f, z, m), (N, Cc, H, W)
+
+
+def _flow_splat_importance(what, importance):
+    if importance not in _FLOW_SPLAT_IMPORTANCES:
+        raise ValueError(f"{what}: importance must be one of {sorted(_FLOW_SPLAT_IMPORTANCES)}, got {importance!r}")
+    return _FLOW_SPLAT_IMPORTANCES[importance]
+
+
+def flow_splat_forward(values, flow, metric=None, src_valid=None, t=1.0, importance="none", normalize=False, fill_value=FILL_ZERO, out=True,
+                       weight=True, hole=False, status=False):
+    """Forward warping (csrc/flow_splat.hip): values [N,C,H,W] carried along t * flow [N,2,H,W] and spread over the four cells around the
+    landing point, weighted by metric [N,1,H,W] (importance "linear": z, "softmax": exp z; "none": not read); src_valid [N,1,H,W]: zero
+    leaves the source out.  Returns (results [N + 1, K] float64 on the device: one row per sample and the totals row, columns
+    evaluate.FLOW_SPLAT_COLUMNS; out [N,C,H,W], weight [N,1,H,W], hole [N,1,H,W], status uint8 [N,1,H,W]: each None where not asked for)."""
+    (v, f, z, m), (N, Cc, H, W) = _flow_splat_blobs("flow_splat_forward", values, flow, metric, src_valid)
+    imp = _flow_splat_importance("flow_splat_forward", importance)
+    dev = v.device
+    ws = torch.empty(flow_splat_sizes(N, Cc, H, W)[0], dtype=torch.uint8, device=dev)
+    results = torch.empty((N + 1, _FLOW_SPLAT_K), dtype=torch.float64, device=dev)
+    new = lambda want, ch, dtype=torch.float32: torch.empty((N, ch, H, W), dtype=dtype, device=dev) if want else None
+    o, w, h, s = new(out, Cc), new(weight, 1), new(hole, 1), new(status, 1, torch.uint8)
+    check(_lib.lib().fn2_flow_splat_forward(_ptr(v), _ptr(f), _ptr(z), _ptr(m), N, Cc, H, W, C.c_float(float(t)), imp, int(bool(normalize)),
+                                            int(fill_value), _ptr(results), _ptr(o), _ptr(w), _ptr(h), _ptr(s), _ptr(ws), ws.numel(),
+                                            _stream()))
+    return results, o, w, h, s
+
+
+def flow_splat_backward(out_diff, weight_diff, values, flow, metric, src_valid, out, weight, t=1.0, importance="none", normalize=False,
+                        need_values=True, need_flow=True, need_metric=True):
+    """The gradients of flow_splat_forward's out (times out_diff) and weight (times weight_diff, or None) for values, flow and metric; out,
+    weight: what the forward returned for the same inputs (out may be None where normalize is off).  Returns (values_diff, flow_diff,
+    metric_diff), each None where not asked for; metric_diff is None with importance "none"."""
+    (v, f, z, m), (N, Cc, H, W) = _flow_splat_blobs("flow_splat_backward", values, flow, metric, src_valid)
+    imp = _flow_splat_importance("flow_splat_backward", importance)
+    dev = v.device
+    g, gw, o, w = _chk(out_diff, "out_diff"), _chk_opt(weight_diff, "weight_diff"), _chk_opt(out, "out"), _chk(weight, "weight")
+    for name, t_, ch in (("out_diff", g, Cc), ("weight_diff", gw, 1), ("out", o, Cc), ("weight", w, 1)):
+        if t_ is not None and (tuple(t_.shape) != (N, ch, H, W) or t_.device != dev):
+            raise ValueError(f"flow_splat_backward: {name} {tuple(t_.shape)} must be [{N},{ch},{H},{W}] on {dev}")
+    new = lambda want, ch: torch.empty((N, ch, H, W), dtype=torch.float32, device=dev) if want else None
+    dv, df, dz = new(need_values, Cc), new(need_flow, 2), new(need_metric and imp != 0 and z is not None, 1)
+    check(_lib.lib().fn2_flow_splat_backward(_ptr(g), _ptr(gw), _ptr(v), _ptr(f), _ptr(z), _ptr(m), _ptr(o), _ptr(w), N, Cc, H, W,
+                                             C.c_float(float(t)), imp, int(bool(normalize)), _ptr(dv), _ptr(df), _ptr(dz), _stream()))
+    return dv, df, dz
+
+
 _FLOW_TRACK_K =_lib.FLOW_TRACK_CONSTANTS["FN2_FLOW_TRACK_K"]      # columns of a results row (evaluate.TRACK_COLUMNS)
 
 

@@ -16,7 +16,7 @@ the coefficient blobs is pinned against the reference's layers.
 --unsupervised trains without the ground truth: FlowNetC on (img0, img1) and on (img1, img0), nets.unsupervised_loss (photometric +
 smoothness, csrc/unsup_loss.hip; --unsup-data census: the census data term of csrc/census_loss.hip) on the two pyramids; the ground truth the records carry is used only to print the EPE (flow_metrics).
 Usage: python scripts/train_pipeline.py [--batch 8] [--iters 10] [--no-train] [--no-prefetch]
-       [--unsupervised [--unsup-smooth W] [--unsup-order 1|2] [--unsup-no-occlusion]
+       [--unsupervised [--unsup-smooth W] [--unsup-order 1|2] [--unsup-no-occlusion] [--unsup-occ consistency|range]
        [--unsup-data brightness|census [--census-radius R]]]"""
 import argparse
 import os
@@ -85,6 +85,8 @@ def build_parser():
     ap.add_argument("--unsup-smooth", type=float, default=1.0, metavar="W", help="smooth_weight of the unsupervised loss")
     ap.add_argument("--unsup-order", type=int, default=2, choices=(1, 2), help="order of its smoothness term")
     ap.add_argument("--unsup-no-occlusion", action="store_true", help="do not mask its data term with flow_consistency's occlusion planes")
+    ap.add_argument("--unsup-occ", default="consistency", choices=("consistency", "range"),
+                    help="where its occlusion planes come from: the forward-backward check, or the range maps of csrc/flow_splat.hip")
     ap.add_argument("--unsup-data", default="brightness", choices=("brightness", "census"),
                     help="its data term: brightness constancy, or the census term (unchanged by an additive change of brightness)")
     ap.add_argument("--census-radius", type=int, default=3, choices=(1, 2, 3), metavar="R", help="patch radius of the census term")
@@ -166,7 +168,7 @@ def main():
                 i0, i1 = t_img0[0].data, t_img1[0].data
                 census = dict(data_term="census", census=dict(radius=a.census_radius)) if a.unsup_data == "census" else {}
                 flows_fw, flows_bw = nets.flownet_c_core(P, i0, i1, Fn), nets.flownet_c_core(P, i1, i0, Fn)
-                loss = nets.unsupervised_loss(flows_fw, flows_bw, i0, i1, Fn, occ=None if a.unsup_no_occlusion else "consistency",
+                loss = nets.unsupervised_loss(flows_fw, flows_bw, i0, i1, Fn, occ=None if a.unsup_no_occlusion else a.unsup_occ,
                                               smooth_weight=a.unsup_smooth, smooth_order=a.unsup_order, **census)
             else:
                 loss = nets.multiscale_loss(nets.flownet_c_core(P, t_img0[0].data, t_img1[0].data, Fn), t_flow[0].data, Fn, loss=spec)
@@ -194,7 +196,7 @@ def main():
                 epe = Fn.flow_metrics(pred, t_flow[0].data).summary()["epe"]
             data = "census data term of radius %d, " % a.census_radius if a.unsup_data == "census" else ""
             print("unsupervised loss %.4f (%ssmooth weight %g, order %d, occlusion masks %s), EPE against the ground truth %.4f" % (
-                float(loss), data, a.unsup_smooth, a.unsup_order, "off" if a.unsup_no_occlusion else "on", epe))
+                float(loss), data, a.unsup_smooth, a.unsup_order, "off" if a.unsup_no_occlusion else "on" if a.unsup_occ == "consistency" else "range", epe))
         else:
             print("loss %.4f, NaN ground truth kept: %s" % (float(loss), bool(torch.isnan(t_flow[0].data).any())))
 
